@@ -11,9 +11,11 @@ ray-marcher at 96 samples -> 64->512 super-resolution, RGB + 19-class seg) for 4
 uint8 RGB|seg frames, and (N > 1) an RCCL gather of the uint8 frames to rank 0 — BASELINE.json config 2 per GPU,
 config 4's sharding across GPUs.  Random-init ide3d-ffhq-64-512 generator, synthetic latents, fp32.
 
-Timing: W untimed warm-up steps, then `--blocks` (default 5) timed blocks of EXACTLY K steps, each bracketed by a barrier +
-`torch.cuda.synchronize()` on both sides, MAX over ranks per block; `value` / `ms_per_step` are the MEDIAN block (min / max
-are reported next to it: box-to-box and run-to-run spread is a few per cent).
+Timing: W untimed warm-up steps, then EXACTLY K timed steps split into `--blocks` (default 5, at most K) blocks, each bracketed by a
+barrier + `torch.cuda.synchronize()` on both sides, MAX over ranks per block; `value` / `ms_per_step` are the MEDIAN block's time per
+step (min / max are reported next to it: box-to-box and run-to-run spread is a few per cent).  The generators are re-seeded in front
+of the timed steps, so with the same arguments their inputs (latents and stratified jitter) are the same in every run;
+`--dump-outputs DIR` writes what the last timed step computed (see `dump_outputs`).
 
 Rank 0 prints ONE COMPACT JSON line (< 4 KB, contract in the task statement; tests/test_bench_launcher_cpu.py checks the size and a
 strict `json.loads`).  `value` is measured with the LIBRARY-DEFAULT convolution arithmetic (bf16x6: every fp32 operand as three bf16
@@ -58,6 +60,10 @@ PARITY_JITTER_SEED = 11      # = oracle/make_bench_parity.py
 HEADLINE_ARITH = 'default'   # the library default (`ide3d_get_conv_arithmetic()` of a fresh process: bf16x6, fp32-grade) - what a drop-in caller runs
 PARITY_TOL = 2e-5            # of the image / logit scale; measured 2-4e-6 in every arithmetic but bf16x3 (1.4e-5)
 LINE_LIMIT = 4096            # bytes of the ONE stdout line (round 3's 20 KB line was not parsed by the driver)
+TIMED_SEED = 1234            # generators re-seeded in front of the timed steps: their jitter draws depend on the step count alone
+DUMP_SAMPLE_ABOVE = 1 << 23  # --dump-outputs: an output with more elements is written as a fixed, seeded sample of DUMP_SAMPLE elements
+DUMP_SAMPLE = 1 << 22
+DUMP_LIMIT = 64 << 20        # bytes of all dumped arrays together
 
 
 # ---- launcher ----------------------------------------------------------------------------------------------------------------
@@ -315,6 +321,29 @@ def check_parity(render, device, tol=PARITY_TOL):
     return rec, (img, seg)
 
 
+def block_sizes(steps, blocks):
+    """`steps` timed steps split into min(blocks, steps) blocks whose sizes differ by at most one."""
+    b = max(1, min(blocks, steps))
+    return [steps // b + (1 if i < steps % b else 0) for i in range(b)]
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy in float32.  Outputs with more than DUMP_SAMPLE_ABOVE elements are written as the DUMP_SAMPLE
+    elements at fixed, seeded flat positions (ascending), the same in every run of the same shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    total, written = 0, {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_SAMPLE_ABOVE:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, DUMP_SAMPLE, replace=False))      # RandomState: a frozen stream
+            a, name = a.reshape(-1)[idx], name + '_sample'
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, f'--dump-outputs: {total} bytes'
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def _finite(o):
     """NaN / +-inf -> None (strict JSON has neither), recursively."""
     if isinstance(o, float):
@@ -451,9 +480,12 @@ ARITH_DTYPE = {'fp32': 'f32', 'f16x3': 'f32 (3x3 convolutions: 2-way fp16 split 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=10)
+    ap.add_argument('--steps', type=int, default=10, help='timed steps in all (split into --blocks blocks)')
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--blocks', type=int, default=5, help='timed blocks of --steps steps each; the median block is reported')
+    ap.add_argument('--blocks', type=int, default=5, help='the --steps timed steps are split into this many blocks (at most one per step); '
+                                                          'the median block is reported')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed step's outputs (image, seg logits, uint8 frames) to DIR/<name>.npy, "
+                                                         'float32 (seg as a fixed sample); the timed steps\' inputs are the same in every run')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-roofline-extra', action='store_true')
@@ -470,6 +502,9 @@ def main():
     ap.add_argument('--dry-run-cpu', action='store_true',
                     help='launcher / protocol self-test without a GPU: tiny generator on CPU tensors, gloo backend (tests/test_bench_launcher_cpu.py)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    sizes = block_sizes(args.steps, args.blocks)
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher, one rank per GPU
@@ -547,7 +582,7 @@ def main():
     # `--blocking-gather` restores the synchronous gather on the compute stream (measured next to it as `ms_per_step_blocking_gather`).
     # `checksums`: every buffer sent / received in the timed blocks gets a position-weighted 64-bit checksum (sums of received buffers on a side
     # stream); after the timed region rank 0 compares what arrived from every rank in EVERY timed step with what that rank says it sent
-    total_subs = max(1, args.blocks) * args.steps
+    total_subs = args.steps
     og = dr.OverlappedFrameGather([BATCH, res, 2 * res, 3], device, rank, world, checksums=total_subs + 8) if dist else None
 
     def latents(i, r=None):
@@ -561,6 +596,8 @@ def main():
         z = z.float().pin_memory()
         return z if graphed is not None else z.to(device, non_blocking=True)
 
+    last = {}
+
     def step(i, blocking=False, jitter=None):
         img, seg = render(latents(i), cond, cams, jitter)
         with torch.no_grad():
@@ -571,6 +608,7 @@ def main():
                 frames = dr.frames_u8(img, seg, palette)
                 if dist:
                     dist.gather(frames, gathered, dst=0)
+        last.update(image=img, seg=seg, frames=frames)      # references only (the graph's static buffers): read before the next step
         return frames
 
     def barrier():
@@ -585,23 +623,25 @@ def main():
 
     for i in range(args.warmup):
         step(i, blocking=args.blocking_gather)
-    block_s, rank_s = [], []
+    block_s, rank_s = [], []          # seconds per step of each timed block (MAX over ranks / this rank's own)
     done = args.warmup
     first_timed_sub = og.submitted if (og is not None and not args.blocking_gather) else None
-    for _b in range(max(1, args.blocks)):
+    torch.manual_seed(TIMED_SEED)
+    for n in sizes:
         barrier()
         t0 = time.perf_counter()
-        for i in range(args.steps):
+        for i in range(n):
             step(done + i, blocking=args.blocking_gather)
         barrier()
-        dt = time.perf_counter() - t0
-        done += args.steps
+        dt = (time.perf_counter() - t0) / n
+        done += n
         mine = dt
         if dist:
             tt = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt)
         block_s.append(dt); rank_s.append(mine)
+    dumped = dump_outputs(args.dump_outputs, last) if (args.dump_outputs and rank == 0) else None
 
     # N > 1 extras: per-rank frame rates (own clock, median block) and the cost of the RCCL gather alone
     per_rank, gather_ms, blocking_ms, gather_check = None, None, None, None
@@ -614,7 +654,7 @@ def main():
         if rank == 0:
             sums_bad = int((og.received_checksums(first_timed_sub, total_subs) != torch.stack(every, dim=1)).sum())
     if dist:
-        mine = torch.tensor([BATCH * args.steps / sorted(rank_s)[len(rank_s) // 2]], device=device, dtype=torch.float64)
+        mine = torch.tensor([BATCH / sorted(rank_s)[len(rank_s) // 2]], device=device, dtype=torch.float64)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = [float(t) for t in allr]
@@ -664,33 +704,35 @@ def main():
 
     if rank == 0:
         order = sorted(block_s)
-        med = order[len(order) // 2]
-        frames_block = BATCH * world * args.steps
+        med = order[len(order) // 2]          # seconds per step of the median block
+        frames_step = BATCH * world
         r3 = lambda v, nd=3: None if v is None else round(float(v), nd)
         # `out` is the ONE stdout line (compact); `full` collects everything else for gpurun_out/bench_full.json + stderr
         out = {
-            'metric': '512x512 RGB+seg frames/s @96 depth samples (whole job)', 'value': r3(frames_block / med, 2), 'unit': 'frames/s',
-            'value_fp32_exact': r3(frames_block / med, 2) if arith == 'fp32' else None,     # else filled from the fp32 leg of the sweep below
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': r3(med / args.steps * 1e3, 4),
+            'metric': '512x512 RGB+seg frames/s @96 depth samples (whole job)', 'value': r3(frames_step / med, 2), 'unit': 'frames/s',
+            'value_fp32_exact': r3(frames_step / med, 2) if arith == 'fp32' else None,     # else filled from the fp32 leg of the sweep below
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': r3(med * 1e3, 4),
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': ARITH_DTYPE_SHORT[arith], 'data': 'synthetic',
             'config': {'workload': 'BASELINE config 2: random-init ide3d-ffhq-64-512, G.mapping + G.synthesis (64 render -> 512, 96 samples, RGB + 19-class seg) '
                                    '+ uint8 frames, batch 4 seeds per GPU',
                        'global_batch': BATCH * world, 'parallelism': f'dp{world}', 'conv_arithmetic': arith,
                        'conv_arithmetic_is_library_default': bool(args.conv_arith == 'default')},
-            'timing': {'blocks': len(block_s), 'reported': 'median block', 'ms_per_step_min': r3(order[0] / args.steps * 1e3, 4),
-                       'ms_per_step_max': r3(order[-1] / args.steps * 1e3, 4)},
-            'conv_tflops': r3(conv_flops(spec, BATCH) * args.steps / med / 1e12, 1),
+            'timing': {'blocks': len(block_s), 'block_steps': sizes, 'reported': 'median block', 'ms_per_step_min': r3(order[0] * 1e3, 4),
+                       'ms_per_step_max': r3(order[-1] * 1e3, 4)},
+            'conv_tflops': r3(conv_flops(spec, BATCH) / med / 1e12, 1),
             'hip_graph': graphed is not None,
         }
         full = {'dtype_long': ARITH_DTYPE[arith], 'native_launches': dict(hip_plugin.CALLS) if hip_plugin else {},
-                'timing_blocks_s': block_s, 'frames_per_s_per_gpu': frames_block / med / world}
+                'timing_s_per_step_by_block': block_s, 'frames_per_s_per_gpu': BATCH / med}
+        if dumped is not None:
+            full['dumped_outputs'] = {'dir': args.dump_outputs, 'shapes': dumped}
         if dist:
             out['rccl_ranks'] = world
             out['frames_per_s_by_rank'] = [r3(v, 1) for v in per_rank]
             out['gather_ms'] = r3(gather_ms)
             out['gather_overlap'] = {'mode': 'blocking (split arithmetic: DESIGN.md 4.2)' if forced_blocking else
                                              'blocking' if args.blocking_gather else 'async double-buffered',
-                                     'ms_per_step_overlapped': r3(med / args.steps * 1e3, 4), 'ms_per_step_blocking_gather': r3(blocking_ms, 4),
+                                     'ms_per_step_overlapped': r3(med * 1e3, 4), 'ms_per_step_blocking_gather': r3(blocking_ms, 4),
                                      'gather_ms_alone': r3(gather_ms)}
             out['gather_check'] = gather_check
             out['gather_bytes_per_rank_per_step'] = BATCH * res * 2 * res * 3
@@ -715,7 +757,7 @@ def main():
         if not cpu and world == 1 and not args.no_arith_sweep:
             # the same step with the other arithmetics of the 3x3 layers: one captured graph each, the headline's timing protocol, parity against
             # the same golden frames (nothing else changes: every other kernel is fp32 in all of them)
-            sweep_full = {arith: {'frames_per_s': frames_block / med, 'ms_per_step': med / args.steps * 1e3, 'blocks': len(block_s), 'steps_per_block': args.steps,
+            sweep_full = {arith: {'frames_per_s': frames_step / med, 'ms_per_step': med * 1e3, 'blocks': len(block_s), 'block_steps': sizes,
                                   'reported': 'median block', 'parity_ok': out.get('parity_ok'), 'parity_max_rel_err': (full.get('parity') or {}).get('max_rel_err')}}
             keep = graphed
             for other in ('fp32', 'bf16x6', 'f16x3', 'bf16x3'):
@@ -727,13 +769,13 @@ def main():
                     for i in range(args.warmup):
                         step(done + i)
                     ts = []
-                    for _b in range(max(1, args.blocks)):          # the protocol of the headline: K steps between synchronisations, median block
+                    for n in sizes:          # the protocol of the headline: the same blocks between synchronisations, median block
                         sync(); t0 = time.perf_counter()
-                        for i in range(args.steps):
+                        for i in range(n):
                             step(done + i)
-                        sync(); ts.append(time.perf_counter() - t0)
+                        sync(); ts.append((time.perf_counter() - t0) / n)
                     med_o = sorted(ts)[len(ts) // 2]
-                    rec = {'frames_per_s': BATCH * args.steps / med_o, 'ms_per_step': med_o / args.steps * 1e3, 'blocks': len(ts), 'steps_per_block': args.steps,
+                    rec = {'frames_per_s': BATCH / med_o, 'ms_per_step': med_o * 1e3, 'blocks': len(ts), 'block_steps': sizes,
                            'reported': 'median block'}
                     if not args.no_parity:
                         par = check_parity(render, device)[0]
@@ -795,7 +837,7 @@ def main():
                     busy_live, busy_why = (None, 'disabled (--no-live-pmc)') if args.no_live_pmc else live_mfma_busy(kname, arith)
                     full['roofline_step_pmc'] = {'mfma_busy_frac_live': busy_live, 'source': busy_why, 'committed': busy}
                     out['roofline_step'] = {'kernel': kname.replace(', ', ',') + ' (3x3 stride-1, 64^2..256^2 layers)', 'bound': f'mfma:{arith}', 'launches_per_step': 4,
-                                            'us_per_step': r3(us, 1), 'share_of_step': r3(us / (med / args.steps * 1e6), 3), 'achieved': r3(fl / us / 1e6, 1), 'peak': r3(peak, 1),
+                                            'us_per_step': r3(us, 1), 'share_of_step': r3(us / (med * 1e6), 3), 'achieved': r3(fl / us / 1e6, 1), 'peak': r3(peak, 1),
                                             'unit': 'TFLOP/s', 'frac': r3(fl / us / 1e6 / peak, 3),
                                             'mfma_busy_frac': (r3(busy_live, 3) if busy_live is not None else None if busy is None else busy['mfma_busy_frac']),
                                             'mfma_busy_measured_in_this_run': busy_live is not None}

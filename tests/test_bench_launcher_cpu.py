@@ -8,8 +8,10 @@ import subprocess
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ['--steps', '1', '--warmup', '1', '--blocks', '3', '--dry-run-cpu']
+ARGS = ['--steps', '3', '--warmup', '1', '--blocks', '3', '--dry-run-cpu']
 
 
 def _one_json_line(stdout):
@@ -24,7 +26,7 @@ def test_launch_ranks_function_two_gloo_ranks():
     rc, out = bench.launch_ranks(2, ['--gpus', '2'] + ARGS, capture=True)
     assert rc == 0
     rec = _one_json_line(out)
-    assert rec['n_gpus'] == 2 and rec['rccl_ranks'] == 2 and rec['steps'] == 1 and rec['warmup'] == 1
+    assert rec['n_gpus'] == 2 and rec['rccl_ranks'] == 2 and rec['steps'] == 3 and rec['warmup'] == 1
     assert rec['config']['global_batch'] == 8 and rec['scaling'] == 'weak'
     assert len(rec['frames_per_s_by_rank']) == 2 and all(v > 0 for v in rec['frames_per_s_by_rank'])
     assert rec['gather_ms'] > 0 and rec['timing']['blocks'] == 3
@@ -32,7 +34,7 @@ def test_launch_ranks_function_two_gloo_ranks():
     assert 'DRY RUN' in rec['metric']
     # the double-buffered asynchronous gather: contents and order checked by rank 0 against its own render of every rank's inputs
     assert rec['gather_check']['ok'] is True and rec['gather_check']['steps'] == 3 and rec['gather_check']['ranks'] == 2
-    assert rec['gather_check']['checksum_mismatches'] == 0 and rec['gather_check']['checksummed_steps'] == rec['steps'] * rec['timing']['blocks']      # every timed step
+    assert rec['gather_check']['checksum_mismatches'] == 0 and rec['gather_check']['checksummed_steps'] == rec['steps']      # every timed step
     ov = rec['gather_overlap']
     assert ov['ms_per_step_overlapped'] > 0 and ov['ms_per_step_blocking_gather'] > 0 and ov['gather_ms_alone'] > 0
 
@@ -60,6 +62,37 @@ def test_single_process_dry_run():
     assert res.returncode == 0
     rec = _one_json_line(res.stdout)
     assert rec['n_gpus'] == 1 and 'rccl_ranks' not in rec and rec['timing']['blocks'] == 3
+
+
+def test_steps_and_dump_outputs(tmp_path):
+    """`--steps K` is the number of timed steps, however the blocks divide it; `--dump-outputs` writes the last timed step's outputs as float32
+    .npy files, identical in two runs with the same arguments."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f'run{run}'
+        res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '1', '--blocks', '2',
+                              '--dry-run-cpu', '--dump-outputs', str(d)], stdout=subprocess.PIPE, text=True, timeout=600)
+        assert res.returncode == 0
+        rec = _one_json_line(res.stdout)
+        assert rec['steps'] == 5 and rec['timing']['block_steps'] == [3, 2] and rec['ms_per_step'] > 0
+        dumps.append({f.name: np.load(f) for f in sorted(d.glob('*.npy'))})
+    assert sorted(dumps[0]) == ['frames.npy', 'image.npy', 'seg.npy']
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, dumps[1][name]), name
+    assert dumps[0]['frames.npy'].shape[-1] == 3 and dumps[0]['frames.npy'].shape[0] == dumps[0]['image.npy'].shape[0] == 4
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    import torch
+    big = torch.arange(bench.DUMP_SAMPLE_ABOVE + 1, dtype=torch.float64)
+    shapes = bench.dump_outputs(str(tmp_path), {'small': torch.ones(2, 3), 'big': big})
+    assert shapes == {'small': [2, 3], 'big_sample': [bench.DUMP_SAMPLE]}
+    s = np.load(tmp_path / 'big_sample.npy')
+    assert s.dtype == np.float32 and np.all(np.diff(s) > 0) and s[-1] <= bench.DUMP_SAMPLE_ABOVE      # distinct positions, ascending
+    bench.dump_outputs(str(tmp_path / 'again'), {'big': big})
+    assert np.array_equal(s, np.load(tmp_path / 'again' / 'big_sample.npy'))          # the same positions in every call
 
 
 def _strict(line):
@@ -120,14 +153,17 @@ def test_compact_line_of_a_full_size_gpu_record():
 def test_live_pmc_passes_degrade_to_a_reason():
     """`bench.live_pmc` (the rocprofv3 counter passes bench.py runs itself for `roofline.traffic` / `roofline_step.mfma_busy_frac`) never raises and
     never hangs the bench: without a GPU, without the profiler or without rows for the kernel it returns (None, reason) and the committed figure is
-    quoted with `traffic_measured_in_this_run: false`."""
+    quoted with `traffic_measured_in_this_run: false`.  Where a GPU is visible the two passes may measure: a positive figure and its source."""
     sys.path.insert(0, ROOT)
     import bench
+    import torch
     t0 = time.time()
     vals, why = bench.live_pmc([('FETCH_SIZE',)], ['-c', 'print(1)'], 'no_such_kernel', timeout_s=60)
     assert vals is None and isinstance(why, str) and why
-    traffic, why = bench.live_gather_traffic()
-    assert traffic is None and isinstance(why, str) and why
-    busy, why = bench.live_mfma_busy('modconv_split_kernel<0, 1, 16, 3, 2, 8, 0>', 'bf16x6')
-    assert busy is None and isinstance(why, str) and why
+    for value, why in (bench.live_gather_traffic(), bench.live_mfma_busy('modconv_split_kernel<0, 1, 16, 3, 2, 8, 0>', 'bf16x6')):
+        assert isinstance(why, str) and why
+        if torch.cuda.is_available():
+            assert value is None or value > 0, value
+        else:
+            assert value is None, value
     assert time.time() - t0 < 170
