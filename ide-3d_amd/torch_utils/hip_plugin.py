@@ -826,11 +826,30 @@ class VolumeRenderPlugin:
         p.feat_ch = nout_tex
 
     @staticmethod
+    def check_render_shapes(n, rays_per_img, steps, rays_d_cam, z_lin, cam2world, jitter=None, sigma_noise=None):
+        """Host-only shape rules of `render_rays`, checked before anything is launched.  The kernel reads rays_d_cam[r * 3 + k],
+        z_lin[s], cam2world[image * 16 + k] and jitter / sigma_noise[ray * steps + s] for every ray of all n images: a shorter
+        buffer would be read past its end."""
+        _require(rays_d_cam.numel() == rays_per_img * 3, f'render_rays: rays_d_cam must be [{rays_per_img}, 3], got {list(rays_d_cam.shape)}')
+        _require(z_lin.numel() == steps, f'render_rays: z_lin must hold {steps} depths, got {list(z_lin.shape)}')
+        _require(cam2world.numel() == n * 16,
+                 f'render_rays: cam2world must be [{n}, 4, 4] (one camera per image), got {list(cam2world.shape)}')
+        for name, t in (('jitter', jitter), ('sigma_noise', sigma_noise)):
+            if t is not None:
+                _require(t.numel() == n * rays_per_img * steps,
+                         f'render_rays: {name} must be [{n}, {rays_per_img}, {steps}] (images, rays, steps), got {list(t.shape)}')
+
+    @staticmethod
     def render_rays(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
                     clamp_mode, last_back, white_back, max_depth):
         dev = tex_planes.device
+        _require(tex_planes.ndim == 4, 'render_rays: tri-planes must be [n, 3*C, H, W]')
+        VolumeRenderPlugin.check_render_shapes(tex_planes.shape[0], rays_d_cam.shape[0], z_lin.shape[0], rays_d_cam, z_lin, cam2world,
+                                               jitter, sigma_noise)
         for t in (rays_d_cam, z_lin, cam2world, tex_planes, geo_planes):
             _require(t.is_cuda and t.dtype == torch.float32, 'render_rays: float32 CUDA tensors required')
+        for t in (jitter, sigma_noise):
+            _require(t is None or (t.dtype == torch.float32 and t.device == dev), 'render_rays: jitter / sigma_noise must be float32 next to the tri-planes')
         rays_d_cam, z_lin = rays_d_cam.contiguous(), z_lin.contiguous()
         cam2world = cam2world.reshape(-1, 16).contiguous()
         p = _RenderParams()

@@ -178,11 +178,14 @@ class TriplaneRenderer(torch.nn.Module):
         pts = shape_extraction.lattice_points(n, voxel_size, corner, scale, first, count, img_v.device)
         return self.sample_voxel(img_v, seg_v, pts.unsqueeze(0).expand(img_v.shape[0], -1, -1), sigma_only=True)
 
-    @staticmethod
-    def _hip_ok(*tensors):
+    def _hip_ok(self, *tensors):
+        """The fused kernels take raw pointers (no autograd): only for fp32 CUDA inputs when nothing they read, the decoder's parameters
+        included, needs a gradient."""
         if any(t.device.type != 'cuda' or t.dtype != torch.float32 for t in tensors):
             return False
-        return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
+        if not torch.is_grad_enabled():
+            return True
+        return not (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.decoder.parameters()))
 
     # -- full rendering -----------------------------------------------------------------------------------
     def forward(self, img_v, seg_v, cam2world, fov=None, num_steps=None, ray_start=None, ray_end=None, img_size=None,
@@ -211,6 +214,9 @@ class TriplaneRenderer(torch.nn.Module):
             jitter = None
         if sigma_noise is None and nerf_noise:
             sigma_noise = torch.randn([n, rays, steps], device=device) * nerf_noise
+        for name, t in (('jitter', jitter), ('sigma_noise', sigma_noise)):
+            if t is not None and tuple(t.shape) != (n, rays, steps):
+                raise ValueError(f'TriplaneRenderer: {name} must be [images, rays, steps] = [{n}, {rays}, {steps}] for this call, got {list(t.shape)}')
 
         hierarchical = sp.hierarchical if hierarchical is None else hierarchical
         if not hierarchical and self._hip_ok(img_v, seg_v, cam2world):

@@ -150,8 +150,9 @@ def sample_voxel(sd, spec, img_v, seg_v, pts, ops=precise_ops):
 
 
 def render(sd, spec, img_v, seg_v, cam2world, jitter=None, sigma_noise=None, ops=precise_ops, num_steps=None,
-           hierarchical=False, importance_u=None):
+           hierarchical=False, importance_u=None, white_back=False, max_depth=None):
     """-> features [N, feat+seg, R, R], depth [N, 1, R, R], weight sum [N, 1, R, R].
+    white_back / max_depth: passed to the final `composite` (fancy_integration's background fill of features / depth).
     hierarchical: SURVEY.md 3.5 step 6 — the first pass's weights (+1e-5, end samples dropped) define a pdf over the
     depth mid-points, `sample_pdf` draws `steps` more depths per ray with `importance_u` [N*R*R, steps], those points
     are queried, both sets are merged by depth and integrated together."""
@@ -180,7 +181,8 @@ def render(sd, spec, img_v, seg_v, cam2world, jitter=None, sigma_noise=None, ops
         z_vals, order = torch.sort(torch.cat([z_fine, z_vals], 2), dim=2)
         out = torch.gather(torch.cat([out_f, out], 2), 2, order.expand(-1, -1, -1, out.shape[-1]))
         noise = None
-    feat, depth, weights = ops.composite(out, d_cam, z_vals, noise=noise, clamp_mode=spec.clamp_mode)
+    feat, depth, weights = ops.composite(out, d_cam, z_vals, noise=noise, clamp_mode=spec.clamp_mode, white_back=white_back,
+                                         max_depth=max_depth)
     feat = feat.permute(0, 2, 1).reshape(n, -1, size, size)
     depth = depth.permute(0, 2, 1).reshape(n, 1, size, size)
     wsum = weights.sum(2).permute(0, 2, 1).reshape(n, 1, size, size)

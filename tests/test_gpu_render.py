@@ -236,7 +236,14 @@ def test_sample_voxel_tiles_that_straddle_images(gpu_device, n, m):
     g = torch.Generator().manual_seed(m)
     tex = (torch.randn(n, 96, 64, 64, generator=g) * 0.7).to(gpu_device).contiguous(memory_format=torch.channels_last)
     geo = (torch.randn(n, 96, 64, 64, generator=g) * 0.7).to(gpu_device).contiguous(memory_format=torch.channels_last)
-    pts = (torch.rand(n, m, 3, generator=g) * 2.2 - 1.1).to(gpu_device)             # some points outside the planes (zero padding)
+    pts = torch.rand(n, m, 3, generator=g) * 2.4 - 1.2                                 # some points outside the planes (zero padding)
+    # exact texel centres ((2i + 1) / 64 - 1: one tap of weight 1) and the plane borders +-1 (half a texel from the last centre)
+    centre = lambda i: (2 * i + 1) / 64 - 1
+    special = torch.tensor([[-1., -1., -1.], [1., 1., 1.], [1., -1., centre(17)], [centre(0), centre(63), centre(31)], [-1., centre(40), 1.],
+                            [centre(5), centre(6), centre(7)], [centre(63), 1., -1.], [centre(62), centre(1), centre(32)]])
+    k = min(len(special), n * m)
+    pts.view(-1, 3)[:k] = special[:k]
+    pts = pts.to(gpu_device)
     before = _calls('sample_voxel')
     with torch.no_grad():
         full = R.sample_voxel(tex, geo, pts)
@@ -249,6 +256,20 @@ def test_sample_voxel_tiles_that_straddle_images(gpu_device, n, m):
     assert torch.equal(full, one), 'batched rows differ from per-image rows'
     assert_close(sig, one[:, -1], rtol=1e-4, atol=1e-5)          # the sigma-only branch sums row 0 of the second layer on the VALU
     assert torch.equal(lat, lat1), 'batched lattice densities differ from per-image ones'
+    # rows and densities against the float64 reference, in both C=32 forms (fp32 MLP and bf16x6 MLP)
+    from torch_utils import hip_plugin
+    sd = {'synthesis.renderer.' + k: v.detach().cpu() for k, v in R.state_dict().items()}
+    want = ogen.sample_voxel(sd, ospec.Spec(), tex.cpu(), geo.cpu(), pts.cpu(), oracle_ops)
+    for arith in ('fp32', 'bf16x6'):
+        try:
+            hip_plugin.conv_arithmetic(arith)
+            with torch.no_grad():
+                got, got_sig = R.sample_voxel(tex, geo, pts), R.sample_voxel(tex, geo, pts, sigma_only=True)
+        finally:
+            hip_plugin.conv_arithmetic('default')
+        _rel(got, want, 2e-4, f'sample_voxel ({arith}) vs float64 reference')
+        _rel(got_sig, want[:, -1], 2e-4, f'sample_voxel sigma_only ({arith}) vs float64 reference')
+    assert _calls('sample_voxel') - before == 2 + n + 4
 
 
 def test_video_sweep_gpu_vs_cpu(golden):

@@ -494,3 +494,45 @@ def test_face_parser_state_dict_layout_and_cpu_path(golden):
     # parsing_img / face_parsing shapes (dnnlib/seg_tools.py:100-123): any input size -> one-hot at 512 x 512
     img, onehot = face_parsing.parsing_img(lambda x: (logits,), t(cases[1][1]['in_x']), return_mask=False)
     assert onehot.shape == (1, 1, 96, 64)
+
+
+def test_render_rays_shape_rules_before_launch(monkeypatch):
+    """`render_rays` checks every buffer the kernel indexes per image / ray / sample against n, rays and steps on the host, before the
+    library is even loaded: a jitter recorded at another step count or one camera for a batch of four is refused, never read past."""
+    from torch_utils import hip_plugin
+    from training import triplane
+    vrp = hip_plugin.VolumeRenderPlugin
+    n, R, S = 4, 225, 17
+    d, z, cam, jit, noise = torch.zeros(R, 3), torch.zeros(S), torch.zeros(n, 4, 4), torch.zeros(n, R, S), torch.zeros(n, R, S)
+    vrp.check_render_shapes(n, R, S, d, z, cam, jit, noise)
+    vrp.check_render_shapes(n, R, S, d, z, cam.reshape(n, 16))
+    bad = [('cam2world', dict(cam2world=torch.zeros(1, 4, 4))), ('cam2world', dict(cam2world=torch.zeros(n + 1, 4, 4))),
+           ('jitter', dict(jitter=torch.zeros(n, R, 96))), ('jitter', dict(jitter=torch.zeros(1, R, S))),
+           ('sigma_noise', dict(sigma_noise=torch.zeros(n, R, S - 1))), ('sigma_noise', dict(sigma_noise=torch.zeros(n, R + 1, S))),
+           ('rays_d_cam', dict(rays_d_cam=torch.zeros(R, 2))), ('z_lin', dict(z_lin=torch.zeros(S + 1)))]
+    for what, kw in bad:
+        args = dict(rays_d_cam=d, z_lin=z, cam2world=cam, jitter=jit, sigma_noise=noise)
+        args.update(kw)
+        with pytest.raises(RuntimeError, match=what):
+            vrp.check_render_shapes(n, R, S, args['rays_d_cam'], args['z_lin'], args['cam2world'], args['jitter'], args['sigma_noise'])
+    # render_rays applies the rules first: nothing is loaded, let alone launched, for a mis-shaped call
+    def no_load():
+        raise AssertionError('render_rays reached the library with mis-shaped inputs')
+    monkeypatch.setattr(hip_plugin, 'load', no_load)
+    planes = torch.zeros(n, 96, 8, 8)
+    for what, kw in bad:
+        args = dict(rays_d_cam=d, z_lin=z, cam2world=cam, jitter=jit, sigma_noise=noise)
+        args.update(kw)
+        with pytest.raises(RuntimeError, match='render_rays: '):
+            vrp.render_rays(args['rays_d_cam'], args['z_lin'], args['cam2world'], args['jitter'], args['sigma_noise'], planes, planes, {},
+                            0, False, False, None)
+    # TriplaneRenderer.forward: caller-supplied draws of the wrong shape are refused with the expected shape in the message
+    Rn = triplane.TriplaneRenderer(triplane.tiny_spec()).eval()
+    tex = torch.randn(2, 48, 16, 16)
+    cam2 = torch.cat([triplane.camera_label(0.1), triplane.camera_label(-0.1)])[:, :16].reshape(-1, 4, 4)
+    with torch.no_grad():
+        Rn(tex, tex, cam2, img_size=4, num_steps=6, jitter=torch.rand(2, 16, 6), sigma_noise=torch.zeros(2, 16, 6))
+        for kw in (dict(jitter=torch.rand(2, 16, 12)), dict(jitter=torch.rand(1, 16, 6)), dict(jitter=torch.rand(2, 16, 6, 1)),
+                   dict(jitter=False, sigma_noise=torch.zeros(2, 16, 5))):
+            with pytest.raises(ValueError, match=r'must be \[images, rays, steps\] = \[2, 16, 6\]'):
+                Rn(tex, tex, cam2, img_size=4, num_steps=6, **kw)
