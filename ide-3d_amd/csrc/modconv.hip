@@ -725,12 +725,162 @@ template <int PENDING>
 __device__ __forceinline__ void lds_wait128(u32x4& first) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(first) : "n"(PENDING)); }
 __device__ __forceinline__ void lds_pin128(u32x4& v) { asm volatile("" : "+v"(v)); }
 
+// Dual heads fused behind a 3x3 layer (ide3d_modconv2d_heads).  Where the layer's workgroup holds ALL cout channels of its pixels (one M
+// block, no split-K, one image per tile), the 1x1 heads that follow it (toRGB + toSeg: per-image folded weights, bias, clamp) need nothing
+// but that tile: the finished activations go to the LDS the K loop has finished with ([cout][pixels] fp32, 128 KB at 128 x 256 and
+// 64 x 512), are optionally stored as the layer's output, and are the B operand of the heads' bf16x6 GEMM.  The products, their order per
+// accumulator and the finish are those of head_resident_kernel (bias_first) or head_split_kernel (bias after the sum), so the heads come out
+// bit-equal to the two-launch sequence; the activations are finished by the expression of modconv_finish.
+struct HeadEpi {
+    const u32x4* w;          // packed head weights [n][cin / 16][PARTS][k half][MT * 32][8] (head_pack_split_kernel)
+    const float* bias;       // [rows] or null
+    float* y;                // [n][rows][h][w]
+    int rows;                // real head outputs (<= MT * 32)
+    float clamp;             // < 0: none
+    int store_x;             // 0: the layer's own output is not written
+    int bias_first;          // 1: accumulators start from the bias (head_resident_kernel), 0: bias added to the sum (head_split_kernel)
+};
+template <int PH, int PW, int NWV, int MTW, int NTW, int BM, int MT, int PARTS, int SCRATCH>
+__device__ __forceinline__ void split_heads_finish(const ide3d_modconv_params& p, const HeadEpi& he, f32x16 (&acc)[1][MTW][NTW], float* smem,
+                                                   int n0, int y0, int x0, int wm, int wn, int lp) {
+    // TP: row pitch of the tile.  +4 floats puts the two k halves of a head B read (rows 8 apart) on disjoint halves of the 64 banks
+    // (the epilogue's writes, rows 4 apart, keep a 2-way conflict on half of the banks: they happen once, the reads once per row group)
+    constexpr int NT = 64 * NWV, BN = PH * PW, TP = BN + 4, ROWS = MT * 32, CCH = BM / 16, A_UNITS = PARTS * 2 * ROWS;
+    static_assert(BM * TP + 2 * BM + ROWS <= SCRATCH, "activation tile + coefficients must fit the loop's LDS");
+    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l32 = lane & 31;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int hw = p.h * p.w_;
+    float* const s_t = smem;                       // [BM][TP] finished activations
+    float* const s_dm = smem + BM * TP;            // [BM]
+    float* const s_bi = s_dm + BM;                 // [BM]
+    float* const s_hb = s_bi + BM;                 // [ROWS] head bias
+    for (int e = tid; e < BM; e += NT) {
+        s_dm[e] = (p.dcoefs && e < p.cout) ? p.dcoefs[(int64_t)n0 * p.cout + e] : 1.f;
+        s_bi[e] = (p.bias && e < p.cout) ? p.bias[e] : 0.f;
+    }
+    for (int e = tid; e < ROWS; e += NT) s_hb[e] = (he.bias && e < he.rows) ? he.bias[e] : 0.f;
+    __syncthreads();
+    // (a) the layer's epilogue, as in modconv_finish, into the tile
+    const float e_alpha = (p.act == 3) ? p.alpha : 1.f, e_gain = p.gain;
+    const float e_clamp = (p.clamp >= 0.f) ? p.clamp : __builtin_inff();
+    const float e_nstr = p.noise ? p.noise_strength : 0.f;
+    auto finish = [&](float v, float d, float nz, float bb) {
+        v *= d; v += nz; v += bb;
+        v = (v > 0.f) ? v : v * e_alpha;
+        v *= e_gain;
+        return fminf(fmaxf(v, -e_clamp), e_clamp);
+    };
+#pragma unroll
+    for (int j = 0; j < NTW; ++j) {
+        const int pix = (wn * NTW + j) * 32 + lp;
+        const int gy = y0 + pix / PW, gx = x0 + pix % PW;
+        const float nz = (e_nstr != 0.f) ? p.noise[gy * p.w_ + gx] * e_nstr : 0.f;
+#pragma unroll
+        for (int i = 0; i < MTW; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rl = (wm * MTW + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                s_t[rl * TP + pix] = finish(acc[0][i][j][r], s_dm[rl], nz, s_bi[rl]);
+            }
+    }
+    __syncthreads();
+    // (b) the layer's output: 16-byte runs of one channel row (stored with 4-byte alignment, like modconv_finish: the ABI asks no more of y)
+    typedef float f32x4a __attribute__((ext_vector_type(4)));
+    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+    if (he.store_x) {
+        float* const yimg = p.y + (int64_t)n0 * p.cout * hw;
+#pragma unroll 4
+        for (int e = tid; e < BM * BN / 4; e += NT) {
+            const int rl = e / (BN / 4), pix = (e % (BN / 4)) * 4;
+            const int gy = y0 + pix / PW, gx = x0 + pix % PW;
+            *reinterpret_cast<f32x4u*>(yimg + (int64_t)rl * hw + gy * p.w_ + gx) = *reinterpret_cast<const f32x4a*>(s_t + rl * TP + pix);
+        }
+    }
+    // (c) the heads: wave = (row group, pixel group); lane = pixel of a 32-pixel tile, 8 channels of its k half (head_resident_kernel's layout)
+    constexpr int NPT = BN / 32;
+    constexpr int RG = (MT % 2 == 0 && NPT / NWV < 2) ? 2 : 1, MTH = MT / RG, PG = NWV / RG, NTH = NPT / PG;
+    static_assert(MTH * RG == MT && NTH * PG == NPT && NTH >= 1, "head work must split evenly over the waves");
+    const int rg = wid / PG, pg = wid % PG;
+    const u32x4* __restrict__ wsrc = he.w + (int64_t)n0 * CCH * A_UNITS + half * ROWS + rg * MTH * 32 + l32;
+    f32x16 hacc[MTH][NTH];
+#pragma unroll
+    for (int m = 0; m < MTH; ++m)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4a b4 = *reinterpret_cast<const f32x4a*>(s_hb + (rg * MTH + m) * 32 + 8 * g + 4 * half);
+#pragma unroll
+            for (int t = 0; t < NTH; ++t)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) hacc[m][t][4 * g + k] = he.bias_first ? b4[k] : 0.f;
+        }
+    // A fragments (L2-resident packed weights) one chunk ahead in registers: the loads of chunk c + 1 fly while chunk c multiplies
+    u32x4 af[2][MTH][PARTS];
+    auto fetch_a = [&](int c, int buf) {
+#pragma unroll
+        for (int m = 0; m < MTH; ++m)
+#pragma unroll
+            for (int q = 0; q < PARTS; ++q) af[buf][m][q] = wsrc[(int64_t)c * A_UNITS + q * 2 * ROWS + m * 32];
+    };
+    fetch_a(0, 0);
+#pragma unroll
+    for (int c = 0; c < CCH; ++c) {
+        const int ab = c & 1;
+        if (c + 1 < CCH) fetch_a(c + 1, ab ^ 1);
+#pragma unroll
+        for (int t = 0; t < NTH; ++t) {
+            const float* xs = s_t + (c * 16 + 8 * half) * TP + (pg * NTH + t) * 32 + l32;
+            u32x4 bfrag[PARTS];
+            {
+                unsigned pk[4][PARTS];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) split_pair<PARTS>(xs[(2 * e) * TP], xs[(2 * e + 1) * TP], pk[e]);
+#pragma unroll
+                for (int q = 0; q < PARTS; ++q) bfrag[q] = u32x4{pk[0][q], pk[1][q], pk[2][q], pk[3][q]};
+            }
+#pragma unroll
+            for (int m = 0; m < MTH; ++m)
+#pragma unroll
+                for (int qa = 0; qa < PARTS; ++qa)
+#pragma unroll
+                    for (int qb = 0; qa + qb < PARTS; ++qb)
+                        hacc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[ab][m][qa]), __builtin_bit_cast(bf16x8, bfrag[qb]), hacc[m][t], 0, 0, 0);
+        }
+    }
+    // (d, f) bias (head_split_kernel's order: the finish of modconv_finish with d = 1, no noise, linear, gain 1) and clamp; lane = pixel
+    const float h_clamp = (he.clamp >= 0.f) ? he.clamp : __builtin_inff();
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) {
+        const int pix = (pg * NTH + t) * 32 + l32;
+        const int gy = y0 + pix / PW, gx = x0 + pix % PW;
+        float* const o = he.y + (int64_t)n0 * he.rows * hw + gy * p.w_ + gx;
+#pragma unroll
+        for (int m = 0; m < MTH; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (rg * MTH + m) * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
+                if (row >= he.rows) continue;
+                float v = hacc[m][t][r];
+                if (he.bias_first) {
+                    v = __builtin_amdgcn_fmed3f(v, -h_clamp, h_clamp);
+                } else {
+                    v *= 1.f; v += 0.f; v += s_hb[row];
+                    v = (v > 0.f) ? v : v * 1.f;
+                    v = fminf(fmaxf(v, -h_clamp), h_clamp);
+                }
+                o[(int64_t)row * hw] = v;
+            }
+    }
+    // exclusive residency: every wave stays until the last head MFMA of the workgroup has retired (its results are stored above)
+    __syncthreads();
+}
+
 // PAR (all-class transposed form): -1 = all four output classes, three stages (kernel rows) per chunk; 0 / 1 = the two column classes of the even /
 // odd output rows only: kernel rows {0, 2} / {1} — out[2 i + ky] += x[i] w[ky] — i.e. two stages / one stage per chunk on twice the positions
-template <int MODE, int BIG, int PH, int PARTS, int WBUF, int NWV, int F16, int TEAMS = 1, int PAR = -1>
+// HEAD_MT > 0: the dual heads (HEAD_MT 32-row tiles) follow in this workgroup (split_heads_finish; `he` describes them)
+template <int MODE, int BIG, int PH, int PARTS, int WBUF, int NWV, int F16, int TEAMS = 1, int PAR = -1, int HEAD_MT = 0>
 __device__ __forceinline__ void modconv_split_tile(const ide3d_modconv_params& p, const u32x4* __restrict__ wp, float* __restrict__ partial,
                                                    const ConvGeom& g, unsigned char* smem, int mb, int tl, int grp, int split, int tiles_x,
-                                                   const float* __restrict__ row_unscale, float* wg_scratch = nullptr) {
+                                                   const float* __restrict__ row_unscale, float* wg_scratch = nullptr, const HeadEpi* he = nullptr) {
     using K = SpCfg<MODE, BIG, PH, PARTS, WBUF, NWV, (PAR >= 0)>;
     static_assert(!F16 || PARTS == 2, "f16x3 = two fp16 pieces per operand");
     static_assert(PAR < 0 || (MODE == MODE_TCONV3A && WBUF == 2 && TEAMS == 1), "row-parity pairs: transposed form, two weight buffers, one team");
@@ -969,6 +1119,10 @@ __device__ __forceinline__ void modconv_split_tile(const ide3d_modconv_params& p
 #ifdef IDE3D_MC_TRACE
     const unsigned long long mc_t1 = __builtin_readcyclecounter();
 #endif
+    if constexpr (HEAD_MT > 0) {
+        static_assert(MODE == MODE_CONV3 && TEAMS == 1 && !F16 && K::NCLS == 1, "fused heads: 3x3 split-bf16 layers");
+        split_heads_finish<PH, PW, K::NWV, K::MTW, K::NTW, K::BM, HEAD_MT, PARTS, K::LDS_BYTES / 4>(p, *he, acc, reinterpret_cast<float*>(smem), n0, y0, x0, wm, wn, lp);
+    } else
     modconv_finish<MODE, 1, PH, PW, K::NWV, K::NCLS, K::MTW, K::NTW, K::BM, K::LDS_BYTES / 4, PAR>(p, partial, g, acc, reinterpret_cast<float*>(smem), mb, n0, y0, x0, split, 0, wm, wn, lp,
                                                                                                 F16 ? row_unscale : nullptr, xus, (TEAMS == 2) ? tid : -1, wg_scratch);
 #ifdef IDE3D_MC_TRACE
@@ -1534,6 +1688,17 @@ modconv_split_kernel(ide3d_modconv_params p, const u32x4* __restrict__ wp, float
     __shared__ __attribute__((aligned(16))) unsigned char sp_smem[K::LDS_BYTES];
     const BlockId b = decode_block(g);
     modconv_split_tile<MODE, BIG, PH, PARTS, WBUF, NWV, F16>(p, wp, partial, g, sp_smem, b.mb, b.tile, b.grp, b.split, g.tiles_x[0], row_unscale);
+}
+
+// The 3x3 layer with the dual heads in its epilogue (ide3d_modconv2d_heads): 8 waves, bf16x6, one M block = cout
+template <int BIG, int PH, int HEAD_MT>
+__global__ void __launch_bounds__(512, 2)
+modconv_split_heads_kernel(ide3d_modconv_params p, const u32x4* __restrict__ wp, ConvGeom g, HeadEpi he) {
+    using K = SpCfg<MODE_CONV3, BIG, PH, 3, 2, 8>;
+    if constexpr (kSpExclusive) asm volatile("" ::: "v255");
+    __shared__ __attribute__((aligned(16))) unsigned char sp_smem[K::LDS_BYTES];
+    const BlockId b = decode_block(g);
+    modconv_split_tile<MODE_CONV3, BIG, PH, 3, 2, 8, 0, 1, -1, HEAD_MT>(p, wp, nullptr, g, sp_smem, b.mb, b.tile, b.grp, b.split, g.tiles_x[0], nullptr, nullptr, &he);
 }
 
 // Row-parity pairs of the all-class transposed 3x3 convolution (round 5).  out[2 i + ky] += x[i] w[ky]: the even output rows take kernel rows 0 and 2,
@@ -2103,6 +2268,20 @@ extern "C" int64_t ide3d_modconv_workspace_bytes(int32_t n, int32_t cin, int32_t
     return bytes;
 }
 
+// the split-bf16 / fp16 loops' weights -> their packed form at the start of the workspace
+static void pack_split_weights(const ide3d_modconv_params& p, const ide3d::ConvPlan& pl, float* wp, hipStream_t st) {
+    using namespace ide3d;
+    const int64_t items = (int64_t)pl.mblocks * pl.cchunks * 9 * 2 * pl.bm;
+    if (pl.f16) {
+        float* const rs = wp + pl.packed_floats;                  // [rows] scale, then [rows] unscale
+        const int rows = pl.mblocks * pl.bm;
+        hipLaunchKernelGGL(modconv_row_scale_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, p.w, p.cout, p.cin * 9, rows, rs, rs + rows);
+        hipLaunchKernelGGL((modconv_pack_split_kernel<2, 1>), dim3(stream_grid(items, 256)), dim3(256), 0, st, p.w, p.cout, p.cin, pl.bm, pl.mblocks, pl.cchunks, reinterpret_cast<u32x4*>(wp), rs);
+    }
+    else if (pl.parts == 2) hipLaunchKernelGGL(modconv_pack_split_kernel<2>, dim3(stream_grid(items, 256)), dim3(256), 0, st, p.w, p.cout, p.cin, pl.bm, pl.mblocks, pl.cchunks, reinterpret_cast<u32x4*>(wp), nullptr);
+    else               hipLaunchKernelGGL(modconv_pack_split_kernel<3>, dim3(stream_grid(items, 256)), dim3(256), 0, st, p.w, p.cout, p.cin, pl.bm, pl.mblocks, pl.cchunks, reinterpret_cast<u32x4*>(wp), nullptr);
+}
+
 extern "C" int ide3d_modconv2d(const ide3d_modconv_params* pp, void* stream) {
     using namespace ide3d;
     IDE3D_CHECK_ARG(pp != nullptr, "modconv2d: null params");
@@ -2152,17 +2331,7 @@ extern "C" int ide3d_modconv2d(const ide3d_modconv_params* pp, void* stream) {
     float* wp = p.workspace;
     float* partial = p.workspace + pl.packed_floats + pl.aux_floats;
     if (pl.parts) {
-        if (!p.weights_packed) {
-            const int64_t items = (int64_t)pl.mblocks * pl.cchunks * 9 * 2 * pl.bm;
-            if (pl.f16) {
-                float* const rs = wp + pl.packed_floats;                  // [rows] scale, then [rows] unscale
-                const int rows = pl.mblocks * pl.bm;
-                hipLaunchKernelGGL(modconv_row_scale_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, p.w, p.cout, p.cin * 9, rows, rs, rs + rows);
-                hipLaunchKernelGGL((modconv_pack_split_kernel<2, 1>), dim3(stream_grid(items, 256)), dim3(256), 0, st, p.w, p.cout, p.cin, pl.bm, pl.mblocks, pl.cchunks, reinterpret_cast<u32x4*>(wp), rs);
-            }
-            else if (pl.parts == 2) hipLaunchKernelGGL(modconv_pack_split_kernel<2>, dim3(stream_grid(items, 256)), dim3(256), 0, st, p.w, p.cout, p.cin, pl.bm, pl.mblocks, pl.cchunks, reinterpret_cast<u32x4*>(wp), nullptr);
-            else               hipLaunchKernelGGL(modconv_pack_split_kernel<3>, dim3(stream_grid(items, 256)), dim3(256), 0, st, p.w, p.cout, p.cin, pl.bm, pl.mblocks, pl.cchunks, reinterpret_cast<u32x4*>(wp), nullptr);
-        }
+        if (!p.weights_packed) pack_split_weights(p, pl, wp, st);
 #define IDE3D_SP_DISPATCH(M) \
         do { if (pl.big == 1) { if (pl.f16) launch_split<M, 1, 2, 1>(p, pl, wp, partial, st); else if (pl.parts == 2) launch_split<M, 1, 2>(p, pl, wp, partial, st); else launch_split<M, 1, 3>(p, pl, wp, partial, st); } \
              else             { if (pl.f16) launch_split<M, 2, 2, 1>(p, pl, wp, partial, st); else if (pl.parts == 2) launch_split<M, 2, 2>(p, pl, wp, partial, st); else launch_split<M, 2, 3>(p, pl, wp, partial, st); } } while (0)
@@ -2203,6 +2372,61 @@ extern "C" int ide3d_modconv2d(const ide3d_modconv_params* pp, void* stream) {
                            pl.oh, pl.ow, (int64_t)(p.y_pitch > 0 ? p.y_pitch : pl.ow), nb_re, nb_ro, nb_ce);
     }
     IDE3D_CHECK_LAUNCH("modconv2d");
+    return IDE3D_OK;
+}
+
+// The layer + heads in one launch where the layer's plan keeps every output channel of a tile in one workgroup (see HeadEpi).  The routing
+// of both halves is the one ide3d_modconv2d would take, so that the fused launch reproduces exactly those two launches.
+extern "C" int ide3d_modconv2d_heads(const ide3d_modconv_params* pp, const ide3d_modconv_head_epilogue* hp, void* stream) {
+    using namespace ide3d;
+    IDE3D_CHECK_ARG(pp != nullptr && hp != nullptr, "modconv2d_heads: null params");
+    const ide3d_modconv_params& p = *pp;
+    const ide3d_modconv_head_epilogue& h = *hp;
+    IDE3D_CHECK_ARG(p.x && p.w && p.workspace && (p.y || h.no_activation_output) && h.w && h.y && h.workspace, "modconv2d_heads: null tensor / workspace pointer");
+    int rc = check_modconv(p);
+    if (rc) return rc;
+    IDE3D_CHECK_ARG(p.act == 1 || p.act == 3, "modconv2d_heads: act must be linear (1) or lrelu (3)");
+    IDE3D_CHECK_ARG(h.rows > 0, "modconv2d_heads: bad head rows");
+    auto no_kernel = [](const char* why) { set_error("modconv2d_heads: %s", why); return IDE3D_ENOKERNEL; };
+    if (knob_live("IDE3D_MODCONV_NO_HEAD_FUSION")) return no_kernel("IDE3D_MODCONV_NO_HEAD_FUSION is set");
+    if (p.k != 3 || p.mode != 0 || p.w_batch_stride != 0 || p.y_amax || p.y_pitch != 0) return no_kernel("not a shared-weight 3x3 layer without side outputs");
+    int arith = resolve_arith(p.arith);
+    if (arith == 16 && !p.x_amax) arith = 6;
+    if (arith != 6) return no_kernel("the fused form exists for bf16x6 only");
+    ConvPlan pl; plan_conv(p, pl, arith);
+    if (pl.parts != 3 || pl.f16 || pl.mode != MODE_CONV3 || pl.pair || pl.g.split_k != 1 || pl.g.mblocks != 1 || pl.bm != p.cout || TIv[pl.tile] != 1)
+        return no_kernel("the layer's plan does not hold all channels of a tile in one workgroup");
+    const bool tile16 = pl.big == 1 && p.cout == 128 && pl.tile != 0 && pl.tile != 4 && pl.tile != 6 && pl.tile != 12 && sp_form(pl).waves == 8;
+    const bool tile32 = pl.big == 2 && p.cout == 64 && pl.tile == 12;
+    const int ph = tile32 ? 32 : 16;
+    if (!(tile16 || tile32) || p.h % ph != 0 || p.w_ % 16 != 0) return no_kernel("no fused instance for this tile");
+    // the heads as ide3d_modconv2d would see them
+    ide3d_modconv_params q{};
+    q.x = p.y; q.w = h.w; q.bias = h.bias; q.y = h.y;
+    q.n = p.n; q.cin = p.cout; q.cout = h.rows; q.h = p.h; q.w_ = p.w_; q.k = 1; q.mode = 0;
+    q.act = 1; q.alpha = 0.f; q.gain = 1.f; q.clamp = h.clamp; q.w_batch_stride = (int64_t)h.rows * p.cout; q.arith = p.arith;
+    const int mt = h.rows <= 32 ? 1 : 6, hcc = p.cout / 16;
+    if (head_small_applies(q) || !head_split_applies(q, resolve_arith(q.arith)) || resolve_arith(q.arith) == 3 || (mt == 6 && !tile16))
+        return no_kernel("the heads do not take the split-bf16 path");
+    IDE3D_CHECK_ARG(p.workspace_bytes >= (pl.packed_floats + pl.aux_floats) * (int64_t)sizeof(float), "modconv2d_heads: workspace too small");
+    IDE3D_CHECK_ARG(h.workspace_bytes >= head_packed_units(p.n, hcc, 3, mt) * 16, "modconv2d_heads: head workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    if (!p.weights_packed) pack_split_weights(p, pl, p.workspace, st);
+    // the head weights keep their own packing launch (head_pack_split_kernel, ~5 us): the packed form is per image and depends on the
+    // styles, so it cannot be cached like the layer's; folding it into ide3d_fold_heads_batch would tie that kernel to this layout
+    u32x4* const hw_packed = reinterpret_cast<u32x4*>(h.workspace);
+    const int64_t items = (int64_t)p.n * hcc * 2 * mt * 32;
+    hipLaunchKernelGGL(head_pack_split_kernel<3>, dim3(stream_grid(items, 256)), dim3(256), 0, st, h.w, q.w_batch_stride, p.n, h.rows, p.cout, mt * 32, hcc, hw_packed);
+    HeadEpi e;
+    e.w = hw_packed; e.bias = h.bias; e.y = h.y; e.rows = h.rows; e.clamp = h.clamp; e.store_x = !h.no_activation_output;
+    e.bias_first = head_resident_applies(q) ? 1 : 0;
+    const ConvGeom& g = pl.g;
+    const unsigned nblocks = (unsigned)((int64_t)g.mblocks * g.tile_base[4] * g.img_groups * g.split_k);
+    const u32x4* wu = reinterpret_cast<const u32x4*>(p.workspace);
+    if (tile32) IDE3D_EXCL_LAUNCH((modconv_split_heads_kernel<2, 32, 1>), dim3(nblocks), 512, 0, st, p, wu, g, e);
+    else if (mt == 1) IDE3D_EXCL_LAUNCH((modconv_split_heads_kernel<1, 16, 1>), dim3(nblocks), 512, 0, st, p, wu, g, e);
+    else IDE3D_EXCL_LAUNCH((modconv_split_heads_kernel<1, 16, 6>), dim3(nblocks), 512, 0, st, p, wu, g, e);
+    IDE3D_CHECK_LAUNCH("modconv2d_heads");
     return IDE3D_OK;
 }
 

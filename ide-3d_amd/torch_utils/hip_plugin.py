@@ -134,6 +134,15 @@ class _ModconvParams(ctypes.Structure):
     ]
 
 
+class _ModconvHeadEpilogue(ctypes.Structure):
+    """ide3d_modconv_head_epilogue (include/ide3d_hip.h): the dual heads fused behind a 3x3 layer (ide3d_modconv2d_heads)."""
+    _fields_ = [
+        ('w', ctypes.c_void_p), ('bias', ctypes.c_void_p), ('y', ctypes.c_void_p),
+        ('rows', ctypes.c_int32), ('clamp', ctypes.c_float), ('no_activation_output', ctypes.c_int32),
+        ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_int64),
+    ]
+
+
 class _ModconvPlanInfo(ctypes.Structure):
     """ide3d_modconv_plan_info (include/ide3d_hip.h): what ide3d_modconv2d would launch."""
     _fields_ = [
@@ -277,6 +286,7 @@ def load():
             'ide3d_lattice_points': [ctypes.POINTER(_Lattice), i64, i64, vp, vp],
             'ide3d_density_lattice': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_Lattice), i64, i64, vp, vp],
             'ide3d_modconv2d': [ctypes.POINTER(_ModconvParams), vp],
+            'ide3d_modconv2d_heads': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), vp],
             'ide3d_modconv_plan': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvPlanInfo)],
             'ide3d_modconv_workspace_bytes': [i32, i32, i32, i32, i32, i32, i32, i32],
             'ide3d_set_conv_arithmetic': [i32],
@@ -310,7 +320,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_filtered_lrelu', 'ide3d_filtered_lrelu_act', 'ide3d_triplane_sample', 'ide3d_triplane_sample_rays', 'ide3d_triplane_taps',
     'ide3d_triplane_sample_backward', 'ide3d_composite', 'ide3d_sample_pdf', 'ide3d_render_rays', 'ide3d_sample_voxel',
     'ide3d_lattice_points', 'ide3d_density_lattice',
-    'ide3d_modconv2d', 'ide3d_modconv_workspace_bytes', 'ide3d_modconv_plan', 'ide3d_set_conv_arithmetic', 'ide3d_get_conv_arithmetic', 'ide3d_frame_u8', 'ide3d_sphere_points', 'ide3d_cam2world', 'ide3d_style_demod', 'ide3d_fold_heads',
+    'ide3d_modconv2d', 'ide3d_modconv2d_heads', 'ide3d_modconv_workspace_bytes', 'ide3d_modconv_plan', 'ide3d_set_conv_arithmetic', 'ide3d_get_conv_arithmetic', 'ide3d_frame_u8', 'ide3d_sphere_points', 'ide3d_cam2world', 'ide3d_style_demod', 'ide3d_fold_heads',
     'ide3d_style_demod_batch', 'ide3d_fold_heads_batch',
     'ide3d_skip_upsample_add_cl', 'ide3d_bilinear_up2_split', 'ide3d_mapping', 'ide3d_mapping_workspace_bytes', 'ide3d_mapping_supported',
     'ide3d_lowres_layers_supported', 'ide3d_lowres_workspace_bytes', 'ide3d_lowres_group',
@@ -935,6 +945,60 @@ class VolumeRenderPlugin:
 class ModconvPlugin:
     # workspace cache: (weight data_ptr, shape, n, h, w, mode) -> [buffer, weight._version the packed copy was made from, weakref(weight)]
     _ws = {}
+    _heads_declined = set()      # (n, cin, cout, h, w, rows, arith) that ide3d_modconv2d_heads has no fused form for
+
+    @staticmethod
+    def _workspace(lib, x, w, n, cin, cout, h, wd, k, mode, per_image, arith):
+        """The workspace of (weight, problem shape, device, launch domain, arithmetic): [buffer, weight._version packed, weakref(weight)]."""
+        # one workspace per (weight, problem shape, device, launch domain): the split-K partials inside it belong to one launch at a
+        # time; the domain is the current stream for eager callers and the owning GraphedRenderer inside `workspace_scope`
+        # ... and per arithmetic: the packed weights of the split-bf16 loops differ from the fp32 loop's
+        key = (0 if per_image else w.data_ptr(), tuple(w.shape), n, h, wd, mode, x.device.index, _ws_domain(x.device), arith)
+        ent = ModconvPlugin._ws.get(key)
+        if ent is None:
+            nbytes = lib.ide3d_modconv_workspace_bytes(n, cin, cout, h, wd, k, mode, int(per_image))
+            _require(nbytes >= 0, 'modconv2d: unsupported configuration')
+            if len(ModconvPlugin._ws) > 1024:
+                # drop only workspaces whose weight tensor is gone (nothing can launch with them again): a captured hipGraph
+                # holds raw pointers into the live ones, so those are never freed behind its back
+                for k_dead in [k_ for k_, e_ in ModconvPlugin._ws.items() if e_[2] is not None and e_[2]() is None]:
+                    del ModconvPlugin._ws[k_dead]
+            ent = [torch.empty([max(nbytes // 4, 1)], dtype=torch.float32, device=x.device), None, None]
+            ModconvPlugin._ws[key] = ent
+        return ent
+
+    @staticmethod
+    def _params(lib, x, w, y, styles, dcoefs, noise, noise_strength, bias, act, alpha, gain, clamp, mode, arith, x_amax, y_amax):
+        """ide3d_modconv_params of one modconv2d call (y_pitch left 0) -> (params, workspace entry, tensors to keep alive)."""
+        n, cin, h, wd = x.shape
+        per_image = (w.ndim == 5)
+        cout, _, k, _ = w.shape[-4:]
+        ent = ModconvPlugin._workspace(lib, x, w, n, cin, cout, h, wd, k, mode, per_image, arith)
+        p = _ModconvParams()
+        p.x, p.w, p.y = x.data_ptr(), w.data_ptr(), (y.data_ptr() if y is not None else None)
+        keep = []
+        for name, t in (('styles', styles), ('dcoefs', dcoefs), ('noise', noise), ('bias', bias)):
+            if t is not None:
+                t = t.contiguous(); keep.append(t)
+                _require(t.is_cuda and t.dtype == torch.float32, f'modconv2d: {name} must be float32 on GPU')
+                _require(t.device == x.device, f'modconv2d: {name} must reside on the same device as x')
+                setattr(p, name, t.data_ptr())
+        p.n, p.cin, p.cout, p.h, p.w_, p.k = n, cin, cout, h, wd, k
+        p.noise_strength = float(noise_strength)
+        p.act, p.alpha, p.gain, p.clamp = int(act), float(alpha), float(gain), float(clamp)
+        p.mode = mode
+        # the packed copy in the workspace is valid only for the very tensor object (and version) it was made from: a data_ptr
+        # can be recycled by the allocator for another weight of the same shape
+        p.weights_packed = int((not per_image) and ent[2] is not None and ent[2]() is w and ent[1] == w._version)
+        p.w_batch_stride = (cout * cin * k * k) if per_image else 0
+        p.arith = arith
+        for name, t in (('x_amax', x_amax), ('y_amax', y_amax)):
+            if t is not None:
+                _require(t.is_cuda and t.device == x.device and t.dtype == torch.float32 and tuple(t.shape) == (n, AMAX_FLOATS) and t.is_contiguous(),
+                         f'modconv2d: {name} must be a contiguous float32 [n, AMAX_FLOATS] tensor on the device of x')
+                setattr(p, name, t.data_ptr())
+        p.workspace, p.workspace_bytes = ent[0].data_ptr(), ent[0].numel() * 4
+        return p, ent, keep
 
     @staticmethod
     def modconv2d(x, w, styles, dcoefs, noise, noise_strength, bias, act, alpha, gain, clamp, mode=0, arith=0, x_amax=None, y_amax=None, pad_rows=False):
@@ -961,54 +1025,61 @@ class ModconvPlugin:
         pitch = (ow + 3) // 4 * 4 if (pad_rows and mode == 2) else ow
         y = torch.empty([n, cout, oh, pitch], dtype=torch.float32, device=x.device)
         lib = load()
-        # one workspace per (weight, problem shape, device, launch domain): the split-K partials inside it belong to one launch at a
-        # time; the domain is the current stream for eager callers and the owning GraphedRenderer inside `workspace_scope`
-        # ... and per arithmetic: the packed weights of the split-bf16 loops differ from the fp32 loop's
         arith = int(arith) or int(lib.ide3d_get_conv_arithmetic())
         if arith == 16 and x_amax is None:
             arith = 6          # f16x3 needs the bound on |x|; decided here so that the workspace (packed weights) is the bf16x6 one
-        key = (0 if per_image else w.data_ptr(), tuple(w.shape), n, h, wd, mode, x.device.index, _ws_domain(x.device), arith)
-        ent = ModconvPlugin._ws.get(key)
-        if ent is None:
-            nbytes = lib.ide3d_modconv_workspace_bytes(n, cin, cout, h, wd, k, mode, int(per_image))
-            _require(nbytes >= 0, 'modconv2d: unsupported configuration')
-            if len(ModconvPlugin._ws) > 1024:
-                # drop only workspaces whose weight tensor is gone (nothing can launch with them again): a captured hipGraph
-                # holds raw pointers into the live ones, so those are never freed behind its back
-                for k_dead in [k_ for k_, e_ in ModconvPlugin._ws.items() if e_[2] is not None and e_[2]() is None]:
-                    del ModconvPlugin._ws[k_dead]
-            ent = [torch.empty([max(nbytes // 4, 1)], dtype=torch.float32, device=x.device), None, None]
-            ModconvPlugin._ws[key] = ent
-        p = _ModconvParams()
-        p.x, p.w, p.y = x.data_ptr(), w.data_ptr(), y.data_ptr()
-        keep = []
-        for name, t in (('styles', styles), ('dcoefs', dcoefs), ('noise', noise), ('bias', bias)):
-            if t is not None:
-                t = t.contiguous(); keep.append(t)
-                _require(t.is_cuda and t.dtype == torch.float32, f'modconv2d: {name} must be float32 on GPU')
-                _require(t.device == x.device, f'modconv2d: {name} must reside on the same device as x')
-                setattr(p, name, t.data_ptr())
-        p.n, p.cin, p.cout, p.h, p.w_, p.k = n, cin, cout, h, wd, k
-        p.noise_strength = float(noise_strength)
-        p.act, p.alpha, p.gain, p.clamp = int(act), float(alpha), float(gain), float(clamp)
-        p.mode = mode
-        # the packed copy in the workspace is valid only for the very tensor object (and version) it was made from: a data_ptr
-        # can be recycled by the allocator for another weight of the same shape
-        p.weights_packed = int((not per_image) and ent[2] is not None and ent[2]() is w and ent[1] == w._version)
-        p.w_batch_stride = (cout * cin * k * k) if per_image else 0
-        p.arith = arith
-        for name, t in (('x_amax', x_amax), ('y_amax', y_amax)):
-            if t is not None:
-                _require(t.is_cuda and t.device == x.device and t.dtype == torch.float32 and tuple(t.shape) == (n, AMAX_FLOATS) and t.is_contiguous(),
-                         f'modconv2d: {name} must be a contiguous float32 [n, AMAX_FLOATS] tensor on the device of x')
-                setattr(p, name, t.data_ptr())
-        p.workspace, p.workspace_bytes = ent[0].data_ptr(), ent[0].numel() * 4
+        p, ent, keep = ModconvPlugin._params(lib, x, w, y, styles, dcoefs, noise, noise_strength, bias, act, alpha, gain, clamp, mode, arith, x_amax, y_amax)
         p.y_pitch = pitch if pitch != ow else 0
         with _dev_guard(x.device):
             rc = lib.ide3d_modconv2d(ctypes.byref(p), _stream(x))
         _check(rc, 'modconv2d')
         ent[1], ent[2] = (None, None) if per_image else (w._version, weakref.ref(w))
         return y if pitch == ow else y[..., :ow]
+
+    @staticmethod
+    def modconv2d_heads(x, w, styles, dcoefs, noise, noise_strength, bias, act, alpha, gain, clamp, head_w, head_bias, head_clamp,
+                        want_x=True, arith=0):
+        """A stride-1 3x3 `modconv2d` and the dual heads that read its output (`modconv2d(y, head_w, None, None, None, 0.0, head_bias, 1,
+        0.0, 1.0, head_clamp)`, head_w [n, rows, cin, 1, 1] per-image) in one launch (ide3d_modconv2d_heads) -> (y or None, heads
+        [n, rows, h, w]), bit-equal to the two calls; None when the fused form does not apply (the caller then makes the two calls).
+        want_x=False: y is not written."""
+        for t in (x, w, head_w):
+            _require(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), 'modconv2d_heads: contiguous float32 CUDA tensors required')
+        n, cin, h, wd = x.shape
+        cout = w.shape[0]
+        _require(w.ndim == 4 and tuple(w.shape[1:]) == (cin, 3, 3), 'modconv2d_heads: w must be [cout, cin, 3, 3]')
+        _require(head_w.ndim == 5 and head_w.shape[0] == n and head_w.shape[2] == cout and tuple(head_w.shape[3:]) == (1, 1),
+                 'modconv2d_heads: head_w must be [n, rows, cout, 1, 1]')
+        lib = load()
+        arith = int(arith) or int(lib.ide3d_get_conv_arithmetic())
+        if arith == 16:
+            arith = 6          # (no x_amax here: what modconv2d runs without one)
+        rows = head_w.shape[1]
+        # the library's decision depends on the shape, the arithmetic and the knob only: a declined shape is remembered, so that callers that
+        # try every dual-path block (the 512-channel ones always decline) pay for the allocations and parameter blocks once
+        shape_key = (n, cin, cout, h, wd, rows, arith)
+        knob_off = 'IDE3D_MODCONV_NO_HEAD_FUSION' in os.environ
+        if knob_off or shape_key in ModconvPlugin._heads_declined:
+            return None
+        y = torch.empty([n, cout, h, wd], dtype=torch.float32, device=x.device) if want_x else None
+        heads = torch.empty([n, rows, h, wd], dtype=torch.float32, device=x.device)
+        p, ent, keep = ModconvPlugin._params(lib, x, w, y, styles, dcoefs, noise, noise_strength, bias, act, alpha, gain, clamp, 0, arith, None, None)
+        hent = ModconvPlugin._workspace(lib, heads, head_w, n, cout, rows, h, wd, 1, 0, True, arith)
+        e = _ModconvHeadEpilogue()
+        e.w, e.y, e.rows, e.clamp, e.no_activation_output = head_w.data_ptr(), heads.data_ptr(), rows, float(head_clamp), int(not want_x)
+        if head_bias is not None:
+            head_bias = head_bias.contiguous()
+            _require(head_bias.is_cuda and head_bias.dtype == torch.float32 and head_bias.numel() == rows, 'modconv2d_heads: head_bias must be float32 [rows] on GPU')
+            e.bias = head_bias.data_ptr()
+        e.workspace, e.workspace_bytes = hent[0].data_ptr(), hent[0].numel() * 4
+        with _dev_guard(x.device):
+            rc = lib.ide3d_modconv2d_heads(ctypes.byref(p), ctypes.byref(e), _stream(x))
+        if rc == -2:        # IDE3D_ENOKERNEL
+            ModconvPlugin._heads_declined.add(shape_key)
+            return None
+        _check(rc, 'modconv2d_heads')
+        ent[1], ent[2] = w._version, weakref.ref(w)
+        return y, heads
 
 
 def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epilogue='conv', x_amax=False):

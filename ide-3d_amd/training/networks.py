@@ -458,17 +458,8 @@ def _adjacent_views(a, b):
     return t
 
 
-def _dual_head(x, torgb, toseg, w):
-    """toRGB + toSeg of a dual-path block (reference networks.py:1109,1130) as ONE 1x1 implicit-GEMM launch.
-    The two heads modulate with different styles, so the styles are folded into per-image weights
-    [N, Cout_rgb + Cout_seg, Cin, 1, 1] (tiny) and the activation tensor x is read from HBM once.
-    Inference on device tensors only; returns None otherwise."""
-    if not (use_hip_modconv and torgb.weight.shape[2] == 1 and torgb.conv_clamp == toseg.conv_clamp
-            and _inference_on_gpu(x, w, torgb.weight, toseg.weight) and _modconv_init()):
-        return None
-    n = x.shape[0]
-    if w.shape[0] != n:
-        return None
+def _dual_head_weights(torgb, toseg, w):
+    """Per-image weights [N, Cout_rgb + Cout_seg, Cin, 1, 1] of the two heads with their styles folded in."""
     wcat = _take_prefetched(torgb, w) if _prefetch_table() else None
     if wcat is None:
         wcat = _folded_head_weights(torgb, toseg, w)
@@ -478,11 +469,72 @@ def _dual_head(x, torgb, toseg, w):
         wr = torgb.weight[None, :, :, 0, 0] * s_rgb[:, None, :]           # [N, Co_rgb, Cin]
         ws = toseg.weight[None, :, :, 0, 0] * s_seg[:, None, :]
         wcat = torch.cat([wr, ws], dim=1)[:, :, :, None, None].contiguous()
+    return wcat
+
+
+def _dual_head(x, torgb, toseg, w, wcat=None):
+    """toRGB + toSeg of a dual-path block (reference networks.py:1109,1130) as ONE 1x1 implicit-GEMM launch.
+    The two heads modulate with different styles, so the styles are folded into per-image weights
+    [N, Cout_rgb + Cout_seg, Cin, 1, 1] (tiny) and the activation tensor x is read from HBM once.
+    Inference on device tensors only; returns None otherwise.  `wcat`: the folded weights, when the caller already has them."""
+    if not (use_hip_modconv and torgb.weight.shape[2] == 1 and torgb.conv_clamp == toseg.conv_clamp
+            and _inference_on_gpu(x, w, torgb.weight, toseg.weight) and _modconv_init()):
+        return None
+    n = x.shape[0]
+    if w.shape[0] != n:
+        return None
+    if wcat is None:
+        wcat = _dual_head_weights(torgb, toseg, w)
     bias = _cat_cached(torgb.bias, toseg.bias)
     clamp = -1.0 if torgb.conv_clamp is None else torgb.conv_clamp
     y = _modconv_plugin.modconv2d(x.contiguous(), wcat, None, None, None, 0.0, bias, 1, 0.0, 1.0, clamp)
     co = torgb.weight.shape[0]
     return y[:, :co], y[:, co:]
+
+
+def _conv1_dual_head(block, x, w1, w_shared, want_x, noise_mode='random', gain=1, input_noise=None, **unused):
+    """`block.conv1(x, w1)` followed by `_dual_head(., block.torgb, block.toseg, w_shared)`, with the heads in the epilogue of the
+    convolution's launch where csrc/modconv.hip has that form (ide3d_modconv2d_heads: bit-equal to the two launches) -> (x, (y, y_seg));
+    x is None when not `want_x` and the fused launch ran.  None, before anything was launched, when the path does not apply: training,
+    hooks on the block or its layers (they want each layer's own call), random or per-call noise, arithmetics other than bf16x6.
+    Where the library declines the shape (split-K or several row blocks at this batch size; or IDE3D_MODCONV_NO_HEAD_FUSION is set), the two
+    launches are made here, from the styles and folded weights already computed."""
+    c1, tr, ts = block.conv1, block.torgb, block.toseg
+    if not (use_hip_modconv and type(c1) is SynthesisLayer and c1.up == 1 and c1.padding == 1 and c1.weight.shape[2:] == (3, 3)
+            and c1.activation in ('linear', 'lrelu') and tr.weight.shape[2] == 1 and tr.conv_clamp == ts.conv_clamp
+            and x.ndim == 4 and x.shape[0] == w1.shape[0] == w_shared.shape[0]
+            and _inference_on_gpu(x, w1, w_shared, c1.weight, c1.bias, tr.weight, ts.weight)
+            and not _hooked(block, c1, tr, ts) and _modconv_init()):
+        return None
+    from torch_utils import hip_plugin
+    if hip_plugin.conv_arithmetic() != 'bf16x6':
+        return None
+    # the noise of SynthesisLayer.forward's single-launch path: none, or the layer's constant noise at this resolution
+    noise = None
+    if c1.use_noise and noise_mode != 'none':
+        if input_noise is not None or noise_mode != 'const' or tuple(c1.noise_const.shape) != tuple(x.shape[2:]):
+            return None
+        noise = _scaled_const_noise(c1.noise_const, c1.noise_strength)
+    styles, dcoefs = _styles_and_dcoefs(c1.affine, w1, c1.weight, True)
+    if dcoefs is None:
+        dcoefs = _demod_coefs(c1.weight, styles)
+    spec = bias_act.activation_funcs[c1.activation]
+    act_gain = c1.act_gain * gain
+    act_clamp = c1.conv_clamp * gain if c1.conv_clamp is not None else None
+    bias = c1.bias.to(x.dtype)
+    wcat = _dual_head_weights(tr, ts, w_shared)
+    hbias = _cat_cached(tr.bias, ts.bias)
+    hclamp = -1.0 if tr.conv_clamp is None else tr.conv_clamp
+    xc = x.contiguous()
+    out = _modconv_plugin.modconv2d_heads(xc, c1.weight.contiguous(), styles.contiguous(), dcoefs, noise, 1.0, bias,
+                                          spec.cuda_idx, spec.def_alpha, act_gain, -1.0 if act_clamp is None else act_clamp,
+                                          wcat, hbias, hclamp, want_x=want_x)
+    if out is None:
+        x = _modconv_bias_act(x, c1.weight, styles, True, noise, 1.0, bias, c1.activation, act_gain, act_clamp, dcoefs=dcoefs)
+        return x, _dual_head(x, tr, ts, w_shared, wcat=wcat)
+    x, y = out
+    co = tr.weight.shape[0]
+    return x, (y[:, :co], y[:, co:])
 
 
 _lowres_plugin = None
@@ -973,7 +1025,9 @@ class SegSynthesisBlock(torch.nn.Module):
     def forward(self, x, img, seg, ws, force_fp32=False, fused_modconv=None, block_noise=None, disable_rgb=False, **layer_kwargs):
         misc.assert_shape(ws, [None, self.num_conv + self.num_torgb, self.w_dim])
         resume_after_conv0 = bool(layer_kwargs.pop('_resume_after_conv0', False))
-        w_iter = iter(ws.unbind(dim=1))
+        x_unused = bool(layer_kwargs.pop('_x_unused', False))       # the caller drops this block's x (the last block of backbone / superres)
+        ws_list = ws.unbind(dim=1)
+        w_iter = iter(ws_list)
         dtype = torch.float16 if self.use_fp16 and not force_fp32 else torch.float32
         memory_format = torch.channels_last if self.channels_last and not force_fp32 else torch.contiguous_format
         # fp16 blocks (reference :1058-1060: the high-resolution blocks of a released pickle store activations in fp16 with
@@ -987,6 +1041,7 @@ class SegSynthesisBlock(torch.nn.Module):
             with misc.suppress_tracer_warnings():
                 fused_modconv = (not self.training) and (dtype == torch.float32 or int(ws.shape[0]) == 1)
 
+        fused = fused_heads = None                  # conv1 + dual heads in one launch (_conv1_dual_head)
         if self.in_channels == 0:
             x = self.const.to(dtype=dtype, memory_format=memory_format)
             x = x.unsqueeze(0).expand(ws.shape[0], *x.size())
@@ -1002,21 +1057,28 @@ class SegSynthesisBlock(torch.nn.Module):
                 x = self.conv0(x, next(w_iter), fused_modconv=fused_modconv, **layer_kwargs)
             if not self.use_single_layer:
                 layer_kwargs['input_noise'] = block_noise[:, 1:2] if block_noise is not None else None
-                x = self.conv1(x, next(w_iter), fused_modconv=fused_modconv, **layer_kwargs)
+                w1 = next(w_iter)
+                if (self.is_last or self.architecture == 'skip') and not disable_rgb and dtype == torch.float32:
+                    fused = _conv1_dual_head(self, x, w1, ws_list[self.num_conv], not x_unused, **layer_kwargs)
+                if fused is not None:
+                    x, fused_heads = fused
+                else:
+                    x = self.conv1(x, w1, fused_modconv=fused_modconv, **layer_kwargs)
 
         w_shared = next(w_iter) if (self.is_last or self.architecture == 'skip') else None
+        ref = x if x is not None else fused_heads[0]               # (x is None: the fused launch did not write it)
         img_lo = seg_lo = None
         heads_follow = (self.is_last or self.architecture == 'skip') and not disable_rgb
-        if heads_follow and _inference_on_gpu(x) and img is not None and seg is not None and img.size(-1) * 2 == x.size(-1):
+        if heads_follow and _inference_on_gpu(ref) and img is not None and seg is not None and img.size(-1) * 2 == ref.size(-1):
             img_lo, seg_lo, img, seg = img, seg, None, None       # defer: upsample + add in one launch (_accumulate)
         else:
-            img = self._merge_skip(img, x)
-            seg = self._merge_skip(seg, x)
+            img = self._merge_skip(img, ref)
+            seg = self._merge_skip(seg, ref)
         if self.is_last or self.architecture == 'skip':
             if disable_rgb:
                 img = seg = None
             else:
-                heads = _dual_head(x, self.torgb, self.toseg, w_shared)
+                heads = fused_heads if fused_heads is not None else _dual_head(x, self.torgb, self.toseg, w_shared)
                 if heads is not None:
                     y, y_seg = heads              # one launch: x is read once for both heads
                 else:
@@ -1032,8 +1094,8 @@ class SegSynthesisBlock(torch.nn.Module):
                 else:
                     img = self._accumulate(img_lo, img, y)
                     seg = self._accumulate(seg_lo, seg, y_seg)
-        assert x.dtype == dtype
-        if out_dtype != dtype:
+        assert x is None or x.dtype == dtype
+        if x is not None and out_dtype != dtype:
             x = x.to(out_dtype)
         assert img is None or img.dtype == torch.float32
         assert seg is None or seg.dtype == torch.float32

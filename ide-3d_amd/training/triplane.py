@@ -338,6 +338,8 @@ class TriplaneSynthesisNetwork(torch.nn.Module):
             if i < start:
                 continue
             extra = dict(_resume_after_conv0=True) if (resume and i == start) else {}
+            if i == len(blocks) - 1:
+                extra['_x_unused'] = True            # only the tri-planes leave the backbone
             x_v, img_v, seg_v = block(x_v, img_v, cur_ws, condition_img=seg_v, **block_kwargs, **extra)
         return img_v, seg_v
 
@@ -393,8 +395,10 @@ class TriplaneSynthesisNetwork(torch.nn.Module):
             x = up(feat[:, :fc])
             img = up(feat[:, :self.img_channels])
             seg = up(feat[:, fc:])
-        for res, cur_ws in zip(self.block_resolutions, block_ws):
-            x, img, seg = getattr(self, f'b{res}')(x, img, seg, cur_ws, **block_kwargs)
+        last = len(self.block_resolutions) - 1
+        for i, (res, cur_ws) in enumerate(zip(self.block_resolutions, block_ws)):
+            extra = dict(_x_unused=True) if i == last else {}          # only img / seg leave the super-resolution blocks
+            x, img, seg = getattr(self, f'b{res}')(x, img, seg, cur_ws, **block_kwargs, **extra)
         return img, seg
 
     def forward(self, ws, c=None, render_params=None, noise_mode='const', return_seg=False, return_raw=False,

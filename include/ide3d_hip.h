@@ -388,6 +388,24 @@ int64_t ide3d_modconv_workspace_bytes(int32_t n, int32_t cin, int32_t cout, int3
                                       int32_t per_image_weights);
 int ide3d_modconv2d(const ide3d_modconv_params* p, void* stream);
 
+/* A 3x3 layer (ide3d_modconv_params, mode 0) and the dual 1x1 heads that read its output (toRGB + toSeg with per-image folded weights:
+ * what ide3d_modconv2d computes for them with w_batch_stride > 0, act linear, gain 1) in ONE launch: the heads run in the epilogue of
+ * the workgroup that holds all cout channels of its pixels.  Results are bit-equal to the two ide3d_modconv2d calls.  Returns
+ * IDE3D_ENOKERNEL (nothing launched) unless the layer runs in bf16x6 on one 128- or 64-channel block without split-K on 16 x 16 /
+ * 32 x 16 tiles that cover the map, with y_amax = NULL and y_pitch = 0, and the heads take the split-bf16 path with <= 32 or
+ * 161..192 rows; and when IDE3D_MODCONV_NO_HEAD_FUSION is set.  The caller then makes the two calls. */
+typedef struct ide3d_modconv_head_epilogue {
+    const float* w;           /* [n, rows, cin] per-image head weights (cin = the layer's cout), styles folded in */
+    const float* bias;        /* [rows] or NULL */
+    float*       y;           /* [n, rows, h, w] head output */
+    int32_t      rows;
+    float        clamp;       /* < 0: none */
+    int32_t      no_activation_output;   /* 1: the layer's own output is not written (p->y may be NULL) */
+    float*       workspace;   /* packed head weights: ide3d_modconv_workspace_bytes(n, cin, rows, h, w, 1, 0, 1) bytes */
+    int64_t      workspace_bytes;
+} ide3d_modconv_head_epilogue;
+int ide3d_modconv2d_heads(const ide3d_modconv_params* p, const ide3d_modconv_head_epilogue* heads, void* stream);
+
 /* Host-only planning query (no launch, no device access): the kernel family, tile and grid that ide3d_modconv2d would use for `p` in the
  * arithmetic `p->arith` resolves to.  Pointers are not dereferenced (set `x_amax` non-null to plan the f16x3 launch; `x` counts for its
  * alignment only).  For tests of the planner and for tooling; not part of the reference's interface. */
