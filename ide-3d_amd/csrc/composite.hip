@@ -16,7 +16,6 @@
 //      and (through L1, same lines as phase 1's sigma reads) exactly once from HBM.
 // HBM roofline: rays*steps*(ch+2)*4 bytes in, rays*(ch+1+steps)*4 out.
 #include "common.h"
-#include "knobs.h"
 #include <stdlib.h>
 
 namespace ide3d {
@@ -221,22 +220,15 @@ extern "C" int ide3d_composite(const float* rgb_sigma, const float* z_vals, cons
         // LDS-staged path: contiguous, 16-byte aligned ray blocks that fit four to a workgroup
         const int64_t block = (int64_t)steps * (ch + 1);
         const size_t lds = (size_t)4 * (block + ((steps + 3) & ~3)) * sizeof(float);
-        const bool off = knobs().composite_no_lds;
-        if (!off && block % 4 == 0 && block <= 40 * 256 && lds <= 160 * 1024 && ((reinterpret_cast<uintptr_t>(rgb_sigma) & 15) == 0)) {
+        if (block % 4 == 0 && block <= 40 * 256 && lds <= 160 * 1024 && ((reinterpret_cast<uintptr_t>(rgb_sigma) & 15) == 0)) {
             const int nld = (int)((block / 4 + kWave - 1) / kWave);
-            // persistent workgroups (as many as fit the LDS of the chip): every wave walks several rays, which is what the
-            // request-ahead pipeline needs
-            // one-wave workgroups: the LDS footprint is per wave (block + weights), so 64-thread workgroups pack the CU's 160 KB
-            // with as many waves as fit (7 at 96 x 53) instead of one 4-wave workgroup
-            const int mode = knobs().composite_mode;
-            const int wpb = (mode == 1 || mode == 3) ? 4 : 1;
-            const size_t lds_w = lds / 4 * wpb;
-            int64_t pgrid = (mode >= 2) ? (int64_t)kNumCU * ((160 * 1024) / (int64_t)lds_w) : cdiv64(rays, wpb);
-            if (pgrid > cdiv64(rays, wpb)) pgrid = cdiv64(rays, wpb);
-            if (pgrid > 0x7fffffff) pgrid = 0x7fffffff;
+            // one-wave workgroups, one per ray: the LDS footprint is per wave (block + weights), so 64-thread workgroups pack the CU's
+            // 160 KB with as many waves as fit (7 at 96 x 53) instead of one 4-wave workgroup
+            const size_t lds_w = lds / 4;
+            const int64_t pgrid = rays < 0x7fffffff ? rays : 0x7fffffff;
             auto go = [&](auto kern) {
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w);
-                hipLaunchKernelGGL(kern, dim3((unsigned)pgrid), dim3(64 * wpb), lds_w, (hipStream_t)stream,
+                hipLaunchKernelGGL(kern, dim3((unsigned)pgrid), dim3(64), lds_w, (hipStream_t)stream,
                                    rgb_sigma, z_vals, dir_norm, noise, rays, steps, ch, clamp_mode, last_back, white_back,
                                    max_depth, fill_mode, rgb, depth, weights);
             };

@@ -13,7 +13,6 @@
 // filtered_lrelu.py:215-216).  The intermediate (up^2 larger) never touches HBM: traffic = in + out
 // (+ signs).  Non-separable filters run the same passes with 2-D tap loops.
 #include "common.h"
-#include "knobs.h"
 #include <stdlib.h>
 
 namespace ide3d {
@@ -545,8 +544,7 @@ static int launch_flr_sep(const ide3d_filtered_lrelu_params& p, hipStream_t st) 
 // Returns 1 when a specialised instance ran, 0 when none matches (the generic kernel then takes the call), < 0 on error.
 template <class T>
 static int try_flr_sep(const ide3d_filtered_lrelu_params& p, hipStream_t st) {
-    const bool off = knobs().flr_generic;
-    if (off || p.fu_h != 0 || p.fd_h != 0) return 0;                // separable filters only
+    if (p.fu_h != 0 || p.fd_h != 0) return 0;                // separable filters only
 #define IDE3D_FLS(U, D, FU, FD) \
     if (p.up == U && p.down == D && p.fu_w == FU && p.fd_w == FD) { const int rc = launch_flr_sep<T, U, D, FU, FD>(p, st); return rc ? rc : 1; }
     IDE3D_FLS(2, 2, 12, 12)

@@ -65,14 +65,14 @@ template <> struct ModeCfg<MODE_TCONV3> { static constexpr int KC = 4, WTAPS = 9
 // patch and all 9 taps (each tap feeds exactly one class), i.e. 4x the MFMA work per staging step / barrier of mode 2.
 template <> struct ModeCfg<MODE_TCONV3A> { static constexpr int KC = 4, WTAPS = 9, MAXT = 9; };
 
-template <int MODE, int BIG, int TI, int PH, int PW, int NWV = 4, int KCO = 0>      // KCO: input channels per K chunk (0 = the mode's default)
+template <int MODE, int BIG, int TI, int PH, int PW>
 struct McCfg {
-    static constexpr int NT = 64 * NWV;                     // threads per workgroup (4 or 8 waves)
+    static constexpr int NWV = 4, NT = 64 * NWV;            // waves, threads per workgroup
     static constexpr int BN = TI * PH * PW;
     static_assert(BN == 64 || BN == 128 || BN == 256, "pixel tile must hold 64, 128 or 256 pixels");
     static constexpr int NCLS = (MODE == MODE_TCONV3A) ? 4 : 1;   // accumulator sets (output parity classes)
     using MC = ModeCfg<MODE>;
-    static constexpr int KC = KCO ? KCO : MC::KC, WTAPS = MC::WTAPS, MAXT = MC::MAXT;
+    static constexpr int KC = MC::KC, WTAPS = MC::WTAPS, MAXT = MC::MAXT;
     // BIG: 1 -> BM 128 (waves 2 x 2, two M tiles each); 2 -> BM 64 (waves 2 x 2, one M tile each); 0 -> BM 32 (waves 1 x 4)
     static constexpr int WM = BIG ? 2 : 1, WN = NWV / WM;
     static constexpr int MTW = (BIG == 1) ? 2 : 1;          // 32-row M tiles per wave
@@ -135,7 +135,6 @@ struct ConvGeom {
     int img_groups;                 // ceil(n / TI)
     int mblocks, cchunks, split_k, chunks_per_split;
     int oh, ow;                     // output size
-    int debug;                      // experiments only: 1 = no staging after the first chunk, 2 = staging but no MFMA
 };
 
 // ---- hand-scheduled LDS operand reads ----------------------------------------------------------------------------
@@ -321,11 +320,11 @@ __device__ __forceinline__ void modconv_finish(const ide3d_modconv_params& p, fl
 
 // One output tile: `tl` = index inside its tile set (row-major, `tiles_x` per row), `cls` = output parity class
 // (MODE_TCONV3 only).  s_w / s_x: two buffers of K::LDS_W / K::LDS_X floats.
-template <int MODE, int BIG, int TI, int PH, int PW, int NWV, int KCO>
+template <int MODE, int BIG, int TI, int PH, int PW>
 __device__ __forceinline__ void modconv_tile(const ide3d_modconv_params& p, const float* __restrict__ wp, float* __restrict__ partial,
                                              const ConvGeom& g, float* s_w, float* s_x, int mb, int tl, int grp, int split, int cls,
                                              int tiles_x) {
-    using K = McCfg<MODE, BIG, TI, PH, PW, NWV, KCO>;
+    using K = McCfg<MODE, BIG, TI, PH, PW>;
 #ifdef IDE3D_MC_TRACE
     const unsigned long long mc_t0 = __builtin_readcyclecounter();
 #endif
@@ -430,7 +429,7 @@ __device__ __forceinline__ void modconv_tile(const ide3d_modconv_params& p, cons
 #endif
     auto fetch = [&](int c, int buf) {
         const float* ws = wsrc + (int64_t)c * (K::WTAPS * K::KC * K::BM);
-        for (int i = wid; i < w_pieces; i += NWV) {
+        for (int i = wid; i < w_pieces; i += K::NWV) {
             const int t = i / PPT, r = (i - t * PPT) * PIECE;
             const float* src = ws + ((MODE == MODE_TCONV3) ? sel(t_widx, t) : t) * (K::KC * K::BM) + r + lane * 4;
             if (lane * 4 < PIECE)
@@ -472,7 +471,7 @@ __device__ __forceinline__ void modconv_tile(const ide3d_modconv_params& p, cons
     for (int c = c_begin; c < c_end; ++c) {
         const int buf = (c - c_begin) & 1;
         IDE3D_MC_TS(0)
-        if (c + 1 < c_end && g.debug != 1) fetch(c + 1, buf ^ 1);
+        if (c + 1 < c_end) fetch(c + 1, buf ^ 1);
         IDE3D_MC_TS(1)
         const float* sw = s_w + buf * K::LDS_W;
         const float* sx = s_x + buf * K::LDS_X;
@@ -541,17 +540,17 @@ __device__ __forceinline__ void modconv_tile(const ide3d_modconv_params& p, cons
             });
         }
         IDE3D_MC_TS(2)
-        if (c + 1 < c_end && g.debug != 1) commit(buf ^ 1, c + 1);
+        if (c + 1 < c_end) commit(buf ^ 1, c + 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the LDS-DMA weight slab of chunk c + 1 has landed
         IDE3D_MC_TS(3)
-        if (g.debug != 1) __syncthreads();
+        __syncthreads();
         IDE3D_MC_TS(4)
     }
 
 #ifdef IDE3D_MC_TRACE
     const unsigned long long mc_t1 = __builtin_readcyclecounter();
 #endif
-    modconv_finish<MODE, TI, PH, PW, NWV, K::NCLS, K::MTW, K::NTW, K::BM, 2 * K::LDS_W>(p, partial, g, acc, s_w, mb, n0, y0, x0, split, cls, wm, wn, l32);
+    modconv_finish<MODE, TI, PH, PW, K::NWV, K::NCLS, K::MTW, K::NTW, K::BM, 2 * K::LDS_W>(p, partial, g, acc, s_w, mb, n0, y0, x0, split, cls, wm, wn, l32);
 #ifdef IDE3D_MC_TRACE
     if (blockIdx.x == 100 && threadIdx.x == 0) {
         for (int k = 0; k < 6; ++k) g_mc_dbg[k] = mc_acc[k];
@@ -1645,21 +1644,19 @@ __device__ __forceinline__ BlockId decode_block(const ConvGeom& g) {
     return b;
 }
 
-template <int MODE, int BIG, int TI, int PH, int PW, int NWV = 4, int KCO = 0>
-// 4-wave workgroups: 128-pixel (and smaller) tiles need <= 168 VGPRs and <= 53 KB of LDS, three workgroups per CU (measured +2 %
-// frames/s over two); the stride-2 mode's (2P + 1) x (2Q + 1) patches need more LDS than that; 16 accumulators per wave take
-// AGPRs and one workgroup per CU.  8-wave workgroups: one per CU, two waves per SIMD.
-__global__ void __launch_bounds__(64 * NWV, NWV == 8 ? 2
-                                  : (McCfg<MODE, BIG, TI, PH, PW, NWV, KCO>::NCLS * McCfg<MODE, BIG, TI, PH, PW, NWV, KCO>::MTW * McCfg<MODE, BIG, TI, PH, PW, NWV, KCO>::NTW > 8) ? 1
-                                  : (TI * PH * PW <= 128 && MODE != MODE_CONV3S2 && KCO == 0) ? 3 : 2)
+template <int MODE, int BIG, int TI, int PH, int PW>
+// 128-pixel (and smaller) tiles need <= 168 VGPRs and <= 53 KB of LDS, three workgroups per CU (measured +2 % frames/s over two);
+// the stride-2 mode's (2P + 1) x (2Q + 1) patches need more LDS than that; 16 accumulators per wave take AGPRs and one workgroup per CU.
+__global__ void __launch_bounds__(256, (McCfg<MODE, BIG, TI, PH, PW>::NCLS * McCfg<MODE, BIG, TI, PH, PW>::MTW * McCfg<MODE, BIG, TI, PH, PW>::NTW > 8) ? 1
+                                       : (TI * PH * PW <= 128 && MODE != MODE_CONV3S2) ? 3 : 2)
 modconv_kernel(ide3d_modconv_params p, const float* __restrict__ wp, float* __restrict__ partial, ConvGeom g) {
-    using K = McCfg<MODE, BIG, TI, PH, PW, NWV, KCO>;
+    using K = McCfg<MODE, BIG, TI, PH, PW>;
     __shared__ __attribute__((aligned(16))) float s_w[2 * K::LDS_W];
     __shared__ __attribute__((aligned(16))) float s_x[2 * K::LDS_X];
     const BlockId b = decode_block(g);
     int cls = 0;
     if (MODE == MODE_TCONV3) { cls = (b.tile >= g.tile_base[1]) + (b.tile >= g.tile_base[2]) + (b.tile >= g.tile_base[3]); }
-    modconv_tile<MODE, BIG, TI, PH, PW, NWV, KCO>(p, wp, partial, g, s_w, s_x, b.mb, b.tile - g.tile_base[cls], b.grp, b.split, cls, g.tiles_x[cls]);
+    modconv_tile<MODE, BIG, TI, PH, PW>(p, wp, partial, g, s_w, s_x, b.mb, b.tile - g.tile_base[cls], b.grp, b.split, cls, g.tiles_x[cls]);
 }
 
 
@@ -1847,8 +1844,15 @@ modconv_epilogue_kernel(ide3d_modconv_params p, const float* __restrict__ partia
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// Pixel tiles of a plan (ConvPlan::tile): images x rows x columns of pixels; TA: the all-class transposed form's rows x columns of grid
+// positions (four output pixels each); TFLAT128: 128 pixels of a 1x1 layer flattened to one row (flatten_pointwise)
+enum Tile { T8x16, T2x8x8, T8x4x4, T16x16, TA4x16, TFLAT128, TA8x16, TA16x16, T32x16 };
+struct TileShape { int images, rows, cols; };
+static const TileShape kTiles[] = {{1, 8, 16}, {2, 8, 8}, {8, 4, 4}, {1, 16, 16}, {1, 4, 16}, {1, 1, 128}, {1, 8, 16}, {1, 16, 16}, {1, 32, 16}};
+
 struct ConvPlan {
-    int mode, big, tile;             // tile: 0 = 1x8x16, 1 = 2x8x8, 2 = 8x4x4
+    int mode, big;
+    Tile tile;
     int bm, kc, taps, mblocks, cchunks, oh, ow;
     int parts;                       // 0: fp32 MFMA loop; 2 / 3: split loop with that many pieces per operand
     int f16;                         // split loop on fp16 pieces (f16x3: parts == 2) instead of bf16
@@ -1859,30 +1863,12 @@ struct ConvPlan {
     ConvGeom g;
 };
 
-// Developer knobs (read once): IDE3D_MODCONV_NO_FLAT / _NO_TCONV3A switch the flattened 1x1 tiles / the all-class
-// transposed kernel off, IDE3D_MODCONV_TILE forces a pixel tile (0..3), IDE3D_MODCONV_DEBUG = 1 drops the staging after
-// the first chunk (timing experiments; wrong results).
-struct McEnv { bool no_flat, no_allcls; int tile, debug, ta_rows; };
-static const McEnv& mc_env() {          // (knobs.h: read once)
-    static const McEnv e = {knobs().mc_no_flat, knobs().mc_no_allcls, knobs().mc_tile, knobs().mc_debug, knobs().mc_ta_rows};
-    return e;
-}
-
-// Experiment switches of plan_conv (A/B runs of scripts/micro/: each is the "before" of a plan rule and is documented where the rule is),
-// read once.  IDE3D_MODCONV_NO_STRIP alone is read per call: tests/test_gpu_conv_arith.py flips it inside one process.
-struct PlanKnobs { bool ta_bm64, head_bm128, ta_kc8, no_smallmap, ta_old, sp_oldplan, no_ph32, no_w8split, no_one_round; int sp_modes; };
-static const PlanKnobs& plan_knobs() {          // (knobs.h: read once)
-    const Knobs& e = knobs();
-    static const PlanKnobs k = {e.ta_bm64, e.head_bm128, e.ta_kc8, e.no_smallmap, e.ta_old, e.sp_oldplan, e.no_ph32, e.no_w8split, e.no_one_round, e.sp_modes};
-    return k;
-}
-
 // A 1x1 convolution does not see the image shape: h x w is treated as one row, tiled in runs of 128 pixels whose patch
 // rows are contiguous in memory (16-byte staging, 128-byte output runs).  Needs 16-byte aligned rows.
 static ide3d_modconv_params flatten_pointwise(const ide3d_modconv_params& in) {
     ide3d_modconv_params p = in;
     const int64_t hw = (int64_t)p.h * p.w_;
-    if (p.k == 1 && p.mode == 0 && hw % 4 == 0 && hw >= 128 && ((uintptr_t)p.x % 16) == 0 && !mc_env().no_flat) { p.h = 1; p.w_ = (int)hw; }
+    if (p.k == 1 && p.mode == 0 && hw % 4 == 0 && hw >= 128 && ((uintptr_t)p.x % 16) == 0) { p.h = 1; p.w_ = (int)hw; }
     return p;
 }
 
@@ -1902,32 +1888,24 @@ static int conv_arith_default() {
 }
 static int resolve_arith(int a) { return (a == 1 || a == 3 || a == 6 || a == 16) ? a : conv_arith_default(); }
 
-// tile index (ConvPlan::tile) -> images per tile, tile height, tile width (pixels; transposed all-class form: grid positions)
-static const int TIv[13] = {1, 2, 8, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1}, PHv[13] = {8, 8, 4, 16, 4, 1, 8, 16, 8, 16, 1, 8, 32}, PWv[13] = {16, 8, 4, 16, 16, 128, 16, 16, 16, 16, 256, 16, 16};
-
 static void plan_conv(const ide3d_modconv_params& p, ConvPlan& pl, int arith) {
     pl.mode = (p.mode == 2) ? MODE_TCONV3 : (p.mode == 1) ? MODE_CONV3S2 : (p.k == 1 ? MODE_CONV1 : MODE_CONV3);
     // all-class form from 4 x 4 maps on (round 3: the per-class form took 65 / 78 us for the 0.3-GFLOP layers at 4^2 / 8^2; 962 -> 974-981
-    // frames/s; IDE3D_MODCONV_ALLCLS_MIN=12 restores the old threshold)
-    const int allcls_min = knobs().allcls_min;
-    const bool allcls = (pl.mode == MODE_TCONV3) && mc_bm(p.cout) >= 64 && p.h >= allcls_min && p.w_ >= allcls_min && !mc_env().no_allcls;
+    // frames/s against the earlier threshold of 12)
+    constexpr int allcls_min = 4;
+    const bool allcls = (pl.mode == MODE_TCONV3) && mc_bm(p.cout) >= 64 && p.h >= allcls_min && p.w_ >= allcls_min;
     if (allcls) pl.mode = MODE_TCONV3A;
     pl.bm = mc_bm(p.cout);
     if (allcls && pl.bm == 128) {
         // all-class transposed conv with too few 128-row blocks to fill the 768 resident slots (3 per CU): 64-row blocks double
         // the block count (512 -> 512 in@32: 432 -> 864 blocks, measured +5 %)
         const int64_t blocks128 = (int64_t)cdiv(p.cout, 128) * cdiv(p.h + 1, 4) * cdiv(p.w_ + 1, 16) * p.n;
-        const bool old_plan = knobs().ta_old;
-        if ((blocks128 < 3 * kNumCU * 3 / 4 && !old_plan) || mc_env().ta_rows == 64 || plan_knobs().ta_bm64) pl.bm = 64;
+        if (blocks128 < 3 * kNumCU * 3 / 4) pl.bm = 64;
     }
     // 1x1 heads with cout = 192 (96 + 96 tri-plane channels): three 64-row blocks instead of 128 + 64 rows padded to 128
-    if (p.k == 1 && pl.bm == 128 && p.cout % 128 != 0 && p.cout % 64 == 0 && !plan_knobs().head_bm128) pl.bm = 64;
-    // experiment (IDE3D_MODCONV_TA_KC8): all-class transposed conv as 64-row blocks x 8 x 16 positions x 8 input channels per chunk:
-    // 72 MFMAs per wave and barrier instead of 36, 18 KB of weights streamed per 72 MFMAs instead of per 36
-    bool ta_kc8 = false;
-    if (allcls && p.cin % 8 == 0 && plan_knobs().ta_kc8) { pl.bm = 64; ta_kc8 = true; }
+    if (p.k == 1 && pl.bm == 128 && p.cout % 128 != 0 && p.cout % 64 == 0) pl.bm = 64;
     pl.big = pl.bm == 128 ? 1 : (pl.bm == 64 ? 2 : 0);
-    pl.kc = ta_kc8 ? 8 : mc_kc(p.k); pl.taps = p.k * p.k;
+    pl.kc = mc_kc(p.k); pl.taps = p.k * p.k;
     pl.mblocks = cdiv(p.cout, pl.bm); pl.cchunks = cdiv(p.cin, pl.kc);
     const bool transposed = (pl.mode == MODE_TCONV3 || pl.mode == MODE_TCONV3A);
     pl.oh = transposed ? 2 * p.h + 1 : (pl.mode == MODE_CONV3S2) ? (p.h - 3) / 2 + 1 : p.h;
@@ -1936,7 +1914,7 @@ static void plan_conv(const ide3d_modconv_params& p, ConvPlan& pl, int arith) {
     pl.parts = 0; pl.f16 = 0; pl.aux_floats = 0; pl.strip_off = 0; pl.strip_floats = 0; pl.pair = 0;
     int want_split = 0;                                         // split-K chosen together with the form (0 = by block count below)
     bool one_round = false;                                     // transposed 8-wave form chosen for whole rounds on the strip plan's grid: no split-K
-    const int split_min = knobs().split_min;      // fewer workgroups than this: split-K
+    constexpr int split_min = 512;                              // fewer workgroups than this: split-K
     // class grids
     int gh[4], gw[4];
     const int ncls = (pl.mode == MODE_TCONV3) ? 4 : 1;
@@ -1947,121 +1925,93 @@ static void plan_conv(const ide3d_modconv_params& p, ConvPlan& pl, int arith) {
         else { gh[c] = p.h; gw[c] = p.w_; }
     }
     const int mind = (pl.mode == MODE_CONV3S2) ? ((pl.oh < pl.ow) ? pl.oh : pl.ow) : ((p.h < p.w_) ? p.h : p.w_);
-    pl.tile = (mind >= 12 || p.w_batch_stride) ? 0 : (mind >= 6 ? 1 : 2);     // per-image weights need one image per tile
+    pl.tile = (mind >= 12 || p.w_batch_stride) ? T8x16 : (mind >= 6 ? T2x8x8 : T8x4x4);     // per-image weights need one image per tile
     // small maps (4^2 .. 8^2) of wide 3x3 layers in a split arithmetic: the 8 x 16-pixel split-bf16 tile (one image per tile, most of it
     // outside the map) with split-K 16 instead of the fp32 loop's several-images tiles: 35.5 -> 23.1 us at 512 -> 512 @8, 33.4 -> 20.2 @4
     // (the launch is weight streaming + latency: 256 workgroups of two 16-channel chunks each)
-    if (arith != 1 && pl.mode == MODE_CONV3 && pl.tile != 0 && !p.w_batch_stride && pl.big != 0 && p.cin >= 256 && mc_env().tile < 0 &&
-        !plan_knobs().no_smallmap) {
-        pl.tile = 0;
+    if (arith != 1 && pl.mode == MODE_CONV3 && pl.tile != T8x16 && !p.w_batch_stride && pl.big != 0 && p.cin >= 256) {
+        pl.tile = T8x16;
         const int c16 = cdiv(p.cin, 16);
         want_split = c16 / 2 < 1 ? 1 : (c16 / 2 > 16 ? 16 : c16 / 2);
     }
     // 256-pixel tiles (8 accumulators per wave) for big-cout 3x3 layers with enough work to fill the chip twice over
-    if (pl.tile == 0 && pl.big == 1 && pl.mode != MODE_CONV1 && pl.mode != MODE_CONV3S2 && !p.w_batch_stride) {
+    if (pl.tile == T8x16 && pl.big == 1 && pl.mode != MODE_CONV1 && pl.mode != MODE_CONV3S2 && !p.w_batch_stride) {
         const int64_t blocks256 = (int64_t)pl.mblocks * cdiv(gh[0], 16) * cdiv(gw[0], 16) * p.n * ((pl.mode == MODE_TCONV3) ? 4 : 1);
-        if (blocks256 >= 2 * kNumCU) pl.tile = 3;
+        if (blocks256 >= 2 * kNumCU) pl.tile = T16x16;
     }
-    if (mc_env().tile >= 0) { const int t = mc_env().tile; if (t >= 0 && t <= 3 && (t == 0 || t == 3 || !p.w_batch_stride)) pl.tile = (t == 3 && (pl.big != 1 || pl.mode == MODE_CONV1 || pl.mode == MODE_CONV3S2)) ? 0 : t; }
     if (pl.mode == MODE_TCONV3A) {
         // grid positions per block x 4 classes: 4 x 16 (8 accumulators per wave at BM = 128, two or three workgroups per CU) or —
         // the weight slab of a K chunk (18 KB at BM = 128) is streamed L2 -> LDS once per chunk and per block, and that stream
         // (~11 B/clk/CU) is what bounds the small tile — 8 x 16 / 16 x 16 positions with 16 accumulators per wave (AGPRs, one
         // workgroup per CU): twice the MFMAs per streamed weight byte
-        pl.tile = 4;
+        pl.tile = TA4x16;
         // 64-row blocks have registers for 8 x 16 positions (8 accumulators per wave): half the weight bytes streamed per MFMA
         // (128 -> 64 in@256: measured +3.5 %) as long as enough blocks remain
-        if (pl.big == 2 && (int64_t)pl.mblocks * cdiv(p.h + 1, 8) * cdiv(p.w_ + 1, 16) * p.n >= 4 * kNumCU && !plan_knobs().ta_old) pl.tile = 6;
-        const int rows = mc_env().ta_rows ? mc_env().ta_rows : 0;
-        if (rows == 4) pl.tile = 4;
-        if (ta_kc8) pl.tile = 11;
-        if (rows == 8 && pl.big == 1) pl.tile = 6;
-        if (rows == 16 && pl.big == 2) pl.tile = 7;
-        if (rows == 8 && pl.big == 2) pl.tile = 6;
-        // 512-thread workgroups: 8 x 16 positions at BM = 128, 16 x 16 at BM = 64 (8 accumulators per wave either way)
-        if (rows == 108) pl.tile = (pl.big == 1) ? 8 : 9;
+        if (pl.big == 2 && (int64_t)pl.mblocks * cdiv(p.h + 1, 8) * cdiv(p.w_ + 1, 16) * p.n >= 4 * kNumCU) pl.tile = TA8x16;
     }
-    if (pl.mode == MODE_CONV1 && p.h == 1 && p.w_ % 4 == 0 && p.w_ >= 128) pl.tile = 5;   // flattened by flatten_pointwise()
+    if (pl.mode == MODE_CONV1 && p.h == 1 && p.w_ % 4 == 0 && p.w_ >= 128) pl.tile = TFLAT128;   // flattened by flatten_pointwise()
     // split-bf16 loop: shared-weight 3x3 / all-class transposed layers on 16-pixel-wide tiles, 64- or 128-row blocks
     // (3x3 layers with fewer than 3 K chunks stay on the fp32 loop: prologue + epilogue dominate)
     // (transposed layers from 32 input channels = 2 K chunks on: 32 -> 128 in@128 78.6 -> 60.5 us on the 8-wave strip-plan form; round 3's 81 vs 76
     // the other way round was the 4-wave (h + 1) x (w + 1) form)
-    const int sp_min_cin = knobs().sp_min_cin;
-    const int min_cin = sp_min_cin ? sp_min_cin : (pl.mode == MODE_TCONV3A ? 32 : 33);
+    const int min_cin = (pl.mode == MODE_TCONV3A) ? 32 : 33;
     if (arith != 1 && (pl.mode == MODE_CONV3 || pl.mode == MODE_TCONV3A) && !p.w_batch_stride && pl.big != 0 && p.cin >= min_cin &&
-        (pl.tile == 0 || pl.tile == 3 || pl.tile == 4 || pl.tile == 6 || pl.tile == 7) && !ta_kc8 &&
-        (plan_knobs().sp_modes & (pl.mode == MODE_CONV3 ? 1 : 2))) {
+        (pl.mode == MODE_TCONV3A || pl.tile == T8x16 || pl.tile == T16x16)) {
         pl.parts = (arith == 3 || arith == 16) ? 2 : 3;
         pl.f16 = (arith == 16) ? 1 : 0;
-        const int sp_rows = knobs().sp_rows;
         // Exclusive residency (round 4): one workgroup per CU, so the forms that put TWO of their own waves on a SIMD (8 waves) are chosen
         // wherever the launch still has >= 2 workgroups per CU to run through; measured per layer, bf16x6 / f16x3 us at batch 4:
         //   64 -> 64 @512: 16 x 16 px x 64 rows, 8 waves 431 / 343 (8 x 16, 4 waves with the whole SIMD claimed: 537 / 457)
         //   transposed 256 -> 128 in@128: 8 x 16 positions x 128 rows, 8 waves 250 / 175 (4 x 16, 4 waves: 269 / 207)
         //   transposed 128 -> 64 in@256: 16 x 16 positions x 64 rows, 8 waves 270 / 211 (8 x 16, 4 waves: 318 / 263)
         //   transposed 512 -> 256 in@64 (360 workgroups of 8 x 16): stays on 4 x 16, 4 waves 292 / 215 (8 waves: 401 / 325)
-        if (kSpExclusive && !plan_knobs().sp_oldplan) {
+        if constexpr (kSpExclusive) {
             if (pl.mode == MODE_CONV3) {
                 const int64_t b256 = (int64_t)pl.mblocks * cdiv(p.h, 16) * cdiv(p.w_, 16) * p.n;
-                if (pl.big == 2 && b256 >= 2 * kNumCU) pl.tile = 3;
+                if (pl.big == 2 && b256 >= 2 * kNumCU) pl.tile = T16x16;
                 // 64 rows: 32 x 16 pixels (64 x 64 outputs per wave, half the tiles) while >= 2 workgroups per CU remain
-                if (pl.big == 2 && (int64_t)pl.mblocks * cdiv(p.h, 32) * cdiv(p.w_, 16) * p.n >= 2 * kNumCU && !plan_knobs().no_ph32) pl.tile = 12;
+                if (pl.big == 2 && (int64_t)pl.mblocks * cdiv(p.h, 32) * cdiv(p.w_, 16) * p.n >= 2 * kNumCU) pl.tile = T32x16;
                 // a quarter .. one workgroup per CU on 16 x 16 pixels (512 -> 512 @32 at batch 4: 64): 8 waves and split-K up to ONE workgroup
                 // per CU with >= 8 chunks each, instead of 8 x 16 pixels / 4 waves / split 6 = 768 workgroups of 2 - 6 chunks: 119 -> 93 us
-                if (pl.big == 1 && b256 < 2 * kNumCU && b256 * 4 >= kNumCU && cdiv(p.cin, 16) * b256 >= 8 * kNumCU && !plan_knobs().no_w8split) {
-                    pl.tile = 3; want_split = (int)(kNumCU / b256);
+                if (pl.big == 1 && b256 < 2 * kNumCU && b256 * 4 >= kNumCU && cdiv(p.cin, 16) * b256 >= 8 * kNumCU) {
+                    pl.tile = T16x16; want_split = (int)(kNumCU / b256);
                 }
             } else {
                 const int64_t b8 = (int64_t)pl.mblocks * cdiv(p.h + 1, 8) * cdiv(p.w_ + 1, 16) * p.n, b16 = (int64_t)pl.mblocks * cdiv(p.h + 1, 16) * cdiv(p.w_ + 1, 16) * p.n;
                 // on the h x w grid of a strip plan (below) the 8-wave form may come out at whole rounds of ONE workgroup per CU where the (h + 1) x
                 // (w + 1) grid did not: 512 -> 256 in@64 = 256 workgroups of 8 x 16 positions x 128 rows, no split-K: 241 -> 211 us (f16x3 181 -> 149)
                 // against 512 four-wave workgroups of 4 x 16; 512 -> 512 in@32 (64 rows): 149 -> 141 against 256 two-team workgroups
-                const bool strip_ok = !p.w_batch_stride && !p.noise && !p.bias && p.act == 1 && p.gain == 1.f && p.clamp < 0.f && !knob_live("IDE3D_MODCONV_NO_STRIP") && !plan_knobs().no_one_round;
+                const bool strip_ok = !p.w_batch_stride && !p.noise && !p.bias && p.act == 1 && p.gain == 1.f && p.clamp < 0.f && !knob_live("IDE3D_MODCONV_NO_STRIP");
                 const int64_t b8s = (int64_t)pl.mblocks * cdiv(p.h, 8) * cdiv(p.w_, 16) * p.n, b4s = (int64_t)pl.mblocks * cdiv(p.h, 4) * cdiv(p.w_, 16) * p.n;
                 const int64_t b16s = (int64_t)pl.mblocks * cdiv(p.h, 16) * cdiv(p.w_, 16) * p.n;
                 auto rounds = [](int64_t blocks) { return (blocks + kNumCU - 1) / kNumCU; };
                 if (pl.big == 1) {
-                    pl.tile = (b8 >= 2 * kNumCU) ? 6 : 4;
+                    pl.tile = (b8 >= 2 * kNumCU) ? TA8x16 : TA4x16;      // 128-row blocks: at most 8 x 16 positions (16 accumulators)
                     // (a 4-wave workgroup of 4 x 16 positions is half the work at ~1.15 x the time per unit)
-                    if (pl.tile == 4 && strip_ok && b8s >= kNumCU && rounds(b8s) * 200 <= rounds(b4s) * 115) { pl.tile = 6; one_round = true; }
+                    if (pl.tile == TA4x16 && strip_ok && b8s >= kNumCU && rounds(b8s) * 200 <= rounds(b4s) * 115) { pl.tile = TA8x16; one_round = true; }
                 }
-                else if (b16 >= 2 * kNumCU) pl.tile = 7;
+                else if (b16 >= 2 * kNumCU) pl.tile = TA16x16;
                 // whole rounds of ONE 8-wave workgroup of 16 x 16 positions per CU on the strip grid (128 -> 64 in@256 at batch 1: 256 workgroups) against
                 // four-wave workgroups of 4 x 16 (a quarter of the work at ~1.15 x the time per unit; no team pairs with an odd block count)
-                else if (strip_ok && (pl.mblocks & 1) && b16s >= kNumCU && rounds(b16s) * 400 <= rounds(b4s) * 115 && !knob_live("IDE3D_MODCONV_NO_R16")) { pl.tile = 7; one_round = true; }
-                else if (strip_ok && (pl.mblocks & 1) == 0 && b8s >= kNumCU && rounds(b8s) * 100 <= rounds(b4s / 2) * 105) { pl.tile = 6; one_round = true; }
-                else if (p.h <= 16 && p.w_ <= 16 && (pl.mblocks & 1)) pl.tile = 6;       // 4^2 .. 16^2 maps with an odd block count (no team pairs): 8 x 16 positions, 8 waves: 99 / 45 / 24 us at in@16 / 8 / 4 (4 waves alone on a CU: 115 / 47 / 31; two 4-wave teams: 92 / 45 / 24)
+                else if (strip_ok && (pl.mblocks & 1) && b16s >= kNumCU && rounds(b16s) * 400 <= rounds(b4s) * 115) { pl.tile = TA16x16; one_round = true; }
+                else if (strip_ok && (pl.mblocks & 1) == 0 && b8s >= kNumCU && rounds(b8s) * 100 <= rounds(b4s / 2) * 105) { pl.tile = TA8x16; one_round = true; }
+                else if (p.h <= 16 && p.w_ <= 16 && (pl.mblocks & 1)) pl.tile = TA8x16;       // 4^2 .. 16^2 maps with an odd block count (no team pairs): 8 x 16 positions, 8 waves: 99 / 45 / 24 us at in@16 / 8 / 4 (4 waves alone on a CU: 115 / 47 / 31; two 4-wave teams: 92 / 45 / 24)
             }
-        }
-        if (pl.mode == MODE_CONV3) {
-            if (sp_rows == 8) pl.tile = 0;
-            if (sp_rows == 16) pl.tile = 3;
-            if (sp_rows == 32 && pl.big == 2) pl.tile = 12;
-        } else {
-            if (pl.big == 1 && pl.tile == 7) pl.tile = 6;            // 128-row blocks: at most 8 x 16 positions (16 accumulators)
-            if (sp_rows == 4) pl.tile = 4;
-            if (sp_rows == 8) pl.tile = 6;
-            if (sp_rows == 16 && pl.big == 2) pl.tile = 7;
-        }
-        const int sp_maxlds = knobs().sp_maxlds;
-        const int ph = (pl.tile == 4) ? 4 : (pl.tile == 0 || pl.tile == 6) ? 8 : (pl.tile == 12) ? 32 : 16;
-        const int lds = 2 * 16 * (3 * pl.parts * 2 * pl.bm + pl.parts * 2 * (ph + 2) * 18);
-        if (sp_maxlds && lds > sp_maxlds) pl.parts = 0;
-        // Row-parity pairs (modconv_split_pair_kernel): twice the positions per workgroup, 72 MFMAs per stage.  The even-row workgroups carry two
-        // stages per chunk, the odd-row ones one, so the form needs at least one whole round of even-row workgroups (one per CU) for the odd rows
-        // to fill in behind: 256 -> 128 in@128 at batch 4; 512 -> 256 in@64 (128 per parity: 215 -> 237 us) keeps the 8 x 16 form; 128-row blocks
-        // only (see the kernel).  IDE3D_MODCONV_PAIR (read per call: the tests flip it): 0 = never, 2 = wherever the form exists.
-        if (pl.parts && pl.mode == MODE_TCONV3A && kSpExclusive && !sp_rows && !sp_maxlds) {
-            const char* pe = knob_live_str("IDE3D_MODCONV_PAIR");
-            const int pair_knob = pe ? atoi(pe) : 1;
-            const bool plain = !p.w_batch_stride && !p.noise && !p.bias && p.act == 1 && p.gain == 1.f && p.clamp < 0.f && !knob_live("IDE3D_MODCONV_NO_STRIP");
-            const int64_t per_parity = (int64_t)pl.mblocks * cdiv(p.h, pl.big == 1 ? 16 : 32) * cdiv(p.w_, 16) * p.n;
-            if (plain && pair_knob && (pair_knob == 2 || (pl.big == 1 && per_parity >= kNumCU && p.cin >= 64))) {
-                pl.pair = 1; pl.tile = (pl.big == 1) ? 7 : 12; one_round = true;
+            // Row-parity pairs (modconv_split_pair_kernel): twice the positions per workgroup, 72 MFMAs per stage.  The even-row workgroups carry two
+            // stages per chunk, the odd-row ones one, so the form needs at least one whole round of even-row workgroups (one per CU) for the odd rows
+            // to fill in behind: 256 -> 128 in@128 at batch 4; 512 -> 256 in@64 (128 per parity: 215 -> 237 us) keeps the 8 x 16 form; 128-row blocks
+            // only (see the kernel).  IDE3D_MODCONV_PAIR (read per call: the tests flip it): 0 = never, 2 = wherever the form exists.
+            if (pl.mode == MODE_TCONV3A) {
+                const char* pe = knob_live_str("IDE3D_MODCONV_PAIR");
+                const int pair_knob = pe ? atoi(pe) : 1;
+                const bool plain = !p.w_batch_stride && !p.noise && !p.bias && p.act == 1 && p.gain == 1.f && p.clamp < 0.f && !knob_live("IDE3D_MODCONV_NO_STRIP");
+                const int64_t per_parity = (int64_t)pl.mblocks * cdiv(p.h, pl.big == 1 ? 16 : 32) * cdiv(p.w_, 16) * p.n;
+                if (plain && pair_knob && (pair_knob == 2 || (pl.big == 1 && per_parity >= kNumCU && p.cin >= 64))) {
+                    pl.pair = 1; pl.tile = (pl.big == 1) ? TA16x16 : T32x16; one_round = true;
+                }
             }
         }
     }
-    if (!pl.parts) pl.f16 = 0;
     if (pl.parts) {
         pl.kc = 16; pl.cchunks = cdiv(p.cin, 16);
         pl.packed_floats = sp_packed_units(pl.mblocks, pl.cchunks, pl.bm, pl.parts) * 4;
@@ -2072,15 +2022,15 @@ static void plan_conv(const ide3d_modconv_params& p, ConvPlan& pl, int arith) {
         pl.strip_floats = (int64_t)p.cin * 6 * (cdiv(p.cout, STRIP_CO) * STRIP_CO);
         pl.aux_floats += pl.strip_floats + (int64_t)p.n * p.cin * (p.h + p.w_);          // + the gathered strip inputs xs[n][cin][w + h]
     }
+    const TileShape ts = kTiles[pl.tile];
     // Strip plan (tconv_strip_kernel): the all-class transposed convolution on the h x w grid when that saves tiles, the launch needs no split-K
     // either way (the reduction kernel would finish the strip's unwritten partials) and the epilogue is the plain one of the up-sampling
     // layers (demodulation only: noise / bias / activation follow the FIR).  IDE3D_MODCONV_NO_STRIP = the (h + 1) x (w + 1) grid everywhere.
     // Shared weights only: the strip's pack / compute kernels read ONE weight tensor (per-image weights stay on the (h + 1) x (w + 1) grid).
     pl.strip = 0;
     if (pl.mode == MODE_TCONV3A && !p.w_batch_stride && !p.noise && !p.bias && p.act == 1 && p.gain == 1.f && p.clamp < 0.f && !knob_live("IDE3D_MODCONV_NO_STRIP")) {
-        const int ph = PHv[pl.tile], pw = PWv[pl.tile];
-        const int64_t t_full = (int64_t)cdiv(p.h + 1, ph) * cdiv(p.w_ + 1, pw), t_main = (int64_t)cdiv(p.h, ph) * cdiv(p.w_, pw);
-        const int64_t groups = cdiv(p.n, TIv[pl.tile]);
+        const int64_t t_full = (int64_t)cdiv(p.h + 1, ts.rows) * cdiv(p.w_ + 1, ts.cols), t_main = (int64_t)cdiv(p.h, ts.rows) * cdiv(p.w_, ts.cols);
+        const int64_t groups = cdiv(p.n, ts.images);
         auto splits = [&](int64_t tiles) { return (int64_t)pl.mblocks * tiles * groups < split_min && pl.cchunks >= 8; };
         if (pl.pair || (t_main < t_full && (one_round || (!splits(t_main) && !splits(t_full))))) {
             pl.strip = 1;
@@ -2090,12 +2040,11 @@ static void plan_conv(const ide3d_modconv_params& p, ConvPlan& pl, int arith) {
     ConvGeom& g = pl.g;
     g.tile_base[0] = 0;
     for (int c = 0; c < 4; ++c) {
-        g.tiles_x[c] = cdiv(gw[c], PWv[pl.tile]); g.tiles_y[c] = cdiv(gh[c], PHv[pl.tile]);
+        g.tiles_x[c] = cdiv(gw[c], ts.cols); g.tiles_y[c] = cdiv(gh[c], ts.rows);
         g.tile_base[c + 1] = g.tile_base[c] + (c < ncls ? g.tiles_x[c] * g.tiles_y[c] : 0);
     }
-    g.img_groups = cdiv(p.n, TIv[pl.tile]);
+    g.img_groups = cdiv(p.n, ts.images);
     g.mblocks = pl.mblocks; g.cchunks = pl.cchunks; g.oh = pl.oh; g.ow = pl.ow;
-    g.debug = mc_env().debug;
     const int64_t base_blocks = (int64_t)g.mblocks * g.tile_base[4] * g.img_groups;
     int split = 1;
     if (base_blocks < split_min && pl.cchunks >= 8) {
@@ -2106,8 +2055,6 @@ static void plan_conv(const ide3d_modconv_params& p, ConvPlan& pl, int arith) {
     }
     if (one_round) want_split = 1;
     if (want_split > 0) split = want_split < pl.cchunks ? want_split : pl.cchunks;
-    const int force_split = knobs().force_split;   // experiments
-    if (force_split > 0 && !pl.strip) split = force_split < pl.cchunks ? force_split : pl.cchunks;
     g.chunks_per_split = cdiv(pl.cchunks, split);
     g.split_k = cdiv(pl.cchunks, g.chunks_per_split);
     pl.partial_floats = (g.split_k > 1) ? (int64_t)g.split_k * p.n * p.cout * pl.oh * pl.ow : 0;
@@ -2119,81 +2066,81 @@ static void launch_tiles(const ide3d_modconv_params& p, const ConvPlan& pl, cons
     const unsigned nblocks = (unsigned)((int64_t)g.mblocks * g.tile_base[4] * g.img_groups * g.split_k);
     if constexpr (MODE == MODE_TCONV3A) {
         if constexpr (BIG != 0) {
-            if (pl.tile == 11) { if constexpr (BIG == 2) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 8, 16, 4, 8>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g); }
-            else if (pl.tile == 8) { if constexpr (BIG == 1) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 8, 16, 8>), dim3(nblocks), dim3(512), 0, st, p, wp, partial, g); }
-            else if (pl.tile == 9) { if constexpr (BIG == 2) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 16, 16, 8>), dim3(nblocks), dim3(512), 0, st, p, wp, partial, g); }
-            else if (pl.tile == 6) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 8, 16>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g);
-            else if (pl.tile == 7) { if constexpr (BIG == 2) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 16, 16>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g); }
+            if (pl.tile == TA8x16) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 8, 16>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g);
+            else if (pl.tile == TA16x16) { if constexpr (BIG == 2) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 16, 16>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g); }
             else hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 4, 16>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g);
         }
     } else
-    if (pl.tile == 5) {
+    if (pl.tile == TFLAT128) {
         if constexpr (MODE == MODE_CONV1)
             hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 1, 128>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g);
     }
-    else if (pl.tile == 0) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 8, 16>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g);
-    else if (pl.tile == 1) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 2, 8, 8>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g);
-    else if (pl.tile == 2) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 8, 4, 4>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g);
+    else if (pl.tile == T8x16) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 8, 16>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g);
+    else if (pl.tile == T2x8x8) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 2, 8, 8>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g);
+    else if (pl.tile == T8x4x4) hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 8, 4, 4>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g);
     else if constexpr (BIG == 1 && MODE != MODE_CONV1 && MODE != MODE_CONV3S2)
         hipLaunchKernelGGL((modconv_kernel<MODE, BIG, 1, 16, 16>), dim3(nblocks), dim3(256), 0, st, p, wp, partial, g);
 }
 
 
-constexpr int kSpW8Default = kSpExclusive ? 2 : 0;
 // Waves per workgroup (per team) of the split-bf16 launch of a plan, and whether two 4-wave teams share a workgroup: the ONE place that decides
 // it (launch_split launches what this says; ide3d_modconv_plan reports it).
-// 8-wave forms (two of this workgroup's waves per SIMD: exclusive residency without giving up the second wave): IDE3D_SP_W8 bit 0 =
-// 3x3 on 8 x 16 pixels, bit 1 = all-class transposed 3x3 (8 x 16 positions at 128 rows, 16 x 16 at 64 rows); IDE3D_MODCONV_SP_W4 = 4 waves
-// on the 16 x 16 tiles as well; IDE3D_SP_NO_TEAMS = no two-team workgroups.
 struct SpForm { int waves; bool teams; };
 static SpForm sp_form(const ConvPlan& pl) {
-    const int w8 = knobs().sp_w8 >= 0 ? knobs().sp_w8 : kSpW8Default;
-    const bool no_teams = knobs().sp_no_teams, no8 = knobs().sp_w4;
-    const bool conv3 = (pl.mode == MODE_CONV3);
-    if (pl.pair) return {8, false};
-    // 64-row blocks, even block count: two teams per workgroup (128-row blocks: LDS does not fit twice in bf16x6, and in f16x3 the teams measured 233 vs 217 us at 512 -> 256 in@64)
-    if (pl.tile == 4) return {4, !conv3 && pl.big == 2 && kSpExclusive && !no_teams && (pl.mblocks & 1) == 0};
-    if (pl.tile == 0 || pl.tile == 6) return {(w8 & (conv3 ? 1 : 2)) ? 8 : 4, false};
-    if (pl.tile == 12) return {8, false};
-    // 16 x 16 pixels: 8 waves with time-shifted roles (3x3: 333 vs 352 us at 128 -> 128 @256, 321 vs 335 at 256 -> 256 @128, bf16x6)
-    return {(!no8 && (conv3 || (w8 & 2))) ? 8 : 4, false};
+    if constexpr (kSpExclusive) {
+        // 64-row blocks, even block count: two teams per workgroup (128-row blocks: LDS does not fit twice in bf16x6, and in f16x3 the teams measured 233 vs 217 us at 512 -> 256 in@64)
+        if (pl.tile == TA4x16) return {4, pl.big == 2 && (pl.mblocks & 1) == 0};
+        // every other tile (row-parity pairs included) on 8 waves, two of this workgroup's waves per SIMD: exclusive residency without giving up
+        // the second wave; the 3x3 8 x 16-pixel tile stays on 4 waves
+        return {pl.tile == T8x16 ? 4 : 8, false};
+    } else {
+        // shared SIMDs: 4-wave workgroups, two per CU; the 3x3 16 x 16-pixel tiles keep 8 waves with time-shifted roles (333 vs 352 us at
+        // 128 -> 128 @256, 321 vs 335 at 256 -> 256 @128, bf16x6)
+        return {(pl.tile == T16x16 || pl.tile == T32x16) ? 8 : 4, false};
+    }
 }
+// Each build instantiates only the forms it can launch.
 template <int MODE, int BIG, int PARTS, int F16 = 0>
 static void launch_split(const ide3d_modconv_params& p, const ConvPlan& pl, const float* wp, float* partial, hipStream_t st) {
     const ConvGeom& g = pl.g;
     const unsigned nblocks = (unsigned)((int64_t)g.mblocks * g.tile_base[4] * g.img_groups * g.split_k);
     const u32x4* wu = reinterpret_cast<const u32x4*>(wp);
     const float* ru = F16 ? wp + pl.packed_floats + (int64_t)pl.mblocks * pl.bm : nullptr;       // [row scale | row unscale] behind the packed weights
-    const SpForm form = sp_form(pl);
-    if (pl.pair) {
-        if constexpr (MODE == MODE_TCONV3A) IDE3D_EXCL_LAUNCH((modconv_split_pair_kernel<BIG, (BIG == 1 ? 16 : 32), PARTS, F16>), dim3(2 * nblocks), 512, 0, st, p, wu, partial, g, ru);
-        return;
-    }
-    if (pl.tile == 4) {
-        if constexpr (MODE == MODE_TCONV3A) {
-            if constexpr (BIG == 2) {
-                if (form.teams) {
-                    IDE3D_EXCL_LAUNCH((modconv_split_teams_kernel<MODE, BIG, 4, PARTS, 2, F16>), dim3(nblocks / 2), 512, 0, st, p, wu, partial, g, ru);
-                    return;
-                }
-            }
-            IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 4, PARTS, 2, 4, F16>), dim3(nblocks), 256, 0, st, p, wu, partial, g, ru);
+    if constexpr (kSpExclusive) {
+        if (pl.pair) {
+            if constexpr (MODE == MODE_TCONV3A) IDE3D_EXCL_LAUNCH((modconv_split_pair_kernel<BIG, (BIG == 1 ? 16 : 32), PARTS, F16>), dim3(2 * nblocks), 512, 0, st, p, wu, partial, g, ru);
         }
-    }
-    else if (pl.tile == 0 || pl.tile == 6) {
-        // 3x3: one weight buffer, two workgroups per CU (measured 338 vs 355 us at 512 -> 512 @64, bf16x6); IDE3D_MODCONV_SP_WBUF2 = old form
-        const bool one_wbuf = !knobs().sp_wbuf2 && !kSpExclusive;
-        if (form.waves == 8) IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 8, PARTS, 2, 8, F16>), dim3(nblocks), 512, 0, st, p, wu, partial, g, ru);
-        else if (one_wbuf && MODE == MODE_CONV3) IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE_CONV3, BIG, 8, PARTS, 1, 4, F16>), dim3(nblocks), 256, 0, st, p, wu, partial, g, ru);
-        else IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 8, PARTS, 2, 4, F16>), dim3(nblocks), 256, 0, st, p, wu, partial, g, ru);
-    }
-    else if (pl.tile == 12) {
-        if constexpr (MODE == MODE_CONV3 && BIG == 2)
-            IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 32, PARTS, 2, 8, F16>), dim3(nblocks), 512, 0, st, p, wu, partial, g, ru);
-    }
-    else if constexpr (MODE == MODE_CONV3 || BIG == 2) {
-        if (form.waves == 8) IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 16, PARTS, 2, 8, F16>), dim3(nblocks), 512, 0, st, p, wu, partial, g, ru);
-        else IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 16, PARTS, 2, 4, F16>), dim3(nblocks), 256, 0, st, p, wu, partial, g, ru);
+        else if (pl.tile == TA4x16) {
+            if constexpr (MODE == MODE_TCONV3A) {
+                if (sp_form(pl).teams) { if constexpr (BIG == 2) IDE3D_EXCL_LAUNCH((modconv_split_teams_kernel<MODE, BIG, 4, PARTS, 2, F16>), dim3(nblocks / 2), 512, 0, st, p, wu, partial, g, ru); }
+                else IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 4, PARTS, 2, 4, F16>), dim3(nblocks), 256, 0, st, p, wu, partial, g, ru);
+            }
+        }
+        else if (pl.tile == T8x16) {
+            if constexpr (MODE == MODE_CONV3) IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 8, PARTS, 2, 4, F16>), dim3(nblocks), 256, 0, st, p, wu, partial, g, ru);
+        }
+        else if (pl.tile == TA8x16) {
+            if constexpr (MODE == MODE_TCONV3A) IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 8, PARTS, 2, 8, F16>), dim3(nblocks), 512, 0, st, p, wu, partial, g, ru);
+        }
+        else if (pl.tile == T32x16) {
+            if constexpr (MODE == MODE_CONV3 && BIG == 2) IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 32, PARTS, 2, 8, F16>), dim3(nblocks), 512, 0, st, p, wu, partial, g, ru);
+        }
+        else if constexpr (MODE == MODE_CONV3 || BIG == 2)          // T16x16, TA16x16
+            IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 16, PARTS, 2, 8, F16>), dim3(nblocks), 512, 0, st, p, wu, partial, g, ru);
+    } else {
+        if (pl.tile == TA4x16) {
+            if constexpr (MODE == MODE_TCONV3A) IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 4, PARTS, 2, 4, F16>), dim3(nblocks), 256, 0, st, p, wu, partial, g, ru);
+        }
+        // 3x3: one weight buffer, two workgroups per CU (measured 338 vs 355 us at 512 -> 512 @64, bf16x6)
+        else if (pl.tile == T8x16) {
+            if constexpr (MODE == MODE_CONV3) IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 8, PARTS, 1, 4, F16>), dim3(nblocks), 256, 0, st, p, wu, partial, g, ru);
+        }
+        else if (pl.tile == TA8x16) {
+            if constexpr (MODE == MODE_TCONV3A && BIG == 2) IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 8, PARTS, 2, 4, F16>), dim3(nblocks), 256, 0, st, p, wu, partial, g, ru);
+        }
+        else if (pl.tile == T16x16) {
+            if constexpr (MODE == MODE_CONV3 && BIG == 1) IDE3D_EXCL_LAUNCH((modconv_split_kernel<MODE, BIG, 16, PARTS, 2, 8, F16>), dim3(nblocks), 512, 0, st, p, wu, partial, g, ru);
+        }
     }
 }
 
@@ -2201,8 +2148,7 @@ static void launch_split(const ide3d_modconv_params& p, const ConvPlan& pl, cons
 
 // per-image 1x1 convolution without modulation / noise, linear, <= 32 or 161..192 outputs: the dual heads
 static bool head_split_applies(const ide3d_modconv_params& p, int arith) {
-    const bool off = ide3d::knobs().head_fp32;
-    return !off && arith != 1 && p.k == 1 && p.mode == 0 && p.w_batch_stride > 0 && !p.styles && !p.dcoefs && !p.noise && p.act == 1 &&
+    return arith != 1 && p.k == 1 && p.mode == 0 && p.w_batch_stride > 0 && !p.styles && !p.dcoefs && !p.noise && p.act == 1 &&
            (p.cout <= 32 || (p.cout > 160 && p.cout <= 192)) && p.cin >= 32 &&
            (int64_t)p.n * ide3d::cdiv64((int64_t)p.h * p.w_, 32 * ide3d::head_waves(p.cout <= 32 ? 1 : 6)) >= ide3d::kNumCU;     // fewer workgroups: the serial K loop of a workgroup is exposed
                                                                               // (512 channels @32^2 / @64^2: 54 us against 16 / 40 us on the fp32 loop)
@@ -2210,16 +2156,14 @@ static bool head_split_applies(const ide3d_modconv_params& p, int arith) {
 
 // per-image linear 1x1 convolution on a small map: one launch of fp32 FMAs (head_small_kernel) in every arithmetic
 static bool head_small_applies(const ide3d_modconv_params& p) {
-    const bool no_small = ide3d::knobs().head_no_small;
-    return !no_small && p.k == 1 && p.mode == 0 && p.w_batch_stride > 0 && !p.styles && !p.dcoefs && !p.noise && p.act == 1 && (int64_t)p.h * p.w_ <= 256 &&
+    return p.k == 1 && p.mode == 0 && p.w_batch_stride > 0 && !p.styles && !p.dcoefs && !p.noise && p.act == 1 && (int64_t)p.h * p.w_ <= 256 &&
            p.y_pitch == 0 && p.n <= 65535;
 }
 // resident-weights form of the split heads: whole K in LDS (K = 64 / 128 at <= 32 rows, K = 128 at 192 rows), >= 2 tiles of 32 pixels per wave
 static bool head_resident_applies(const ide3d_modconv_params& p) {
-    const bool no_resident = ide3d::knobs().head_no_resident;
     const int mt = p.cout <= 32 ? 1 : 6, cchunks = ide3d::cdiv(p.cin, 16);
     const int hw = p.h * p.w_, wgs_img = ide3d::kNumCU / p.n, tiles32 = hw / 32;
-    return !no_resident && ide3d::kSpExclusive && p.cin % 16 == 0 && hw % 32 == 0 && wgs_img >= 1 && p.y_pitch == 0 &&
+    return ide3d::kSpExclusive && p.cin % 16 == 0 && hw % 32 == 0 && wgs_img >= 1 && p.y_pitch == 0 &&
            ((mt == 1 && (cchunks == 4 || cchunks == 8)) || (mt == 6 && cchunks == 8)) && tiles32 >= 2 * wgs_img * 8;
 }
 
@@ -2394,10 +2338,10 @@ extern "C" int ide3d_modconv2d_heads(const ide3d_modconv_params* pp, const ide3d
     if (arith == 16 && !p.x_amax) arith = 6;
     if (arith != 6) return no_kernel("the fused form exists for bf16x6 only");
     ConvPlan pl; plan_conv(p, pl, arith);
-    if (pl.parts != 3 || pl.f16 || pl.mode != MODE_CONV3 || pl.pair || pl.g.split_k != 1 || pl.g.mblocks != 1 || pl.bm != p.cout || TIv[pl.tile] != 1)
+    if (pl.parts != 3 || pl.f16 || pl.mode != MODE_CONV3 || pl.pair || pl.g.split_k != 1 || pl.g.mblocks != 1 || pl.bm != p.cout || kTiles[pl.tile].images != 1)
         return no_kernel("the layer's plan does not hold all channels of a tile in one workgroup");
-    const bool tile16 = pl.big == 1 && p.cout == 128 && pl.tile != 0 && pl.tile != 4 && pl.tile != 6 && pl.tile != 12 && sp_form(pl).waves == 8;
-    const bool tile32 = pl.big == 2 && p.cout == 64 && pl.tile == 12;
+    const bool tile16 = pl.big == 1 && p.cout == 128 && pl.tile == T16x16 && sp_form(pl).waves == 8;
+    const bool tile32 = pl.big == 2 && p.cout == 64 && pl.tile == T32x16;
     const int ph = tile32 ? 32 : 16;
     if (!(tile16 || tile32) || p.h % ph != 0 || p.w_ % 16 != 0) return no_kernel("no fused instance for this tile");
     // the heads as ide3d_modconv2d would see them
@@ -2457,14 +2401,14 @@ extern "C" int ide3d_modconv_plan(const ide3d_modconv_params* pp, ide3d_modconv_
     if (arith_eff == 16 && !p.x_amax) arith_eff = 6;
     ConvPlan pl; plan_conv(p, pl, arith_eff);
     const int64_t blocks = (int64_t)pl.g.mblocks * pl.g.tile_base[4] * pl.g.img_groups * pl.g.split_k * (pl.pair ? 2 : 1);
-    out->tile_h = PHv[pl.tile]; out->tile_w = PWv[pl.tile]; out->images_per_tile = TIv[pl.tile];
+    out->tile_h = kTiles[pl.tile].rows; out->tile_w = kTiles[pl.tile].cols; out->images_per_tile = kTiles[pl.tile].images;
     out->rows = pl.bm; out->parts = pl.parts; out->f16 = pl.f16; out->split_k = pl.g.split_k; out->strip = pl.strip;
     out->transposed_all_class = (pl.mode == MODE_TCONV3A);
     if (pl.parts) {
         const SpForm f = sp_form(pl);
         out->kind = f.teams ? IDE3D_PLAN_SPLIT_TEAMS : IDE3D_PLAN_SPLIT; out->waves = f.teams ? 8 : f.waves; out->workgroups = f.teams ? blocks / 2 : blocks;
     } else {
-        out->kind = IDE3D_PLAN_FP32; out->waves = (pl.tile == 8 || pl.tile == 9) ? 8 : 4; out->workgroups = blocks;
+        out->kind = IDE3D_PLAN_FP32; out->waves = 4; out->workgroups = blocks;      // the fp32 loop: 4 waves
     }
     return IDE3D_OK;
 }

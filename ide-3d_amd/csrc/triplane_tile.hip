@@ -868,7 +868,6 @@ bool launch_triplane_tile(const float* planes, const int64_t* s, int n, int C, i
     if (group < 1) return false;
     const int chunks = steps / TT_DS;
     const int tiles_per_image = (rays_h / TT_EDGE) * (rays_w / TT_EDGE);
-    const int env_segs = knobs().gather_segs;
     // IDE3D_GATHER_PC=0: the 4-wave kernel with two workgroups per CU (rounds 1-2)
     const int pc_form = knobs().gather_pc;      // 4 / 8: blending waves
     const bool use_pc = pc_form == 4 || pc_form == 8;
@@ -877,7 +876,6 @@ bool launch_triplane_tile(const float* planes, const int64_t* s, int n, int C, i
         // depth segments: enough workgroups for >= 2 per CU in flight on every CU, as few as possible otherwise
         int segs = 1;
         while (segs < chunks && ((int64_t)cnt * tiles_per_image * segs < 2 * kNumCU || chunks % segs)) ++segs;
-        if (env_segs > 0 && chunks % env_segs == 0) segs = env_segs;
         TileArgs a;
         a.planes = planes + (int64_t)n0 * s[0];
         a.coords = coords + (int64_t)n0 * m * 3;
@@ -890,7 +888,6 @@ bool launch_triplane_tile(const float* planes, const int64_t* s, int n, int C, i
             // producer / consumer form: one 8-wave workgroup per CU; depth segments only until every CU has one
             int ps = 1;
             while (ps < chunks && ((int64_t)cnt * tiles_per_image * ps < kNumCU || chunks % ps)) ++ps;
-            if (env_segs > 0 && chunks % env_segs == 0) ps = env_segs;
             a.segs = ps; a.chunks_per_seg = chunks / ps;
             const dim3 grid((unsigned)(cnt * tiles_per_image * ps));
             if (pc_form == 8) hipLaunchKernelGGL((triplane_sample_tile_pc_kernel<8, 2>), grid, dim3(1024), 0, st, a);
