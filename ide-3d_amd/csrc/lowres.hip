@@ -575,7 +575,33 @@ struct Layout {
     int rin[MAX_LAYERS];
 };
 
-// how many leading layers of the group fit (LDS: all images' input slots of a K slice beside the weight slice)
+// LDS scratch of phase R behind the weight slice, the largest band's: red[npos][32], outs[npix][33], par[96 + npix] floats (r_item's carve-up)
+int64_t r_scratch_bytes(int up, int rin, int bands) {
+    const int R = up == 2 ? 2 * rin : rin, T = 2 * rin + 1, width = up == 2 ? T : R;
+    int64_t most = 0;
+    for (int band = 0; band < bands; ++band) {
+        const int y0 = band * R / bands, y1 = (band + 1) * R / bands, npix = (y1 - y0) * R;
+        const int ry0 = up == 2 ? std::max(y0 - 1, 0) : y0, ry1 = up == 2 ? std::min(y1 + 2, T) : y1;
+        const int64_t npos = (int64_t)(ry1 - ry0) * width;
+        most = std::max<int64_t>(most, 4 * (((npos * BC + 3) & ~int64_t(3)) + ((npix * 33 + 3) & ~int64_t(3)) + 96 + npix));
+    }
+    return most;
+}
+
+// row bands per (image, channel block) of a layer's phase R: enough items to fill the chip (an up layer's band also reads 3 halo rows of
+// every partial slab, so its bands keep >= 4 rows: 2-row bands read 2.5 x the slabs, 31.6 -> us at 16^2 -> 32^2, batch 1), then more until
+// the band's scratch fits behind the weight slice and its noise row fits r_item's two loads per thread.  0: not even 1-row bands fit.
+int r_bands(int n, int CB, int up, int rin, int parts) {
+    const int res = up == 2 ? 2 * rin : rin;
+    const int64_t room = LDS_BYTES - (int64_t)w_units(parts) * 16;
+    int bands = 1;
+    while (bands * 2 <= res && (int64_t)n * CB * bands * 2 <= 2 * kNumCU && (up != 2 || res / (bands * 2) >= 4)) bands *= 2;
+    for (; bands <= res; ++bands)
+        if (r_scratch_bytes(up, rin, bands) <= room && (res + bands - 1) / bands * res <= 2 * THREADS) return bands;
+    return 0;
+}
+
+// how many leading layers of the group fit (LDS: all images' input slots of a K slice beside the weight slice; phase R's band scratch)
 int layers_that_fit(int n, int C, int res0, const int32_t* ups, int nlayers, int parts) {
     if (n < 1 || C < KS || C % KS != 0 || res0 < 2) return 0;
     int res = res0, fit = 0;
@@ -585,6 +611,7 @@ int layers_that_fit(int n, int C, int res0, const int32_t* ups, int nlayers, int
         if (ups[l] == 2) res *= 2; else if (ups[l] != 1) break;
         const int64_t rows = (int64_t)n * (ups[l] == 2 ? (rin + 1) * (rin + 1) : res * res);
         if (rows > 1024 || (int64_t)n * (2 * rin + 1) * (2 * rin + 1) >= (1 << 24)) break;
+        if (r_bands(n, C / BC, ups[l], rin, parts) == 0) break;
         ++fit;
     }
     return fit;
@@ -667,11 +694,9 @@ int launch_group(const ide3d_lowres_params& p, hipStream_t st) {
         D.nslot_in = (rin + 2) * (rin + 2); D.nslot_out = (res + 2) * (res + 2);
         D.npos = L.up == 2 ? (rin + 1) * (rin + 1) : res * res;
         D.outpix = L.up == 2 ? (2 * rin + 1) * (2 * rin + 1) : res * res;
-        // row bands of phase R: enough items to fill the chip; an up layer's band also reads 3 halo rows of every partial slab, so its bands
-        // keep >= 4 rows (2-row bands read 2.5 x the slabs: 31.6 -> us at 16^2 -> 32^2, batch 1)
-        int bands = 1;
-        while (bands * 2 <= res && g.n * g.CB * bands * 2 <= 2 * kNumCU && (L.up != 2 || res / (bands * 2) >= 4)) bands *= 2;
-        D.bands = bands;
+        D.bands = r_bands(g.n, g.CB, L.up, rin, PARTS);
+        IDE3D_CHECK_ARG(D.bands > 0 && r_scratch_bytes(L.up, rin, D.bands) <= LDS_BYTES - w_units(PARTS) * 16,
+                        "lowres_group: layer %d: phase R scratch does not fit LDS beside the weight slice", l);
         D.img_pad_in = img_pad(PARTS, D.nslot_in); D.img_pad_out = img_pad(PARTS, D.nslot_out);
         D.wpt = waves_per_tile((g.n * D.npos + 31) / 32);
         D.first = (l == 0);
@@ -727,6 +752,19 @@ extern "C" int32_t ide3d_lowres_layers_supported(int32_t n, int32_t C, int32_t r
     const int parts = resolve_parts(arith);
     if (parts == 0 || !ups) return 0;
     return layers_that_fit(n, C, res0, ups, nlayers, parts);
+}
+
+extern "C" int32_t ide3d_lowres_phase_r_plan(int32_t n, int32_t C, int32_t res0, const int32_t* ups, int32_t nlayers, int32_t arith,
+                                             int32_t* bands, int64_t* scratch_bytes) {
+    const int parts = resolve_parts(arith);
+    if (parts == 0 || !ups) return 0;
+    const int fit = layers_that_fit(n, C, res0, ups, nlayers, parts);
+    for (int l = 0, rin = res0; l < fit; rin = ups[l] == 2 ? 2 * rin : rin, ++l) {
+        const int b = r_bands(n, C / BC, ups[l], rin, parts);
+        if (bands) bands[l] = b;
+        if (scratch_bytes) scratch_bytes[l] = r_scratch_bytes(ups[l], rin, b);
+    }
+    return fit;
 }
 
 extern "C" int64_t ide3d_lowres_workspace_bytes(const ide3d_lowres_params* pp) {

@@ -323,7 +323,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_modconv2d', 'ide3d_modconv2d_heads', 'ide3d_modconv_workspace_bytes', 'ide3d_modconv_plan', 'ide3d_set_conv_arithmetic', 'ide3d_get_conv_arithmetic', 'ide3d_frame_u8', 'ide3d_sphere_points', 'ide3d_cam2world', 'ide3d_style_demod', 'ide3d_fold_heads',
     'ide3d_style_demod_batch', 'ide3d_fold_heads_batch',
     'ide3d_skip_upsample_add_cl', 'ide3d_bilinear_up2_split', 'ide3d_mapping', 'ide3d_mapping_workspace_bytes', 'ide3d_mapping_supported',
-    'ide3d_lowres_layers_supported', 'ide3d_lowres_workspace_bytes', 'ide3d_lowres_group',
+    'ide3d_lowres_layers_supported', 'ide3d_lowres_phase_r_plan', 'ide3d_lowres_workspace_bytes', 'ide3d_lowres_group',
 )
 
 
@@ -1448,6 +1448,14 @@ class LowresPlugin:
     def layers_supported(n, C, res0, ups, arith=0):
         arr = (ctypes.c_int32 * len(ups))(*[int(u) for u in ups])
         return int(load().ide3d_lowres_layers_supported(int(n), int(C), int(res0), arr, len(ups), int(arith)))
+
+    @staticmethod
+    def phase_r_plan(n, C, res0, ups, arith=0):
+        """[(row bands, LDS scratch bytes of the largest band)] of phase R for each layer the group accepts (host only)"""
+        arr = (ctypes.c_int32 * len(ups))(*[int(u) for u in ups])
+        bands, scratch = (ctypes.c_int32 * len(ups))(), (ctypes.c_int64 * len(ups))()
+        fit = int(load().ide3d_lowres_phase_r_plan(int(n), int(C), int(res0), arr, len(ups), int(arith), bands, scratch))
+        return [(int(bands[l]), int(scratch[l])) for l in range(fit)]
 
     @staticmethod
     def persistent_default():

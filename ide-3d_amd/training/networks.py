@@ -201,7 +201,7 @@ def _styles_and_dcoefs(affine, w, weight, demodulate):
         hit = _take_prefetched(affine, w)
         if hit is not None:
             return hit
-    if (_inference_on_gpu(w, affine.weight, weight) and w.ndim == 2 and w.stride(1) == 1 and affine.activation == 'linear'
+    if (_inference_on_gpu(w, affine.weight, affine.bias, weight) and w.ndim == 2 and w.stride(1) == 1 and affine.activation == 'linear'
             and affine.bias is not None and _style_init()):
         return _style_plugin.style_demod(w, affine.weight, affine.bias, affine.weight_gain, affine.bias_gain,
                                          _wsq_t(weight) if demodulate else None)
@@ -283,6 +283,17 @@ def _inference_on_gpu(*tensors):
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
         return False
     return True
+
+
+def _layer_params(lay):
+    """What the HIP launches of a SynthesisLayer read by pointer, directly or through a cached product (styles and dcoefs, the scaled noise):
+    a fast path that takes them must decline when one of them requires grad."""
+    return (lay.weight, lay.bias, lay.affine.weight, lay.affine.bias, getattr(lay, 'noise_strength', None), getattr(lay, 'noise_const', None))
+
+
+def _head_params(torgb, toseg):
+    """The same for the dual heads (folded weights, concatenated biases)."""
+    return tuple(t for h in (torgb, toseg) for t in (h.weight, h.bias, h.affine.weight, h.affine.bias))
 
 
 @misc.profiled_function
@@ -421,7 +432,7 @@ def _modconv_bias_act(x, weight, styles, demodulate, noise2d, noise_strength, bi
     Returns None when the fused kernel does not apply."""
     cout, cin, kh, kw = weight.shape
     if not (use_hip_modconv and kh == kw and kh in (1, 3) and act in ('linear', 'lrelu')
-            and _inference_on_gpu(x, weight, styles, bias) and _modconv_init()):
+            and _inference_on_gpu(x, weight, styles, bias, noise2d) and _modconv_init()):
         return None
     spec = bias_act.activation_funcs[act]
     if demodulate and dcoefs is None:
@@ -437,7 +448,8 @@ def _modconv_bias_act(x, weight, styles, demodulate, noise2d, noise_strength, bi
 def _folded_head_weights(torgb, toseg, w):
     """Per-image 1x1 weights [N, Co_rgb + Co_seg, Cin, 1, 1] of the two heads with their styles folded in (ONE launch of
     csrc/style.hip), or None when the HIP path does not apply."""
-    if not (w.ndim == 2 and w.stride(1) == 1 and torgb.weight.shape[2] == 1 and _inference_on_gpu(w, torgb.weight, toseg.weight)
+    if not (w.ndim == 2 and w.stride(1) == 1 and torgb.weight.shape[2] == 1
+            and _inference_on_gpu(w, torgb.weight, toseg.weight, torgb.affine.weight, torgb.affine.bias, toseg.affine.weight, toseg.affine.bias)
             and _style_init()):
         return None
     return _style_plugin.fold_heads(w, torgb.affine.weight_gain,
@@ -478,7 +490,7 @@ def _dual_head(x, torgb, toseg, w, wcat=None):
     [N, Cout_rgb + Cout_seg, Cin, 1, 1] (tiny) and the activation tensor x is read from HBM once.
     Inference on device tensors only; returns None otherwise.  `wcat`: the folded weights, when the caller already has them."""
     if not (use_hip_modconv and torgb.weight.shape[2] == 1 and torgb.conv_clamp == toseg.conv_clamp
-            and _inference_on_gpu(x, w, torgb.weight, toseg.weight) and _modconv_init()):
+            and _inference_on_gpu(x, w, *_head_params(torgb, toseg)) and _modconv_init()):
         return None
     n = x.shape[0]
     if w.shape[0] != n:
@@ -503,7 +515,7 @@ def _conv1_dual_head(block, x, w1, w_shared, want_x, noise_mode='random', gain=1
     if not (use_hip_modconv and type(c1) is SynthesisLayer and c1.up == 1 and c1.padding == 1 and c1.weight.shape[2:] == (3, 3)
             and c1.activation in ('linear', 'lrelu') and tr.weight.shape[2] == 1 and tr.conv_clamp == ts.conv_clamp
             and x.ndim == 4 and x.shape[0] == w1.shape[0] == w_shared.shape[0]
-            and _inference_on_gpu(x, w1, w_shared, c1.weight, c1.bias, tr.weight, ts.weight)
+            and _inference_on_gpu(x, w1, w_shared, *_layer_params(c1), *_head_params(tr, ts))
             and not _hooked(block, c1, tr, ts) and _modconv_init()):
         return None
     from torch_utils import hip_plugin
@@ -562,7 +574,7 @@ def lowres_group_forward(blocks, ws_per_block, noise_mode='const', force_fp32=Fa
     and `ToRGBLayer` (:670-713) in inference: const noise or none, fp32 blocks, 'skip' architecture, 3x3 layers of one width C, lrelu, the
     [1, 3, 3, 1] resample filter, products in the bf16x6 / bf16x3 arithmetic (`hip_plugin.conv_arithmetic`).  Anything else — autograd, a
     forward hook on one of the blocks or layers (viz/renderer.py:437), random noise, fp16 blocks, other arithmetics, `IDE3D_NO_LOWRES_GROUP` —
-    keeps the per-layer path: returns None.
+    keeps the per-layer path: returns None.  With grad enabled the group ends in front of the first block that has a tensor requiring grad.
     Returns (x, img, seg, next_block, resume): the running tensors in front of `blocks[next_block]`; `resume` = x is already the output of that
     block's conv0 (the group may end in the middle of a block: `forward(..., _resume_after_conv0=True)`)."""
     if os.environ.get('IDE3D_NO_LOWRES_GROUP') or not use_hip_modconv or other_kwargs or noise_mode not in ('const', 'none'):
@@ -589,6 +601,11 @@ def lowres_group_forward(blocks, ws_per_block, noise_mode='const', force_fp32=Fa
               and blk.torgb.conv_clamp == blk.toseg.conv_clamp and blk.torgb.weight.shape[2] == 1 and blk._filter_is_1331()
               and blk.resolution == b0.resolution << bi
               and not _hooked(blk, blk.conv1, blk.torgb, blk.toseg, *([blk.conv0] if bi else [])))
+        # the launch reads the block's parameters, styles and heads by pointer: a block with anything to differentiate stays out (and so do the
+        # blocks after it); a block in front of it may still run here
+        if ok and torch.is_grad_enabled():
+            ok = _inference_on_gpu(ws_per_block[bi], *([blk.const] if bi == 0 else _layer_params(blk.conv0)), *_layer_params(blk.conv1),
+                                   *_head_params(blk.torgb, blk.toseg))
         if not ok:
             break
         for name in (('conv1',) if bi == 0 else ('conv0', 'conv1')):
@@ -894,7 +911,7 @@ class SynthesisLayer(torch.nn.Module):
         act_clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
 
         if (self.up == 2 and use_hip_modconv and self.weight.shape[2] == 3 and self.padding == 1
-                and _inference_on_gpu(x, self.weight, styles, self.bias) and _modconv_init()):
+                and _inference_on_gpu(x, self.weight, styles, self.bias, noise) and _modconv_init()):
             # up-sampling layer, MI355X inference path (same strategy as conv2d_resample.py:112-129): transposed
             # 3x3 stride-2 conv as a parity-class implicit GEMM (demodulation fused), then the 4x4 FIR with gain 4.
             dcoefs = dcoefs_pre if dcoefs_pre is not None else _demod_coefs(self.weight, styles)
@@ -1069,7 +1086,8 @@ class SegSynthesisBlock(torch.nn.Module):
         ref = x if x is not None else fused_heads[0]               # (x is None: the fused launch did not write it)
         img_lo = seg_lo = None
         heads_follow = (self.is_last or self.architecture == 'skip') and not disable_rgb
-        if heads_follow and _inference_on_gpu(ref) and img is not None and seg is not None and img.size(-1) * 2 == ref.size(-1):
+        if (heads_follow and _inference_on_gpu(ref, img, seg, w_shared, *_head_params(self.torgb, self.toseg)) and img is not None and seg is not None
+                and img.size(-1) * 2 == ref.size(-1)):
             img_lo, seg_lo, img, seg = img, seg, None, None       # defer: upsample + add in one launch (_accumulate)
         else:
             img = self._merge_skip(img, ref)

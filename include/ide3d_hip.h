@@ -559,6 +559,10 @@ typedef struct ide3d_lowres_params {
 } ide3d_lowres_params;
 /* number of leading layers (ups[l] in {1, 2}) of a group that starts at res0 which ide3d_lowres_group accepts for this batch size */
 int32_t ide3d_lowres_layers_supported(int32_t n, int32_t C, int32_t res0, const int32_t* ups, int32_t nlayers, int32_t arith);
+/* host only: for each of those layers, phase R's row bands per (image, channel block) and the LDS bytes its largest band needs beside the weight
+ * slice (bands / scratch_bytes: nlayers entries each, or NULL); returns the same count as ide3d_lowres_layers_supported */
+int32_t ide3d_lowres_phase_r_plan(int32_t n, int32_t C, int32_t res0, const int32_t* ups, int32_t nlayers, int32_t arith,
+                                  int32_t* bands, int64_t* scratch_bytes);
 int64_t ide3d_lowres_workspace_bytes(const ide3d_lowres_params* p);     /* only n, C, res0, nlayers, arith and layers[].up are read */
 int ide3d_lowres_group(const ide3d_lowres_params* p, void* stream);
 

@@ -148,3 +148,37 @@ def test_lowres_group_extent_by_batch_size():
     assert fit(1, arith=3) >= 6          # bf16x3: two pieces per value, more room
     assert fit(4, arith=1) == 0 and fit(4, arith=16) == 0          # exact fp32 products / f16x3 have no such form: per-layer path
     assert hip_plugin.LowresPlugin.layers_supported(4, 500, 4, ups, 6) == 0          # C must be a multiple of 32
+
+
+def _fill_rule_bands(n, C, up, rin):
+    """phase R's row bands by the fill rule alone (enough (image, channel block, band) items for two per CU, >= 4-row bands for up layers)"""
+    res, bands = (2 * rin if up == 2 else rin), 1
+    while bands * 2 <= res and n * (C // 32) * bands * 2 <= 2 * CU and (up != 2 or res // (bands * 2) >= 4):
+        bands *= 2
+    return bands
+
+
+def test_lowres_phase_r_scratch_fits_beside_the_weight_slice():
+    """`ide3d_lowres_phase_r_plan` (host only): phase R's band scratch red[npos][32] + outs[npix][33] + par[96 + npix] floats sits behind the
+    weight slice, in 160 KB - 9 x PARTS x 4 x 32 x 16 B (126,976 B for bf16x3, 108,544 B for bf16x6).  The 512-wide backbone keeps the bands
+    of the fill rule at every batch size; a shape whose fill-rule band would overflow gets more, narrower bands instead."""
+    from torch_utils import hip_plugin
+    room = {3: 160 * 1024 - 9 * 2 * 4 * 32 * 16, 6: 160 * 1024 - 9 * 3 * 4 * 32 * 16}
+    assert room == {3: 126976, 6: 108544}
+    ups = [1, 2, 1, 2, 1, 2, 1]
+    for arith in (6, 3):
+        for n in range(1, 9):
+            plan = hip_plugin.LowresPlugin.phase_r_plan(n, 512, 4, ups, arith)
+            assert len(plan) == hip_plugin.LowresPlugin.layers_supported(n, 512, 4, ups, arith)
+            rin = 4
+            for (bands, scratch), up in zip(plan, ups):
+                assert bands == _fill_rule_bands(n, 512, up, rin), (arith, n, up, rin)
+                assert scratch <= room[arith]
+                rin = 2 * rin if up == 2 else rin
+    # up-sampling 16^2 -> 32^2 with n x C / 32 > 128: the fill rule gives 2 bands of 16 rows (+ 3 halo rows of the 33-wide partial map):
+    # 594 x 32 + 512 x 33 + 608 floats = 146,048 B.  Three bands of <= 11 rows need 107,392 B.
+    for n, C, arith in ((2, 2080, 3), (1, 4128, 6)):          # the narrowest such widths
+        assert _fill_rule_bands(n, C, 2, 16) == 2 and _fill_rule_bands(n, C - 32, 2, 16) == 4
+        assert 4 * (594 * 32 + 512 * 33 + 96 + 512) == 146048 > room[arith]
+        assert hip_plugin.LowresPlugin.phase_r_plan(n, C, 16, [2], arith) == [(3, 107392)]
+    assert hip_plugin.LowresPlugin.phase_r_plan(1, 4096, 16, [2], 6) == [(4, 81664)]          # CB = 128: the fill rule's 4 bands fit
