@@ -1,6 +1,6 @@
 """bench.py — throughput of the IDE-3D render hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
 
 With `--gpus N > 1` and no torch.distributed environment the script launches itself once per GPU
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, one rank per HIP device, RCCL);
@@ -19,8 +19,13 @@ of the timed steps, so with the same arguments their inputs (latents and stratif
 
 Rank 0 prints ONE COMPACT JSON line (< 4 KB, contract in the task statement; tests/test_bench_launcher_cpu.py checks the size and a
 strict `json.loads`).  `value` is measured with the LIBRARY-DEFAULT convolution arithmetic (bf16x6: every fp32 operand as three bf16
-pieces, six products, fp32 accumulation — as accurate as the fp32 matrix instruction against float64) — what a drop-in caller gets; exact
-fp32 products (`value_fp32_exact`) and the other arithmetics are listed next to it in `by_conv_arithmetic`.  Extra objects in the line:
+pieces, six products, fp32 accumulation — as accurate as the fp32 matrix instruction against float64) — what a drop-in caller gets.
+
+A plain run does only what the headline needs: set-up, the W warm-up and K timed steps, `--dump-outputs` if given, the line.  `--full`
+adds, after the timed steps (the gather roofline also before the warm-up), everything that takes runs of its own: exact fp32 products
+(`value_fp32_exact`) and the other arithmetics next to it in `by_conv_arithmetic`, and the objects below.  At N > 1 it also re-times the
+steps with a blocking gather, times the gather alone and checks what arrived (`gather_overlap`, `gather_ms`, `gather_check`).  The `--no-*`
+options switch single legs of `--full` off.  Extra objects in the `--full` line:
   roofline         the tri-plane gather kernel (the kernel BASELINE's metric names): algorithmic bytes / HIP-event time
   roofline_worst   the five hand-written kernels furthest below their roofline at their config-2 shapes (scripts/kernel_rooflines.py)
   cpu_baseline     the CPU oracle ("port" of the reference's PyTorch CPU path) timed on the host cores, rank 0, N = 1 only
@@ -30,8 +35,9 @@ fp32 products (`value_fp32_exact`) and the other arithmetics are listed next to 
   parity_ok        after the timed region the SAME captured graph renders fixed inputs (seeds 0-3, fixed jitter) and the frames are
                    compared with the oracle fixture tests/golden/bench_parity.npz (oracle/make_bench_parity.py); with the
                    cpu_baseline leg on, the oracle frame computed there is compared live as well (`parity_live`)
-The FULL record (every kernel's roofline row, the arithmetic sweep with timings, thread probes, notes) goes to
-`gpurun_out/bench_full.json` and, pretty-printed, to stderr — never to stdout.
+  gpu_state        clock and power of the GPU while 300 steps are queued on it
+With `--full` the FULL record (every kernel's roofline row, the arithmetic sweep with timings, thread probes, notes) goes to
+`out/bench_full.json` and, pretty-printed, to stderr — never to stdout.
 """
 
 import argparse
@@ -486,6 +492,9 @@ def main():
                                                           'the median block is reported')
     ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed step's outputs (image, seg logits, uint8 frames) to DIR/<name>.npy, "
                                                          'float32 (seg as a fixed sample); the timed steps\' inputs are the same in every run')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also run the CPU baseline, the other conv arithmetics, parity, '
+                                                        'the batch-1 loop, rooflines, counters, GPU clocks and (N > 1) the gather checks; '
+                                                        'write the full record to out/bench_full.json')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-roofline-extra', action='store_true')
@@ -617,9 +626,9 @@ def main():
             dist.barrier()
         sync()
 
-    # The roofline kernel of BASELINE's metric (the isolated tri-plane gather) is measured first thing, on the GPU as the job finds it, and once
-    # more after everything else; see below where the line is assembled.
-    rf_first = bench_gather(device) if (not cpu and rank == 0 and not args.no_roofline) else None
+    # --full: the roofline kernel of BASELINE's metric (the isolated tri-plane gather) is measured first thing, on the GPU as the job finds it,
+    # and once more after everything else; see below where the line is assembled.
+    rf_first = bench_gather(device) if (args.full and not cpu and rank == 0 and not args.no_roofline) else None
 
     for i in range(args.warmup):
         step(i, blocking=args.blocking_gather)
@@ -643,10 +652,10 @@ def main():
         block_s.append(dt); rank_s.append(mine)
     dumped = dump_outputs(args.dump_outputs, last) if (args.dump_outputs and rank == 0) else None
 
-    # N > 1 extras: per-rank frame rates (own clock, median block) and the cost of the RCCL gather alone
+    # N > 1 extras: per-rank frame rates (own clock, median block); with --full the cost of the RCCL gather alone and what arrived
     per_rank, gather_ms, blocking_ms, gather_check = None, None, None, None
     sums_bad = None
-    if dist and first_timed_sub is not None and og.submitted - first_timed_sub == total_subs:
+    if args.full and dist and first_timed_sub is not None and og.submitted - first_timed_sub == total_subs:
         barrier()
         sent = og.sent_checksums(first_timed_sub, total_subs).contiguous()
         every = [torch.zeros_like(sent) for _ in range(world)]
@@ -658,6 +667,7 @@ def main():
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = [float(t) for t in allr]
+    if args.full and dist:
         # the same K steps with the gather synchronous on the compute stream (what round 2 timed), for comparison
         barrier()
         t0 = time.perf_counter()
@@ -707,10 +717,10 @@ def main():
         med = order[len(order) // 2]          # seconds per step of the median block
         frames_step = BATCH * world
         r3 = lambda v, nd=3: None if v is None else round(float(v), nd)
-        # `out` is the ONE stdout line (compact); `full` collects everything else for gpurun_out/bench_full.json + stderr
+        # `out` is the ONE stdout line (compact); `full` collects everything else for the --full record (out/bench_full.json + stderr)
         out = {
             'metric': '512x512 RGB+seg frames/s @96 depth samples (whole job)', 'value': r3(frames_step / med, 2), 'unit': 'frames/s',
-            'value_fp32_exact': r3(frames_step / med, 2) if arith == 'fp32' else None,     # else filled from the fp32 leg of the sweep below
+            'value_fp32_exact': r3(frames_step / med, 2) if arith == 'fp32' else None,     # else filled from the fp32 leg of the --full sweep below
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': r3(med * 1e3, 4),
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': ARITH_DTYPE_SHORT[arith], 'data': 'synthetic',
             'config': {'workload': 'BASELINE config 2: random-init ide3d-ffhq-64-512, G.mapping + G.synthesis (64 render -> 512, 96 samples, RGB + 19-class seg) '
@@ -729,32 +739,33 @@ def main():
         if dist:
             out['rccl_ranks'] = world
             out['frames_per_s_by_rank'] = [r3(v, 1) for v in per_rank]
+            out['gather_bytes_per_rank_per_step'] = BATCH * res * 2 * res * 3
+        if args.full and dist:
             out['gather_ms'] = r3(gather_ms)
             out['gather_overlap'] = {'mode': 'blocking (split arithmetic: DESIGN.md 4.2)' if forced_blocking else
                                              'blocking' if args.blocking_gather else 'async double-buffered',
                                      'ms_per_step_overlapped': r3(med * 1e3, 4), 'ms_per_step_blocking_gather': r3(blocking_ms, 4),
                                      'gather_ms_alone': r3(gather_ms)}
             out['gather_check'] = gather_check
-            out['gather_bytes_per_rank_per_step'] = BATCH * res * 2 * res * 3
         if cpu:
             out['metric'] = 'DRY RUN (CPU tensors, tiny generator, gloo): launcher / protocol self-test, not a measurement'
             out['data'] = 'synthetic (cpu dry run)'
-        if not cpu and world == 1:
+        if args.full and not cpu and world == 1:
             state = gpu_state_under_load(lambda i: step(i))
             full['gpu_state_under_load'] = state
             if state and 'error' not in state:
                 out['gpu_state'] = {k: state[k] for k in list(state)[:5]}
         pin = None
-        if not cpu and not args.no_parity:
+        if args.full and not cpu and not args.no_parity:
             par, got = check_parity(render, device)
             full['parity'] = par
             out['parity_ok'] = par.get('ok')
             out['parity'] = {'max_rel_err': {k: float(f'{v:.3g}') for k, v in (par.get('max_rel_err') or {}).items()}, 'tol_rel': par['tol_rel'],
                              'vs': 'tests/golden/bench_parity.npz (CPU oracle)'}
             pin = parity_inputs()
-        if not cpu and world == 1 and not args.no_dropin:
+        if args.full and not cpu and world == 1 and not args.no_dropin:
             out['dropin_b1'] = dropin_b1(G, device, palette)
-        if not cpu and world == 1 and not args.no_arith_sweep:
+        if args.full and not cpu and world == 1 and not args.no_arith_sweep:
             # the same step with the other arithmetics of the 3x3 layers: one captured graph each, the headline's timing protocol, parity against
             # the same golden frames (nothing else changes: every other kernel is fp32 in all of them)
             sweep_full = {arith: {'frames_per_s': frames_step / med, 'ms_per_step': med * 1e3, 'blocks': len(block_s), 'block_steps': sizes,
@@ -787,7 +798,7 @@ def main():
             full['by_conv_arithmetic'] = sweep_full
             out['by_conv_arithmetic'] = {k: {'frames_per_s': r3(v['frames_per_s'], 1), 'parity_ok': v.get('parity_ok')} for k, v in sweep_full.items()}
             out['value_fp32_exact'] = r3(sweep_full['fp32']['frames_per_s'], 2)      # exact-fp32 products (v_mfma_f32_32x32x2_f32) in every convolution
-        if not cpu and not args.no_roofline:
+        if args.full and not cpu and not args.no_roofline:
             # two measurements of the same kernel in one run (first thing / after everything else): their spread is the box's clock state, not
             # the kernel.  `roofline` is their MEAN — a fixed estimator (round 5 reported the faster one: min-of-N on the headline figure, ADVICE
             # r5 / VERDICT r5 #4) — and both travel in the line.
@@ -810,7 +821,7 @@ def main():
                                'frac': r3(rf['frac'], 4), 'traffic': (int(rf['traffic']) if rf['traffic'] is not None else None), 'traffic_measured_in_this_run': live is not None,
                                'bytes_per_launch': rf['bytes_per_launch'], 'avg_launch_us': r3(rf['avg_launch_us'], 2), 'timed_launches': rf['timed_launches'],
                                'measured': 'twice in this run (first thing, and after everything else), 400 warm launches each; the MEAN of the two launch times is reported', **both}
-        if not cpu and world == 1 and not args.no_roofline_extra:
+        if args.full and not cpu and world == 1 and not args.no_roofline_extra:
             try:
                 sys.path.insert(0, os.path.join(ROOT, 'scripts'))
                 import kernel_rooflines
@@ -843,7 +854,7 @@ def main():
                                             'mfma_busy_measured_in_this_run': busy_live is not None}
             except Exception as e:
                 out['roofline_worst'] = {'error': f'{type(e).__name__}: {e}'[:200]}
-        if not cpu and world == 1 and not args.no_cpu_baseline:
+        if args.full and not cpu and world == 1 and not args.no_cpu_baseline:
             cb, live = cpu_baseline(parity_inputs=pin)
             full['cpu_baseline'] = cb
             out['cpu_baseline'] = {k: (r3(cb[k]) if k == 'value' else cb[k]) for k in ('value', 'unit', 'cores', 'kind', 'sample')}
@@ -854,16 +865,17 @@ def main():
                 out['parity_live'] = {'vs': 'oracle frame computed in this run (image 0, full frame)', 'max_rel_err': {'img': float(f'{e_img:.3g}'), 'seg': float(f'{e_seg:.3g}')},
                                       'tol_rel': PARITY_TOL, 'ok': bool(max(e_img, e_seg) <= PARITY_TOL)}
         line = compact_line(out)
-        full.update(line=json.loads(line))
-        try:
-            os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
-            with open(os.path.join(ROOT, 'gpurun_out', 'bench_full.json'), 'w') as f:
-                json.dump(full, f, indent=1, default=str)
-            out_path = 'gpurun_out/bench_full.json'
-        except OSError:
-            out_path = None
-        if not cpu:
-            sys.stderr.write('[bench.py] full record' + (f' ({out_path})' if out_path else '') + ':\n' + json.dumps(full, indent=1, default=str) + '\n')
+        if args.full:
+            full.update(line=json.loads(line))
+            try:
+                os.makedirs(os.path.join(ROOT, 'out'), exist_ok=True)
+                with open(os.path.join(ROOT, 'out', 'bench_full.json'), 'w') as f:
+                    json.dump(full, f, indent=1, default=str)
+                out_path = 'out/bench_full.json'
+            except OSError:
+                out_path = None
+            if not cpu:
+                sys.stderr.write('[bench.py] full record' + (f' ({out_path})' if out_path else '') + ':\n' + json.dumps(full, indent=1, default=str) + '\n')
         os.write(json_fd, (line + '\n').encode())
     if dist:
         dist.barrier()

@@ -23,7 +23,7 @@ def _one_json_line(stdout):
 def test_launch_ranks_function_two_gloo_ranks():
     sys.path.insert(0, ROOT)
     import bench
-    rc, out = bench.launch_ranks(2, ['--gpus', '2'] + ARGS, capture=True)
+    rc, out = bench.launch_ranks(2, ['--gpus', '2', '--full'] + ARGS, capture=True)
     assert rc == 0
     rec = _one_json_line(out)
     assert rec['n_gpus'] == 2 and rec['rccl_ranks'] == 2 and rec['steps'] == 3 and rec['warmup'] == 1
@@ -42,19 +42,22 @@ def test_launch_ranks_function_two_gloo_ranks():
 def test_blocking_gather_flag_two_gloo_ranks():
     sys.path.insert(0, ROOT)
     import bench
-    rc, out = bench.launch_ranks(2, ['--gpus', '2', '--blocking-gather'] + ARGS, capture=True)
+    rc, out = bench.launch_ranks(2, ['--gpus', '2', '--blocking-gather', '--full'] + ARGS, capture=True)
     assert rc == 0
     rec = _one_json_line(out)
     assert rec['n_gpus'] == 2 and rec['gather_check']['ok'] is True
 
 
 def test_plain_invocation_self_launches():
-    """`python bench.py --gpus 2` with no torch.distributed environment (what the driver may run)."""
+    """`python bench.py --gpus 2` with no torch.distributed environment (what the driver may run).  Without --full the run ends after the
+    timed steps: no blocking-gather re-run, no gather-alone timing, no contents check."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2'] + ARGS, env=env, stdout=subprocess.PIPE, text=True, timeout=600)
     assert res.returncode == 0
     rec = _one_json_line(res.stdout)
     assert rec['n_gpus'] == 2 and rec['value'] > 0
+    assert len(rec['frames_per_s_by_rank']) == 2
+    assert not {'gather_ms', 'gather_overlap', 'gather_check'} & set(rec), rec
 
 
 def test_single_process_dry_run():
