@@ -33,6 +33,7 @@
 // or the matrix pipe — see DESIGN.md.
 #include "common.h"
 #include "triplane_tap.h"
+#include "raymarch_ray.h"
 
 namespace ide3d {
 
@@ -72,14 +73,6 @@ __device__ void stage_mlp(float* __restrict__ s, const float* __restrict__ w0, c
     }
     for (int i = threadIdx.x; i < K::B0; i += blockDim.x) sb0[i] = b0[i];          // index = 16 mt + 4 g + r
     for (int i = threadIdx.x; i < K::B1; i += blockDim.x) sb1[i] = (i < nout) ? b1[i] : 0.f;
-}
-
-__device__ __forceinline__ float softplus_fast(float x) {
-    // softplus(x) = max(x, 0) + log(1 + exp(-|x|)); abs error ~1e-7, saturates like threshold=20.  Raw v_exp_f32 / v_log_f32: the
-    // exponent is <= 0 (a result below the normal range is 0 beside the 1 it is added to) and the logarithm's argument is in [1, 2], so
-    // the denormal guards of __expf / __logf (a compare, a select and an ldexp each) have nothing to do here.
-    const float e = __builtin_amdgcn_exp2f(-1.44269504088896340736f * fabsf(x));
-    return fmaf(0.69314718055994530942f, __builtin_amdgcn_logf(1.0f + e), fmaxf(x, 0.f));
 }
 
 // ---- decoder MLPs on the bf16 matrix path (round 3) -----------------------------------------------------------------------------------
@@ -478,18 +471,8 @@ render_rays_kernel(ide3d_render_params p, int64_t rays_per_block) {
     // Taps of that sample: camera space -> jitter -> world.  Everything per ray is wave-uniform (scalar loads), so a tile of the NEXT
     // ray costs the same as one of this ray.
     auto tile_taps = [&](int n, int r, float zl, float jl, TapAddr (&t)[3]) {
-        const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];
-        const float* M = p.cam2world + n * 16;
-        float px = __fmul_rn(dx, zl), py = __fmul_rn(dy, zl), pz = __fmul_rn(dz, zl);
-        if (p.jitter) {
-            const float off = __fmul_rn(__fsub_rn(jl, 0.5f), zstep);
-            px = __fadd_rn(px, __fmul_rn(off, dx));
-            py = __fadd_rn(py, __fmul_rn(off, dy));
-            pz = __fadd_rn(pz, __fmul_rn(off, dz));
-        }
-        const float wx = fmaf(M[0], px, fmaf(M[1], py, fmaf(M[2], pz, M[3])));
-        const float wy = fmaf(M[4], px, fmaf(M[5], py, fmaf(M[6], pz, M[7])));
-        const float wz = fmaf(M[8], px, fmaf(M[9], py, fmaf(M[10], pz, M[11])));
+        float wx, wy, wz;
+        ray_world_point(p, n, r, zl, jl, zstep, wx, wy, wz);
         t[0] = make_tap_addr(wx, wy, p.W, p.H, sH, sW);
         t[1] = make_tap_addr(wy, wz, p.W, p.H, sH, sW);
         t[2] = make_tap_addr(wx, wz, p.W, p.H, sH, sW);
@@ -915,31 +898,6 @@ static int launch_voxel(const ide3d_render_params& p, const Src& src, int64_t m,
     else hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * NW), lds_bytes, st, p, src, m, out, tpb);
     IDE3D_CHECK_LAUNCH("sample_voxel");
     return IDE3D_OK;
-}
-
-static int check_render_params(const ide3d_render_params& p, const char* who, bool need_rays) {
-    IDE3D_CHECK_ARG(p.tex_planes && p.geo_planes, "%s: null tri-plane pointer", who);
-    IDE3D_CHECK_ARG(p.geo_w0 && p.geo_b0 && p.geo_w1 && p.geo_b1 && p.tex_w0 && p.tex_b0 && p.tex_w1 && p.tex_b1,
-                    "%s: null MLP weight pointer", who);
-    IDE3D_CHECK_ARG(p.n > 0 && p.C > 0 && p.H > 0 && p.W > 0, "%s: bad tri-plane shape", who);
-    IDE3D_CHECK_ARG(p.feat_ch >= 1 && p.feat_ch <= 32 && p.seg_ch >= 0 && p.seg_ch <= 31,
-                    "%s: feat_ch <= 32 and seg_ch <= 31 required", who);
-    if (need_rays) {
-        IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world && p.out_feat, "%s: null ray / output pointer", who);
-        IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "%s: bad ray shape", who);
-        IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "%s: Need to choose clamp mode", who);
-    }
-    return IDE3D_OK;
-}
-
-static bool planes_fast(const ide3d_render_params& p) {
-    auto ok = [&](const float* base, const int64_t* s) {
-        return s[1] == 1 && (s[0] % 4 == 0) && (s[2] % 4 == 0) && (s[3] % 4 == 0) &&
-               ((reinterpret_cast<uintptr_t>(base) & 15) == 0);
-    };
-    return ok(p.tex_planes, p.tex_stride) && ok(p.geo_planes, p.geo_stride) &&
-           p.tex_stride[2] == p.geo_stride[2] && p.tex_stride[3] == p.geo_stride[3] &&
-           (p.tex_stride[2] * p.H + p.tex_stride[3] * p.W + 3 * p.C) * 4 < 0x7fffffffLL;       // byte offsets inside an image: 31 bits (launch_voxel bounds the image strides a straddling tile adds)
 }
 
 }  // namespace ide3d

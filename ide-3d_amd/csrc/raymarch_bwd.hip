@@ -1,0 +1,374 @@
+// raymarch_bwd.hip — backward of the fused ray-marcher (render_rays_kernel, raymarch.hip) with respect to the two tri-planes.
+//
+// Given dL/dfeat [n, feat+seg, rays], dL/ddepth [n, rays] and dL/dwsum [n, rays] (each may be NULL = zero), accumulates dL/dtex_planes
+// and dL/dgeo_planes into caller-zeroed fp32 buffers.  Nothing per sample is saved by the forward: the samples are rebuilt here exactly as
+// the forward builds them (raymarch_ray.h: depth, jitter, cam2world, tap indices of triplane_tap.h, density noise).
+//
+// Per ray (one wavefront; lane = sample, the ray walked in chunks of 64 samples):
+//   sweep 1    both gathers and MLPs; per sample keep alpha_i, the transmittance T_i and
+//              h_i = dL/dw_i = sum_c gfeat_c out_ic + gd z_i + gw',   gw' = gw - [white_back] sum_c gfeat_c - gd max_depth.
+//              The output layer is never formed: sum_c gfeat_c out_ic = sum_k u_k hid_k + sum_c gfeat_c b1_c with the per-ray vector
+//              u = W1^T gfeat (one per branch, kept in LDS), which is also the whole output-layer backward in sweep 2.
+//   reverse    R_i = alpha_i h_i + (1 - alpha_i + 1e-10) R_{i+1}, R_S = 0 (a 64-lane scan of affine maps, chunks from the last);
+//              dL/dalpha_i = T_i (h_i - R_{i+1}) — no division, so the last sample (delta 1e10, alpha may round to 1) is safe.
+//   sweep 2    gathers and hidden layers again; dsigma_i = dL/dalpha_i delta_i exp(-delta_i a) a'(sigma_i + noise_i), back through the
+//              hidden softplus and layer 0 of each MLP, and the feature gradient is scattered to the bilinear taps of all three planes.
+// Arithmetic: exact fp32 on the VALU (weights are wave-uniform: scalar loads, v_fma with an SGPR operand), whatever arithmetic the
+// forward's MLPs ran in; there is no matrix loop here, so DESIGN.md section 4.2's exclusive residency does not apply.
+//
+// Gradient output: no-return float atomics on channels_last buffers.  The per-sample feature gradients and tap weights are staged in
+// LDS, then every atomic wave-instruction covers C consecutive channels of 64 / C taps (C = 32: one 128-byte segment per tap).  Taps outside
+// the plane get nothing (zeros padding).  The sums depend on the order in which atomics arrive: results are NOT bit-reproducible from run
+// to run (they agree to fp32 rounding).
+#include "common.h"
+#include "triplane_tap.h"
+#include "raymarch_ray.h"
+
+namespace ide3d {
+
+// LDS.  Per workgroup: both layer-0 weight matrices and biases, row 0 (sigma) of the geometry output layer and its bias, read as
+// broadcasts by every lane.  Per wave, in floats: feature-gradient staging [64][C + 1], tap offsets [64][12] (int) and weights [64][12],
+// the two u vectors [2][64], then four per-sample arrays of the ray [Sp] (Sp = steps rounded up to 64).
+template <int C, int HID>
+struct BwdLds {
+    static constexpr int W0 = HID * C;
+    static constexpr int SHARED = 2 * W0 + 2 * HID + HID + 4;        // geo w0, tex w0, geo b0, tex b0, geo w1 row 0, geo b1[0] (+ pad)
+    static constexpr int DF = 64 * (C + 1);
+    static constexpr int TAPS = 64 * 12;
+    static constexpr int U = 2 * 64;
+    static constexpr int FIXED = DF + 2 * TAPS + U;
+    static constexpr int ARRAYS = 4;
+};
+
+// One sample's C features from one tri-plane (channels_last), summed over the three planes like the forward's blend: (xy + yz) + xz.
+template <int C>
+__device__ __forceinline__ void gather_sample_cl(const float* __restrict__ base, const TapAddr (&a)[3], float (&f)[C]) {
+#pragma unroll
+    for (int ci = 0; ci < C / 4; ++ci) {
+        // one channel slice (12 tap loads) in flight at a time: left alone the scheduler issues all 96 loads of the sample first and the
+        // kernel spills
+        if (ci > 0) __builtin_amdgcn_sched_barrier(0);
+        const float4 v0 = gather_plane_cl(base + 0 * C + 4 * ci, a[0]);
+        const float4 v1 = gather_plane_cl(base + 1 * C + 4 * ci, a[1]);
+        const float4 v2 = gather_plane_cl(base + 2 * C + 4 * ci, a[2]);
+        f[4 * ci + 0] = (v0.x + v1.x) + v2.x;
+        f[4 * ci + 1] = (v0.y + v1.y) + v2.y;
+        f[4 * ci + 2] = (v0.z + v1.z) + v2.z;
+        f[4 * ci + 3] = (v0.w + v1.w) + v2.w;
+    }
+}
+
+// Hidden pre-activation k of one MLP: b0[k] + sum_c w0[k][c] f[c] (weights in LDS, the same address in every lane)
+template <int C>
+__device__ __forceinline__ float hidden_pre(const float* w0, const float* b0, int k, const float (&f)[C]) {
+    const float4* row = reinterpret_cast<const float4*>(w0 + k * C);
+    float acc = b0[k];
+#pragma unroll
+    for (int c4 = 0; c4 < C / 4; ++c4) {
+        const float4 w = row[c4];
+        acc = fmaf(w.x, f[4 * c4 + 0], acc); acc = fmaf(w.y, f[4 * c4 + 1], acc);
+        acc = fmaf(w.z, f[4 * c4 + 2], acc); acc = fmaf(w.w, f[4 * c4 + 3], acc);
+    }
+    return acc;
+}
+
+// df[c] += w0[k][c] dpre
+template <int C>
+__device__ __forceinline__ void hidden_back(const float* w0, int k, float dpre, float (&df)[C]) {
+    const float4* row = reinterpret_cast<const float4*>(w0 + k * C);
+#pragma unroll
+    for (int c4 = 0; c4 < C / 4; ++c4) {
+        const float4 w = row[c4];
+        df[4 * c4 + 0] = fmaf(w.x, dpre, df[4 * c4 + 0]); df[4 * c4 + 1] = fmaf(w.y, dpre, df[4 * c4 + 1]);
+        df[4 * c4 + 2] = fmaf(w.z, dpre, df[4 * c4 + 2]); df[4 * c4 + 3] = fmaf(w.w, dpre, df[4 * c4 + 3]);
+    }
+}
+
+__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Stage the feature gradient df of this lane's sample and its 12 taps (offsets in the gradient buffer, -1 = no tap), then scatter
+// w_tap * df[c] to the taps of the `live` samples s0 .. s0 + live - 1 of the chunk with one atomic per (tap, channel).
+template <int C>
+__device__ __forceinline__ void scatter_sample_grads(float* __restrict__ gimg, const int64_t* gs, const Tap2 (&t)[3], bool valid,
+                                                     const float (&df)[C], int live, float* s_df, int* s_off, float* s_tw) {
+    const int lane = lane_id();
+    const int gH = (int)gs[2], gW = (int)gs[3];
+#pragma unroll
+    for (int c = 0; c < C; ++c) s_df[lane * (C + 1) + c] = df[c];
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+        const float wk[4] = {t[pl].w00, t[pl].w01, t[pl].w10, t[pl].w11};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int x = t[pl].ix0 + (k & 1), y = t[pl].iy0 + (k >> 1);
+            const bool on = valid && ((t[pl].mask >> k) & 1u);
+            s_off[lane * 12 + pl * 4 + k] = on ? y * gH + x * gW + pl * C : -1;
+            s_tw[lane * 12 + pl * 4 + k] = wk[k];
+        }
+    }
+    wave_lds_sync();
+    constexpr int PER = 64 / C;                 // taps per wave-instruction
+    const int c = lane % C, q_lane = lane / C;
+    const int pairs = live * 12;
+    for (int q0 = 0; q0 < pairs; q0 += PER) {
+        const int q = q0 + q_lane;
+        if (q < pairs) {
+            const int off = s_off[q];
+            if (off >= 0) {
+                const int j = q / 12;
+                atomicAdd(gimg + off + c, s_tw[q] * s_df[j * (C + 1) + c]);
+            }
+        }
+    }
+    wave_lds_sync();
+}
+
+template <int C, int HID>
+__global__ void __launch_bounds__(512)
+render_rays_backward_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp) {
+    using L = BwdLds<C, HID>;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* const s_gw0 = lds;
+    float* const s_tw0 = s_gw0 + L::W0;
+    float* const s_gb0 = s_tw0 + L::W0;
+    float* const s_tb0 = s_gb0 + HID;
+    float* const s_gw1 = s_tb0 + HID;              // row 0 of geo_w1, then geo_b1[0]
+    for (int i = threadIdx.x; i < L::W0; i += blockDim.x) { s_gw0[i] = p.geo_w0[i]; s_tw0[i] = p.tex_w0[i]; }
+    for (int i = threadIdx.x; i < HID; i += blockDim.x) { s_gb0[i] = p.geo_b0[i]; s_tb0[i] = p.tex_b0[i]; s_gw1[i] = p.geo_w1[i]; }
+    if (threadIdx.x == 0) s_gw1[HID] = p.geo_b1[0];
+    __syncthreads();
+
+    const int lane = lane_id(), wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int nw = blockDim.x >> 6;
+    float* const s_df = lds + L::SHARED + wid * (L::FIXED + L::ARRAYS * sp);
+    int* const s_off = reinterpret_cast<int*>(s_df + L::DF);
+    float* const s_tw = s_df + L::DF + L::TAPS;
+    float* const s_u = s_tw + L::TAPS;             // [0, 64): geometry branch, [64, 128): texture branch
+    float* const s_a = s_u + L::U;                 // alpha_i, then dL/dalpha_i
+    float* const s_h = s_a + sp;                   // h_i, then w_i = alpha_i T_i
+    float* const s_t = s_h + sp;                   // T_i
+    float* const s_x = s_t + sp;                   // sigma_i + noise_i
+
+    const int S = p.steps, R = p.rays_per_img, nch = p.feat_ch + p.seg_ch;
+    const int64_t total_rays = (int64_t)p.n * R;
+    const int sH = (int)p.tex_stride[2], sW = (int)p.tex_stride[3];
+    const float zstep = (S > 1) ? (p.z_lin[1] - p.z_lin[0]) : 0.f;
+
+    for (int64_t ray = (int64_t)blockIdx.x * nw + wid; ray < total_rays; ray += (int64_t)gridDim.x * nw) {
+        const int n = __builtin_amdgcn_readfirstlane((int)(ray / R));
+        const int r = __builtin_amdgcn_readfirstlane((int)(ray - (int64_t)n * R));
+        const float* gfeat = gr.grad_feat ? gr.grad_feat + (int64_t)n * nch * R + r : nullptr;
+        const float gd = gr.grad_depth ? gr.grad_depth[ray] : 0.f;
+        const float gw = gr.grad_wsum ? gr.grad_wsum[ray] : 0.f;
+        // per-ray constants: u = W1^T gfeat of each branch (lane k = hidden unit k), the bias part of h and the background terms
+        float hconst = gw - ((p.max_depth != 0.f) ? gd * p.max_depth : 0.f);
+        {
+            float ug = 0.f, ut = 0.f;
+            if (gfeat) {
+                float gsum = 0.f, bsum = 0.f;
+                for (int o = 0; o < p.feat_ch; ++o) {
+                    const float g = gfeat[(int64_t)o * R];
+                    gsum += g; bsum = fmaf(g, p.tex_b1[o], bsum);
+                    if (lane < HID) ut = fmaf(g, p.tex_w1[o * HID + lane], ut);
+                }
+                for (int o = 1; o <= p.seg_ch; ++o) {
+                    const float g = gfeat[(int64_t)(p.feat_ch + o - 1) * R];
+                    gsum += g; bsum = fmaf(g, p.geo_b1[o], bsum);
+                    if (lane < HID) ug = fmaf(g, p.geo_w1[o * HID + lane], ug);
+                }
+                hconst += bsum - (p.white_back ? gsum : 0.f);
+            }
+            s_u[lane] = ug;
+            s_u[64 + lane] = ut;
+        }
+        wave_lds_sync();
+        float dnorm;
+        {
+            const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];
+            dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
+        }
+        const float* geo_img = p.geo_planes + n * p.geo_stride[0];
+        const float* tex_img = p.tex_planes + n * p.tex_stride[0];
+
+        // what both sweeps rebuild of sample s: its taps, its depth and its delta
+        auto sample_setup = [&](int s, Tap2 (&t)[3], TapAddr (&a)[3], float& z, float& delta) {
+            const int sc = s < S ? s : S - 1;
+            const float zl = p.z_lin[sc];
+            const float jl = p.jitter ? p.jitter[ray * S + sc] : 0.5f;
+            float wx, wy, wz;
+            ray_world_point(p, n, r, zl, jl, zstep, wx, wy, wz);
+            triplane_taps(wx, wy, wz, p.W, p.H, t);
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) a[pl] = tap_addr(t[pl], p.W, p.H, sH, sW);
+            z = ray_sample_depth(p, ray, sc, zstep);
+            const float znext = (sc + 1 < S) ? ray_sample_depth(p, ray, sc + 1, zstep) : 0.f;
+            delta = (sc + 1 < S) ? (znext - z) * dnorm : 1e10f;
+        };
+
+        // ---- sweep 1: alpha_i, T_i, h_i, sigma_i + noise_i ----
+        float carry = 1.0f;
+        for (int c0 = 0; c0 < S; c0 += 64) {
+            const int s = c0 + lane;
+            const bool live = s < S;
+            Tap2 t[3]; TapAddr a[3];
+            float z, delta;
+            sample_setup(s, t, a, z, delta);
+            float f[C];
+            gather_sample_cl<C>(geo_img, a, f);
+            float sigma = s_gw1[HID], hg = 0.f;
+#pragma unroll 2
+            for (int k = 0; k < HID; ++k) {
+                const float hid = softplus_fast(hidden_pre<C>(s_gw0, s_gb0, k, f));
+                sigma = fmaf(s_gw1[k], hid, sigma);
+                hg = fmaf(s_u[k], hid, hg);
+            }
+            gather_sample_cl<C>(tex_img, a, f);
+            float ht = 0.f;
+#pragma unroll 2
+            for (int k = 0; k < HID; ++k) ht = fmaf(s_u[64 + k], softplus_fast(hidden_pre<C>(s_tw0, s_tb0, k, f)), ht);
+            const float x = sigma + (p.sigma_noise ? p.sigma_noise[ray * S + (live ? s : S - 1)] : 0.f);
+            const float dens = p.clamp_mode == 0 ? softplus_fast(x) : fmaxf(x, 0.f);
+            const float alpha = live ? 1.0f - __expf(-delta * dens) : 0.f;
+            const float fac = live ? (1.0f - alpha + 1e-10f) : 1.0f;
+            // exclusive prefix product of fac over the 64 lanes, carried across chunks
+            float incl = fac;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const float o = __shfl_up(incl, off);
+                if (lane >= off) incl *= o;
+            }
+            const float prev = __shfl_up(incl, 1);
+            const float T = carry * (lane == 0 ? 1.0f : prev);
+            carry *= __shfl(incl, 63);
+            if (live) {
+                s_a[s] = alpha;
+                s_h[s] = hconst + hg + ht + gd * z;
+                s_t[s] = T;
+                s_x[s] = x;
+            }
+        }
+        wave_lds_sync();
+
+        // ---- reverse scan: dL/dalpha_i and w_i ----
+        float rcarry = 0.f;
+        for (int c0 = ((S - 1) / 64) * 64; c0 >= 0; c0 -= 64) {
+            const int s = c0 + lane;
+            const bool live = s < S;
+            const float alpha = live ? s_a[s] : 0.f, h = live ? s_h[s] : 0.f, T = live ? s_t[s] : 0.f;
+            // R_i = A + B R_end over lanes i .. 63 of the chunk (composition of the affine maps R -> alpha h + (1 - alpha + 1e-10) R)
+            float A = alpha * h, B = live ? (1.0f - alpha + 1e-10f) : 1.0f;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const float An = __shfl_down(A, off), Bn = __shfl_down(B, off);
+                if (lane + off < 64) { A = fmaf(B, An, A); B *= Bn; }
+            }
+            const float incl = fmaf(B, rcarry, A);
+            const float down = __shfl_down(incl, 1);
+            const float rnext = lane == 63 ? rcarry : down;
+            rcarry = __shfl(incl, 0);
+            if (live) {
+                s_a[s] = T * (h - rnext);
+                s_h[s] = alpha * T;
+            }
+        }
+        wave_lds_sync();
+
+        // ---- sweep 2: back through both MLPs to the taps ----
+        for (int c0 = 0; c0 < S; c0 += 64) {
+            const int s = c0 + lane;
+            const bool live = s < S;
+            const int nlive = min(64, S - c0);
+            Tap2 t[3]; TapAddr a[3];
+            float z, delta;
+            sample_setup(s, t, a, z, delta);
+            const float dalpha = live ? s_a[s] : 0.f, w = live ? s_h[s] : 0.f, x = live ? s_x[s] : 0.f;
+            float dens, dact;
+            if (p.clamp_mode == 0) { dens = softplus_fast(x); dact = sigmoid_fast(x); }
+            else { dens = fmaxf(x, 0.f); dact = x > 0.f ? 1.0f : 0.f; }
+            // exp(-delta a) directly, not 1 - alpha: at the last sample (delta 1e10) alpha rounds to 1 while delta exp(-delta a) is finite
+            const float dsigma = live ? dalpha * delta * __expf(-delta * dens) * dact : 0.f;
+            float f[C], df[C];
+            gather_sample_cl<C>(geo_img, a, f);
+#pragma unroll
+            for (int c = 0; c < C; ++c) df[c] = 0.f;
+#pragma unroll 2
+            for (int k = 0; k < HID; ++k) {
+                const float dpre = fmaf(w, s_u[k], dsigma * s_gw1[k]) * sigmoid_fast(hidden_pre<C>(s_gw0, s_gb0, k, f));
+                hidden_back<C>(s_gw0, k, dpre, df);
+            }
+            scatter_sample_grads<C>(gr.grad_geo_planes + n * gr.grad_geo_stride[0], gr.grad_geo_stride, t, live, df, nlive, s_df, s_off, s_tw);
+
+            gather_sample_cl<C>(tex_img, a, f);
+#pragma unroll
+            for (int c = 0; c < C; ++c) df[c] = 0.f;
+#pragma unroll 2
+            for (int k = 0; k < HID; ++k) {
+                const float dpre = w * s_u[64 + k] * sigmoid_fast(hidden_pre<C>(s_tw0, s_tb0, k, f));
+                hidden_back<C>(s_tw0, k, dpre, df);
+            }
+            scatter_sample_grads<C>(gr.grad_tex_planes + n * gr.grad_tex_stride[0], gr.grad_tex_stride, t, live, df, nlive, s_df, s_off, s_tw);
+        }
+        wave_lds_sync();
+    }
+}
+
+template <int C, int HID>
+static int launch_render_backward(const ide3d_render_params& p, const ide3d_render_grads& g, hipStream_t st) {
+    using L = BwdLds<C, HID>;
+    const int sp = (int)cdiv64(p.steps, 64) * 64;
+    // 8 waves per workgroup, one workgroup per CU (the layer-0 weights are staged once per workgroup); fewer waves when the per-ray
+    // arrays of many steps do not fit
+    const size_t wave_bytes = (L::FIXED + (size_t)L::ARRAYS * sp) * sizeof(float), shared_bytes = L::SHARED * sizeof(float);
+    int nw = 8;
+    while (nw > 1 && shared_bytes + nw * wave_bytes > 160 * 1024) nw /= 2;
+    const size_t lds_bytes = shared_bytes + nw * wave_bytes;
+    if (lds_bytes > 160 * 1024) {
+        set_error("render_rays_backward: %d steps per ray need %zu bytes of LDS per workgroup (at most 160 KiB)", p.steps, lds_bytes);
+        return IDE3D_ENOKERNEL;
+    }
+    const int64_t total_rays = (int64_t)p.n * p.rays_per_img;
+    int64_t nblk = cdiv64(total_rays, nw);
+    const int64_t cap = (int64_t)kNumCU * 8 / nw;
+    if (nblk > cap) nblk = cap;
+    auto kern = render_rays_backward_kernel<C, HID>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * nw), lds_bytes, st, p, g, sp);
+    IDE3D_CHECK_LAUNCH("render_rays_backward");
+    return IDE3D_OK;
+}
+
+static bool grads_fit(const ide3d_render_params& p, const ide3d_render_grads& g) {
+    auto ok = [&](const int64_t* s) {
+        return s[1] == 1 && s[2] >= 0 && s[3] >= 0 && (s[2] * (p.H - 1) + s[3] * (p.W - 1) + 3 * p.C) < 0x7fffffffLL;
+    };
+    return ok(g.grad_tex_stride) && ok(g.grad_geo_stride);
+}
+
+}  // namespace ide3d
+
+extern "C" int ide3d_render_rays_backward(const ide3d_render_params* pp, const ide3d_render_grads* gg, void* stream) {
+    using namespace ide3d;
+    IDE3D_CHECK_ARG(pp != nullptr && gg != nullptr, "render_rays_backward: null params");
+    const ide3d_render_params& p = *pp;
+    const ide3d_render_grads& g = *gg;
+    int rc = check_render_params(p, "render_rays_backward", false);
+    if (rc) return rc;
+    IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world, "render_rays_backward: null ray pointer");
+    IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "render_rays_backward: bad ray shape");
+    IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "render_rays_backward: Need to choose clamp mode");
+    IDE3D_CHECK_ARG(g.grad_tex_planes && g.grad_geo_planes, "render_rays_backward: null gradient output");
+    if (p.last_back) { set_error("render_rays_backward: last_back is not fused; use the step-wise ops"); return IDE3D_ENOKERNEL; }
+    if (!planes_fast(p)) { set_error("render_rays_backward: tri-planes must be channels_last, 16-byte aligned"); return IDE3D_ENOKERNEL; }
+    if (!grads_fit(p, g)) { set_error("render_rays_backward: gradient buffers must be channels_last (channel stride 1)"); return IDE3D_ENOKERNEL; }
+    hipStream_t st = (hipStream_t)stream;
+    if (p.C == 32 && p.hidden == 64) return launch_render_backward<32, 64>(p, g, st);
+    if (p.C == 16 && p.hidden == 32) return launch_render_backward<16, 32>(p, g, st);
+    set_error("render_rays_backward: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
+    return IDE3D_ENOKERNEL;
+}

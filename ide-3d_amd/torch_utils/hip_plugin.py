@@ -98,6 +98,13 @@ class _FlreluParams(ctypes.Structure):
     ]
 
 
+class _RenderGrads(ctypes.Structure):
+    _fields_ = [
+        ('grad_feat', ctypes.c_void_p), ('grad_depth', ctypes.c_void_p), ('grad_wsum', ctypes.c_void_p),
+        ('grad_tex_planes', ctypes.c_void_p), ('grad_geo_planes', ctypes.c_void_p),
+        ('grad_tex_stride', ctypes.c_int64 * 4), ('grad_geo_stride', ctypes.c_int64 * 4),
+    ]
+
 class _Lattice(ctypes.Structure):
     _fields_ = [('n', ctypes.c_int32), ('voxel_size', ctypes.c_float), ('corner', ctypes.c_float * 3), ('scale', ctypes.c_float)]
 
@@ -282,6 +289,7 @@ def load():
                                 ctypes.c_int, vp, vp, vp, vp],
             'ide3d_sample_pdf': [vp, vp, vp, i64, i64, i32, i32, f32, vp, vp],
             'ide3d_render_rays': [ctypes.POINTER(_RenderParams), vp],
+            'ide3d_render_rays_backward': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_RenderGrads), vp],
             'ide3d_sample_voxel': [ctypes.POINTER(_RenderParams), vp, i64, vp, vp, ctypes.c_int, vp],
             'ide3d_lattice_points': [ctypes.POINTER(_Lattice), i64, i64, vp, vp],
             'ide3d_density_lattice': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_Lattice), i64, i64, vp, vp],
@@ -318,7 +326,7 @@ def load():
 EXPORTED_SYMBOLS = (
     'ide3d_last_error', 'ide3d_abi_version', 'ide3d_build_arch', 'ide3d_build_flags', 'ide3d_exclusive_violations', 'ide3d_exclusive_violation_text', 'ide3d_bias_act', 'ide3d_upfirdn2d', 'ide3d_upfirdn2d_ex',
     'ide3d_filtered_lrelu', 'ide3d_filtered_lrelu_act', 'ide3d_triplane_sample', 'ide3d_triplane_sample_rays', 'ide3d_triplane_taps',
-    'ide3d_triplane_sample_backward', 'ide3d_composite', 'ide3d_sample_pdf', 'ide3d_render_rays', 'ide3d_sample_voxel',
+    'ide3d_triplane_sample_backward', 'ide3d_composite', 'ide3d_sample_pdf', 'ide3d_render_rays', 'ide3d_render_rays_backward', 'ide3d_sample_voxel',
     'ide3d_lattice_points', 'ide3d_density_lattice',
     'ide3d_modconv2d', 'ide3d_modconv2d_heads', 'ide3d_modconv_workspace_bytes', 'ide3d_modconv_plan', 'ide3d_set_conv_arithmetic', 'ide3d_get_conv_arithmetic', 'ide3d_frame_u8', 'ide3d_sphere_points', 'ide3d_cam2world', 'ide3d_style_demod', 'ide3d_fold_heads',
     'ide3d_style_demod_batch', 'ide3d_fold_heads_batch',
@@ -850,8 +858,9 @@ class VolumeRenderPlugin:
                          f'render_rays: {name} must be [{n}, {rays_per_img}, {steps}] (images, rays, steps), got {list(t.shape)}')
 
     @staticmethod
-    def render_rays(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
-                    clamp_mode, last_back, white_back, max_depth):
+    def _ray_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_mode, last_back, white_back,
+                    max_depth):
+        """-> (ide3d_render_params without outputs, tensors that must stay alive while it is in use)"""
         dev = tex_planes.device
         _require(tex_planes.ndim == 4, 'render_rays: tri-planes must be [n, 3*C, H, W]')
         VolumeRenderPlugin.check_render_shapes(tex_planes.shape[0], rays_d_cam.shape[0], z_lin.shape[0], rays_d_cam, z_lin, cam2world,
@@ -873,6 +882,14 @@ class VolumeRenderPlugin:
             sigma_noise = sigma_noise.contiguous(); keep.append(sigma_noise); p.sigma_noise = sigma_noise.data_ptr()
         p.clamp_mode, p.last_back, p.white_back = int(clamp_mode), int(bool(last_back)), int(bool(white_back))
         p.max_depth = float(max_depth or 0.0)
+        return p, keep
+
+    @staticmethod
+    def render_rays(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
+                    clamp_mode, last_back, white_back, max_depth):
+        dev = tex_planes.device
+        p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
+                                                 clamp_mode, last_back, white_back, max_depth)
         n, R = p.n, p.rays_per_img
         feat = torch.empty([n, p.feat_ch + p.seg_ch, R], dtype=torch.float32, device=dev)
         depth = torch.empty([n, R], dtype=torch.float32, device=dev)
@@ -884,6 +901,34 @@ class VolumeRenderPlugin:
             return None
         _check(rc, 'render_rays')
         return feat, depth, wsum
+
+    @staticmethod
+    def render_rays_backward(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_mode, last_back,
+                             white_back, max_depth, grad_feat, grad_depth, grad_wsum):
+        """Gradients of `render_rays` with respect to the two tri-planes: the same arguments as the forward, then dL/dfeat [n, feat+seg,
+        rays], dL/ddepth [n, rays], dL/dwsum [n, rays] (each may be None = zero) -> (dL/dtex_planes, dL/dgeo_planes), channels_last
+        float32 of the planes' shape; None when the library has no backward kernel for the configuration (IDE3D_ENOKERNEL)."""
+        dev = tex_planes.device
+        p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
+                                                 clamp_mode, last_back, white_back, max_depth)
+        n, R, nch = p.n, p.rays_per_img, p.feat_ch + p.seg_ch
+        g = _RenderGrads()
+        for name, t, shape in (('grad_feat', grad_feat, (n, nch, R)), ('grad_depth', grad_depth, (n, R)), ('grad_wsum', grad_wsum, (n, R))):
+            if t is not None:
+                _require(t.numel() == math.prod(shape), f'render_rays_backward: {name} must hold {list(shape)} values, got {list(t.shape)}')
+                t = t.to(device=dev, dtype=torch.float32).contiguous()
+                keep.append(t)
+                setattr(g, name, t.data_ptr())
+        dtex = torch.empty(tex_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
+        dgeo = torch.empty(geo_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
+        g.grad_tex_planes, g.grad_geo_planes = dtex.data_ptr(), dgeo.data_ptr()
+        g.grad_tex_stride, g.grad_geo_stride = _i64x4(dtex.stride()), _i64x4(dgeo.stride())
+        with _dev_guard(dev):
+            rc = load().ide3d_render_rays_backward(ctypes.byref(p), ctypes.byref(g), _stream(tex_planes))
+        if rc == -2:        # IDE3D_ENOKERNEL
+            return None
+        _check(rc, 'render_rays_backward')
+        return dtex, dgeo
 
     @staticmethod
     def sample_voxel(tex_planes, geo_planes, mlp, pts, sigma_only=False):

@@ -41,6 +41,10 @@ from training import graph_cache
 from training import networks
 from training import volumetric_rendering as vr
 
+# Route TriplaneRenderer.forward through the fused renderer's backward kernel (csrc/raymarch_bwd.hip) when only the tri-planes need a
+# gradient (PTI-style latent optimisation with a frozen generator); False = the step-wise definition, as for every other gradient.
+fused_render_grad = True
+
 
 @dataclasses.dataclass
 class GeneratorSpec:
@@ -187,6 +191,17 @@ class TriplaneRenderer(torch.nn.Module):
             return True
         return not (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.decoder.parameters()))
 
+    def _fused_grad_ok(self, img_v, seg_v, cam2world, jitter, sigma_noise):
+        """The fused renderer with its backward kernel: fp32 CUDA planes of which at least one needs a gradient, and nothing else it
+        reads (decoder parameters, camera, jitter, density noise) does — the backward kernel differentiates the planes only."""
+        if not torch.is_grad_enabled() or not (img_v.requires_grad or seg_v.requires_grad):
+            return False
+        if any(t.device.type != 'cuda' or t.dtype != torch.float32 for t in (img_v, seg_v, cam2world)):
+            return False
+        if cam2world.requires_grad or any(p.requires_grad for p in self.decoder.parameters()):
+            return False
+        return not any(t is not None and t.requires_grad for t in (jitter, sigma_noise))
+
     # -- full rendering -----------------------------------------------------------------------------------
     def forward(self, img_v, seg_v, cam2world, fov=None, num_steps=None, ray_start=None, ray_end=None, img_size=None,
                 nerf_noise=0.0, jitter=None, sigma_noise=None, white_back=False, clamp_mode=None,
@@ -220,6 +235,12 @@ class TriplaneRenderer(torch.nn.Module):
 
         hierarchical = sp.hierarchical if hierarchical is None else hierarchical
         if not hierarchical and self._hip_ok(img_v, seg_v, cam2world):
+            res = vr.render_triplane_fused(_as_channels_last(img_v), _as_channels_last(seg_v), self.decoder.kernel_weights(),
+                                           cam2world.float(), fov, (size, size), steps, t0, t1, jitter=jitter,
+                                           sigma_noise=sigma_noise, clamp_mode=clamp_mode, white_back=white_back)
+            if res is not None:
+                return res
+        elif not hierarchical and fused_render_grad and self._fused_grad_ok(img_v, seg_v, cam2world, jitter, sigma_noise):
             res = vr.render_triplane_fused(_as_channels_last(img_v), _as_channels_last(seg_v), self.decoder.kernel_weights(),
                                            cam2world.float(), fov, (size, size), steps, t0, t1, jitter=jitter,
                                            sigma_noise=sigma_noise, clamp_mode=clamp_mode, white_back=white_back)

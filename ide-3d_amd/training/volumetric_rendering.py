@@ -335,6 +335,39 @@ def _fused_ray_setup(device, fov, resolution, num_steps, ray_start, ray_end):
     return ent
 
 
+class _NoFusedKernel(Exception):
+    """The library has no fused kernel for the configuration (IDE3D_ENOKERNEL)."""
+
+
+class _RenderRaysFused(torch.autograd.Function):
+    """`ide3d_render_rays` with a gradient for the two tri-planes (`ide3d_render_rays_backward`, csrc/raymarch_bwd.hip).  The forward is
+    the inference launch unchanged; what is saved is its inputs (planes, decoder weights, camera, jitter, noise), nothing per sample: the
+    backward kernel rebuilds the samples.  No gradient for anything but the planes."""
+
+    @staticmethod
+    def forward(ctx, tex_planes, geo_planes, rays_d_cam, z_lin, cam2world, jitter, sigma_noise, mlp, clamp_code, white_back, max_depth):
+        args = (rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_code, False, white_back, max_depth)
+        res = _plugin.render_rays(*args)
+        if res is None:
+            raise _NoFusedKernel()
+        ctx.save_for_backward(tex_planes, geo_planes)
+        ctx.args = args[:5] + args[7:]
+        return res
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_feat, grad_depth, grad_wsum):
+        tex_planes, geo_planes = ctx.saved_tensors
+        a = ctx.args
+        res = _plugin.render_rays_backward(*a[:5], tex_planes, geo_planes, *a[5:], grad_feat, grad_depth, grad_wsum)
+        if res is None:
+            from torch_utils import hip_plugin
+            raise RuntimeError('render_rays_backward: no backward kernel for this configuration: '
+                               + hip_plugin.load().ide3d_last_error().decode('utf-8', 'replace'))
+        dtex, dgeo = res
+        return (dtex if ctx.needs_input_grad[0] else None, dgeo if ctx.needs_input_grad[1] else None) + (None,) * 9
+
+
 def render_triplane_fused(tex_planes, geo_planes, mlp, cam2world, fov, resolution, num_steps, ray_start, ray_end,
                           jitter=None, sigma_noise=None, clamp_mode='softplus', white_back=False, max_depth=None):
     """One HIP launch for: get_initial_rays_trig -> perturb_points -> cam2world transform -> two
@@ -348,6 +381,11 @@ def render_triplane_fused(tex_planes, geo_planes, mlp, cam2world, fov, resolutio
     Returns (features [N, feat+seg, H_r, W_r], depth [N, 1, H_r, W_r], weight_sum [N, 1, H_r, W_r]), or None when the
     library has no fused kernel for the configuration (IDE3D_ENOKERNEL: plane_channels / decoder widths other than
     the compiled (32, 64) and (16, 32)) — the caller then runs the step-wise HIP ops.  Launch failures raise RuntimeError.
+
+    Gradients: when grad mode is on and a tri-plane requires grad, the outputs are differentiable with respect to tex_planes and
+    geo_planes (one `ide3d_render_rays_backward` launch per backward; first order only).  No gradient is returned for `mlp`,
+    `cam2world`, `jitter` or `sigma_noise`, whether or not they require grad: a caller that needs those must run the step-wise
+    definition (TriplaneRenderer.forward does).  The forward values are those of the no-grad call, bit for bit.
     """
     assert clamp_mode in ('softplus', 'relu')
     _init()
@@ -358,8 +396,16 @@ def render_triplane_fused(tex_planes, geo_planes, mlp, cam2world, fov, resolutio
         tex_planes = tex_planes.contiguous(memory_format=torch.channels_last)
     if geo_planes.stride(1) != 1:
         geo_planes = geo_planes.contiguous(memory_format=torch.channels_last)
-    res = _plugin.render_rays(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
-                              0 if clamp_mode == 'softplus' else 1, False, white_back, max_depth)
+    clamp_code = 0 if clamp_mode == 'softplus' else 1
+    if torch.is_grad_enabled() and (tex_planes.requires_grad or geo_planes.requires_grad):
+        try:
+            res = _RenderRaysFused.apply(tex_planes, geo_planes, rays_d_cam, z_lin, cam2world, jitter, sigma_noise, mlp, clamp_code,
+                                         white_back, max_depth)
+        except _NoFusedKernel:
+            return None
+    else:
+        res = _plugin.render_rays(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_code, False,
+                                  white_back, max_depth)
     if res is None:
         return None
     feat, depth, wsum = res

@@ -304,6 +304,24 @@ typedef struct ide3d_render_params {
 int ide3d_render_rays(const ide3d_render_params* p, void* stream);
 
 /*
+ * Backward of ide3d_render_rays with respect to the two tri-planes (no gradient for the decoder weights, the camera, the jitter or
+ * the density noise).  p: the parameters the forward received (its out_* fields are ignored).  grad_feat [n, feat_ch + seg_ch,
+ * rays_per_img], grad_depth / grad_wsum [n, rays_per_img]: dL/d of the forward's three outputs, each may be NULL (= zero).  dL/dtex_planes
+ * and dL/dgeo_planes are ADDED to grad_tex_planes / grad_geo_planes, [n, 3*C, H, W] through element strides with channel stride 1
+ * (channels_last), which the caller zeroes.  The samples are rebuilt from p exactly as the forward built them; exact fp32 arithmetic.
+ * Accumulation uses float atomics, so the sums depend on arrival order: results agree to fp32 rounding, not bit for bit, between runs.
+ * IDE3D_ENOKERNEL for what the forward also declines (last_back, planes not channels_last, (C, hidden) other than (32, 64) / (16, 32)),
+ * gradient buffers that are not channels_last, and step counts whose per-ray state does not fit in LDS.
+ */
+typedef struct ide3d_render_grads {
+    const float* grad_feat;  const float* grad_depth;  const float* grad_wsum;   /* each may be NULL */
+    float* grad_tex_planes;  float* grad_geo_planes;                            /* [n, 3C, H, W], accumulated into */
+    int64_t grad_tex_stride[4];  int64_t grad_geo_stride[4];
+} ide3d_render_grads;
+
+int ide3d_render_rays_backward(const ide3d_render_params* p, const ide3d_render_grads* g, void* stream);
+
+/*
  * `renderer.sample_voxel(img_v, seg_v, pts)` (call site extract_shapes.py:146): the same two
  * gathers + MLPs for arbitrary points, no compositing.  out: [n*m, feat_ch + seg_ch + 1]
  * (sigma last).  If sigma_only != 0 only out_sigma [n*m] is written (the 256^3 density-cube
