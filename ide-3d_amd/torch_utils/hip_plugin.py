@@ -141,6 +141,18 @@ class _ModconvParams(ctypes.Structure):
     ]
 
 
+class _ActBwdParams(ctypes.Structure):
+    """ide3d_act_bwd_params (include/ide3d_hip.h): K1 of the convolution backward (ide3d_modconv_act_backward)."""
+    _fields_ = [
+        ('dy', ctypes.c_void_p), ('y', ctypes.c_void_p), ('dz', ctypes.c_void_p),
+        ('noise', ctypes.c_void_p), ('noise_strength', ctypes.c_float), ('bias', ctypes.c_void_p),
+        ('dcoefs', ctypes.c_void_p), ('ddcoefs', ctypes.c_void_p),
+        ('n', ctypes.c_int32), ('c', ctypes.c_int32), ('h', ctypes.c_int32), ('w', ctypes.c_int32), ('y_pitch', ctypes.c_int32),
+        ('act', ctypes.c_int32), ('alpha', ctypes.c_float), ('gain', ctypes.c_float), ('clamp', ctypes.c_float),
+        ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_int64),
+    ]
+
+
 class _ModconvHeadEpilogue(ctypes.Structure):
     """ide3d_modconv_head_epilogue (include/ide3d_hip.h): the dual heads fused behind a 3x3 layer (ide3d_modconv2d_heads)."""
     _fields_ = [
@@ -297,6 +309,11 @@ def load():
             'ide3d_modconv2d_heads': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), vp],
             'ide3d_modconv_plan': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvPlanInfo)],
             'ide3d_modconv_workspace_bytes': [i32, i32, i32, i32, i32, i32, i32, i32],
+            'ide3d_act_bwd_workspace_bytes': [i32, i32, i32, i32],
+            'ide3d_modconv_act_backward': [ctypes.POINTER(_ActBwdParams), vp],
+            'ide3d_modconv_scale_dot': [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp],
+            'ide3d_head_wgrad_workspace_bytes': [i32, i32, i32, i32, i32],
+            'ide3d_head_weight_grad': [vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp],
             'ide3d_set_conv_arithmetic': [i32],
             'ide3d_get_conv_arithmetic': [],
             'ide3d_frame_u8': [vp, vp, vp, i32, i32, i32, i32, vp, vp],
@@ -332,6 +349,8 @@ EXPORTED_SYMBOLS = (
     'ide3d_style_demod_batch', 'ide3d_fold_heads_batch',
     'ide3d_skip_upsample_add_cl', 'ide3d_bilinear_up2_split', 'ide3d_mapping', 'ide3d_mapping_workspace_bytes', 'ide3d_mapping_supported',
     'ide3d_lowres_layers_supported', 'ide3d_lowres_phase_r_plan', 'ide3d_lowres_workspace_bytes', 'ide3d_lowres_group',
+    'ide3d_act_bwd_workspace_bytes', 'ide3d_modconv_act_backward', 'ide3d_modconv_scale_dot', 'ide3d_head_wgrad_workspace_bytes',
+    'ide3d_head_weight_grad',
 )
 
 
@@ -1127,6 +1146,103 @@ class ModconvPlugin:
         return y, heads
 
 
+class ModconvGradPlugin:
+    """The streaming and reduction passes of the frozen-generator convolution backward (csrc/modconv_bwd.hip, DESIGN.md section 5.10);
+    the matrix work of that backward is `ModconvPlugin.modconv2d`."""
+
+    @staticmethod
+    def _f32(t, name, dev, shape=None):
+        _require(t.is_cuda and t.dtype == torch.float32 and t.device == dev, f'{name} must be float32 on the device of the gradient')
+        if shape is not None:
+            _require(tuple(t.shape) == tuple(shape), f'{name} must be {list(shape)}, got {list(t.shape)}')
+        return t
+
+    @staticmethod
+    def act_backward(dy, y, act, alpha, gain, clamp, noise=None, noise_strength=1.0, bias=None, dcoefs=None):
+        """K1 (ide3d_modconv_act_backward) -> (dz or None, ddcoefs or None).  act 1 / 3: dz = bias_act's grad = 1 form with yref = y (clamp < 0:
+        none); with `dcoefs`: ddcoefs = sum_p dz * (u - noise_strength * noise - bias) / dcoefs, u recovered from y.  act 0: the dot-only form,
+        ddcoefs = sum_p dy * y / dcoefs, no dz.  dy [n, c, h, w] dense; y of that shape (rows may be padded: a view [..., :w] of wider rows)."""
+        dev = dy.device
+        ModconvGradPlugin._f32(dy, 'dy', dev)
+        _require(dy.ndim == 4 and dy.is_contiguous(), 'act_backward: dy must be a contiguous [n, c, h, w] tensor')
+        n, c, h, w = dy.shape
+        ModconvGradPlugin._f32(y, 'y', dev, dy.shape)
+        _require(y.stride(3) == 1 and y.stride(2) >= w and y.stride(1) == h * y.stride(2) and y.stride(0) == c * y.stride(1),
+                 'act_backward: y must be dense apart from padded rows')
+        _require(act in (0, 1, 3), 'act_backward: act must be 0 (dot only), 1 (linear) or 3 (lrelu)')
+        _require(act != 0 or dcoefs is not None, 'act_backward: the dot-only form needs dcoefs')
+        lib = load()
+        p = _ActBwdParams()
+        keep = []
+        p.dy, p.y = dy.data_ptr(), y.data_ptr()
+        p.y_pitch = y.stride(2) if y.stride(2) != w else 0
+        dz = torch.empty_like(dy) if act != 0 else None
+        if dz is not None:
+            p.dz = dz.data_ptr()
+        if noise is not None:
+            noise = ModconvGradPlugin._f32(noise, 'noise', dev).contiguous(); keep.append(noise)
+            _require(noise.numel() == h * w, 'act_backward: noise must be [h, w]')
+            p.noise = noise.data_ptr()
+        p.noise_strength = float(noise_strength)
+        if bias is not None:
+            bias = ModconvGradPlugin._f32(bias, 'bias', dev, (c,)).contiguous(); keep.append(bias)
+            p.bias = bias.data_ptr()
+        dd = ws = None
+        if dcoefs is not None:
+            dcoefs = ModconvGradPlugin._f32(dcoefs, 'dcoefs', dev, (n, c)).contiguous(); keep.append(dcoefs)
+            dd = torch.empty([n, c], dtype=torch.float32, device=dev)
+            nbytes = lib.ide3d_act_bwd_workspace_bytes(n, c, h, w)
+            _require(nbytes > 0, 'act_backward: unsupported shape')
+            ws = torch.empty([nbytes // 4], dtype=torch.float32, device=dev)
+            p.dcoefs, p.ddcoefs, p.workspace, p.workspace_bytes = dcoefs.data_ptr(), dd.data_ptr(), ws.data_ptr(), nbytes
+        p.n, p.c, p.h, p.w = n, c, h, w
+        p.act, p.alpha, p.gain, p.clamp = int(act), float(alpha), float(gain), float(clamp)
+        with _dev_guard(dev):
+            rc = lib.ide3d_modconv_act_backward(ctypes.byref(p), _stream(dy))
+        _check(rc, 'modconv_act_backward')
+        return dz, dd
+
+    @staticmethod
+    def scale_dot(x, t, styles):
+        """K2 (ide3d_modconv_scale_dot): (dx = styles[n, c] * t, dstyles = sum_p x * t) for x, t [n, c, h, w], styles [n, c]."""
+        dev = t.device
+        ModconvGradPlugin._f32(t, 't', dev)
+        _require(t.ndim == 4 and t.is_contiguous(), 'scale_dot: t must be a contiguous [n, c, h, w] tensor')
+        n, c, h, w = t.shape
+        x = ModconvGradPlugin._f32(x, 'x', dev, t.shape).contiguous()
+        styles = ModconvGradPlugin._f32(styles, 'styles', dev, (n, c)).contiguous()
+        lib = load()
+        dx = torch.empty_like(t)
+        ds = torch.empty([n, c], dtype=torch.float32, device=dev)
+        nbytes = lib.ide3d_act_bwd_workspace_bytes(n, c, h, w)
+        _require(nbytes > 0, 'scale_dot: unsupported shape')
+        ws = torch.empty([nbytes // 4], dtype=torch.float32, device=dev)
+        with _dev_guard(dev):
+            rc = lib.ide3d_modconv_scale_dot(_ptr(x), _ptr(t), _ptr(styles), _ptr(dx), _ptr(ds), n, c, h, w, _ptr(ws), nbytes, _stream(t))
+        _check(rc, 'modconv_scale_dot')
+        return dx, ds
+
+    @staticmethod
+    def head_weight_grad(dy, x):
+        """K3 (ide3d_head_weight_grad): dw[n, o, i] = sum_p dy[n, o, p] * x[n, i, p] for dy [n, rows, h, w], x [n, cin, h, w]."""
+        dev = dy.device
+        ModconvGradPlugin._f32(dy, 'dy', dev)
+        _require(dy.ndim == 4 and x.ndim == 4 and x.shape[0] == dy.shape[0] and x.shape[2:] == dy.shape[2:], 'head_weight_grad: dy [n, rows, h, w], x [n, cin, h, w]')
+        dy = dy.contiguous()
+        x = ModconvGradPlugin._f32(x, 'x', dev).contiguous()
+        n, rows, h, w = dy.shape
+        cin = x.shape[1]
+        lib = load()
+        nbytes = lib.ide3d_head_wgrad_workspace_bytes(n, rows, cin, h, w)
+        _require(nbytes > 0, 'head_weight_grad: unsupported shape')
+        ws = torch.empty([nbytes // 4], dtype=torch.float32, device=dev)
+        dw = torch.empty([n, rows, cin], dtype=torch.float32, device=dev)
+        with _dev_guard(dev):
+            rc = lib.ide3d_head_weight_grad(_ptr(dy), _ptr(x), _ptr(dw), n, rows, cin, h, w, _ptr(ws), nbytes, _stream(dy))
+        _check(rc, 'head_weight_grad')
+        return dw
+
+
 def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epilogue='conv', x_amax=False):
     """Host-only (works without a GPU): the kernel family, tile and grid `modconv2d` would launch for this shape -> dict of the
     ide3d_modconv_plan_info fields, `kind` as a name from PLAN_KINDS.  epilogue: 'conv' (noise, bias, lrelu, gain sqrt(2): the 3x3 layers),
@@ -1588,6 +1704,7 @@ PLUGINS = {
     'triplane_plugin': TriplanePlugin,
     'volume_render_plugin': VolumeRenderPlugin,
     'modconv_plugin': ModconvPlugin,
+    'modconv_grad_plugin': ModconvGradPlugin,
     'frame_plugin': FramePlugin,
     'camera_plugin': CameraPlugin,
     'style_plugin': StylePlugin,

@@ -12,7 +12,9 @@ MI355X specifics: on device tensors in inference (no autograd graph) a stride-1 
 and its epilogue (noise, bias, leaky ReLU, gain, clamp) are ONE fp32-MFMA implicit-GEMM launch
 (`csrc/modconv.hip`); up-sampling layers run the reference's transposed-convolution + FIR strategy
 with the FIR, the demodulation/noise and the bias-activation on HIP kernels.  With autograd the blocks
-evaluate the same mathematics through differentiable ops.
+evaluate the same mathematics through differentiable ops, except where only the layer inputs and styles need
+a gradient (frozen weights: PTI-style projection), where the same HIP launches run with a HIP backward
+(`hip_conv_grad`, csrc/modconv_bwd.hip).
 """
 
 import math
@@ -445,6 +447,152 @@ def _modconv_bias_act(x, weight, styles, demodulate, noise2d, noise_strength, bi
         x_amax=(_amax_of(x) if xc is x else None), y_amax=amax), amax)
 
 
+# ---- frozen-generator gradients -------------------------------------------------------------------------------
+# With the weights frozen and the layer inputs or styles requiring grad (PTI-style projection: `G.synthesis(ws)` with `ws.requires_grad`), the
+# 3x3 layers, the up-sampling layers and the dual heads run their inference launches inside an autograd Function whose backward is HIP too:
+# ide3d_modconv2d for the input gradient, csrc/modconv_bwd.hip for the activation gradient, the style dots and the folded head weights.
+# False = the differentiable ATen definition, as for every other gradient.
+hip_conv_grad = True
+
+_modconv_grad_plugin = None
+_wgrad_cache = {}
+
+
+def _modconv_grad_init():
+    global _modconv_grad_plugin
+    if _modconv_grad_plugin is None:
+        _modconv_grad_plugin = custom_ops.get_plugin(module_name='modconv_grad_plugin', sources=['modconv_bwd.hip'])
+    return True
+
+
+def _conv_grad_ok(x, styles, *params):
+    """A layer takes the frozen-generator gradient path: grad enabled, its input or styles need a gradient, fp32 CUDA tensors, and none of the
+    tensors its launches read by pointer (`params`: _layer_params / _head_params) requires grad — a gradient would be dropped otherwise."""
+    return (hip_conv_grad and use_hip_modconv and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+            and styles.is_cuda and styles.dtype == torch.float32 and (x.requires_grad or styles.requires_grad)
+            and not any(t is not None and t.requires_grad for t in params) and _modconv_init() and _modconv_grad_init())
+
+
+def _grad_weight(weight, flip):
+    """weight.transpose(0, 1) (.flip(2, 3) when `flip`): the weights of the input gradient's convolution, cached per (tensor object,
+    version) like `_scaled_weight`, so that the packed copy in the HIP workspace stays valid across calls."""
+    key = (id(weight), bool(flip))
+    ent = _wgrad_cache.get(key)
+    if ent is None or ent[0]() is not weight or ent[1] != _stamp(weight):
+        _evict_dead(_wgrad_cache)
+        wt = weight.detach().transpose(0, 1)
+        ent = (weakref.ref(weight), _stamp(weight), (wt.flip(2, 3) if flip else wt).contiguous())
+        _wgrad_cache[key] = ent
+    return ent[2]
+
+
+class _ModconvActGrad(torch.autograd.Function):
+    """A stride-1 3x3 SynthesisLayer: forward = the one launch of `_modconv_bias_act`; gradients for x, styles and dcoefs.
+      u = d[n,o] * conv(w, s * x) + noise + b[o],  y = clamp(act(u) * gain)
+      dz = dy * act'(.) (K1),  d dcoefs = sum_p dz * (u - noise - b) / d (K1, u recovered from y),
+      t = conv(w^T flipped, d * dz) (ide3d_modconv2d mode 0),  dx = s * t,  d styles = sum_p x * t (K2)."""
+
+    @staticmethod
+    def forward(ctx, x, styles, dcoefs, weight, noise, bias, act, gain, clamp):
+        spec = bias_act.activation_funcs[act]
+        xc, styles, dcoefs = x.contiguous(), styles.contiguous(), dcoefs.contiguous()
+        y = _modconv_plugin.modconv2d(xc, weight.contiguous(), styles, dcoefs, noise, 1.0, bias, spec.cuda_idx, spec.def_alpha, gain,
+                                      -1.0 if clamp is None else clamp)
+        ctx.save_for_backward(xc, styles, dcoefs, y)
+        ctx.weight, ctx.noise, ctx.bias, ctx.act, ctx.gain, ctx.clamp = weight, noise, bias, act, gain, clamp
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, styles, dcoefs, y = ctx.saved_tensors
+        spec = bias_act.activation_funcs[ctx.act]
+        dz, ddc = _modconv_grad_plugin.act_backward(dy.contiguous(), y, spec.cuda_idx, spec.def_alpha, ctx.gain,
+                                                    -1.0 if ctx.clamp is None else ctx.clamp, noise=ctx.noise, noise_strength=1.0,
+                                                    bias=ctx.bias, dcoefs=dcoefs)
+        dx = ds = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            t = _modconv_plugin.modconv2d(dz, _grad_weight(ctx.weight, True), dcoefs, None, None, 0.0, None, 1, 0.0, 1.0, -1.0)
+            dx, ds = _modconv_grad_plugin.scale_dot(x, t, styles)
+        return dx, ds, ddc, None, None, None, None, None, None
+
+
+class _ModconvUpGrad(torch.autograd.Function):
+    """An up-sampling SynthesisLayer: forward = the two inference launches (transposed conv, mode 2; FIR + noise + bias + act); gradients for
+    x, styles and dcoefs.  y_t = d * convT(w, s * x) (demodulated, (2h+1) x (2w+1)), y = clamp(act(FIR(y_t) * 4 + noise + b) * gain)
+      dz = dy * act'(.) (K1),  g_t = FIR adjoint of dz (upfirdn2d: flipped filter, pad 2),  d dcoefs = sum_p g_t * y_t / d (K1, dot only),
+      t = conv(w^T, d * g_t, stride 2) (ide3d_modconv2d mode 1),  dx = s * t,  d styles = sum_p x * t (K2)."""
+
+    @staticmethod
+    def forward(ctx, x, styles, dcoefs, weight, fir, noise, bias, act, gain, clamp):
+        spec = bias_act.activation_funcs[act]
+        xc, styles, dcoefs = x.contiguous(), styles.contiguous(), dcoefs.contiguous()
+        yt = _modconv_plugin.modconv2d(xc, weight.contiguous(), styles, dcoefs, None, 0.0, None, 1, 0.0, 1.0, -1.0, mode=2, pad_rows=True)
+        y = _upfirdn_plugin().upfirdn2d_ex(yt, fir, 1, 1, 1, 1, 1, 1, 1, 1, False, 4.0, noise=noise, noise_strength=1.0, bias=bias,
+                                           act=spec.cuda_idx, alpha=spec.def_alpha, act_gain=gain, clamp=(-1.0 if clamp is None else clamp))
+        ctx.save_for_backward(xc, styles, dcoefs, yt, y)
+        ctx.weight, ctx.fir, ctx.act, ctx.gain, ctx.clamp = weight, fir, act, gain, clamp
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, styles, dcoefs, yt, y = ctx.saved_tensors
+        spec = bias_act.activation_funcs[ctx.act]
+        dz, _ = _modconv_grad_plugin.act_backward(dy.contiguous(), y, spec.cuda_idx, spec.def_alpha, ctx.gain,
+                                                  -1.0 if ctx.clamp is None else ctx.clamp)
+        gt = _upfirdn_plugin().upfirdn2d(dz, ctx.fir, 1, 1, 1, 1, 2, 2, 2, 2, True, 4.0)
+        _, ddc = _modconv_grad_plugin.act_backward(gt, yt, 0, 0.0, 1.0, -1.0, dcoefs=dcoefs)
+        dx = ds = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            t = _modconv_plugin.modconv2d(gt, _grad_weight(ctx.weight, False), dcoefs, None, None, 0.0, None, 1, 0.0, 1.0, -1.0, mode=1)
+            dx, ds = _modconv_grad_plugin.scale_dot(x, t, styles)
+        return dx, ds, ddc, None, None, None, None, None, None, None
+
+
+class _DualHeadGrad(torch.autograd.Function):
+    """The dual heads as one 1x1 launch over per-image folded weights Wf [n, rows, C, 1, 1]: y = clamp(conv(Wf, x) + b); gradients for x and
+    Wf (autograd carries dWf back through the fold).  Like bias_act's linear activation, the gradient passes the clamp unmasked.
+      dx = conv(Wf^T, dy) (ide3d_modconv2d, per-image weights),  dWf[n, o, i] = sum_p dy[n, o, p] * x[n, i, p] (K3)."""
+
+    @staticmethod
+    def forward(ctx, x, wcat, bias, clamp):
+        xc = x.contiguous()
+        y = _modconv_plugin.modconv2d(xc, wcat, None, None, None, 0.0, bias, 1, 0.0, 1.0, clamp)
+        ctx.save_for_backward(xc, wcat)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wcat = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = _modconv_plugin.modconv2d(dy, wcat.detach().transpose(1, 2).contiguous(), None, None, None, 0.0, None, 1, 0.0, 1.0, -1.0)
+        if ctx.needs_input_grad[1]:
+            dw = _modconv_grad_plugin.head_weight_grad(dy, x).reshape(wcat.shape)
+        return dx, dw, None, None
+
+
+def _synthesis_layer_grad(lay, x, styles, dcoefs, noise, act_gain, act_clamp):
+    """SynthesisLayer.forward on the frozen-generator gradient path, or None when it does not apply (the caller keeps its path)."""
+    if not (lay.weight.shape[2:] == (3, 3) and lay.padding == 1 and lay.up in (1, 2) and lay.activation in ('linear', 'lrelu') and x.ndim == 4
+            and styles.shape[0] == x.shape[0] and _conv_grad_ok(x, styles, *_layer_params(lay))):
+        return None
+    oh, ow = lay.up * x.shape[2], lay.up * x.shape[3]
+    # the backward's launches index with 32 bits: the input of its convolution (the up-sampling layer's FIR adjoint is (2h+1) x (2w+1))
+    # must stay below 2^31 elements, or the layer keeps the ATen path instead of failing in backward
+    gh, gw = (oh + 1, ow + 1) if lay.up == 2 else (oh, ow)
+    if x.shape[0] * lay.weight.shape[0] * gh * gw >= 2 ** 31 or x.numel() >= 2 ** 31:
+        return None
+    if noise is not None and not (noise.ndim == 2 and tuple(noise.shape) == (oh, ow) and not noise.requires_grad):
+        return None
+    if dcoefs is None:
+        dcoefs = _demod_coefs(lay.weight, styles)
+    bias = lay.bias.to(x.dtype)
+    if lay.up == 1:
+        return _ModconvActGrad.apply(x, styles, dcoefs, lay.weight, noise, bias, lay.activation, act_gain, act_clamp)
+    return _ModconvUpGrad.apply(x, styles, dcoefs, lay.weight, lay.resample_filter, noise, bias, lay.activation, act_gain, act_clamp)
+
+
 def _folded_head_weights(torgb, toseg, w):
     """Per-image 1x1 weights [N, Co_rgb + Co_seg, Cin, 1, 1] of the two heads with their styles folded in (ONE launch of
     csrc/style.hip), or None when the HIP path does not apply."""
@@ -488,7 +636,16 @@ def _dual_head(x, torgb, toseg, w, wcat=None):
     """toRGB + toSeg of a dual-path block (reference networks.py:1109,1130) as ONE 1x1 implicit-GEMM launch.
     The two heads modulate with different styles, so the styles are folded into per-image weights
     [N, Cout_rgb + Cout_seg, Cin, 1, 1] (tiny) and the activation tensor x is read from HBM once.
-    Inference on device tensors only; returns None otherwise.  `wcat`: the folded weights, when the caller already has them."""
+    Inference on device tensors only; returns None otherwise.  `wcat`: the folded weights, when the caller already has them.
+    With the heads' input or styles requiring grad and their parameters frozen: the same launch with a HIP backward (_DualHeadGrad)."""
+    if (hip_conv_grad and torch.is_grad_enabled() and torgb.weight.shape[2] == 1 and torgb.conv_clamp == toseg.conv_clamp and x.ndim == 4
+            and w.ndim == 2 and w.shape[0] == x.shape[0] and x.numel() < 2 ** 31
+            and x.shape[0] * (torgb.weight.shape[0] + toseg.weight.shape[0]) * x.shape[2] * x.shape[3] < 2 ** 31
+            and _conv_grad_ok(x, w, *_head_params(torgb, toseg))):
+        y = _DualHeadGrad.apply(x, _dual_head_weights(torgb, toseg, w), _cat_cached(torgb.bias, toseg.bias),
+                                -1.0 if torgb.conv_clamp is None else torgb.conv_clamp)
+        co = torgb.weight.shape[0]
+        return y[:, :co], y[:, co:]
     if not (use_hip_modconv and torgb.weight.shape[2] == 1 and torgb.conv_clamp == toseg.conv_clamp
             and _inference_on_gpu(x, w, *_head_params(torgb, toseg)) and _modconv_init()):
         return None
@@ -910,6 +1067,11 @@ class SynthesisLayer(torch.nn.Module):
         act_gain = self.act_gain * gain
         act_clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
 
+        if hip_conv_grad and torch.is_grad_enabled() and input_noise is None and (noise is None or const_noise):
+            # frozen weights, input or styles requiring grad: the inference launches with a HIP backward
+            y = _synthesis_layer_grad(self, x, styles, dcoefs_pre, noise, act_gain, act_clamp)
+            if y is not None:
+                return y
         if (self.up == 2 and use_hip_modconv and self.weight.shape[2] == 3 and self.padding == 1
                 and _inference_on_gpu(x, self.weight, styles, self.bias, noise) and _modconv_init()):
             # up-sampling layer, MI355X inference path (same strategy as conv2d_resample.py:112-129): transposed

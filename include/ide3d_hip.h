@@ -424,6 +424,49 @@ typedef struct ide3d_modconv_head_epilogue {
 } ide3d_modconv_head_epilogue;
 int ide3d_modconv2d_heads(const ide3d_modconv_params* p, const ide3d_modconv_head_epilogue* heads, void* stream);
 
+/*
+ * Frozen-generator backward of the synthesis convolutions (gradients for the layer inputs and the styles; weights, biases and affines
+ * frozen).  Replaces the autograd of `modulated_conv2d` + `bias_act` (inversion/networks.py:55-130, SynthesisLayer :457-512), of the
+ * transposed up-sampling convolution (conv2d_resample.py:112-129) and of ToRGBLayer (:670-713).  The matrix work is ide3d_modconv2d
+ * (input gradient of a stride-1 layer: mode 0 with w.transpose(0,1).flip(2,3) and styles = dcoefs; of an up-sampling layer: mode 1 with
+ * w.transpose(0,1); of the dual heads: per-image transposed folded weights); these entry points are the streaming and reduction passes
+ * around it.  Reductions use fixed-order partial sums and a second launch, no atomics: results are bit-reproducible from run to run.
+ *
+ * ide3d_modconv_act_backward (K1).  act 1 / 3: dz = the grad = 1 form of ide3d_bias_act with yref = y, dy = NULL (bit-equal to it) and,
+ * when ddcoefs != NULL, ddcoefs[n, c] = sum_p dz * (u - noise_strength * noise - bias) / dcoefs[n, c], u = the pre-activation recovered
+ * from y (lrelu inverted; clamped elements have dz = 0).  act 0 (dot-only form): ddcoefs[n, c] = sum_p dy * y / dcoefs[n, c], dz unused.
+ * dy, dz [n, c, h, w] dense; y [n, c, h, y_pitch] (y_pitch 0 = w: dense; else padded rows, e.g. the `y_pitch` output of a mode-2
+ * ide3d_modconv2d); noise [h, w] or NULL; bias [c] or NULL.  workspace: ide3d_act_bwd_workspace_bytes() bytes (needed with ddcoefs only).
+ */
+typedef struct ide3d_act_bwd_params {
+    const float* dy;
+    const float* y;
+    float*       dz;
+    const float* noise;
+    float        noise_strength;
+    const float* bias;
+    const float* dcoefs;
+    float*       ddcoefs;
+    int32_t      n, c, h, w, y_pitch;
+    int32_t      act;
+    float        alpha, gain, clamp;
+    float*       workspace;
+    int64_t      workspace_bytes;
+} ide3d_act_bwd_params;
+
+int64_t ide3d_act_bwd_workspace_bytes(int32_t n, int32_t c, int32_t h, int32_t w);
+int ide3d_modconv_act_backward(const ide3d_act_bwd_params* p, void* stream);
+
+/* K2: dx = styles[n, c] * t and dstyles[n, c] = sum_p x * t; x, t, dx [n, c, h, w] dense, workspace of ide3d_act_bwd_workspace_bytes(). */
+int ide3d_modconv_scale_dot(const float* x, const float* t, const float* styles, float* dx, float* dstyles,
+                            int32_t n, int32_t c, int32_t h, int32_t w, float* workspace, int64_t workspace_bytes, void* stream);
+
+/* K3: dw[n, o, i] = sum_p dy[n, o, p] * x[n, i, p] — the gradient of per-image 1x1 weights (ide3d_modconv2d with w_batch_stride > 0, the
+ * folded dual heads); dy [n, rows, h, w], x [n, cin, h, w] dense, dw [n, rows, cin].  Exact fp32 FMAs on the vector pipe. */
+int64_t ide3d_head_wgrad_workspace_bytes(int32_t n, int32_t rows, int32_t cin, int32_t h, int32_t w);
+int ide3d_head_weight_grad(const float* dy, const float* x, float* dw, int32_t n, int32_t rows, int32_t cin, int32_t h, int32_t w,
+                           float* workspace, int64_t workspace_bytes, void* stream);
+
 /* Host-only planning query (no launch, no device access): the kernel family, tile and grid that ide3d_modconv2d would use for `p` in the
  * arithmetic `p->arith` resolves to.  Pointers are not dereferenced (set `x_amax` non-null to plan the f16x3 launch; `x` counts for its
  * alignment only).  For tests of the planner and for tooling; not part of the reference's interface. */
