@@ -153,6 +153,15 @@ class _ActBwdParams(ctypes.Structure):
     ]
 
 
+class _WgradParams(ctypes.Structure):
+    """ide3d_wgrad_params (include/ide3d_hip.h): the direct weight gradient of a modulated 3x3 convolution (ide3d_modconv_weight_grad)."""
+    _fields_ = [
+        ('g', ctypes.c_void_p), ('x', ctypes.c_void_p), ('styles', ctypes.c_void_p), ('dcoefs', ctypes.c_void_p), ('dw', ctypes.c_void_p),
+        ('n', ctypes.c_int32), ('cin', ctypes.c_int32), ('cout', ctypes.c_int32), ('h', ctypes.c_int32), ('w', ctypes.c_int32),
+        ('mode', ctypes.c_int32), ('arith', ctypes.c_int32), ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_int64),
+    ]
+
+
 class _ModconvHeadEpilogue(ctypes.Structure):
     """ide3d_modconv_head_epilogue (include/ide3d_hip.h): the dual heads fused behind a 3x3 layer (ide3d_modconv2d_heads)."""
     _fields_ = [
@@ -314,6 +323,10 @@ def load():
             'ide3d_modconv_scale_dot': [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp],
             'ide3d_head_wgrad_workspace_bytes': [i32, i32, i32, i32, i32],
             'ide3d_head_weight_grad': [vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp],
+            'ide3d_wgrad_workspace_bytes': [i32, i32, i32, i32, i32],
+            'ide3d_modconv_weight_grad': [ctypes.POINTER(_WgradParams), vp],
+            'ide3d_bias_noise_workspace_bytes': [i32, i32, i32, i32],
+            'ide3d_bias_noise_grad': [vp, vp, vp, i32, i32, i32, i32, vp, i64, vp],
             'ide3d_set_conv_arithmetic': [i32],
             'ide3d_get_conv_arithmetic': [],
             'ide3d_frame_u8': [vp, vp, vp, i32, i32, i32, i32, vp, vp],
@@ -350,7 +363,8 @@ EXPORTED_SYMBOLS = (
     'ide3d_skip_upsample_add_cl', 'ide3d_bilinear_up2_split', 'ide3d_mapping', 'ide3d_mapping_workspace_bytes', 'ide3d_mapping_supported',
     'ide3d_lowres_layers_supported', 'ide3d_lowres_phase_r_plan', 'ide3d_lowres_workspace_bytes', 'ide3d_lowres_group',
     'ide3d_act_bwd_workspace_bytes', 'ide3d_modconv_act_backward', 'ide3d_modconv_scale_dot', 'ide3d_head_wgrad_workspace_bytes',
-    'ide3d_head_weight_grad',
+    'ide3d_head_weight_grad', 'ide3d_wgrad_workspace_bytes', 'ide3d_modconv_weight_grad', 'ide3d_bias_noise_workspace_bytes',
+    'ide3d_bias_noise_grad',
 )
 
 
@@ -1241,6 +1255,59 @@ class ModconvGradPlugin:
             rc = lib.ide3d_head_weight_grad(_ptr(dy), _ptr(x), _ptr(dw), n, rows, cin, h, w, _ptr(ws), nbytes, _stream(dy))
         _check(rc, 'head_weight_grad')
         return dw
+
+    @staticmethod
+    def weight_grad(g, x, styles, dcoefs, mode=0, arith=0):
+        """ide3d_modconv_weight_grad -> dw [cout, cin, 3, 3], the direct weight gradient of a modulated 3x3 convolution.
+        mode 0: g [n, cout, h, w] (dz of a stride-1 layer); mode 2: g [n, cout, 2h + 1, 2w + 1] (the FIR adjoint g_t of an up-sampling layer);
+        x [n, cin, h, w]; styles [n, cin], dcoefs [n, cout] or None.  arith: 0 = the process arithmetic, 1 fp32, 6 bf16x6."""
+        dev = g.device
+        ModconvGradPlugin._f32(g, 'g', dev)
+        _require(g.ndim == 4 and x.ndim == 4 and x.shape[0] == g.shape[0], 'weight_grad: g [n, cout, gh, gw], x [n, cin, h, w]')
+        _require(mode in (0, 2), 'weight_grad: mode must be 0 or 2')
+        n, cout = g.shape[:2]
+        cin, h, w = x.shape[1:]
+        _require(tuple(g.shape[2:]) == ((h, w) if mode == 0 else (2 * h + 1, 2 * w + 1)), f'weight_grad: g must be {"h x w" if mode == 0 else "(2h+1) x (2w+1)"} of x')
+        g = g.contiguous()
+        x = ModconvGradPlugin._f32(x, 'x', dev).contiguous()
+        if styles is not None:
+            styles = ModconvGradPlugin._f32(styles, 'styles', dev, (n, cin)).contiguous()
+        if dcoefs is not None:
+            dcoefs = ModconvGradPlugin._f32(dcoefs, 'dcoefs', dev, (n, cout)).contiguous()
+        lib = load()
+        nbytes = lib.ide3d_wgrad_workspace_bytes(n, cin, cout, h, w)
+        _require(nbytes > 0, 'weight_grad: unsupported shape')
+        ws = torch.empty([nbytes // 4], dtype=torch.float32, device=dev)
+        dw = torch.empty([cout, cin, 3, 3], dtype=torch.float32, device=dev)
+        p = _WgradParams()
+        p.g, p.x, p.dw = g.data_ptr(), x.data_ptr(), dw.data_ptr()
+        p.styles = styles.data_ptr() if styles is not None else None
+        p.dcoefs = dcoefs.data_ptr() if dcoefs is not None else None
+        p.n, p.cin, p.cout, p.h, p.w, p.mode, p.arith = n, cin, cout, h, w, int(mode), int(arith)
+        p.workspace, p.workspace_bytes = ws.data_ptr(), nbytes
+        with _dev_guard(dev):
+            rc = lib.ide3d_modconv_weight_grad(ctypes.byref(p), _stream(g))
+        _check(rc, 'modconv_weight_grad')
+        return dw
+
+    @staticmethod
+    def bias_noise_grad(dz, noise=False):
+        """ide3d_bias_noise_grad -> (db [c], dnoise [h, w] or None): db = sum_{n,p} dz, dnoise = sum_{n,c} dz for dz [n, c, h, w]."""
+        dev = dz.device
+        ModconvGradPlugin._f32(dz, 'dz', dev)
+        _require(dz.ndim == 4, 'bias_noise_grad: dz must be [n, c, h, w]')
+        dz = dz.contiguous()
+        n, c, h, w = dz.shape
+        lib = load()
+        nbytes = lib.ide3d_bias_noise_workspace_bytes(n, c, h, w)
+        _require(nbytes > 0, 'bias_noise_grad: unsupported shape')
+        ws = torch.empty([nbytes // 4], dtype=torch.float32, device=dev)
+        db = torch.empty([c], dtype=torch.float32, device=dev)
+        dn = torch.empty([h, w], dtype=torch.float32, device=dev) if noise else None
+        with _dev_guard(dev):
+            rc = lib.ide3d_bias_noise_grad(dz.data_ptr(), db.data_ptr(), _ptr(dn), n, c, h, w, ws.data_ptr(), nbytes, _stream(dz))
+        _check(rc, 'bias_noise_grad')
+        return db, dn
 
 
 def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epilogue='conv', x_amax=False):

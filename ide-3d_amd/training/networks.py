@@ -14,7 +14,8 @@ and its epilogue (noise, bias, leaky ReLU, gain, clamp) are ONE fp32-MFMA implic
 with the FIR, the demodulation/noise and the bias-activation on HIP kernels.  With autograd the blocks
 evaluate the same mathematics through differentiable ops, except where only the layer inputs and styles need
 a gradient (frozen weights: PTI-style projection), where the same HIP launches run with a HIP backward
-(`hip_conv_grad`, csrc/modconv_bwd.hip).
+(`hip_conv_grad`, csrc/modconv_bwd.hip).  With `hip_param_grad` (opt-in) the same launches also serve trainable layer
+parameters (PTI pivotal tuning): the weight, bias and noise gradients are HIP too.
 """
 
 import math
@@ -453,6 +454,10 @@ def _modconv_bias_act(x, weight, styles, demodulate, noise2d, noise_strength, bi
 # ide3d_modconv2d for the input gradient, csrc/modconv_bwd.hip for the activation gradient, the style dots and the folded head weights.
 # False = the differentiable ATen definition, as for every other gradient.
 hip_conv_grad = True
+# Parameter gradients (PTI pivotal tuning): with this switch on, a layer whose weight, bias, noise strength or affine
+# requires grad takes the same path; its backward adds the direct weight gradient (ide3d_modconv_weight_grad) and the bias / noise
+# reductions (ide3d_bias_noise_grad).  Off: such a layer keeps the differentiable ATen definition.
+hip_param_grad = False
 
 _modconv_grad_plugin = None
 _wgrad_cache = {}
@@ -466,11 +471,15 @@ def _modconv_grad_init():
 
 
 def _conv_grad_ok(x, styles, *params):
-    """A layer takes the frozen-generator gradient path: grad enabled, its input or styles need a gradient, fp32 CUDA tensors, and none of the
-    tensors its launches read by pointer (`params`: _layer_params / _head_params) requires grad — a gradient would be dropped otherwise."""
+    """A layer takes the HIP gradient path: grad enabled, fp32 CUDA tensors, and its input or styles need a gradient.  Without
+    `hip_param_grad`, none of the tensors its launches read by pointer (`params`: _layer_params / _head_params) may require grad (a gradient
+    would be dropped otherwise); with it, a trainable parameter is a reason to take the path (the caller checks what still declines)."""
+    trainable = any(t is not None and t.requires_grad for t in params)
+    if trainable and not (hip_param_grad and all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in params)):
+        return False
     return (hip_conv_grad and use_hip_modconv and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
-            and styles.is_cuda and styles.dtype == torch.float32 and (x.requires_grad or styles.requires_grad)
-            and not any(t is not None and t.requires_grad for t in params) and _modconv_init() and _modconv_grad_init())
+            and styles.is_cuda and styles.dtype == torch.float32 and (x.requires_grad or styles.requires_grad or trainable)
+            and _modconv_init() and _modconv_grad_init())
 
 
 def _grad_weight(weight, flip):
@@ -484,6 +493,16 @@ def _grad_weight(weight, flip):
         ent = (weakref.ref(weight), _stamp(weight), (wt.flip(2, 3) if flip else wt).contiguous())
         _wgrad_cache[key] = ent
     return ent[2]
+
+
+def _bias_noise_grads(ctx, dz, i_noise, i_bias):
+    """(d bias, d noise) of a layer from dz (ide3d_bias_noise_grad), each None unless autograd asks for it (a trainable bias; a const noise
+    map that carries a trainable noise strength)."""
+    want_n = ctx.needs_input_grad[i_noise] and ctx.noise is not None
+    if not (ctx.needs_input_grad[i_bias] or want_n):
+        return None, None
+    db, dn = _modconv_grad_plugin.bias_noise_grad(dz, noise=want_n)
+    return (db if ctx.needs_input_grad[i_bias] else None), dn
 
 
 class _ModconvActGrad(torch.autograd.Function):
@@ -513,7 +532,9 @@ class _ModconvActGrad(torch.autograd.Function):
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             t = _modconv_plugin.modconv2d(dz, _grad_weight(ctx.weight, True), dcoefs, None, None, 0.0, None, 1, 0.0, 1.0, -1.0)
             dx, ds = _modconv_grad_plugin.scale_dot(x, t, styles)
-        return dx, ds, ddc, None, None, None, None, None, None
+        dw = _modconv_grad_plugin.weight_grad(dz, x, styles, dcoefs, mode=0) if ctx.needs_input_grad[3] else None
+        db, dn = _bias_noise_grads(ctx, dz, 4, 5)
+        return dx, ds, ddc, dw, dn, db, None, None, None
 
 
 class _ModconvUpGrad(torch.autograd.Function):
@@ -530,7 +551,7 @@ class _ModconvUpGrad(torch.autograd.Function):
         y = _upfirdn_plugin().upfirdn2d_ex(yt, fir, 1, 1, 1, 1, 1, 1, 1, 1, False, 4.0, noise=noise, noise_strength=1.0, bias=bias,
                                            act=spec.cuda_idx, alpha=spec.def_alpha, act_gain=gain, clamp=(-1.0 if clamp is None else clamp))
         ctx.save_for_backward(xc, styles, dcoefs, yt, y)
-        ctx.weight, ctx.fir, ctx.act, ctx.gain, ctx.clamp = weight, fir, act, gain, clamp
+        ctx.weight, ctx.fir, ctx.noise, ctx.act, ctx.gain, ctx.clamp = weight, fir, noise, act, gain, clamp
         return y
 
     @staticmethod
@@ -545,7 +566,9 @@ class _ModconvUpGrad(torch.autograd.Function):
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             t = _modconv_plugin.modconv2d(gt, _grad_weight(ctx.weight, False), dcoefs, None, None, 0.0, None, 1, 0.0, 1.0, -1.0, mode=1)
             dx, ds = _modconv_grad_plugin.scale_dot(x, t, styles)
-        return dx, ds, ddc, None, None, None, None, None, None, None
+        dw = _modconv_grad_plugin.weight_grad(gt, x, styles, dcoefs, mode=2) if ctx.needs_input_grad[3] else None
+        db, dn = _bias_noise_grads(ctx, dz, 5, 6)
+        return dx, ds, ddc, dw, None, dn, db, None, None, None
 
 
 class _DualHeadGrad(torch.autograd.Function):
@@ -569,7 +592,8 @@ class _DualHeadGrad(torch.autograd.Function):
             dx = _modconv_plugin.modconv2d(dy, wcat.detach().transpose(1, 2).contiguous(), None, None, None, 0.0, None, 1, 0.0, 1.0, -1.0)
         if ctx.needs_input_grad[1]:
             dw = _modconv_grad_plugin.head_weight_grad(dy, x).reshape(wcat.shape)
-        return dx, dw, None, None
+        db = _modconv_grad_plugin.bias_noise_grad(dy)[0] if ctx.needs_input_grad[2] else None
+        return dx, dw, db, None
 
 
 def _synthesis_layer_grad(lay, x, styles, dcoefs, noise, act_gain, act_clamp):
@@ -583,7 +607,10 @@ def _synthesis_layer_grad(lay, x, styles, dcoefs, noise, act_gain, act_clamp):
     gh, gw = (oh + 1, ow + 1) if lay.up == 2 else (oh, ow)
     if x.shape[0] * lay.weight.shape[0] * gh * gw >= 2 ** 31 or x.numel() >= 2 ** 31:
         return None
-    if noise is not None and not (noise.ndim == 2 and tuple(noise.shape) == (oh, ow) and not noise.requires_grad):
+    if noise is not None and not (noise.ndim == 2 and tuple(noise.shape) == (oh, ow) and (hip_param_grad or not noise.requires_grad)):
+        return None
+    # trainable parameters (hip_param_grad): the const noise map itself and the FIR filter have no gradient on this path
+    if (getattr(lay, 'noise_const', None) is not None and lay.noise_const.requires_grad) or lay.resample_filter.requires_grad:
         return None
     if dcoefs is None:
         dcoefs = _demod_coefs(lay.weight, styles)

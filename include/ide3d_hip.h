@@ -467,6 +467,43 @@ int64_t ide3d_head_wgrad_workspace_bytes(int32_t n, int32_t rows, int32_t cin, i
 int ide3d_head_weight_grad(const float* dy, const float* x, float* dw, int32_t n, int32_t rows, int32_t cin, int32_t h, int32_t w,
                            float* workspace, int64_t workspace_bytes, void* stream);
 
+/*
+ * Parameter gradients of the synthesis convolutions (PTI pivotal tuning, the generator trainable).
+ *
+ * ide3d_modconv_weight_grad: the direct weight gradient of a modulated 3x3 convolution, dw [cout, cin, 3, 3] (the demodulation part of
+ * the weight gradient is not included: autograd adds it through the dcoefs).  g: the gradient at the convolution output before
+ * demodulation; styles [n, cin] and dcoefs [n, cout] (NULL = 1).
+ *   mode 0 (stride 1, pad 1, correlation; ide3d_modconv2d mode 0): g [n, cout, h, w],
+ *          dw[o, i, ky, kx] = sum_n dcoefs[n, o] styles[n, i] sum_{y,x} g[n, o, y, x] x[n, i, y + ky - 1, x + kx - 1];
+ *   mode 2 (transposed, stride 2, pad 0; ide3d_modconv2d mode 2): g [n, cout, 2h + 1, 2w + 1],
+ *          dw[o, i, ky, kx] = sum_n dcoefs[n, o] styles[n, i] sum_{y,x} g[n, o, 2y + ky, 2x + kx] x[n, i, y, x].
+ * x [n, cin, h, w]; all dense.  arith: 0 = the process arithmetic (ide3d_get_conv_arithmetic), 1 = exact fp32 products
+ * (v_mfma_f32_32x32x2_f32), 6 = bf16x6; 3 (bf16x3) and 16 (f16x3) run bf16x6.  Split-K partial slices per (image, pixel range) in the
+ * workspace (ide3d_wgrad_workspace_bytes(), the same for both modes), added in a fixed order by a second launch: bit-reproducible, no
+ * atomics.  Exclusive residency (its matrix loop is LDS-fed bf16).
+ */
+typedef struct ide3d_wgrad_params {
+    const float* g;
+    const float* x;
+    const float* styles;
+    const float* dcoefs;
+    float*       dw;
+    int32_t      n, cin, cout, h, w;
+    int32_t      mode;
+    int32_t      arith;
+    float*       workspace;
+    int64_t      workspace_bytes;
+} ide3d_wgrad_params;
+
+int64_t ide3d_wgrad_workspace_bytes(int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w);
+int ide3d_modconv_weight_grad(const ide3d_wgrad_params* p, void* stream);
+
+/* db[c] = sum_{n,p} dz[n, c, p] and, when dnoise != NULL, dnoise[p] = sum_{n,c} dz[n, c, p] (the gradients of a layer's bias and of its
+ * [h, w] noise map); dz [n, c, h, w] dense; workspace of ide3d_bias_noise_workspace_bytes().  Fixed-order sums, bit-reproducible. */
+int64_t ide3d_bias_noise_workspace_bytes(int32_t n, int32_t c, int32_t h, int32_t w);
+int ide3d_bias_noise_grad(const float* dz, float* db, float* dnoise, int32_t n, int32_t c, int32_t h, int32_t w,
+                          float* workspace, int64_t workspace_bytes, void* stream);
+
 /* Host-only planning query (no launch, no device access): the kernel family, tile and grid that ide3d_modconv2d would use for `p` in the
  * arithmetic `p->arith` resolves to.  Pointers are not dereferenced (set `x_amax` non-null to plan the f16x3 launch; `x` counts for its
  * alignment only).  For tests of the planner and for tooling; not part of the reference's interface. */
