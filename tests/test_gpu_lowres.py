@@ -8,6 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+# the blocks in float64 (tests/blocks64.py): plain torch operations, none of the product's code paths
+from blocks64 import blocks64 as _blocks64, layer64 as _layer64, styles64 as _styles64
+
 pytestmark = pytest.mark.gpu
 
 
@@ -146,90 +149,6 @@ def test_group_against_float64_definition(gpu_device):
     assert info is not None and info[0] == 3
     x, img, seg = _blocks64(blocks, ws_list)
     assert _rel(xg, x) < 4e-6 and _rel(ig, img) < 4e-6 and _rel(sg, seg) < 4e-6, (_rel(xg, x), _rel(ig, img), _rel(sg, seg))
-
-
-# ---- the blocks in float64 (inversion/networks.py:330-514 SynthesisLayer, :670-713 ToRGBLayer, :966-1139 SegSynthesisBlock; conv2d_resample.py
-# :112-129; upfirdn2d.py:313-349): plain float64 torch operations on the modules' device, differentiable (the gradient tests run it on a float64
-# CPU copy of the blocks).  None of the product's code paths is used.
-
-def _styles64(aff, w):
-    return (w.double() @ aff.weight.double().t()) * aff.weight_gain + aff.bias.double() * aff.bias_gain
-
-
-def _clamp64(y, clamp):
-    return y if clamp is None else y.clamp(-clamp, clamp)
-
-
-def _fir64(x, f, gain):
-    """true 2-D convolution of the (already padded) x with the 4x4 filter f, times gain: out[y, x] = sum_ab x[y + a, x + b] f[3 - a, 3 - b]"""
-    f = f.double() * gain
-    h, w = x.shape[-2] - 3, x.shape[-1] - 3
-    out = 0
-    for a in range(4):
-        for b in range(4):
-            out = out + x[..., a:a + h, b:b + w] * f[3 - a, 3 - b]
-    return out
-
-
-def _up2_f64(x, f):
-    """upsample2d(x, f) (upfirdn2d.py:313-349) in float64: zero insertion x 2, pad (2, 1), true convolution with f, gain 4"""
-    import torch.nn.functional as F
-    n, c, h, w = x.shape
-    xu = torch.zeros([n, c, 2 * h, 2 * w], dtype=x.dtype, device=x.device)
-    xu[:, :, ::2, ::2] = x
-    return _fir64(F.pad(xu, [2, 1, 2, 1]), f, 4)
-
-
-def _layer64(lay, x, w, noise_mode='const'):
-    """SynthesisLayer: styles, weights modulated and demodulated per image, 3x3 conv (up = 1) or stride-2 transposed conv + pad 1 + 4x4 FIR x 4
-    (up = 2), const noise x strength, bias, lrelu 0.2, act gain, conv clamp"""
-    import torch.nn.functional as F
-    s = _styles64(lay.affine, w)
-    wm = lay.weight.double()[None] * s[:, None, :, None, None]
-    wm = wm * (wm.square().sum(dim=[2, 3, 4]) + 1e-8).rsqrt()[:, :, None, None, None]
-    ys = []
-    for i in range(x.shape[0]):
-        if lay.up == 2:
-            y = F.conv_transpose2d(x[i:i + 1].double(), wm[i].transpose(0, 1), stride=2)
-            ys.append(_fir64(F.pad(y, [1, 1, 1, 1]), lay.resample_filter, 4))
-        else:
-            ys.append(F.conv2d(x[i:i + 1].double(), wm[i], padding=1))
-    y = torch.cat(ys)
-    if lay.use_noise and noise_mode == 'const':
-        y = y + lay.noise_const.double() * lay.noise_strength.double()
-    y = F.leaky_relu(y + lay.bias.double()[None, :, None, None], 0.2) * lay.act_gain
-    return _clamp64(y, lay.conv_clamp)
-
-
-def _head64(t, x, w):
-    """ToRGBLayer: 1x1 modulated conv without demodulation, bias, conv clamp"""
-    s = _styles64(t.affine, w) * t.weight_gain
-    y = torch.einsum('oc,nc,nchw->nohw', t.weight.double()[:, :, 0, 0], s, x) + t.bias.double()[None, :, None, None]
-    return _clamp64(y, t.conv_clamp)
-
-
-def _blocks64(blocks, ws_list, stop=None, x0=None, noise_mode='const'):
-    """-> (x, img, seg) in float64 at `stop` = (next block, resume) (None: after all blocks): x in front of blocks[next block], or that block's
-    conv0 output when resume; img / seg after the last complete block.  x0: a per-image input [n, C, r, r] of blocks[0] in place of its constant."""
-    nb, resume = stop if stop is not None else (len(blocks), False)
-    x = img = seg = None
-    for bi, (b, w) in enumerate(zip(blocks, ws_list)):
-        if bi > nb or (bi == nb and not resume):
-            break
-        if bi == 0:
-            x = x0.double() if x0 is not None else b.const.double()[None].expand(w.shape[0], -1, -1, -1)
-        else:
-            x = _layer64(b.conv0, x, w[:, 0], noise_mode)
-            if bi == nb:
-                break
-        x = _layer64(b.conv1, x, w[:, b.num_conv - 1], noise_mode)
-        wh = w[:, b.num_conv]
-        yi, ys = _head64(b.torgb, x, wh), _head64(b.toseg, x, wh)
-        if img is not None:
-            img, seg = _up2_f64(img, b.resample_filter) + yi, _up2_f64(seg, b.resample_filter) + ys
-        else:
-            img, seg = yi, ys
-    return x, img, seg
 
 
 def test_backbone_uses_the_group_and_replays_bit_equal(gpu_device):
