@@ -475,11 +475,41 @@ _scope = threading.local()
 _scope_finalizers = {}
 
 
+class _Workspaces:
+    """The workspaces of one plugin: key (built by the caller, with `_ws_domain(device)` in it) -> [buffer, packed-weight stamp].  The stamp is
+    one (weakref(weight), weight._version) per weight whose packed copy the buffer holds, written after a successful launch: a packed copy is
+    valid only for the very tensor object (and version) it was made from — the key pins address, shape and device, but the allocator
+    recycles a data_ptr for another weight of the same shape.  Per-image weights are never "packed": their stamp stays empty."""
+
+    def __init__(self, limit=None):
+        self.limit, self.table = limit, {}
+
+    def entry(self, key, alloc):
+        ent = self.table.get(key)
+        if ent is None:
+            if self.limit is not None and len(self.table) > self.limit:
+                # only those with a packed weight whose tensor is gone (nothing can launch with them again): a captured hipGraph holds raw pointers into the live ones
+                for dead in [k for k, e in self.table.items() if any(ref() is None for ref, _ in e[1])]:
+                    del self.table[dead]
+            ent = self.table[key] = [alloc(), ()]
+        return ent
+
+    def packed(self, ent, weights):
+        """Per weight: does the entry hold the packed copy of this very tensor at its current version?  (A fresh entry: of none.)"""
+        return [ref() is w and ver == w._version for (ref, ver), w in zip(ent[1], weights)] or [False] * len(weights)
+
+    def mark_packed(self, ent, weights):
+        ent[1] = [(weakref.ref(w), w._version) for w in weights]
+
+    def drop(self, domain):
+        for k in [k for k in self.table if domain in k]:
+            del self.table[k]
+
+
 def _drop_owner(domain):
     _scope_finalizers.pop(domain, None)
-    for cache in (ModconvPlugin._ws, MappingPlugin._ws, LowresPlugin._ws):
-        for k in [k for k in cache if domain in k]:
-            del cache[k]
+    for plugin in (ModconvPlugin, MappingPlugin, LowresPlugin):
+        plugin._ws.drop(domain)
 
 
 class workspace_scope:
@@ -1021,29 +1051,21 @@ class VolumeRenderPlugin:
 
 
 class ModconvPlugin:
-    # workspace cache: (weight data_ptr, shape, n, h, w, mode) -> [buffer, weight._version the packed copy was made from, weakref(weight)]
-    _ws = {}
+    _ws = _Workspaces(limit=1024)
     _heads_declined = set()      # (n, cin, cout, h, w, rows, arith) that ide3d_modconv2d_heads has no fused form for
 
     @staticmethod
     def _workspace(lib, x, w, n, cin, cout, h, wd, k, mode, per_image, arith):
-        """The workspace of (weight, problem shape, device, launch domain, arithmetic): [buffer, weight._version packed, weakref(weight)]."""
+        """The workspace entry of (weight, problem shape, device, launch domain, arithmetic)."""
         # one workspace per (weight, problem shape, device, launch domain): the split-K partials inside it belong to one launch at a
         # time; the domain is the current stream for eager callers and the owning GraphedRenderer inside `workspace_scope`
         # ... and per arithmetic: the packed weights of the split-bf16 loops differ from the fp32 loop's
         key = (0 if per_image else w.data_ptr(), tuple(w.shape), n, h, wd, mode, x.device.index, _ws_domain(x.device), arith)
-        ent = ModconvPlugin._ws.get(key)
-        if ent is None:
+        def alloc():
             nbytes = lib.ide3d_modconv_workspace_bytes(n, cin, cout, h, wd, k, mode, int(per_image))
             _require(nbytes >= 0, 'modconv2d: unsupported configuration')
-            if len(ModconvPlugin._ws) > 1024:
-                # drop only workspaces whose weight tensor is gone (nothing can launch with them again): a captured hipGraph
-                # holds raw pointers into the live ones, so those are never freed behind its back
-                for k_dead in [k_ for k_, e_ in ModconvPlugin._ws.items() if e_[2] is not None and e_[2]() is None]:
-                    del ModconvPlugin._ws[k_dead]
-            ent = [torch.empty([max(nbytes // 4, 1)], dtype=torch.float32, device=x.device), None, None]
-            ModconvPlugin._ws[key] = ent
-        return ent
+            return torch.empty([max(nbytes // 4, 1)], dtype=torch.float32, device=x.device)
+        return ModconvPlugin._ws.entry(key, alloc)
 
     @staticmethod
     def _params(lib, x, w, y, styles, dcoefs, noise, noise_strength, bias, act, alpha, gain, clamp, mode, arith, x_amax, y_amax):
@@ -1065,9 +1087,7 @@ class ModconvPlugin:
         p.noise_strength = float(noise_strength)
         p.act, p.alpha, p.gain, p.clamp = int(act), float(alpha), float(gain), float(clamp)
         p.mode = mode
-        # the packed copy in the workspace is valid only for the very tensor object (and version) it was made from: a data_ptr
-        # can be recycled by the allocator for another weight of the same shape
-        p.weights_packed = int((not per_image) and ent[2] is not None and ent[2]() is w and ent[1] == w._version)
+        p.weights_packed = int((not per_image) and ModconvPlugin._ws.packed(ent, (w,))[0])
         p.w_batch_stride = (cout * cin * k * k) if per_image else 0
         p.arith = arith
         for name, t in (('x_amax', x_amax), ('y_amax', y_amax)):
@@ -1111,7 +1131,7 @@ class ModconvPlugin:
         with _dev_guard(x.device):
             rc = lib.ide3d_modconv2d(ctypes.byref(p), _stream(x))
         _check(rc, 'modconv2d')
-        ent[1], ent[2] = (None, None) if per_image else (w._version, weakref.ref(w))
+        ModconvPlugin._ws.mark_packed(ent, () if per_image else (w,))
         return y if pitch == ow else y[..., :ow]
 
     @staticmethod
@@ -1156,7 +1176,7 @@ class ModconvPlugin:
             ModconvPlugin._heads_declined.add(shape_key)
             return None
         _check(rc, 'modconv2d_heads')
-        ent[1], ent[2] = w._version, weakref.ref(w)
+        ModconvPlugin._ws.mark_packed(ent, (w,))          # (the 3x3 layer's entry only: `hent` belongs to per-image weights)
         return y, heads
 
 
@@ -1555,7 +1575,7 @@ class CameraPlugin:
 
 class MappingPlugin:
     MAX_N, MAX_WIDTH, MAX_LAYERS = 8, 1024, 16
-    _ws = {}          # (device index, launch domain) -> workspace tensor (per-layer activations + barrier counter); see workspace_scope
+    _ws = _Workspaces()          # (device index, launch domain) -> per-layer activations + barrier counter (zero-filled once); see workspace_scope
 
     @staticmethod
     def supports(n, z_dim, embed, widths, device=None):
@@ -1602,10 +1622,7 @@ class MappingPlugin:
         embed = 0 if embed_w is None else embed_w.shape[0]
         k = fc_ws[-1].shape[0]
         lib = load()
-        key = (dev.index, _ws_domain(dev))
-        wsp = MappingPlugin._ws.get(key)
-        if wsp is None:
-            wsp = MappingPlugin._ws[key] = torch.zeros([lib.ide3d_mapping_workspace_bytes() // 4 + 4], dtype=torch.float32, device=dev)
+        wsp = MappingPlugin._ws.entry((dev.index, _ws_domain(dev)), lambda: torch.zeros([lib.ide3d_mapping_workspace_bytes() // 4 + 4], dtype=torch.float32, device=dev))[0]
         out = torch.empty([n, num_ws, k], dtype=torch.float32, device=dev)
         p = _MappingParams()
         p.z, p.c = z.data_ptr(), (c.data_ptr() if c is not None else 0)
@@ -1669,8 +1686,7 @@ class ResamplePlugin:
 
 class LowresPlugin:
     """The low-resolution block group of the backbone in one launch (csrc/lowres.hip, include/ide3d_hip.h `ide3d_lowres_group`)."""
-    # workspace cache: key -> [buffer (zero-filled once: the halo slots of the activation images are never written), per layer (weakref(weight), version)]
-    _ws = {}
+    _ws = _Workspaces(limit=64)          # buffers zero-filled once: the halo slots of the activation images are never written
 
     @staticmethod
     def layers_supported(n, C, res0, ups, arith=0):
@@ -1725,17 +1741,14 @@ class LowresPlugin:
             if q.head >= 0:
                 head_res[q.head] = res
         key = (tuple(L['weight'].data_ptr() for L in layers), n, C, x0.shape[-1], tuple(int(L['up']) for L in layers), dev.index, _ws_domain(dev), arith)
-        ent = LowresPlugin._ws.get(key)
-        if ent is None:
+        def alloc():
             nbytes = lib.ide3d_lowres_workspace_bytes(ctypes.byref(p))
             _require(nbytes > 0, 'lowres_group: unsupported configuration')
-            if len(LowresPlugin._ws) > 64:
-                for k_dead in [k_ for k_, e_ in LowresPlugin._ws.items() if any(r() is None for r, _ in e_[1])]:
-                    del LowresPlugin._ws[k_dead]
-            ent = LowresPlugin._ws[key] = [torch.zeros([nbytes // 4 + 1], dtype=torch.float32, device=dev), [(lambda: None, None)] * len(layers)]
-        for l, L in enumerate(layers):
-            ref, ver = ent[1][l]
-            p.layers[l].weights_packed = int(ref() is L['weight'] and ver == L['weight']._version)
+            return torch.zeros([nbytes // 4 + 1], dtype=torch.float32, device=dev)
+        ent = LowresPlugin._ws.entry(key, alloc)
+        weights = [L['weight'] for L in layers]
+        for l, packed in enumerate(LowresPlugin._ws.packed(ent, weights)):
+            p.layers[l].weights_packed = int(packed)
         p.workspace, p.workspace_bytes = ent[0].data_ptr(), ent[0].numel() * 4
         skips = []
         for k, H in enumerate(heads):
@@ -1759,7 +1772,7 @@ class LowresPlugin:
         with _dev_guard(dev):
             rc = lib.ide3d_lowres_group(ctypes.byref(p), _stream(x0))
         _check(rc, 'lowres_group')
-        ent[1] = [(weakref.ref(L['weight']), L['weight']._version) for L in layers]
+        LowresPlugin._ws.mark_packed(ent, weights)
         return x_out, skips
 
 

@@ -2,8 +2,45 @@
 
 import contextlib
 import warnings
+import weakref
 
 import torch
+
+
+def _stamp(t):
+    """What has to be unchanged for a tensor derived from parameter `t` to be still valid: `Module.to(device)` and
+    `param.data = ...` keep the Parameter object and its `_version` but change the storage, so device and address count."""
+    return (t._version, t.device, t.data_ptr())
+
+
+class DerivedCache:
+    """Tensors derived from parameters, kept between calls so that inference does not recompute them and so that a captured
+    hipGraph and the packed-weight copies in the HIP workspaces keep pointing at valid memory.  The rules:
+    1. an entry is valid only for the very tensor objects it was made from (ids and storage addresses get recycled), at the same `_stamp`;
+    2. a live entry is never freed (a captured graph holds raw pointers into it; a blanket `.clear()` would leave its replays reading
+       freed memory): only entries whose first source is gone are dropped, and only once the table has outgrown `limit`;
+    3. (the caller's) with grad enabled and a source that requires grad nothing is cached: it returns its differentiable expression."""
+
+    def __init__(self, limit=512):
+        self.limit, self.table = limit, {}     # key -> (weak references to the sources, (their stamps, extra), value)
+
+    def get(self, sources, build, *, key=None, extra=None):
+        """The value `build()` made from the tensors `sources`.  `key` joins id(sources[0]) in the table key (several values per source),
+        `extra` is compared together with the stamps (a value that also depends on a number)."""
+        k = id(sources[0]) if key is None else (id(sources[0]), key)
+        stamp = (*map(_stamp, sources), extra)
+        ent = self.table.get(k)
+        if ent is not None and ent[1] == stamp:
+            for ref, t in zip(ent[0], sources):
+                if ref() is not t:
+                    break
+            else:
+                return ent[2]
+        if len(self.table) > self.limit:
+            for dead in [d for d, e in self.table.items() if e[0][0]() is None]:
+                del self.table[dead]
+        ent = self.table[k] = (tuple(map(weakref.ref, sources)), stamp, build())
+        return ent[2]
 
 
 @contextlib.contextmanager

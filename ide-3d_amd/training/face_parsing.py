@@ -13,37 +13,32 @@ Pooling, the sigmoid gates, the residual additions and the `align_corners=True` 
 (as they are in the reference).  CPU tensors and autograd take the plain PyTorch definition.
 """
 
-import weakref
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from torch_utils import misc
 from training import networks
 
 # dnnlib/seg_tools.py:59: label id of the parser's 20 classes -> the generator's 19 semantic classes
 REMAP = (0, 1, 6, 7, 4, 5, 2, 2, 10, 11, 12, 8, 9, 15, 3, 17, 16, 18, 13, 14)
 
-_fold_cache = {}
+_fold_cache = misc.DerivedCache()
 
 
 def _folded(conv, bn):
     """(weight, bias) of `bn(conv(x))` in eval mode as one convolution: w * g / sqrt(var + eps) per output channel, b = beta - mean * that.
-    Cached per (parameter versions / addresses): inference only."""
-    tensors = [conv.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-    stamp = tuple(networks._stamp(t) for t in tensors)
-    ent = _fold_cache.get(id(conv))
-    if ent is None or ent[0]() is not conv or ent[1] != stamp:
-        networks._evict_dead(_fold_cache)
+    Cached per (the 1 or 5 tensors it is computed from, eps): inference only."""
+    def fold():
         w = conv.weight.detach().float()
         b = None
         if bn is not None:
             scale = bn.weight.detach().float() * (bn.running_var.float() + bn.eps).rsqrt()
             w = w * scale[:, None, None, None]
             b = (bn.bias.detach().float() - bn.running_mean.float() * scale).contiguous()
-        ent = (weakref.ref(conv), stamp, w.contiguous(), b)
-        _fold_cache[id(conv)] = ent
-    return ent[2], ent[3]
+        return w.contiguous(), b
+    tensors = (conv.weight,) + ((bn.weight, bn.bias, bn.running_mean, bn.running_var) if bn is not None else ())
+    return _fold_cache.get(tensors, fold, extra=(None if bn is None else bn.eps))
 
 
 def _on_hip(x, conv):

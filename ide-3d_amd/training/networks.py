@@ -19,7 +19,6 @@ parameters (PTI pivotal tuning): the weight, bias and noise gradients are HIP to
 """
 
 import math
-import weakref
 
 import numpy as np
 import torch
@@ -63,29 +62,14 @@ def _style_init():
     return True
 
 
-def _stamp(t):
-    """What has to be unchanged for a tensor derived from parameter `t` to be still valid: `Module.to(device)` and
-    `param.data = ...` keep the Parameter object and its `_version` but change the storage, so device and address count."""
-    return (t._version, t.device, t.data_ptr())
-
-
-def _evict_dead(cache, limit=512):
-    """Bound a derived-tensor cache by dropping entries whose source tensor is gone.  Live entries are never freed: a
-    captured hipGraph holds raw pointers into them (a blanket `.clear()` would leave its replays reading freed memory)."""
-    if len(cache) > limit:
-        for k in [k for k, e in cache.items() if e[0]() is None]:
-            del cache[k]
+_stamp = misc._stamp       # (the name graph_cache.py and callers outside know it by)
+# one table per helper below that keeps a tensor derived from parameters; what makes an entry valid and when one may go: misc.DerivedCache
+_wsq_cache, _cat_cache, _wscale_cache, _noise_cache, _wgrad_cache = (misc.DerivedCache() for _ in range(5))
 
 
 def _wsq_t(weight):
-    """[Cin, Cout] = sum_k W[o, i, k]^2 transposed, cached per weight tensor (inference only).  An entry is valid only for
-    the tensor object it was computed from (ids and storage addresses get recycled) at the same version / device / address."""
-    ent = _wsq_cache.get(id(weight))
-    if ent is None or ent[0]() is not weight or ent[1] != _stamp(weight):
-        _evict_dead(_wsq_cache)
-        ent = (weakref.ref(weight), _stamp(weight), weight.detach().square().sum(dim=[2, 3]).t().contiguous())
-        _wsq_cache[id(weight)] = ent
-    return ent[2]
+    """[Cin, Cout] = sum_k W[o, i, k]^2 transposed, cached per weight tensor (inference only)."""
+    return _wsq_cache.get((weight,), lambda: weight.detach().square().sum(dim=[2, 3]).t().contiguous())
 
 
 # ---- style prefetch (GPU inference) ----------------------------------------------------------------------------------
@@ -313,33 +297,17 @@ def _demod_coefs(weight, styles):
     return torch.addmm(_eps_like(styles), styles.square(), wsq_t).rsqrt()     # [N, O]
 
 
-_wsq_cache = {}
-_noise_cache = {}
-_wscale_cache = {}
-_cat_cache = {}
-
-
 def _cat_cached(a, b):
     """torch.cat([a, b]) of two parameters, formed once per (tensor objects, versions) in inference."""
     if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
         return torch.cat([a, b])
-    ent = _cat_cache.get(id(a))
-    if ent is None or ent[0]() is not a or ent[1]() is not b or ent[2] != (_stamp(a), _stamp(b)):
-        _evict_dead(_cat_cache)
-        ent = (weakref.ref(a), weakref.ref(b), (_stamp(a), _stamp(b)), torch.cat([a.detach(), b.detach()]))
-        _cat_cache[id(a)] = ent
-    return ent[3]
+    return _cat_cache.get((a, b), lambda: torch.cat([a.detach(), b.detach()]))
 
 
 def _scaled_weight(weight, gain):
     """weight * gain (the equalised-learning-rate factor), formed once per (tensor object, version) in inference so that
     the packed copy inside the HIP workspace stays valid across calls."""
-    ent = _wscale_cache.get(id(weight))
-    if ent is None or ent[0]() is not weight or ent[1] != (_stamp(weight), float(gain)):
-        _evict_dead(_wscale_cache)
-        ent = (weakref.ref(weight), (_stamp(weight), float(gain)), (weight.detach() * gain).contiguous())
-        _wscale_cache[id(weight)] = ent
-    return ent[2]
+    return _wscale_cache.get((weight,), lambda: (weight.detach() * gain).contiguous(), extra=float(gain))
 
 
 def _scaled_const_noise(noise_const, noise_strength):
@@ -347,14 +315,7 @@ def _scaled_const_noise(noise_const, noise_strength):
     versions) instead of by one element-wise launch per layer and frame; with autograd it is the plain product."""
     if torch.is_grad_enabled() and (noise_strength.requires_grad or noise_const.requires_grad):
         return noise_const * noise_strength
-    ent = _noise_cache.get(id(noise_const))
-    if (ent is None or ent[0]() is not noise_const or ent[1]() is not noise_strength
-            or ent[2] != (_stamp(noise_const), _stamp(noise_strength))):
-        _evict_dead(_noise_cache)
-        ent = (weakref.ref(noise_const), weakref.ref(noise_strength), (_stamp(noise_const), _stamp(noise_strength)),
-               (noise_const * noise_strength).detach())
-        _noise_cache[id(noise_const)] = ent
-    return ent[3]
+    return _noise_cache.get((noise_const, noise_strength), lambda: (noise_const * noise_strength).detach())
 _eps_cache = {}
 
 
@@ -460,7 +421,6 @@ hip_conv_grad = True
 hip_param_grad = False
 
 _modconv_grad_plugin = None
-_wgrad_cache = {}
 
 
 def _modconv_grad_init():
@@ -485,14 +445,7 @@ def _conv_grad_ok(x, styles, *params):
 def _grad_weight(weight, flip):
     """weight.transpose(0, 1) (.flip(2, 3) when `flip`): the weights of the input gradient's convolution, cached per (tensor object,
     version) like `_scaled_weight`, so that the packed copy in the HIP workspace stays valid across calls."""
-    key = (id(weight), bool(flip))
-    ent = _wgrad_cache.get(key)
-    if ent is None or ent[0]() is not weight or ent[1] != _stamp(weight):
-        _evict_dead(_wgrad_cache)
-        wt = weight.detach().transpose(0, 1)
-        ent = (weakref.ref(weight), _stamp(weight), (wt.flip(2, 3) if flip else wt).contiguous())
-        _wgrad_cache[key] = ent
-    return ent[2]
+    return _wgrad_cache.get((weight,), lambda: (weight.detach().transpose(0, 1).flip(2, 3) if flip else weight.detach().transpose(0, 1)).contiguous(), key=bool(flip))
 
 
 def _bias_noise_grads(ctx, dz, i_noise, i_bias):
