@@ -20,6 +20,18 @@
 // LDS, then every atomic wave-instruction covers C consecutive channels of 64 / C taps (C = 32: one 128-byte segment per tap).  Taps outside
 // the plane get nothing (zeros padding).  The sums depend on the order in which atomics arrive: results are NOT bit-reproducible from run
 // to run (they agree to fp32 rounding).
+//
+// Decoder parameters (ide3d_render_rays_backward_params, a second instantiation of the same body; the tri-plane-only kernel is compiled
+// from the body with every statement below removed):
+//   hidden layers   dW0[k, c] = sum_samples dpre_k f_c, db0[k] = sum_samples dpre_k with the dpre sweep 2 forms anyway.  Eight hidden units
+//                   at a time, dpre and hid of the chunk's 64 samples go through the staging area the scatter is not using, f is staged
+//                   once per branch; lane (k, c-group) then sums its C / 8 products over the chunk's live samples.
+//   output layers   per ray A^tex_k = sum_i w_i hid^tex_ik, A^geo_k = sum_i w_i hid^geo_ik, B_k = sum_i dsigma_i hid^geo_ik (summed by the
+//                   same lanes into LDS); at the end of the ray dW1[c, k] += gfeat_c A_k, db1[c] += gfeat_c sum_i w_i, and the sigma row
+//                   gets B_k and sum_i dsigma_i.
+//   Every sum is added to the wave's own slice of a global workspace with plain vector loads and stores (an address of a slice is only
+//   ever touched by one lane of one wave), and a second launch adds the slices in a fixed order: no atomics, so the decoder gradients ARE
+//   bit-reproducible from run to run.
 #include "common.h"
 #include "triplane_tap.h"
 #include "raymarch_ray.h"
@@ -38,6 +50,25 @@ struct BwdLds {
     static constexpr int U = 2 * 64;
     static constexpr int FIXED = DF + 2 * TAPS + U;
     static constexpr int ARRAYS = 4;
+    // decoder-parameter variant: the staging area (DF + 2 * TAPS floats) holds f [64][C + 4], dpre [64][9] and hid [64][9] between two
+    // scatters; three more per-ray vectors A^geo, A^tex, B [3][64] follow the u vectors
+    static constexpr int FROW = C + 4, KB = 8, KROW = KB + 1;
+    static constexpr int PSTAGE = 64 * FROW + 2 * 64 * KROW;
+    static constexpr int PSUMS = 3 * 64;
+    static_assert(PSTAGE <= DF + 2 * TAPS, "parameter-gradient staging must fit in the scatter's staging area");
+    static_assert(C % 8 == 0 && HID % KB == 0 && HID <= 64, "lane (k, c-group) mapping");
+};
+
+// One wave's slice of the parameter-gradient workspace, in floats: geo dW0 [HID, C], tex dW0, geo db0 [HID], tex db0, geo dW1 [1 + seg, HID],
+// tex dW1 [feat, HID], geo db1 [1 + seg], tex db1 [feat] — the order of the eight outputs of ide3d_render_param_grads.
+template <int C, int HID>
+struct ParamSlice {
+    static constexpr int GW0 = 0, TW0 = HID * C, GB0 = 2 * HID * C, TB0 = GB0 + HID, GW1 = TB0 + HID;
+    __host__ __device__ static int tw1(int seg) { return GW1 + (1 + seg) * HID; }
+    __host__ __device__ static int gb1(int seg, int feat) { return tw1(seg) + feat * HID; }
+    __host__ __device__ static int tb1(int seg, int feat) { return gb1(seg, feat) + 1 + seg; }
+    __host__ __device__ static int total(int seg, int feat) { return tb1(seg, feat) + feat; }
+    __host__ __device__ static int stride(int seg, int feat) { return (total(seg, feat) + 3) & ~3; }      // slices stay 16-byte aligned
 };
 
 // One sample's C features from one tri-plane (channels_last), summed over the three planes like the forward's blend: (xy + yz) + xz.
@@ -129,10 +160,61 @@ __device__ __forceinline__ void scatter_sample_grads(float* __restrict__ gimg, c
     wave_lds_sync();
 }
 
-template <int C, int HID>
-__global__ void __launch_bounds__(512)
-render_rays_backward_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp) {
+// Parameter sums of one block of 8 hidden units over the chunk's live samples.  Lane = (k = lane / 8, c-group = lane % 8): C / 8 products
+// dpre_k f_c each, added to the wave's dW0 rows (one contiguous run of 8 * C floats per wave-instruction); beside them c-group 0 sums dpre_k
+// (db0, to the slice), c-group 1 w hid_k and c-group 2 dsigma hid_k (to the per-ray vectors a_w / a_ds in LDS; a_ds NULL = not this branch).
+template <int C>
+__device__ __forceinline__ void param_block_sums(const float* s_f, const float* s_dp, const float* s_hd, const float* s_w, const float* s_ds,
+                                                 int live, float* g_w0, float* g_b0, float* a_w, float* a_ds) {
+    constexpr int NC = C / 8, FROW = C + 4, KROW = 9;
+    const int lane = lane_id(), cg = lane & 7, kl = lane >> 3;
+    const float* msrc = (cg == 0 ? s_dp : s_hd) + kl;
+    const float* ssrc = cg == 2 ? s_ds : s_w;
+    const float* frow = s_f + cg * NC;
+    float acc[NC], e = 0.f;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) acc[i] = 0.f;
+#pragma unroll 4
+    for (int j = 0; j < live; ++j) {
+        const float d = s_dp[j * KROW + kl];
+        const float m = msrc[j * KROW];
+        const float sc = cg == 0 ? 1.0f : ssrc[j];
+        if constexpr (NC == 4) {
+            const float4 v = *reinterpret_cast<const float4*>(frow + j * FROW);
+            acc[0] = fmaf(d, v.x, acc[0]); acc[1] = fmaf(d, v.y, acc[1]); acc[2] = fmaf(d, v.z, acc[2]); acc[3] = fmaf(d, v.w, acc[3]);
+        } else {
+            const float2 v = *reinterpret_cast<const float2*>(frow + j * FROW);
+            acc[0] = fmaf(d, v.x, acc[0]); acc[1] = fmaf(d, v.y, acc[1]);
+        }
+        e = fmaf(m, sc, e);
+    }
+    float* g = g_w0 + kl * C + cg * NC;
+    if constexpr (NC == 4) {
+        float4 v = *reinterpret_cast<float4*>(g);
+        v.x += acc[0]; v.y += acc[1]; v.z += acc[2]; v.w += acc[3];
+        *reinterpret_cast<float4*>(g) = v;
+    } else {
+        float2 v = *reinterpret_cast<float2*>(g);
+        v.x += acc[0]; v.y += acc[1];
+        *reinterpret_cast<float2*>(g) = v;
+    }
+    if (cg == 0) g_b0[kl] += e;
+    else if (cg == 1) a_w[kl] += e;
+    else if (cg == 2 && a_ds) a_ds[kl] += e;
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// The body of both kernels.  PARAMS = false: gradients of the tri-planes only (sl unused).  PARAMS = true: also the decoder-parameter sums,
+// into the wave's slice of `slices`; a NULL grad_tex_planes / grad_geo_planes then skips that plane's scatter.
+template <int C, int HID, bool PARAMS>
+__device__ __forceinline__ void render_rays_backward_body(const ide3d_render_params& p, const ide3d_render_grads& gr, int sp, float* slices) {
     using L = BwdLds<C, HID>;
+    using PS = ParamSlice<C, HID>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* const s_gw0 = lds;
     float* const s_tw0 = s_gw0 + L::W0;
@@ -146,14 +228,20 @@ render_rays_backward_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp
 
     const int lane = lane_id(), wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nw = blockDim.x >> 6;
-    float* const s_df = lds + L::SHARED + wid * (L::FIXED + L::ARRAYS * sp);
+    float* const s_df = lds + L::SHARED + wid * (L::FIXED + (PARAMS ? L::PSUMS : 0) + L::ARRAYS * sp);
     int* const s_off = reinterpret_cast<int*>(s_df + L::DF);
     float* const s_tw = s_df + L::DF + L::TAPS;
     float* const s_u = s_tw + L::TAPS;             // [0, 64): geometry branch, [64, 128): texture branch
-    float* const s_a = s_u + L::U;                 // alpha_i, then dL/dalpha_i
+    float* const s_a = s_u + L::U + (PARAMS ? L::PSUMS : 0);        // alpha_i, then dL/dalpha_i
     float* const s_h = s_a + sp;                   // h_i, then w_i = alpha_i T_i
     float* const s_t = s_h + sp;                   // T_i
-    float* const s_x = s_t + sp;                   // sigma_i + noise_i
+    float* const s_x = s_t + sp;                   // sigma_i + noise_i, then (PARAMS) dsigma_i
+    // PARAMS only: the staging area between two scatters, the per-ray sums A^geo, A^tex, B, and this wave's slice
+    float* const s_f = s_df;
+    float* const s_dp = s_f + 64 * L::FROW;
+    float* const s_hd = s_dp + 64 * L::KROW;
+    float* const s_sum = s_u + L::U;
+    float* const sl = PARAMS ? slices + ((int64_t)blockIdx.x * nw + wid) * PS::stride(p.seg_ch, p.feat_ch) : nullptr;
 
     const int S = p.steps, R = p.rays_per_img, nch = p.feat_ch + p.seg_ch;
     const int64_t total_rays = (int64_t)p.n * R;
@@ -186,6 +274,7 @@ render_rays_backward_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp
             }
             s_u[lane] = ug;
             s_u[64 + lane] = ut;
+            if constexpr (PARAMS) { s_sum[lane] = 0.f; s_sum[64 + lane] = 0.f; s_sum[128 + lane] = 0.f; }
         }
         wave_lds_sync();
         float dnorm;
@@ -294,52 +383,209 @@ render_rays_backward_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp
             // exp(-delta a) directly, not 1 - alpha: at the last sample (delta 1e10) alpha rounds to 1 while delta exp(-delta a) is finite
             const float dsigma = live ? dalpha * delta * __expf(-delta * dens) * dact : 0.f;
             float f[C], df[C];
-            gather_sample_cl<C>(geo_img, a, f);
+            if constexpr (!PARAMS) {
+                gather_sample_cl<C>(geo_img, a, f);
 #pragma unroll
-            for (int c = 0; c < C; ++c) df[c] = 0.f;
+                for (int c = 0; c < C; ++c) df[c] = 0.f;
 #pragma unroll 2
-            for (int k = 0; k < HID; ++k) {
-                const float dpre = fmaf(w, s_u[k], dsigma * s_gw1[k]) * sigmoid_fast(hidden_pre<C>(s_gw0, s_gb0, k, f));
-                hidden_back<C>(s_gw0, k, dpre, df);
-            }
-            scatter_sample_grads<C>(gr.grad_geo_planes + n * gr.grad_geo_stride[0], gr.grad_geo_stride, t, live, df, nlive, s_df, s_off, s_tw);
+                for (int k = 0; k < HID; ++k) {
+                    const float dpre = fmaf(w, s_u[k], dsigma * s_gw1[k]) * sigmoid_fast(hidden_pre<C>(s_gw0, s_gb0, k, f));
+                    hidden_back<C>(s_gw0, k, dpre, df);
+                }
+                scatter_sample_grads<C>(gr.grad_geo_planes + n * gr.grad_geo_stride[0], gr.grad_geo_stride, t, live, df, nlive, s_df, s_off, s_tw);
 
-            gather_sample_cl<C>(tex_img, a, f);
+                gather_sample_cl<C>(tex_img, a, f);
 #pragma unroll
-            for (int c = 0; c < C; ++c) df[c] = 0.f;
+                for (int c = 0; c < C; ++c) df[c] = 0.f;
 #pragma unroll 2
-            for (int k = 0; k < HID; ++k) {
-                const float dpre = w * s_u[64 + k] * sigmoid_fast(hidden_pre<C>(s_tw0, s_tb0, k, f));
-                hidden_back<C>(s_tw0, k, dpre, df);
+                for (int k = 0; k < HID; ++k) {
+                    const float dpre = w * s_u[64 + k] * sigmoid_fast(hidden_pre<C>(s_tw0, s_tb0, k, f));
+                    hidden_back<C>(s_tw0, k, dpre, df);
+                }
+                scatter_sample_grads<C>(gr.grad_tex_planes + n * gr.grad_tex_stride[0], gr.grad_tex_stride, t, live, df, nlive, s_df, s_off, s_tw);
+            } else {
+                if (live) s_x[s] = dsigma;          // x is in a register of its lane by now; param_block_sums reads dsigma of the chunk
+#pragma unroll 1
+                for (int br = 0; br < 2; ++br) {    // 0: geometry, 1: texture
+                    const bool geo = br == 0;
+                    const float* w0 = geo ? s_gw0 : s_tw0;
+                    const float* b0 = geo ? s_gb0 : s_tb0;
+                    float* gplanes = geo ? gr.grad_geo_planes : gr.grad_tex_planes;
+                    gather_sample_cl<C>(geo ? geo_img : tex_img, a, f);
+#pragma unroll
+                    for (int c4 = 0; c4 < C / 4; ++c4)
+                        *reinterpret_cast<float4*>(s_f + lane * L::FROW + 4 * c4) = make_float4(f[4 * c4], f[4 * c4 + 1], f[4 * c4 + 2], f[4 * c4 + 3]);
+#pragma unroll
+                    for (int c = 0; c < C; ++c) df[c] = 0.f;
+#pragma unroll 1
+                    for (int kb = 0; kb < HID; kb += L::KB) {
+#pragma unroll 2
+                        for (int kk = 0; kk < L::KB; ++kk) {
+                            const int k = kb + kk;
+                            const float pre = hidden_pre<C>(w0, b0, k, f);
+                            const float dhid = geo ? fmaf(w, s_u[k], dsigma * s_gw1[k]) : w * s_u[64 + k];
+                            const float dpre = dhid * sigmoid_fast(pre);
+                            if (gplanes) hidden_back<C>(w0, k, dpre, df);
+                            s_dp[lane * L::KROW + kk] = dpre;
+                            s_hd[lane * L::KROW + kk] = softplus_fast(pre);
+                        }
+                        wave_lds_sync();
+                        param_block_sums<C>(s_f, s_dp, s_hd, s_h + c0, s_x + c0, nlive, sl + (geo ? PS::GW0 : PS::TW0) + kb * C,
+                                            sl + (geo ? PS::GB0 : PS::TB0) + kb, s_sum + br * 64 + kb, geo ? s_sum + 128 + kb : nullptr);
+                        wave_lds_sync();
+                    }
+                    if (gplanes) {
+                        const int64_t* gs = geo ? gr.grad_geo_stride : gr.grad_tex_stride;
+                        scatter_sample_grads<C>(gplanes + n * gs[0], gs, t, live, df, nlive, s_df, s_off, s_tw);
+                    }
+                }
             }
-            scatter_sample_grads<C>(gr.grad_tex_planes + n * gr.grad_tex_stride[0], gr.grad_tex_stride, t, live, df, nlive, s_df, s_off, s_tw);
         }
         wave_lds_sync();
+        if constexpr (PARAMS) {
+            // ---- output layers: dW1 += gfeat (x) A, db1 += gfeat sum_i w_i; the sigma row gets B and sum_i dsigma_i ----
+            float sw = 0.f, sds = 0.f;
+            for (int c0 = 0; c0 < S; c0 += 64) {
+                const int s = c0 + lane;
+                if (s < S) { sw += s_h[s]; sds += s_x[s]; }
+            }
+            sw = wave_sum(sw); sds = wave_sum(sds);
+            float* const gw1 = sl + PS::GW1;
+            float* const tw1 = sl + PS::tw1(p.seg_ch);
+            float* const gb1 = sl + PS::gb1(p.seg_ch, p.feat_ch);
+            float* const tb1 = sl + PS::tb1(p.seg_ch, p.feat_ch);
+            if (lane < HID) {
+                gw1[lane] += s_sum[128 + lane];
+                if (gfeat) {
+                    const float ag = s_sum[lane], at = s_sum[64 + lane];
+                    for (int o = 0; o < p.feat_ch; ++o) tw1[o * HID + lane] = fmaf(gfeat[(int64_t)o * R], at, tw1[o * HID + lane]);
+                    for (int o = 1; o <= p.seg_ch; ++o)
+                        gw1[o * HID + lane] = fmaf(gfeat[(int64_t)(p.feat_ch + o - 1) * R], ag, gw1[o * HID + lane]);
+                }
+            }
+            if (lane == 0) gb1[0] += sds;
+            if (gfeat) {
+                if (lane < p.feat_ch) tb1[lane] = fmaf(gfeat[(int64_t)lane * R], sw, tb1[lane]);
+                if (lane >= 1 && lane <= p.seg_ch) gb1[lane] = fmaf(gfeat[(int64_t)(p.feat_ch + lane - 1) * R], sw, gb1[lane]);
+            }
+            wave_lds_sync();
+        }
     }
 }
 
 template <int C, int HID>
-static int launch_render_backward(const ide3d_render_params& p, const ide3d_render_grads& g, hipStream_t st) {
+__global__ void __launch_bounds__(512)
+render_rays_backward_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp) {
+    render_rays_backward_body<C, HID, false>(p, gr, sp, nullptr);
+}
+
+template <int C, int HID>
+__global__ void __launch_bounds__(512)
+render_rays_backward_params_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp, float* slices) {
+    render_rays_backward_body<C, HID, true>(p, gr, sp, slices);
+}
+
+// Adds the slices in a fixed order: thread (element e, group g) sums slices g, g + 8, ..., then group 0 adds the 8 partial sums.
+struct ParamOut {
+    float* dst[8];
+    int end[8];          // element range of dst[i] in a slice: [end[i - 1], end[i])
+};
+
+__global__ void __launch_bounds__(512)
+reduce_param_slices_kernel(const float* __restrict__ slices, int nslices, int stride, ParamOut out) {
+    __shared__ float part[8][64];
+    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int e = blockIdx.x * 64 + lane, total = out.end[7];
+    float sum = 0.f;
+    if (e < total)
+        for (int i = g; i < nslices; i += 8) sum += slices[(int64_t)i * stride + e];
+    part[g][lane] = sum;
+    __syncthreads();
+    if (g == 0 && e < total) {
+        float t = part[0][lane];
+#pragma unroll
+        for (int q = 1; q < 8; ++q) t += part[q][lane];
+        float* d = out.dst[0];
+        int first = 0;
+#pragma unroll
+        for (int q = 1; q < 8; ++q)
+            if (e >= out.end[q - 1]) { d = out.dst[q]; first = out.end[q - 1]; }
+        d[e - first] = t;
+    }
+}
+
+// Launch shape: 8 waves per workgroup, one workgroup per CU (the layer-0 weights are staged once per workgroup); fewer waves when the
+// per-ray arrays of many steps do not fit.  nw = 0: the steps do not fit at all (lds_bytes = what one wave would need).
+struct BwdPlan {
+    int sp, nw;
+    size_t lds_bytes;
+    int64_t nblk;
+};
+
+template <int C, int HID, bool PARAMS>
+static BwdPlan plan_render_backward(const ide3d_render_params& p) {
     using L = BwdLds<C, HID>;
-    const int sp = (int)cdiv64(p.steps, 64) * 64;
-    // 8 waves per workgroup, one workgroup per CU (the layer-0 weights are staged once per workgroup); fewer waves when the per-ray
-    // arrays of many steps do not fit
-    const size_t wave_bytes = (L::FIXED + (size_t)L::ARRAYS * sp) * sizeof(float), shared_bytes = L::SHARED * sizeof(float);
-    int nw = 8;
-    while (nw > 1 && shared_bytes + nw * wave_bytes > 160 * 1024) nw /= 2;
-    const size_t lds_bytes = shared_bytes + nw * wave_bytes;
-    if (lds_bytes > 160 * 1024) {
-        set_error("render_rays_backward: %d steps per ray need %zu bytes of LDS per workgroup (at most 160 KiB)", p.steps, lds_bytes);
+    BwdPlan pl;
+    pl.sp = (int)cdiv64(p.steps, 64) * 64;
+    const size_t wave_bytes = (L::FIXED + (PARAMS ? L::PSUMS : 0) + (size_t)L::ARRAYS * pl.sp) * sizeof(float), shared_bytes = L::SHARED * sizeof(float);
+    pl.nw = 8;
+    while (pl.nw > 1 && shared_bytes + pl.nw * wave_bytes > 160 * 1024) pl.nw /= 2;
+    pl.lds_bytes = shared_bytes + pl.nw * wave_bytes;
+    if (pl.lds_bytes > 160 * 1024) pl.nw = 0;
+    const int64_t total_rays = (int64_t)p.n * p.rays_per_img;
+    pl.nblk = cdiv64(total_rays, pl.nw ? pl.nw : 1);
+    const int64_t cap = (int64_t)kNumCU * 8 / (pl.nw ? pl.nw : 1);
+    if (pl.nblk > cap) pl.nblk = cap;
+    return pl;
+}
+
+template <int C, int HID>
+static int launch_render_backward(const ide3d_render_params& p, const ide3d_render_grads& g, hipStream_t st) {
+    const BwdPlan pl = plan_render_backward<C, HID, false>(p);
+    if (!pl.nw) {
+        set_error("render_rays_backward: %d steps per ray need %zu bytes of LDS per workgroup (at most 160 KiB)", p.steps, pl.lds_bytes);
         return IDE3D_ENOKERNEL;
     }
-    const int64_t total_rays = (int64_t)p.n * p.rays_per_img;
-    int64_t nblk = cdiv64(total_rays, nw);
-    const int64_t cap = (int64_t)kNumCU * 8 / nw;
-    if (nblk > cap) nblk = cap;
     auto kern = render_rays_backward_kernel<C, HID>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * nw), lds_bytes, st, p, g, sp);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.nblk), dim3(64 * pl.nw), pl.lds_bytes, st, p, g, pl.sp);
     IDE3D_CHECK_LAUNCH("render_rays_backward");
+    return IDE3D_OK;
+}
+
+template <int C, int HID>
+static int64_t param_workspace_bytes(const ide3d_render_params& p) {
+    const BwdPlan pl = plan_render_backward<C, HID, true>(p);
+    return pl.nw ? pl.nblk * pl.nw * (int64_t)ParamSlice<C, HID>::stride(p.seg_ch, p.feat_ch) * (int64_t)sizeof(float) : 0;
+}
+
+template <int C, int HID>
+static int launch_render_backward_params(const ide3d_render_params& p, const ide3d_render_grads& g, const ide3d_render_param_grads& q,
+                                         hipStream_t st) {
+    using PS = ParamSlice<C, HID>;
+    const BwdPlan pl = plan_render_backward<C, HID, true>(p);
+    if (!pl.nw) {
+        set_error("render_rays_backward_params: %d steps per ray need %zu bytes of LDS per workgroup (at most 160 KiB)", p.steps, pl.lds_bytes);
+        return IDE3D_ENOKERNEL;
+    }
+    const int64_t need = param_workspace_bytes<C, HID>(p);
+    IDE3D_CHECK_ARG(q.workspace != nullptr && q.workspace_bytes >= need && (reinterpret_cast<uintptr_t>(q.workspace) & 15) == 0,
+                    "render_rays_backward_params: workspace of %lld bytes (16-byte aligned) required, got %lld", (long long)need,
+                    (long long)q.workspace_bytes);
+    float* slices = static_cast<float*>(q.workspace);
+    if (hipMemsetAsync(slices, 0, (size_t)need, st) != hipSuccess) { set_error("render_rays_backward_params: hipMemsetAsync failed"); return IDE3D_ELAUNCH; }
+    auto kern = render_rays_backward_params_kernel<C, HID>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.nblk), dim3(64 * pl.nw), pl.lds_bytes, st, p, g, pl.sp, slices);
+    IDE3D_CHECK_LAUNCH("render_rays_backward_params");
+    ParamOut out;
+    float* const dst[8] = {q.grad_geo_w0, q.grad_tex_w0, q.grad_geo_b0, q.grad_tex_b0, q.grad_geo_w1, q.grad_tex_w1, q.grad_geo_b1, q.grad_tex_b1};
+    const int end[8] = {PS::TW0, PS::GB0, PS::TB0, PS::GW1, PS::tw1(p.seg_ch), PS::gb1(p.seg_ch, p.feat_ch), PS::tb1(p.seg_ch, p.feat_ch),
+                        PS::total(p.seg_ch, p.feat_ch)};
+    for (int i = 0; i < 8; ++i) { out.dst[i] = dst[i]; out.end[i] = end[i]; }
+    hipLaunchKernelGGL(reduce_param_slices_kernel, dim3((unsigned)cdiv64(out.end[7], 64)), dim3(512), 0, st, slices, (int)(pl.nblk * pl.nw),
+                       PS::stride(p.seg_ch, p.feat_ch), out);
+    IDE3D_CHECK_LAUNCH("render_rays_backward_params (slice sums)");
     return IDE3D_OK;
 }
 
@@ -347,7 +593,7 @@ static bool grads_fit(const ide3d_render_params& p, const ide3d_render_grads& g)
     auto ok = [&](const int64_t* s) {
         return s[1] == 1 && s[2] >= 0 && s[3] >= 0 && (s[2] * (p.H - 1) + s[3] * (p.W - 1) + 3 * p.C) < 0x7fffffffLL;
     };
-    return ok(g.grad_tex_stride) && ok(g.grad_geo_stride);
+    return (!g.grad_tex_planes || ok(g.grad_tex_stride)) && (!g.grad_geo_planes || ok(g.grad_geo_stride));
 }
 
 }  // namespace ide3d
@@ -370,5 +616,37 @@ extern "C" int ide3d_render_rays_backward(const ide3d_render_params* pp, const i
     if (p.C == 32 && p.hidden == 64) return launch_render_backward<32, 64>(p, g, st);
     if (p.C == 16 && p.hidden == 32) return launch_render_backward<16, 32>(p, g, st);
     set_error("render_rays_backward: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
+    return IDE3D_ENOKERNEL;
+}
+
+extern "C" int64_t ide3d_render_param_grad_workspace_bytes(const ide3d_render_params* pp) {
+    using namespace ide3d;
+    if (pp == nullptr || pp->n <= 0 || pp->rays_per_img <= 0 || pp->steps <= 0 || pp->feat_ch < 0 || pp->seg_ch < 0) return 0;
+    if (pp->C == 32 && pp->hidden == 64) return param_workspace_bytes<32, 64>(*pp);
+    if (pp->C == 16 && pp->hidden == 32) return param_workspace_bytes<16, 32>(*pp);
+    return 0;
+}
+
+extern "C" int ide3d_render_rays_backward_params(const ide3d_render_params* pp, const ide3d_render_grads* gg, const ide3d_render_param_grads* qq,
+                                                 void* stream) {
+    using namespace ide3d;
+    IDE3D_CHECK_ARG(pp != nullptr && gg != nullptr && qq != nullptr, "render_rays_backward_params: null params");
+    const ide3d_render_params& p = *pp;
+    const ide3d_render_grads& g = *gg;
+    const ide3d_render_param_grads& q = *qq;
+    int rc = check_render_params(p, "render_rays_backward_params", false);
+    if (rc) return rc;
+    IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world, "render_rays_backward_params: null ray pointer");
+    IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "render_rays_backward_params: bad ray shape");
+    IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "render_rays_backward_params: Need to choose clamp mode");
+    IDE3D_CHECK_ARG(q.grad_geo_w0 && q.grad_geo_b0 && q.grad_geo_w1 && q.grad_geo_b1 && q.grad_tex_w0 && q.grad_tex_b0 && q.grad_tex_w1 && q.grad_tex_b1,
+                    "render_rays_backward_params: null parameter-gradient output");
+    if (p.last_back) { set_error("render_rays_backward_params: last_back is not fused; use the step-wise ops"); return IDE3D_ENOKERNEL; }
+    if (!planes_fast(p)) { set_error("render_rays_backward_params: tri-planes must be channels_last, 16-byte aligned"); return IDE3D_ENOKERNEL; }
+    if (!grads_fit(p, g)) { set_error("render_rays_backward_params: gradient buffers must be channels_last (channel stride 1)"); return IDE3D_ENOKERNEL; }
+    hipStream_t st = (hipStream_t)stream;
+    if (p.C == 32 && p.hidden == 64) return launch_render_backward_params<32, 64>(p, g, q, st);
+    if (p.C == 16 && p.hidden == 32) return launch_render_backward_params<16, 32>(p, g, q, st);
+    set_error("render_rays_backward_params: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
     return IDE3D_ENOKERNEL;
 }

@@ -105,6 +105,16 @@ class _RenderGrads(ctypes.Structure):
         ('grad_tex_stride', ctypes.c_int64 * 4), ('grad_geo_stride', ctypes.c_int64 * 4),
     ]
 
+
+class _RenderParamGrads(ctypes.Structure):
+    """ide3d_render_param_grads (include/ide3d_hip.h): the decoder gradients of ide3d_render_rays_backward_params."""
+    _fields_ = [
+        ('grad_geo_w0', ctypes.c_void_p), ('grad_geo_b0', ctypes.c_void_p), ('grad_geo_w1', ctypes.c_void_p), ('grad_geo_b1', ctypes.c_void_p),
+        ('grad_tex_w0', ctypes.c_void_p), ('grad_tex_b0', ctypes.c_void_p), ('grad_tex_w1', ctypes.c_void_p), ('grad_tex_b1', ctypes.c_void_p),
+        ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_int64),
+    ]
+
+
 class _Lattice(ctypes.Structure):
     _fields_ = [('n', ctypes.c_int32), ('voxel_size', ctypes.c_float), ('corner', ctypes.c_float * 3), ('scale', ctypes.c_float)]
 
@@ -311,6 +321,8 @@ def load():
             'ide3d_sample_pdf': [vp, vp, vp, i64, i64, i32, i32, f32, vp, vp],
             'ide3d_render_rays': [ctypes.POINTER(_RenderParams), vp],
             'ide3d_render_rays_backward': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_RenderGrads), vp],
+            'ide3d_render_param_grad_workspace_bytes': [ctypes.POINTER(_RenderParams)],
+            'ide3d_render_rays_backward_params': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_RenderGrads), ctypes.POINTER(_RenderParamGrads), vp],
             'ide3d_sample_voxel': [ctypes.POINTER(_RenderParams), vp, i64, vp, vp, ctypes.c_int, vp],
             'ide3d_lattice_points': [ctypes.POINTER(_Lattice), i64, i64, vp, vp],
             'ide3d_density_lattice': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_Lattice), i64, i64, vp, vp],
@@ -364,7 +376,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_lowres_layers_supported', 'ide3d_lowres_phase_r_plan', 'ide3d_lowres_workspace_bytes', 'ide3d_lowres_group',
     'ide3d_act_bwd_workspace_bytes', 'ide3d_modconv_act_backward', 'ide3d_modconv_scale_dot', 'ide3d_head_wgrad_workspace_bytes',
     'ide3d_head_weight_grad', 'ide3d_wgrad_workspace_bytes', 'ide3d_modconv_weight_grad', 'ide3d_bias_noise_workspace_bytes',
-    'ide3d_bias_noise_grad',
+    'ide3d_bias_noise_grad', 'ide3d_render_param_grad_workspace_bytes', 'ide3d_render_rays_backward_params',
 )
 
 
@@ -508,7 +520,7 @@ class _Workspaces:
 
 def _drop_owner(domain):
     _scope_finalizers.pop(domain, None)
-    for plugin in (ModconvPlugin, MappingPlugin, LowresPlugin):
+    for plugin in (ModconvPlugin, MappingPlugin, LowresPlugin, VolumeRenderPlugin):
         plugin._ws.drop(domain)
 
 
@@ -838,6 +850,8 @@ class TriplanePlugin:
 
 
 class VolumeRenderPlugin:
+    _ws = _Workspaces()          # (bytes, device index, launch domain) -> the per-wave partial sums of render_rays_backward_params
+
     @staticmethod
     def composite(rgb_sigma, z_vals, dir_norm, noise, clamp_mode, last_back, white_back, max_depth, fill_mode,
                   want_weights=True):
@@ -992,6 +1006,51 @@ class VolumeRenderPlugin:
             return None
         _check(rc, 'render_rays_backward')
         return dtex, dgeo
+
+    MLP_KEYS = ('geo_w0', 'geo_b0', 'geo_w1', 'geo_b1', 'tex_w0', 'tex_b0', 'tex_w1', 'tex_b1')
+
+    @staticmethod
+    def render_rays_backward_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_mode, last_back,
+                                    white_back, max_depth, grad_feat, grad_depth, grad_wsum, plane_grads=True):
+        """`render_rays_backward` with the gradients of the eight decoder tensors of `mlp` as well (ide3d_render_rays_backward_params) ->
+        (dL/dtex_planes | None, dL/dgeo_planes | None, {key of mlp: gradient of that gain-folded tensor}); None when the library has no
+        kernel for the configuration.  `plane_grads=False`: no plane buffer is allocated and the kernel skips the tap scatter (decoder-only
+        training on detached planes).  The decoder gradients are bit-reproducible from run to run; the per-wave partial sums live in a
+        workspace of this plugin's cache (one per shape and launch domain, see `workspace_scope`)."""
+        dev = tex_planes.device
+        p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
+                                                 clamp_mode, last_back, white_back, max_depth)
+        n, R, nch = p.n, p.rays_per_img, p.feat_ch + p.seg_ch
+        g = _RenderGrads()
+        for name, t, shape in (('grad_feat', grad_feat, (n, nch, R)), ('grad_depth', grad_depth, (n, R)), ('grad_wsum', grad_wsum, (n, R))):
+            if t is not None:
+                _require(t.numel() == math.prod(shape), f'render_rays_backward_params: {name} must hold {list(shape)} values, got {list(t.shape)}')
+                t = t.to(device=dev, dtype=torch.float32).contiguous()
+                keep.append(t)
+                setattr(g, name, t.data_ptr())
+        dtex = dgeo = None
+        if plane_grads:
+            dtex = torch.empty(tex_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
+            dgeo = torch.empty(geo_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
+            g.grad_tex_planes, g.grad_geo_planes = dtex.data_ptr(), dgeo.data_ptr()
+            g.grad_tex_stride, g.grad_geo_stride = _i64x4(dtex.stride()), _i64x4(dgeo.stride())
+        lib = load()
+        nbytes = lib.ide3d_render_param_grad_workspace_bytes(ctypes.byref(p))
+        if nbytes <= 0:        # no compiled form for (C, hidden), or too many steps: what the launch would answer with IDE3D_ENOKERNEL
+            return None
+        q = _RenderParamGrads()
+        grads = {k: torch.empty_like(mlp[k]) for k in VolumeRenderPlugin.MLP_KEYS}
+        for k, t in grads.items():
+            setattr(q, 'grad_' + k, t.data_ptr())
+        key = ('render_param_grad', nbytes, dev.index, _ws_domain(dev))
+        ws = VolumeRenderPlugin._ws.entry(key, lambda: torch.empty([nbytes // 4], dtype=torch.float32, device=dev))[0]
+        q.workspace, q.workspace_bytes = ws.data_ptr(), nbytes
+        with _dev_guard(dev):
+            rc = lib.ide3d_render_rays_backward_params(ctypes.byref(p), ctypes.byref(g), ctypes.byref(q), _stream(tex_planes))
+        if rc == -2:        # IDE3D_ENOKERNEL
+            return None
+        _check(rc, 'render_rays_backward_params')
+        return dtex, dgeo, grads
 
     @staticmethod
     def sample_voxel(tex_planes, geo_planes, mlp, pts, sigma_only=False):

@@ -45,6 +45,11 @@ from training import volumetric_rendering as vr
 # gradient (PTI-style latent optimisation with a frozen generator); False = the step-wise definition, as for every other gradient.
 fused_render_grad = True
 
+# Also take that path when the decoder's parameters train (PTI pivotal tuning: Adam over G.parameters()): its backward then is
+# ide3d_render_rays_backward_params, which returns the gradients of geo0 / geo1 / tex0 / tex1 beside the planes'.  Opt-in like
+# networks.hip_param_grad, and set next to it by a coach before its tuning loop; False = a trainable decoder renders step-wise.
+fused_render_param_grad = False
+
 
 @dataclasses.dataclass
 class GeneratorSpec:
@@ -194,6 +199,8 @@ class TriplaneRenderer(torch.nn.Module):
     def _fused_grad_ok(self, img_v, seg_v, cam2world, jitter, sigma_noise):
         """The fused renderer with its backward kernel: fp32 CUDA planes of which at least one needs a gradient, and nothing else it
         reads (decoder parameters, camera, jitter, density noise) does — the backward kernel differentiates the planes only."""
+        if fused_render_param_grad:
+            return self._fused_param_grad_ok(img_v, seg_v, cam2world, jitter, sigma_noise)
         if not torch.is_grad_enabled() or not (img_v.requires_grad or seg_v.requires_grad):
             return False
         if any(t.device.type != 'cuda' or t.dtype != torch.float32 for t in (img_v, seg_v, cam2world)):
@@ -201,6 +208,16 @@ class TriplaneRenderer(torch.nn.Module):
         if cam2world.requires_grad or any(p.requires_grad for p in self.decoder.parameters()):
             return False
         return not any(t is not None and t.requires_grad for t in (jitter, sigma_noise))
+
+    def _fused_param_grad_ok(self, img_v, seg_v, cam2world, jitter, sigma_noise):
+        """`_fused_grad_ok` under `fused_render_param_grad`: the decoder's parameters may need a gradient too (fp32 CUDA, all of them), and
+        one of them needing it is reason enough; the camera, the jitter and the density noise still may not."""
+        params = list(self.decoder.parameters())
+        if not torch.is_grad_enabled() or not (img_v.requires_grad or seg_v.requires_grad or any(p.requires_grad for p in params)):
+            return False
+        if any(t.device.type != 'cuda' or t.dtype != torch.float32 for t in (img_v, seg_v, cam2world, *params)):
+            return False
+        return not any(t is not None and t.requires_grad for t in (cam2world, jitter, sigma_noise))
 
     # -- full rendering -----------------------------------------------------------------------------------
     def forward(self, img_v, seg_v, cam2world, fov=None, num_steps=None, ray_start=None, ray_end=None, img_size=None,

@@ -339,33 +339,47 @@ class _NoFusedKernel(Exception):
     """The library has no fused kernel for the configuration (IDE3D_ENOKERNEL)."""
 
 
+_MLP_KEYS = ('geo_w0', 'geo_b0', 'geo_w1', 'geo_b1', 'tex_w0', 'tex_b0', 'tex_w1', 'tex_b1')
+
+
 class _RenderRaysFused(torch.autograd.Function):
-    """`ide3d_render_rays` with a gradient for the two tri-planes (`ide3d_render_rays_backward`, csrc/raymarch_bwd.hip).  The forward is
-    the inference launch unchanged; what is saved is its inputs (planes, decoder weights, camera, jitter, noise), nothing per sample: the
-    backward kernel rebuilds the samples.  No gradient for anything but the planes."""
+    """`ide3d_render_rays` with a gradient for the two tri-planes (`ide3d_render_rays_backward`) and for the eight decoder tensors
+    (`ide3d_render_rays_backward_params`, csrc/raymarch_bwd.hip).  The forward is the inference launch unchanged; what is saved is its
+    inputs (planes, decoder weights, camera, jitter, noise), nothing per sample: the backward kernel rebuilds the samples.  The backward
+    is one call: the parameter entry point when a decoder tensor needs a gradient (without the tap scatter when no plane does), the
+    tri-plane-only one otherwise.  No gradient for the camera, the jitter or the noise."""
 
     @staticmethod
-    def forward(ctx, tex_planes, geo_planes, rays_d_cam, z_lin, cam2world, jitter, sigma_noise, mlp, clamp_code, white_back, max_depth):
+    def forward(ctx, tex_planes, geo_planes, rays_d_cam, z_lin, cam2world, jitter, sigma_noise, clamp_code, white_back, max_depth, *mlp_tensors):
+        mlp = dict(zip(_MLP_KEYS, mlp_tensors))
         args = (rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_code, False, white_back, max_depth)
         res = _plugin.render_rays(*args)
         if res is None:
             raise _NoFusedKernel()
-        ctx.save_for_backward(tex_planes, geo_planes)
-        ctx.args = args[:5] + args[7:]
+        ctx.save_for_backward(tex_planes, geo_planes, *mlp_tensors)
+        ctx.args = args[:5] + args[8:]
         return res
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_feat, grad_depth, grad_wsum):
-        tex_planes, geo_planes = ctx.saved_tensors
+        tex_planes, geo_planes, *mlp_tensors = ctx.saved_tensors
+        mlp = dict(zip(_MLP_KEYS, mlp_tensors))
         a = ctx.args
-        res = _plugin.render_rays_backward(*a[:5], tex_planes, geo_planes, *a[5:], grad_feat, grad_depth, grad_wsum)
+        need = ctx.needs_input_grad
+        if any(need[10:]):
+            res = _plugin.render_rays_backward_params(*a[:5], tex_planes, geo_planes, mlp, *a[5:], grad_feat, grad_depth, grad_wsum,
+                                                      plane_grads=need[0] or need[1])
+        else:
+            res = _plugin.render_rays_backward(*a[:5], tex_planes, geo_planes, mlp, *a[5:], grad_feat, grad_depth, grad_wsum)
         if res is None:
             from torch_utils import hip_plugin
             raise RuntimeError('render_rays_backward: no backward kernel for this configuration: '
                                + hip_plugin.load().ide3d_last_error().decode('utf-8', 'replace'))
-        dtex, dgeo = res
-        return (dtex if ctx.needs_input_grad[0] else None, dgeo if ctx.needs_input_grad[1] else None) + (None,) * 9
+        dtex, dgeo = res[:2]
+        dmlp = res[2] if len(res) > 2 else {}
+        return (dtex if need[0] else None, dgeo if need[1] else None) + (None,) * 8 + tuple(
+            dmlp[k] if need[10 + i] else None for i, k in enumerate(_MLP_KEYS))
 
 
 def render_triplane_fused(tex_planes, geo_planes, mlp, cam2world, fov, resolution, num_steps, ray_start, ray_end,
@@ -382,10 +396,12 @@ def render_triplane_fused(tex_planes, geo_planes, mlp, cam2world, fov, resolutio
     library has no fused kernel for the configuration (IDE3D_ENOKERNEL: plane_channels / decoder widths other than
     the compiled (32, 64) and (16, 32)) — the caller then runs the step-wise HIP ops.  Launch failures raise RuntimeError.
 
-    Gradients: when grad mode is on and a tri-plane requires grad, the outputs are differentiable with respect to tex_planes and
-    geo_planes (one `ide3d_render_rays_backward` launch per backward; first order only).  No gradient is returned for `mlp`,
+    Gradients: when grad mode is on and a tri-plane or a tensor of `mlp` requires grad, the outputs are differentiable with respect to
+    tex_planes, geo_planes and the eight tensors of `mlp` (one backward call: `ide3d_render_rays_backward`, or
+    `ide3d_render_rays_backward_params` when a tensor of `mlp` needs a gradient; first order only).  No gradient is returned for
     `cam2world`, `jitter` or `sigma_noise`, whether or not they require grad: a caller that needs those must run the step-wise
-    definition (TriplaneRenderer.forward does).  The forward values are those of the no-grad call, bit for bit.
+    definition (TriplaneRenderer.forward does, and it only sends a trainable decoder here under `triplane.fused_render_param_grad`).
+    The forward values are those of the no-grad call, bit for bit.
     """
     assert clamp_mode in ('softplus', 'relu')
     _init()
@@ -397,10 +413,10 @@ def render_triplane_fused(tex_planes, geo_planes, mlp, cam2world, fov, resolutio
     if geo_planes.stride(1) != 1:
         geo_planes = geo_planes.contiguous(memory_format=torch.channels_last)
     clamp_code = 0 if clamp_mode == 'softplus' else 1
-    if torch.is_grad_enabled() and (tex_planes.requires_grad or geo_planes.requires_grad):
+    if torch.is_grad_enabled() and (tex_planes.requires_grad or geo_planes.requires_grad or any(mlp[k].requires_grad for k in _MLP_KEYS)):
         try:
-            res = _RenderRaysFused.apply(tex_planes, geo_planes, rays_d_cam, z_lin, cam2world, jitter, sigma_noise, mlp, clamp_code,
-                                         white_back, max_depth)
+            res = _RenderRaysFused.apply(tex_planes, geo_planes, rays_d_cam, z_lin, cam2world, jitter, sigma_noise, clamp_code,
+                                         white_back, max_depth, *(mlp[k] for k in _MLP_KEYS))
         except _NoFusedKernel:
             return None
     else:

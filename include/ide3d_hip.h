@@ -322,6 +322,27 @@ typedef struct ide3d_render_grads {
 int ide3d_render_rays_backward(const ide3d_render_params* p, const ide3d_render_grads* g, void* stream);
 
 /*
+ * The same backward with the gradients of the decoder's eight tensors as well: what autograd computes for `renderer.decoder` in PTI's
+ * pivotal tuning (Adam over G.parameters(), inversion/training/coaches/base_coach.py:148; the step-wise definition's four linear layers
+ * and their backwards, volumetric_rendering.py:34-74 composited on top).  p and g as for ide3d_render_rays_backward, except that
+ * g->grad_tex_planes / g->grad_geo_planes may each be NULL: that plane's scatter is skipped (decoder-only training on detached planes).
+ * The eight outputs are WRITTEN (not added to), fp32, contiguous, with the shapes of the tensors p points to; they are gradients with
+ * respect to those gain-folded tensors.  workspace: ide3d_render_param_grad_workspace_bytes(p) bytes, 16-byte aligned, owned by this
+ * call until the stream has passed it: one slice of partial sums per wave, added in a fixed order by a second launch, so the eight
+ * gradients are bit-reproducible from run to run (the plane gradients are not).  IDE3D_ENOKERNEL in the cases of
+ * ide3d_render_rays_backward.  The workspace query reads n, rays_per_img, steps, C, hidden, feat_ch and seg_ch; 0 = no kernel.
+ */
+typedef struct ide3d_render_param_grads {
+    float* grad_geo_w0; float* grad_geo_b0; float* grad_geo_w1; float* grad_geo_b1;
+    float* grad_tex_w0; float* grad_tex_b0; float* grad_tex_w1; float* grad_tex_b1;
+    void* workspace;
+    int64_t workspace_bytes;
+} ide3d_render_param_grads;
+
+int64_t ide3d_render_param_grad_workspace_bytes(const ide3d_render_params* p);
+int ide3d_render_rays_backward_params(const ide3d_render_params* p, const ide3d_render_grads* g, const ide3d_render_param_grads* q, void* stream);
+
+/*
  * `renderer.sample_voxel(img_v, seg_v, pts)` (call site extract_shapes.py:146): the same two
  * gathers + MLPs for arbitrary points, no compositing.  out: [n*m, feat_ch + seg_ch + 1]
  * (sigma last).  If sigma_only != 0 only out_sigma [n*m] is written (the 256^3 density-cube
