@@ -19,13 +19,22 @@
 //   * The two MLPs run in the *transposed* form out^T[features x samples] = W[features x K] * act^T[K x samples]: the features sit in
 //     the B-operand layout and the D layout of layer 1 (row = 4*(l>>4)+r, col = l&15) is again a valid B operand for layer 2 once K
 //     is enumerated accordingly — activations never leave registers between gather, layer 1, layer 2 and compositing.  Weights are
-//     re-ordered once per workgroup into LDS in A-operand order.  Arithmetic: exact fp32 products on v_mfma_f32_16x16x4_f32
+//     re-ordered once per workgroup into LDS in A-operand order.  (sample_voxel_kernel runs both layers per sample; render_rays_kernel
+//     only the hidden layers — see the next point.)  Arithmetic: exact fp32 products on v_mfma_f32_16x16x4_f32
 //     (library default), or bf16x6 (fp32-grade: 3 bf16 pieces per operand, 6 products) on v_mfma_f32_16x16x32_bf16 when a split
 //     arithmetic is selected (ide3d_set_conv_arithmetic).
-//   * Compositing: sigma is broadcast from the g = 0 lanes, alpha / transmittance are evaluated by a 16-lane segmented shuffle scan
-//     with the running transmittance carried across tiles, each lane accumulates w * feature for the 16 output features it holds
-//     (the geometry outputs right after their MLP: they die before the texture MLP), a 4-step xor-shuffle reduction over the 16
-//     samples closes the ray.  Nothing but the final [n, feat+seg, rays] image, depth and weight sum is written.
+//   * Compositing, and the output layers once per ray: nothing non-linear sits between a branch's output layer and the sum over the
+//     samples, so sum_i w_i (W1 h_i + b1) = W1 (sum_i w_i h_i) + b1 sum_i w_i.  Per sample the kernel runs the hidden layers only; sigma —
+//     the one output the weights are made from — is the row-0 dot product over the lane's 16 hidden units plus two xor-shuffles across g
+//     (as in density_kernel), which leaves it in every lane of the sample.  alpha / transmittance are evaluated by a 16-lane segmented
+//     shuffle scan with the running transmittance carried across tiles, and each lane accumulates w * h for the 16 hidden units it holds
+//     of either branch (the geometry ones right after their hidden layer: it dies before the texture MLP).  Closing a ray: a DPP
+//     row reduction over the 16 samples (34 values, no LDS crossbar), then both 32-row output layers as exact fp32 FMAs in every
+//     arithmetic — lane (g, j) takes rows j and j + 16 over its 16 units from a plain fp32 LDS image (conflict-free 16-byte reads), two
+//     xor-shuffles add the four g slices — plus b1 * sum_i w_i; white_back / max_depth follow.  Per 16-sample tile this removed 48 of the
+//     96 bf16 (64 of the 128 fp32) matrix instructions, the second bf16 split (28 v_cvt_pk + v_dot2c per 8 values) and 24 of 60 LDS
+//     reads: 381 -> 320 us for the benchmark's batch (fp32 MLPs 454 -> 354; profiles/per_ray_heads/).  Nothing but the final
+//     [n, feat+seg, rays] image, depth and weight sum is written.
 //   * Persistent workgroups (2 per CU) take contiguous ray ranges; the range order is XCD-remapped so neighbouring rays
 //     (neighbouring plane lines) share one XCD L2.
 // Compulsory HBM traffic per image: 2 tri-planes + jitter/noise in + (feat+seg+2)*rays*4 out.  The planes are cache resident
@@ -53,6 +62,20 @@ struct RmCfg {
     static constexpr int MLP = A1 + A2 + B0 + B1;
 };
 
+// The output layer w1 [nout, HID] (nout <= 32) as plain fp32, [m2][mt][lane][4]: lane 16 g + j holds w1[16 m2 + j][16 mt + 4 g + 0..3], rows
+// past nout are zero.  This is the A-operand order of the fp32 matrix path, and also the order in which a lane (g, j) that holds the hidden
+// units 16 mt + 4 g + r meets rows j and j + 16 (render_rays_kernel's per-ray output layer): consecutive lanes read consecutive 16 bytes.
+template <int HID>
+__device__ __forceinline__ void stage_out_fp32(float* __restrict__ a2, const float* __restrict__ w1, int nout) {
+    constexpr int MT1 = HID / 16;
+    for (int i = threadIdx.x; i < 2 * MT1 * 64 * 4; i += blockDim.x) {
+        const int e = i & 3, lane = (i >> 2) & 63, rest = i >> 8;
+        const int tq = rest % MT1, mt = rest / MT1;
+        const int row = 16 * mt + (lane & 15), col = 16 * tq + 4 * (lane >> 4) + e;
+        a2[i] = (row < nout) ? w1[row * HID + col] : 0.f;
+    }
+}
+
 // Re-order one MLP's weights into LDS (A-operand order).  w0 [HID, C], w1 [nout, HID] (nout <= 32).
 template <int C, int HID>
 __device__ void stage_mlp(float* __restrict__ s, const float* __restrict__ w0, const float* __restrict__ b0,
@@ -65,12 +88,7 @@ __device__ void stage_mlp(float* __restrict__ s, const float* __restrict__ w0, c
         const int row = 16 * mt + (lane & 15), col = 4 * ((lane >> 4) + 4 * ci) + e;
         a1[i] = w0[row * C + col];
     }
-    for (int i = threadIdx.x; i < K::A2; i += blockDim.x) {
-        const int e = i & 3, lane = (i >> 2) & 63, rest = i >> 8;
-        const int tq = rest % K::MT1, mt = rest / K::MT1;
-        const int row = 16 * mt + (lane & 15), col = 16 * tq + 4 * (lane >> 4) + e;
-        a2[i] = (row < nout) ? w1[row * HID + col] : 0.f;
-    }
+    stage_out_fp32<HID>(a2, w1, nout);
     for (int i = threadIdx.x; i < K::B0; i += blockDim.x) sb0[i] = b0[i];          // index = 16 mt + 4 g + r
     for (int i = threadIdx.x; i < K::B1; i += blockDim.x) sb1[i] = (i < nout) ? b1[i] : 0.f;
 }
@@ -138,13 +156,10 @@ __device__ __forceinline__ f32x4 mfma6(const u32x4 (&a)[3], const u32x4 (&b)[3],
     return acc;
 }
 
+// first layer, pre-split: [mt][piece][lane]
 template <int C, int HID>
-__device__ void stage_mlp_split(unsigned char* __restrict__ sm, const float* __restrict__ w0, const float* __restrict__ b0,
-                                const float* __restrict__ w1, const float* __restrict__ b1, int nout) {
+__device__ __forceinline__ void stage_split_layer1(u32x4* __restrict__ a1, const float* __restrict__ w0) {
     using K = RmSplit<C, HID>;
-    u32x4* a1 = reinterpret_cast<u32x4*>(sm);
-    u32x4* a2 = a1 + K::A1;
-    float* sb = reinterpret_cast<float*>(a2 + K::A2);
     for (int i = threadIdx.x; i < K::MT1 * 64; i += blockDim.x) {
         const int lane = i & 63, mt = i >> 6, g = lane >> 4, row = 16 * mt + (lane & 15);
         float v[8];
@@ -155,6 +170,21 @@ __device__ void stage_mlp_split(unsigned char* __restrict__ sm, const float* __r
 #pragma unroll
         for (int q = 0; q < 3; ++q) a1[(mt * 3 + q) * 64 + lane] = pc[q];
     }
+}
+// biases: b0 at index 16 mt + 4 g + r, then the 32 output rows' (zero past nout)
+template <int HID>
+__device__ __forceinline__ void stage_split_biases(float* __restrict__ sb, const float* __restrict__ b0, const float* __restrict__ b1, int nout) {
+    for (int i = threadIdx.x; i < HID; i += blockDim.x) sb[i] = b0[i];
+    for (int i = threadIdx.x; i < 32; i += blockDim.x) sb[HID + i] = (i < nout) ? b1[i] : 0.f;
+}
+
+template <int C, int HID>
+__device__ void stage_mlp_split(unsigned char* __restrict__ sm, const float* __restrict__ w0, const float* __restrict__ b0,
+                                const float* __restrict__ w1, const float* __restrict__ b1, int nout) {
+    using K = RmSplit<C, HID>;
+    u32x4* a1 = reinterpret_cast<u32x4*>(sm);
+    u32x4* a2 = a1 + K::A1;
+    stage_split_layer1<C, HID>(a1, w0);
     for (int i = threadIdx.x; i < 2 * K::KH * 64; i += blockDim.x) {
         const int lane = i & 63, kh = (i >> 6) % K::KH, m2 = i / (64 * K::KH), g = lane >> 4, row = 16 * m2 + (lane & 15);
         float v[8];
@@ -165,16 +195,16 @@ __device__ void stage_mlp_split(unsigned char* __restrict__ sm, const float* __r
 #pragma unroll
         for (int q = 0; q < 3; ++q) a2[((m2 * K::KH + kh) * 3 + q) * 64 + lane] = pc[q];
     }
-    for (int i = threadIdx.x; i < K::MT1 * 16; i += blockDim.x) sb[i] = b0[i];                       // index = 16 mt + 4 g + r
-    for (int i = threadIdx.x; i < 32; i += blockDim.x) sb[K::MT1 * 16 + i] = (i < nout) ? b1[i] : 0.f;
+    stage_split_biases<HID>(reinterpret_cast<float*>(a2 + K::A2), b0, b1, nout);
 }
 
-template <int C, int HID>
+// A2U: the 16-byte units of the output layer's image that lie between the first layer and the biases (render_rays_kernel keeps a smaller one)
+template <int C, int HID, int A2U = RmSplit<C, HID>::A2>
 __device__ __forceinline__ void mlp_hidden_split(const unsigned char* __restrict__ sm, const float (&f)[C / 4], f32x4 (&h)[HID / 16]) {
     using K = RmSplit<C, HID>;
     const int lane = lane_id(), g = lane >> 4;
     const u32x4* a1 = reinterpret_cast<const u32x4*>(sm);
-    const f32x4* sb0 = reinterpret_cast<const f32x4*>(sm + (K::A1 + K::A2) * 16);
+    const f32x4* sb0 = reinterpret_cast<const f32x4*>(sm + (K::A1 + A2U) * 16);
     u32x4 fb[3];
     split8(f, fb);
 #pragma unroll
@@ -215,16 +245,15 @@ __device__ __forceinline__ void mlp_tile_split(const unsigned char* __restrict__
     }
 }
 
-// (density only, split form) hidden layer on the bf16 matrix path, row 0 of the second layer as a VALU dot product like mlp_sigma
-template <int C, int HID>
-__device__ __forceinline__ float mlp_sigma_split(const unsigned char* __restrict__ sm, const float* __restrict__ s_row, const float (&f)[C / 4]) {
-    using K = RmSplit<C, HID>;
+// Row 0 of the geometry output layer (sigma) from the hidden vector of a sample, which is spread over its four lanes (lane (g, j) holds
+// units 16 mt + 4 g + r): a 16-term partial sum on the VALU and two xor-shuffles across g; every lane of sample j returns the value.
+// s_row: w1[0][0..HID) followed by b1[0].
+template <int HID>
+__device__ __forceinline__ float sigma_row0(const float* __restrict__ s_row, const f32x4 (&h)[HID / 16]) {
     const int g = lane_id() >> 4;
-    f32x4 h[K::MT1];
-    mlp_hidden_split<C, HID>(sm, f, h);
     float acc = 0.f;
 #pragma unroll
-    for (int mt = 0; mt < K::MT1; ++mt) {
+    for (int mt = 0; mt < HID / 16; ++mt) {
         const f32x4 w = *reinterpret_cast<const f32x4*>(s_row + 16 * mt + 4 * g);
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc += w[r] * h[mt][r];
@@ -232,6 +261,14 @@ __device__ __forceinline__ float mlp_sigma_split(const unsigned char* __restrict
     acc += __shfl_xor(acc, 16);
     acc += __shfl_xor(acc, 32);
     return acc + s_row[HID];
+}
+
+// (density only, split form) hidden layer on the bf16 matrix path, row 0 of the second layer as a VALU dot product like mlp_sigma
+template <int C, int HID>
+__device__ __forceinline__ float mlp_sigma_split(const unsigned char* __restrict__ sm, const float* __restrict__ s_row, const float (&f)[C / 4]) {
+    f32x4 h[HID / 16];
+    mlp_hidden_split<C, HID>(sm, f, h);
+    return sigma_row0<HID>(s_row, h);
 }
 
 // Gather this lane's NF features of one sample from one tri-plane (channels_last, channel stride 1).
@@ -378,26 +415,13 @@ __device__ __forceinline__ void mlp_tile(const float* __restrict__ s, const floa
     }
 }
 
-// Density only: of the second layer just row 0 (sigma) is needed — a 64-term dot product per sample.  The hidden vector of a
-// sample is spread over its four lanes (lane (g, j) holds units 16 mt + 4 g + r), so each lane forms a 16-term partial sum on
-// the VALU and two xor-shuffles across g close it: ~20 vector instructions instead of the 32 MFMAs (1024 cycles) of the
-// 32-row layer.  s_row: w1[0][0..HID) followed by b1[0].
+// Density only: of the second layer just row 0 (sigma) is needed — a 64-term dot product per sample (sigma_row0): ~20 vector
+// instructions instead of the 32 MFMAs (1024 cycles) of the 32-row layer.
 template <int C, int HID>
 __device__ __forceinline__ float mlp_sigma(const float* __restrict__ s, const float* __restrict__ s_row, const float (&f)[C / 4]) {
-    using K = RmCfg<C, HID>;
-    const int g = lane_id() >> 4;
-    f32x4 h[K::MT1];
+    f32x4 h[HID / 16];
     mlp_hidden<C, HID>(s, f, h);
-    float acc = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < K::MT1; ++mt) {
-        const f32x4 w = *reinterpret_cast<const f32x4*>(s_row + 16 * mt + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc += w[r] * h[mt][r];
-    }
-    acc += __shfl_xor(acc, 16);
-    acc += __shfl_xor(acc, 32);
-    return acc + s_row[HID];
+    return sigma_row0<HID>(s_row, h);
 }
 
 __device__ __forceinline__ float seg16_excl_prod(float v, float& total) {
@@ -429,6 +453,81 @@ __device__ __forceinline__ void mlp_branch(const unsigned char* sm, const float 
     else mlp_tile<C, HID>(reinterpret_cast<const float*>(sm), f, out);
 }
 
+// ---- render_rays_kernel: the output layers once per ray -------------------------------------------------------------------------------
+// Between the output layer of a decoder branch and the sum over a ray's samples nothing is non-linear (white_back and max_depth are added
+// after the sum), so   sum_i w_i (W1 h_i + b1)  =  W1 (sum_i w_i h_i) + b1 sum_i w_i :   the sample loop runs the hidden layers only, takes
+// sigma — the one output the weights w_i are made from — as the row-0 dot product (sigma_row0, as density_kernel does) and composites the
+// hidden vectors; the 32-row output layers run once per ray on the composited vector, as exact fp32 FMAs in every arithmetic.
+//
+// LDS image of one branch: the first layer and the biases as the arithmetic's hidden layer reads them; in between the output layer as plain
+// fp32 in stage_out_fp32's order, which the fp32 form's image holds anyway — the split form keeps it in place of its pre-split A2 pieces.
+// Row 0 of the geometry layer and its bias follow the two branches (`s_row`, RmRender::ROW floats).
+template <int C, int HID, bool SPLIT> struct RmRender {
+    using K = RmCfg<C, HID>;
+    static constexpr int W2_OFF = K::A1 * 4, B1_OFF = (K::A1 + K::A2 + K::B0) * 4, BYTES = K::MLP * 4;          // bytes
+    static constexpr int ROW = HID + 4;
+};
+template <int C, int HID> struct RmRender<C, HID, true> {
+    using K = RmSplit<C, HID>;
+    static constexpr int W2 = 2 * K::MT1 * 64;                                                                   // 16-byte units
+    static constexpr int W2_OFF = K::A1 * 16, B1_OFF = (K::A1 + W2) * 16 + HID * 4, BYTES = (K::A1 + W2) * 16 + K::BIAS * 4;
+    static constexpr int ROW = HID + 4;
+};
+
+template <int C, int HID, bool SPLIT>
+__device__ __forceinline__ void stage_render_branch(unsigned char* sm, const float* w0, const float* b0, const float* w1, const float* b1, int nout) {
+    if constexpr (SPLIT) {
+        using R = RmRender<C, HID, true>;
+        stage_split_layer1<C, HID>(reinterpret_cast<u32x4*>(sm), w0);
+        stage_out_fp32<HID>(reinterpret_cast<float*>(sm + R::W2_OFF), w1, nout);
+        stage_split_biases<HID>(reinterpret_cast<float*>(sm + R::W2_OFF + R::W2 * 16), b0, b1, nout);
+    } else {
+        stage_mlp<C, HID>(reinterpret_cast<float*>(sm), w0, b0, w1, b1, nout);
+    }
+}
+template <int C, int HID, bool SPLIT>
+__device__ __forceinline__ void hidden_branch(const unsigned char* sm, const float (&f)[C / 4], f32x4 (&h)[HID / 16]) {
+    if constexpr (SPLIT) mlp_hidden_split<C, HID, RmRender<C, HID, true>::W2>(sm, f, h);
+    else mlp_hidden<C, HID>(reinterpret_cast<const float*>(sm), f, h);
+}
+
+// v + (v of the lane that `CTRL` names), a DPP operand of the addition: no LDS crossbar round trip
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+// sum over each aligned row of 16 lanes, in every lane of the row: neighbours in a quad (quad_perm [1,0,3,2], [2,3,0,1]), then the other quad
+// of the half row and the other half row (row_half_mirror, row_mirror: the quads / half rows are uniform by then)
+__device__ __forceinline__ float row16_sum(float v) {
+    v = dpp_add<0xB1>(v); v = dpp_add<0x4E>(v); v = dpp_add<0x141>(v); v = dpp_add<0x140>(v);
+    return v;
+}
+
+// One branch's output layer on the composited hidden vector of a ray: acc[4 mt + r] = sum_i w_i h_i[16 mt + 4 g + r], already summed over the
+// ray's samples in every lane.  Lane (g, j) forms the partial sums of rows j and j + 16 over its 16 units, two xor-shuffles add the four g
+// slices: out[m2] = b1[16 m2 + j] * wsum + sum_u W1[16 m2 + j][u] H[u] in every lane (zero for rows past the decoder's).
+template <int C, int HID, bool SPLIT>
+__device__ __forceinline__ void heads_per_ray(const unsigned char* sm, const float (&acc)[HID / 4], float wsum, float (&out)[2]) {
+    using R = RmRender<C, HID, SPLIT>;
+    constexpr int MT1 = HID / 16;
+    const int lane = lane_id();
+    const f32x4* w2 = reinterpret_cast<const f32x4*>(sm + R::W2_OFF);
+    const float* sb1 = reinterpret_cast<const float*>(sm + R::B1_OFF);
+#pragma unroll
+    for (int m2 = 0; m2 < 2; ++m2) {
+        float a = 0.f;
+#pragma unroll
+        for (int mt = 0; mt < MT1; ++mt) {
+            const f32x4 w = w2[(m2 * MT1 + mt) * 64 + lane];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a = fmaf(w[r], acc[4 * mt + r], a);
+        }
+        a += __shfl_xor(a, 16);
+        a += __shfl_xor(a, 32);
+        out[m2] = fmaf(sb1[16 * m2 + (lane & 15)], wsum, a);
+    }
+}
+
 // Exclusive residency (modconv.hip `kSpExclusive`): the SPLIT forms of the three kernels below run LDS-fed bf16
 // MFMA loops, beside which a foreign wave's packed-fp32 instructions return wrong values on MI355X.  They are therefore launched as 8-wave
 // workgroups, one per CU: two of the workgroup's own waves, 256 registers each (`rm_claim_half_simd`), fill every SIMD, and no wave leaves
@@ -444,10 +543,14 @@ render_rays_kernel(ide3d_render_params p, int64_t rays_per_block) {
     constexpr int NW = RmWaves<SPLIT>::value;
     rm_claim_half_simd<SPLIT>();
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    using R = RmRender<C, HID, SPLIT>;
+    constexpr int NA = HID / 4;                            // hidden units per lane and branch
     unsigned char* s_geo = reinterpret_cast<unsigned char*>(lds);
-    unsigned char* s_tex = s_geo + MlpBytes<C, HID, SPLIT>::value;
-    stage_branch<C, HID, SPLIT>(s_geo, p.geo_w0, p.geo_b0, p.geo_w1, p.geo_b1, 1 + p.seg_ch);
-    stage_branch<C, HID, SPLIT>(s_tex, p.tex_w0, p.tex_b0, p.tex_w1, p.tex_b1, p.feat_ch);
+    unsigned char* s_tex = s_geo + R::BYTES;
+    float* const s_row = reinterpret_cast<float*>(s_tex + R::BYTES);           // row 0 of geo_w1 + its bias
+    stage_render_branch<C, HID, SPLIT>(s_geo, p.geo_w0, p.geo_b0, p.geo_w1, p.geo_b1, 1 + p.seg_ch);
+    stage_render_branch<C, HID, SPLIT>(s_tex, p.tex_w0, p.tex_b0, p.tex_w1, p.tex_b1, p.feat_ch);
+    for (int i = threadIdx.x; i <= HID; i += blockDim.x) s_row[i] = (i < HID) ? p.geo_w1[i] : p.geo_b1[0];
     __syncthreads();
 
     const int lane = lane_id(), wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -499,9 +602,9 @@ render_rays_kernel(ide3d_render_params p, int64_t rays_per_block) {
         tile_taps(n, r, zl, jl, t);
         issue_taps<C>(uniform_ptr(p.geo_planes + n * p.geo_stride[0]), t, gl, buf);
     }
-    float acc_t[8], acc_g[8];
+    float acc_t[NA], acc_g[NA];                           // sum_i w_i h_i of the units 16 mt + 4 g + r, over this lane's samples
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { acc_t[i] = 0.f; acc_g[i] = 0.f; }
+    for (int i = 0; i < NA; ++i) { acc_t[i] = 0.f; acc_g[i] = 0.f; }
     float carry = 1.0f, wsum = 0.f, dsum = 0.f;
 
     while (have) {
@@ -533,14 +636,14 @@ render_rays_kernel(ide3d_render_params p, int64_t rays_per_block) {
         tile_depth(rayp, s0p, zln, jln);
 
         float fg[K::NF], ft[K::NF];
-        f32x4 og[2], ot[2];
+        f32x4 hg[K::MT1], ht[K::MT1];
         blend_taps<C>(buf, t, fg);
         to_matrix_lanes(fg);
         issue_taps<C>(uniform_ptr(p.tex_planes + n * p.tex_stride[0]), t, gl, buf);          // in flight during the geometry MLP
-        mlp_branch<C, HID, SPLIT>(s_geo, fg, og);
+        hidden_branch<C, HID, SPLIT>(s_geo, fg, hg);
 
-        // --- compositing weights (before the texture MLP: the geometry outputs die here) ---
-        float sigma = __shfl(og[0][0], j);                    // feature 0 lives in lanes g = 0
+        // --- compositing weights (before the texture MLP: the geometry hidden vector dies here) ---
+        float sigma = sigma_row0<HID>(s_row, hg);             // in every lane of sample j
         sigma += noise;
         const float dens = p.clamp_mode == 0 ? softplus_fast(sigma) : fmaxf(sigma, 0.f);
         float dnorm;
@@ -557,48 +660,48 @@ render_rays_kernel(ide3d_render_params p, int64_t rays_per_block) {
         carry *= tot;
         wsum += w; dsum += w * z;
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
+        for (int mt = 0; mt < K::MT1; ++mt)
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr) acc_g[mt * 4 + rr] += w * og[mt][rr];
+            for (int rr = 0; rr < 4; ++rr) acc_g[mt * 4 + rr] += w * hg[mt][rr];
 
         blend_taps<C>(buf, t, ft);
         to_matrix_lanes(ft);
         tile_taps(np, rp, zln, jln, t);                                         // next tile's geometry taps: during the texture MLP
         issue_taps<C>(uniform_ptr(p.geo_planes + np * p.geo_stride[0]), t, gl, buf);
-        mlp_branch<C, HID, SPLIT>(s_tex, ft, ot);
+        hidden_branch<C, HID, SPLIT>(s_tex, ft, ht);
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
+        for (int mt = 0; mt < K::MT1; ++mt)
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr) acc_t[mt * 4 + rr] += w * ot[mt][rr];
+            for (int rr = 0; rr < 4; ++rr) acc_t[mt * 4 + rr] += w * ht[mt][rr];
 
         if (s0n == 0) {
-            // --- close the ray: reduce over the 16 samples held by lanes with equal g ---
+            // --- close the ray: reduce over the 16 samples held by lanes with equal g, then the output layers on the sums ---
+            wsum = row16_sum(wsum); dsum = row16_sum(dsum);
 #pragma unroll
-            for (int off = 8; off > 0; off >>= 1) {
-                wsum += __shfl_xor(wsum, off); dsum += __shfl_xor(dsum, off);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { acc_g[i] += __shfl_xor(acc_g[i], off); acc_t[i] += __shfl_xor(acc_t[i], off); }
-            }
-            if (j == 0) {
+            for (int i = 0; i < NA; ++i) { acc_g[i] = row16_sum(acc_g[i]); acc_t[i] = row16_sum(acc_t[i]); }
+            float o_t[2], o_g[2];
+            heads_per_ray<C, HID, SPLIT>(s_tex, acc_t, wsum, o_t);
+            heads_per_ray<C, HID, SPLIT>(s_geo, acc_g, wsum, o_g);
+            {
+                // every lane holds rows j and j + 16 of both branches: the g = 0 .. 3 lanes write texture row j, j + 16, geometry row j, j + 16.
                 // last_back needs the un-weighted features of the final sample; not supported in the fused
                 // kernel (host guards), white_back / max_depth are.
                 const float bg = p.white_back ? (1.0f - wsum) : 0.f;
                 float* of = p.out_feat + (int64_t)n * nch * p.rays_per_img + r;
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) {
-                        const int idx = 16 * mt + 4 * g + rr;
-                        if (idx < p.feat_ch) of[(int64_t)idx * p.rays_per_img] = acc_t[mt * 4 + rr] + bg;
-                        if (idx >= 1 && idx <= p.seg_ch) of[(int64_t)(p.feat_ch + idx - 1) * p.rays_per_img] = acc_g[mt * 4 + rr] + bg;
-                    }
-                if (g == 0) {
+                const int idx = j + 16 * (g & 1);
+                const float v = (g & 2) ? ((g & 1) ? o_g[1] : o_g[0]) : ((g & 1) ? o_t[1] : o_t[0]);
+                if (g < 2) {
+                    if (idx < p.feat_ch) of[(int64_t)idx * p.rays_per_img] = v + bg;
+                } else {
+                    if (idx >= 1 && idx <= p.seg_ch) of[(int64_t)(p.feat_ch + idx - 1) * p.rays_per_img] = v + bg;      // row 0 is sigma
+                }
+                if (lane == 0) {
                     if (p.out_depth) p.out_depth[ray] = dsum + ((p.max_depth != 0.f) ? (1.0f - wsum) * p.max_depth : 0.f);
                     if (p.out_wsum) p.out_wsum[ray] = wsum;
                 }
             }
 #pragma unroll
-            for (int i = 0; i < 8; ++i) { acc_t[i] = 0.f; acc_g[i] = 0.f; }
+            for (int i = 0; i < NA; ++i) { acc_t[i] = 0.f; acc_g[i] = 0.f; }
             carry = 1.0f; wsum = 0.f; dsum = 0.f;
         }
         ray = rayn; n = nn; r = rn; s0 = s0n; have = haven;
@@ -844,7 +947,8 @@ density_kernel(ide3d_render_params p, const Src src, int64_t m, float* __restric
 
 template <int C, int HID, bool SPLIT = false>
 static int launch_render(const ide3d_render_params& p, hipStream_t st) {
-    const size_t lds_bytes = (size_t)2 * MlpBytes<C, HID, SPLIT>::value;
+    using R = RmRender<C, HID, SPLIT>;
+    const size_t lds_bytes = (size_t)2 * R::BYTES + (size_t)R::ROW * sizeof(float);
     const int64_t total_rays = (int64_t)p.n * p.rays_per_img;
     constexpr int NW = RmWaves<SPLIT>::value;
     int64_t nblk = kNumCU * 8 / NW;                                // 8 waves per CU either way

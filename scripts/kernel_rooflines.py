@@ -162,7 +162,8 @@ def cases(device):
     geo = (rn(N, 96, 256, 256) * 0.7).contiguous(memory_format=torch.channels_last)
     cam2 = torch.cat([triplane.camera_label(y, device=device) for y in (-0.5, 0.0, 0.5, 0.25)])[:, :16].reshape(-1, 4, 4)
     jit3 = jit.reshape(N, 4096, 96)
-    mlp_flops = N * M * 2 * (2 * 32 * 64 + 64 * 20 + 64 * 32)
+    # per sample the two hidden layers (the matrix pipe's work); the output layers (20 + 32 rows) run once per ray of 96 samples, on the VALU
+    mlp_flops = N * M * 2 * (2 * 32 * 64) + N * 4096 * 2 * (64 * 20 + 64 * 32)
     fused_bytes = N * (2 * 3 * C * H * H + 4096 * 53 + M) * 4
     # the decoder MLPs run bf16x6 (v_mfma_f32_16x16x32_bf16, 6 products per fp32 product) unless exact fp32 products are selected
     # (v_mfma_f32_16x16x4_f32): the row is priced against the peak of what it runs.  The kernel itself is gather / VALU limited, not

@@ -25,4 +25,6 @@ with torch.no_grad():
     e1.record(); torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / iters
 samples = n * 4096 * 96
-print(f'render_rays: {ms * 1e3:.1f} us per batch of {n}; {samples / ms / 1e6:.2f} Gsamples/s; MLP {samples * 2 * (32 * 64 * 2 + 64 * 52) / ms / 1e9:.1f} TFLOP/s')
+# what the kernel computes: the two hidden layers per sample (matrix pipe), the two output layers (52 rows) once per ray of 96 samples
+mlp_flops = samples * 2 * (32 * 64 * 2) + (samples // 96) * 2 * (64 * 52)
+print(f'render_rays: {ms * 1e3:.1f} us per batch of {n}; {samples / ms / 1e6:.2f} Gsamples/s; MLP {mlp_flops / ms / 1e9:.1f} TFLOP/s')
