@@ -339,6 +339,12 @@ def load():
             'ide3d_modconv_weight_grad': [ctypes.POINTER(_WgradParams), vp],
             'ide3d_bias_noise_workspace_bytes': [i32, i32, i32, i32],
             'ide3d_bias_noise_grad': [vp, vp, vp, i32, i32, i32, i32, vp, i64, vp],
+            'ide3d_noise_reg_workspace_bytes': [ctypes.POINTER(i32), i32],
+            'ide3d_noise_reg_levels': [ctypes.POINTER(i32), i32],
+            'ide3d_noise_reg': [vp, ctypes.POINTER(i32), i32, vp, i64, vp, vp, vp],
+            'ide3d_noise_reg_backward': [vp, ctypes.POINTER(i32), i32, vp, i64, vp, vp, vp, vp],
+            'ide3d_noise_normalize_workspace_bytes': [ctypes.POINTER(i32), i32],
+            'ide3d_noise_normalize': [vp, ctypes.POINTER(i32), i32, vp, i64, vp],
             'ide3d_set_conv_arithmetic': [i32],
             'ide3d_get_conv_arithmetic': [],
             'ide3d_frame_u8': [vp, vp, vp, i32, i32, i32, i32, vp, vp],
@@ -377,6 +383,8 @@ EXPORTED_SYMBOLS = (
     'ide3d_act_bwd_workspace_bytes', 'ide3d_modconv_act_backward', 'ide3d_modconv_scale_dot', 'ide3d_head_wgrad_workspace_bytes',
     'ide3d_head_weight_grad', 'ide3d_wgrad_workspace_bytes', 'ide3d_modconv_weight_grad', 'ide3d_bias_noise_workspace_bytes',
     'ide3d_bias_noise_grad', 'ide3d_render_param_grad_workspace_bytes', 'ide3d_render_rays_backward_params',
+    'ide3d_noise_reg_workspace_bytes', 'ide3d_noise_reg_levels', 'ide3d_noise_reg', 'ide3d_noise_reg_backward',
+    'ide3d_noise_normalize_workspace_bytes', 'ide3d_noise_normalize',
 )
 
 
@@ -1387,6 +1395,102 @@ class ModconvGradPlugin:
             rc = lib.ide3d_bias_noise_grad(dz.data_ptr(), db.data_ptr(), _ptr(dn), n, c, h, w, ws.data_ptr(), nbytes, _stream(dz))
         _check(rc, 'bias_noise_grad')
         return db, dn
+
+
+class _NoiseMap(ctypes.Structure):
+    _fields_ = [('data', ctypes.c_void_p), ('side', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+class NoisePlugin:
+    """The projector's noise regulariser and noise normaliser, batched over all maps of a call (csrc/noise_reg.hip).
+    `maps`: a non-empty list of contiguous float32 [R, R] tensors on one device, R a power of two in 4..512."""
+
+    MIN_SIDE, MAX_SIDE, MAX_MAPS = 4, 512, 1024
+    _tables = {}          # (device, ((data_ptr, side), ...)) -> _Table: the device table is uploaded once per set of maps
+
+    class _Table:
+        pass
+
+    @staticmethod
+    def supported(t):
+        """One map the kernels take (the callers' dispatch rule)."""
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.ndim == 2 and t.shape[0] == t.shape[1]
+                and NoisePlugin.MIN_SIDE <= t.shape[0] <= NoisePlugin.MAX_SIDE and (t.shape[0] & (t.shape[0] - 1)) == 0 and t.is_contiguous())
+
+    @staticmethod
+    def _table(maps, what):
+        _require(0 < len(maps) <= NoisePlugin.MAX_MAPS, f'{what}: 1..{NoisePlugin.MAX_MAPS} maps')
+        dev = maps[0].device
+        for t in maps:
+            _require(NoisePlugin.supported(t) and t.device == dev,
+                     f'{what}: every map must be a contiguous float32 [R, R] tensor on one device, R a power of two in 4..512')
+        key = (dev, tuple((t.data_ptr(), t.shape[0]) for t in maps))
+        tab = NoisePlugin._tables.get(key)
+        if tab is None:
+            lib = load()
+            k = len(maps)
+            tab = NoisePlugin._Table()
+            tab.k = k
+            tab.sides = (ctypes.c_int32 * k)(*[t.shape[0] for t in maps])
+            host = (_NoiseMap * k)()
+            for i, t in enumerate(maps):
+                host[i].data, host[i].side = t.data_ptr(), t.shape[0]
+            tab.device = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(dev)
+            tab.reg_bytes = lib.ide3d_noise_reg_workspace_bytes(tab.sides, k)
+            tab.levels = lib.ide3d_noise_reg_levels(tab.sides, k)
+            tab.norm_bytes = lib.ide3d_noise_normalize_workspace_bytes(tab.sides, k)
+            _require(tab.reg_bytes > 0 and tab.levels > 0 and tab.norm_bytes > 0, f'{what}: unsupported maps')
+            tab.numels = [t.numel() for t in maps]
+            if len(NoisePlugin._tables) >= 16:
+                NoisePlugin._tables.clear()
+            NoisePlugin._tables[key] = tab
+        return tab, dev
+
+    @staticmethod
+    def noise_reg(maps):
+        """ide3d_noise_reg -> (loss [] float32, means [levels, 2], workspace): the last two are what `noise_reg_backward` reads."""
+        tab, dev = NoisePlugin._table(maps, 'noise_reg')
+        ws = torch.empty([tab.reg_bytes // 4], dtype=torch.float32, device=dev)
+        means = torch.empty([tab.levels, 2], dtype=torch.float32, device=dev)
+        loss = torch.empty([], dtype=torch.float32, device=dev)
+        with _dev_guard(dev):
+            rc = load().ide3d_noise_reg(_ptr(tab.device), tab.sides, tab.k, _ptr(ws), tab.reg_bytes, _ptr(means), _ptr(loss), _stream(ws))
+        _check(rc, 'noise_reg')
+        return loss, means, ws
+
+    @staticmethod
+    def noise_reg_backward(maps, ws, means, dloss):
+        """ide3d_noise_reg_backward -> [d loss / d map for every map] (views of one buffer); `dloss`: the upstream gradient, a one-element
+        float32 tensor on the maps' device (read by the kernel, never by the host)."""
+        tab, dev = NoisePlugin._table(maps, 'noise_reg_backward')
+        _require(ws.is_cuda and ws.dtype == torch.float32 and ws.device == dev and ws.numel() * 4 >= tab.reg_bytes and ws.is_contiguous(),
+                 'noise_reg_backward: workspace of another call')
+        _require(means.dtype == torch.float32 and means.device == dev and tuple(means.shape) == (tab.levels, 2) and means.is_contiguous(),
+                 'noise_reg_backward: means of another call')
+        _require(dloss.dtype == torch.float32 and dloss.device == dev and dloss.numel() == 1, 'noise_reg_backward: dloss must be one float32 on the device')
+        dloss = dloss.contiguous()
+        grad = torch.empty([sum(tab.numels)], dtype=torch.float32, device=dev)
+        with _dev_guard(dev):
+            rc = load().ide3d_noise_reg_backward(_ptr(tab.device), tab.sides, tab.k, _ptr(ws), tab.reg_bytes, _ptr(means), _ptr(dloss), _ptr(grad),
+                                                 _stream(grad))
+        _check(rc, 'noise_reg_backward')
+        return [g.view_as(t) for g, t in zip(grad.split(tab.numels), maps)]
+
+    @staticmethod
+    def noise_normalize(maps):
+        """ide3d_noise_normalize, in place: n -= mean(n); n *= rsqrt(mean(n^2)) for every map.  The kernels write through raw pointers, so the
+        version counter of every map is advanced here, as a torch in-place op would (caches and graph signatures keyed on versions go stale);
+        like a torch in-place op it refuses a leaf that requires grad unless grad mode is off."""
+        tab, dev = NoisePlugin._table(maps, 'noise_normalize')
+        if torch.is_grad_enabled():
+            _require(not any(t.requires_grad for t in maps), 'noise_normalize: an in-place update of a tensor that requires grad needs torch.no_grad()')
+        ws = torch.empty([tab.norm_bytes // 4], dtype=torch.float32, device=dev)
+        with _dev_guard(dev):
+            rc = load().ide3d_noise_normalize(_ptr(tab.device), tab.sides, tab.k, _ptr(ws), tab.norm_bytes, _stream(ws))
+        _check(rc, 'noise_normalize')
+        for t in maps:
+            torch.autograd.graph.increment_version(t)
+        return maps
 
 
 def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epilogue='conv', x_amax=False):

@@ -419,6 +419,11 @@ hip_conv_grad = True
 # requires grad takes the same path; its backward adds the direct weight gradient (ide3d_modconv_weight_grad) and the bias / noise
 # reductions (ide3d_bias_noise_grad).  Off: such a layer keeps the differentiable ATen definition.
 hip_param_grad = False
+# Trainable noise maps (latent projection: the reference's projectors optimise every `noise_const` beside w): with this
+# switch on, a layer whose only trainable tensor is its const noise map takes the same path without `hip_param_grad`, and under
+# `hip_param_grad` a trainable map no longer makes a layer decline.  The map's gradient is ide3d_bias_noise_grad's pixel sum, carried through
+# the multiply by `noise_strength` by autograd.  Off: such a layer keeps the differentiable ATen definition.
+hip_noise_grad = True
 
 _modconv_grad_plugin = None
 
@@ -430,12 +435,16 @@ def _modconv_grad_init():
     return True
 
 
-def _conv_grad_ok(x, styles, *params):
+def _conv_grad_ok(x, styles, *params, noise_map=None):
     """A layer takes the HIP gradient path: grad enabled, fp32 CUDA tensors, and its input or styles need a gradient.  Without
     `hip_param_grad`, none of the tensors its launches read by pointer (`params`: _layer_params / _head_params) may require grad (a gradient
-    would be dropped otherwise); with it, a trainable parameter is a reason to take the path (the caller checks what still declines)."""
+    would be dropped otherwise); with it, a trainable parameter is a reason to take the path (the caller checks what still declines).
+    `noise_map`: the layer's const noise map (one of `params`) when this call uses it at the output size; with `hip_noise_grad` it may be
+    the one trainable tensor of an otherwise frozen layer, and is a reason to take the path too."""
     trainable = any(t is not None and t.requires_grad for t in params)
-    if trainable and not (hip_param_grad and all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in params)):
+    map_only = (hip_noise_grad and noise_map is not None and noise_map.requires_grad
+                and not any(t is not None and t is not noise_map and t.requires_grad for t in params))
+    if trainable and not ((hip_param_grad or map_only) and all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in params)):
         return False
     return (hip_conv_grad and use_hip_modconv and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
             and styles.is_cuda and styles.dtype == torch.float32 and (x.requires_grad or styles.requires_grad or trainable)
@@ -513,9 +522,10 @@ class _ModconvUpGrad(torch.autograd.Function):
         spec = bias_act.activation_funcs[ctx.act]
         dz, _ = _modconv_grad_plugin.act_backward(dy.contiguous(), y, spec.cuda_idx, spec.def_alpha, ctx.gain,
                                                   -1.0 if ctx.clamp is None else ctx.clamp)
-        gt = _upfirdn_plugin().upfirdn2d(dz, ctx.fir, 1, 1, 1, 1, 2, 2, 2, 2, True, 4.0)
-        _, ddc = _modconv_grad_plugin.act_backward(gt, yt, 0, 0.0, 1.0, -1.0, dcoefs=dcoefs)
-        dx = ds = None
+        dx = ds = ddc = gt = None
+        if any(ctx.needs_input_grad[:4]):          # (a trainable noise map alone, hip_noise_grad: dz is all its gradient needs)
+            gt = _upfirdn_plugin().upfirdn2d(dz, ctx.fir, 1, 1, 1, 1, 2, 2, 2, 2, True, 4.0)
+            _, ddc = _modconv_grad_plugin.act_backward(gt, yt, 0, 0.0, 1.0, -1.0, dcoefs=dcoefs)
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             t = _modconv_plugin.modconv2d(gt, _grad_weight(ctx.weight, False), dcoefs, None, None, 0.0, None, 1, 0.0, 1.0, -1.0, mode=1)
             dx, ds = _modconv_grad_plugin.scale_dot(x, t, styles)
@@ -552,18 +562,24 @@ class _DualHeadGrad(torch.autograd.Function):
 def _synthesis_layer_grad(lay, x, styles, dcoefs, noise, act_gain, act_clamp):
     """SynthesisLayer.forward on the frozen-generator gradient path, or None when it does not apply (the caller keeps its path)."""
     if not (lay.weight.shape[2:] == (3, 3) and lay.padding == 1 and lay.up in (1, 2) and lay.activation in ('linear', 'lrelu') and x.ndim == 4
-            and styles.shape[0] == x.shape[0] and _conv_grad_ok(x, styles, *_layer_params(lay))):
+            and styles.shape[0] == x.shape[0]):
         return None
     oh, ow = lay.up * x.shape[2], lay.up * x.shape[3]
+    # a trainable const noise map (hip_noise_grad): only when this call adds it, at the output size (its gradient is K5's pixel sum)
+    noise_const = getattr(lay, 'noise_const', None)
+    map_grad = noise_const is not None and noise_const.requires_grad
+    map_used = map_grad and noise is not None and noise.ndim == 2 and tuple(noise_const.shape) == (oh, ow)
+    if (map_grad and not (hip_noise_grad and map_used)) or not _conv_grad_ok(x, styles, *_layer_params(lay), noise_map=(noise_const if map_used else None)):
+        return None
     # the backward's launches index with 32 bits: the input of its convolution (the up-sampling layer's FIR adjoint is (2h+1) x (2w+1))
     # must stay below 2^31 elements, or the layer keeps the ATen path instead of failing in backward
     gh, gw = (oh + 1, ow + 1) if lay.up == 2 else (oh, ow)
     if x.shape[0] * lay.weight.shape[0] * gh * gw >= 2 ** 31 or x.numel() >= 2 ** 31:
         return None
-    if noise is not None and not (noise.ndim == 2 and tuple(noise.shape) == (oh, ow) and (hip_param_grad or not noise.requires_grad)):
+    if noise is not None and not (noise.ndim == 2 and tuple(noise.shape) == (oh, ow) and (hip_param_grad or map_used or not noise.requires_grad)):
         return None
-    # trainable parameters (hip_param_grad): the const noise map itself and the FIR filter have no gradient on this path
-    if (getattr(lay, 'noise_const', None) is not None and lay.noise_const.requires_grad) or lay.resample_filter.requires_grad:
+    # trainable parameters (hip_param_grad): the FIR filter has no gradient on this path
+    if lay.resample_filter.requires_grad:
         return None
     if dcoefs is None:
         dcoefs = _demod_coefs(lay.weight, styles)

@@ -768,6 +768,40 @@ int ide3d_sphere_points(const float* theta, const float* pitch, int32_t n, float
 int ide3d_cam2world(const float* forward, const float* origin, const float* lookat, int32_t lookat_stride, int32_t n,
                     float* out, void* stream);
 
+/*
+ * ABI 8 (entry points added).  The projector's per-step work on the trainable noise maps, batched over all maps (csrc/noise_reg.hip, DESIGN.md
+ * section 5.13).  `table`: k entries in DEVICE memory, one per map: a dense fp32 [side, side] map, side a power of two in 4..512.  `sides`:
+ * the same k sides in HOST memory (the launch geometry and the buffer layout follow from them alone; table[i].side must equal sides[i]).
+ * The number of launches does not depend on k or on the sides; no atomics, fixed-order sums, bit-reproducible; no host synchronisation.
+ *
+ * ide3d_noise_reg — the noise regulariser of the reference's projectors (inversion/training/projectors/w_projector_ide3d.py:114-122):
+ *   loss[0] = sum over maps and pyramid levels of mean(n * roll(n, 1, x))^2 + mean(n * roll(n, 1, y))^2, the levels of a map being side,
+ *   side / 2, ..., 8 by 2x2 average pooling (one level for side <= 8), the rolls wrapping around.  means [ide3d_noise_reg_levels(), 2]
+ *   receives (m_x, m_y) of every (map, level) in table order, and the workspace (ide3d_noise_reg_workspace_bytes()) keeps the pooled
+ *   levels; the backward reads both.
+ * ide3d_noise_reg_backward — d loss / d map of the same (:123 and autograd's walk back through :116-122), for the table, workspace and
+ *   means of the forward call: at level L a pixel receives (2 m_x (n_left + n_right) + 2 m_y (n_up + n_down)) / N_L, spread to its 4^L
+ *   level-0 descendants with weight 4^-L.  dloss: DEVICE pointer to the upstream scalar gradient, multiplied in once per level-0 pixel.
+ *   grad: the maps' gradients back to back in table order (sum of side^2 floats).
+ * ide3d_noise_normalize — the re-normalisation after the optimiser step (:140-142), in place and in the reference's order:
+ *   n -= mean(n); n *= rsqrt(mean(n^2)).  Workspace of ide3d_noise_normalize_workspace_bytes().
+ */
+typedef struct ide3d_noise_map {
+    float*  data;
+    int32_t side;
+    int32_t reserved;
+} ide3d_noise_map;
+
+int64_t ide3d_noise_reg_workspace_bytes(const int32_t* sides, int32_t k);
+int ide3d_noise_reg_levels(const int32_t* sides, int32_t k);
+int ide3d_noise_reg(const ide3d_noise_map* table, const int32_t* sides, int32_t k, float* workspace, int64_t workspace_bytes,
+                    float* means, float* loss, void* stream);
+int ide3d_noise_reg_backward(const ide3d_noise_map* table, const int32_t* sides, int32_t k, const float* workspace, int64_t workspace_bytes,
+                             const float* means, const float* dloss, float* grad, void* stream);
+int64_t ide3d_noise_normalize_workspace_bytes(const int32_t* sides, int32_t k);
+int ide3d_noise_normalize(const ide3d_noise_map* table, const int32_t* sides, int32_t k, float* workspace, int64_t workspace_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
