@@ -32,6 +32,22 @@
 //   Every sum is added to the wave's own slice of a global workspace with plain vector loads and stores (an address of a slice is only
 //   ever touched by one lane of one wave), and a second launch adds the slices in a fixed order: no atomics, so the decoder gradients ARE
 //   bit-reproducible from run to run.
+//
+// Camera pose (ide3d_render_rays_backward_camera, the body's third compile-time switch CAM; the instantiations above are compiled from the
+// body with every statement below removed):
+//   The outputs depend on cam2world only through the sample points p = M[:3,:3] q + M[:3,3].  Once sweep 2 holds a branch's feature
+//   gradient g of its sample, the lane reads that sample's 12 taps a second time (L2-resident: the gather has just touched them) and forms
+//   the 12 dot products g . v_tap; with the per-axis tap factors of make_tap_frac the derivative of a plane's blend with respect to its tap
+//   position is (1 - fy)(D01 - D00) + fy (D11 - D10) along x and (1 - fx)(D10 - D00) + fx (D11 - D01) along y (a tap outside the plane
+//   counts as 0, a plane with no tap inside - non-finite coordinates among them - contributes nothing), times size / 2 per normalised
+//   coordinate.  Summed over 3 planes x 2 branches this is gp = dL/dp (3 floats per sample), and dL/dM[r][c] = sum gp_r q_c, dL/dM[r][3] =
+//   sum gp_r.  Everything is local to the lane: no LDS, no staging.
+//   Per chunk the 12 products are summed over the wave (xor butterflies: a fixed order) and lanes 0 .. 11 add them to the 12 numbers of the
+//   ray's image in the wave's own slice [n][12] of a second workspace, plain vector loads and stores again; a second launch adds the slices in
+//   a fixed order and writes [n, 4, 4] with a zero last row.  No atomics: the camera gradient IS bit-reproducible, and equal whether the
+//   call also scatters to the planes or sums the decoder gradients.
+#include <algorithm>
+
 #include "common.h"
 #include "triplane_tap.h"
 #include "raymarch_ray.h"
@@ -87,6 +103,57 @@ __device__ __forceinline__ void gather_sample_cl(const float* __restrict__ base,
         f[4 * ci + 2] = (v0.z + v1.z) + v2.z;
         f[4 * ci + 3] = (v0.w + v1.w) + v2.w;
     }
+}
+
+// g . v for the 12 tap vectors v of one sample in one tri-plane: the loads of gather_sample_cl (clamped offsets, so unconditional), each
+// dotted with the sample's feature gradient instead of blended.  D[pl][k]: k = 0 nw, 1 ne, 2 sw, 3 se like Tap2's mask bits.
+template <int C>
+__device__ __forceinline__ void tap_dots_cl(const float* __restrict__ base, const TapAddr (&a)[3], const float (&g)[C], float (&D)[3][4]) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) D[pl][k] = 0.f;
+#pragma unroll
+    for (int ci = 0; ci < C / 4; ++ci) {
+        if (ci > 0) __builtin_amdgcn_sched_barrier(0);          // as in gather_sample_cl: one channel slice in flight at a time
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) {
+            const float* b = base + pl * C + 4 * ci;
+            const float4 v[4] = {ld4(b + a[pl].o00), ld4(b + a[pl].o01), ld4(b + a[pl].o10), ld4(b + a[pl].o11)};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                D[pl][k] = fmaf(v[k].w, g[4 * ci + 3], fmaf(v[k].z, g[4 * ci + 2], fmaf(v[k].y, g[4 * ci + 1], fmaf(v[k].x, g[4 * ci], D[pl][k]))));
+        }
+        // the slice's products are formed here: nothing reads D before the last slice, and left free they all move below the last load
+        // (12 * C loaded values live at once)
+        asm volatile("" : "+v"(D[0][0]), "+v"(D[0][1]), "+v"(D[0][2]), "+v"(D[0][3]), "+v"(D[1][0]), "+v"(D[1][1]), "+v"(D[1][2]), "+v"(D[1][3]),
+                          "+v"(D[2][0]), "+v"(D[2][1]), "+v"(D[2][2]), "+v"(D[2][3]));
+    }
+}
+
+// dL/dp of one sample from one branch, added to gp: the derivative of the three planes' blends with respect to their tap positions
+// (du/dc = size / 2), dotted with the branch's feature gradient g.  Plane 0 reads (x, y), plane 1 (y, z), plane 2 (x, z).
+template <int C>
+__device__ __forceinline__ void add_point_grad(const float* __restrict__ img, const Tap2 (&t)[3], const TapAddr (&a)[3], const TapFrac (&fr)[3],
+                                               const float (&g)[C], float half_w, float half_h, float (&gp)[3]) {
+    float D[3][4];
+    tap_dots_cl<C>(img, a, g, D);
+    float dx[3], dy[3];
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+        // a tap outside the plane counts as 0: by a factor, as the forward's zero weight does (selecting between the dot product and 0
+        // instead lets the compiler sink each dot product into a branch of its own, below all 12 * C / 4 loads: it spills)
+        const unsigned m = t[pl].mask;
+        const float d00 = D[pl][0] * ((m & 1u) ? 1.0f : 0.f), d01 = D[pl][1] * ((m & 2u) ? 1.0f : 0.f);
+        const float d10 = D[pl][2] * ((m & 4u) ? 1.0f : 0.f), d11 = D[pl][3] * ((m & 8u) ? 1.0f : 0.f);
+        // a plane without a tap inside has fractions that may not be finite: nothing, not 0 * inf
+        const float ax = m ? fr[pl].ax : 0.f, bx = m ? fr[pl].bx : 0.f, ay = m ? fr[pl].ay : 0.f, by = m ? fr[pl].by : 0.f;
+        dx[pl] = fmaf(ay, d01 - d00, by * (d11 - d10)) * half_w;
+        dy[pl] = fmaf(ax, d10 - d00, bx * (d11 - d01)) * half_h;
+    }
+    gp[0] += dx[0] + dx[2];
+    gp[1] += dy[0] + dx[1];
+    gp[2] += dy[1] + dy[2];
 }
 
 // Hidden pre-activation k of one MLP: b0[k] + sum_c w0[k][c] f[c] (weights in LDS, the same address in every lane)
@@ -209,10 +276,12 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// The body of both kernels.  PARAMS = false: gradients of the tri-planes only (sl unused).  PARAMS = true: also the decoder-parameter sums,
-// into the wave's slice of `slices`; a NULL grad_tex_planes / grad_geo_planes then skips that plane's scatter.
-template <int C, int HID, bool PARAMS>
-__device__ __forceinline__ void render_rays_backward_body(const ide3d_render_params& p, const ide3d_render_grads& gr, int sp, float* slices) {
+// The body of all kernels.  PARAMS = false: gradients of the tri-planes only (sl unused).  PARAMS = true: also the decoder-parameter sums,
+// into the wave's slice of `slices`; a NULL grad_tex_planes / grad_geo_planes then skips that plane's scatter.  CAM = true: also the 12
+// camera sums per image, into the wave's slice of `cam_slices`; a NULL plane gradient skips that plane's scatter without PARAMS too.
+template <int C, int HID, bool PARAMS, bool CAM = false>
+__device__ __forceinline__ void render_rays_backward_body(const ide3d_render_params& p, const ide3d_render_grads& gr, int sp, float* slices,
+                                                          float* cam_slices = nullptr) {
     using L = BwdLds<C, HID>;
     using PS = ParamSlice<C, HID>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -242,6 +311,7 @@ __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_par
     float* const s_hd = s_dp + 64 * L::KROW;
     float* const s_sum = s_u + L::U;
     float* const sl = PARAMS ? slices + ((int64_t)blockIdx.x * nw + wid) * PS::stride(p.seg_ch, p.feat_ch) : nullptr;
+    float* const csl = CAM ? cam_slices + ((int64_t)blockIdx.x * nw + wid) * ((int64_t)p.n * 12) : nullptr;
 
     const int S = p.steps, R = p.rays_per_img, nch = p.feat_ch + p.seg_ch;
     const int64_t total_rays = (int64_t)p.n * R;
@@ -383,6 +453,28 @@ __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_par
             // exp(-delta a) directly, not 1 - alpha: at the last sample (delta 1e10) alpha rounds to 1 while delta exp(-delta a) is finite
             const float dsigma = live ? dalpha * delta * __expf(-delta * dens) * dact : 0.f;
             float f[C], df[C];
+            // CAM only: dL/d(world point) of the lane's sample, summed over both branches.  The taps are rebuilt from the sample index where
+            // they are used, behind an opaque copy of it: merged with sample_setup's, their 60 values would stay live across the MLP loops
+            float gp[3] = {0.f, 0.f, 0.f};
+            auto sample_index = [&]() {
+                int sc = live ? s : S - 1;
+                asm volatile("" : "+v"(sc));
+                return sc;
+            };
+            auto point_grad = [&](const float* img, const float (&g)[C]) {
+                const int sc = sample_index();
+                float wx, wy, wz;
+                ray_world_point(p, n, r, p.z_lin[sc], p.jitter ? p.jitter[ray * S + sc] : 0.5f, zstep, wx, wy, wz);
+                Tap2 t2[3]; TapAddr a2[3];
+                triplane_taps(wx, wy, wz, p.W, p.H, t2);
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) a2[pl] = tap_addr(t2[pl], p.W, p.H, sH, sW);
+                const TapFrac fr[3] = {make_tap_frac(wx, wy, p.W, p.H), make_tap_frac(wy, wz, p.W, p.H), make_tap_frac(wx, wz, p.W, p.H)};
+                add_point_grad<C>(img, t2, a2, fr, g, 0.5f * (float)p.W, 0.5f * (float)p.H, gp);
+                // gp is read only after both branches: left free, the dot products sink below the scatter while their loads cannot, and
+                // 12 * C loaded values stay live across it
+                asm volatile("" : "+v"(gp[0]), "+v"(gp[1]), "+v"(gp[2]));
+            };
             if constexpr (!PARAMS) {
                 gather_sample_cl<C>(geo_img, a, f);
 #pragma unroll
@@ -392,7 +484,12 @@ __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_par
                     const float dpre = fmaf(w, s_u[k], dsigma * s_gw1[k]) * sigmoid_fast(hidden_pre<C>(s_gw0, s_gb0, k, f));
                     hidden_back<C>(s_gw0, k, dpre, df);
                 }
-                scatter_sample_grads<C>(gr.grad_geo_planes + n * gr.grad_geo_stride[0], gr.grad_geo_stride, t, live, df, nlive, s_df, s_off, s_tw);
+                if constexpr (CAM) point_grad(geo_img, df);
+                if constexpr (CAM) {
+                    if (gr.grad_geo_planes)
+                        scatter_sample_grads<C>(gr.grad_geo_planes + n * gr.grad_geo_stride[0], gr.grad_geo_stride, t, live, df, nlive, s_df, s_off, s_tw);
+                } else
+                    scatter_sample_grads<C>(gr.grad_geo_planes + n * gr.grad_geo_stride[0], gr.grad_geo_stride, t, live, df, nlive, s_df, s_off, s_tw);
 
                 gather_sample_cl<C>(tex_img, a, f);
 #pragma unroll
@@ -402,7 +499,12 @@ __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_par
                     const float dpre = w * s_u[64 + k] * sigmoid_fast(hidden_pre<C>(s_tw0, s_tb0, k, f));
                     hidden_back<C>(s_tw0, k, dpre, df);
                 }
-                scatter_sample_grads<C>(gr.grad_tex_planes + n * gr.grad_tex_stride[0], gr.grad_tex_stride, t, live, df, nlive, s_df, s_off, s_tw);
+                if constexpr (CAM) point_grad(tex_img, df);
+                if constexpr (CAM) {
+                    if (gr.grad_tex_planes)
+                        scatter_sample_grads<C>(gr.grad_tex_planes + n * gr.grad_tex_stride[0], gr.grad_tex_stride, t, live, df, nlive, s_df, s_off, s_tw);
+                } else
+                    scatter_sample_grads<C>(gr.grad_tex_planes + n * gr.grad_tex_stride[0], gr.grad_tex_stride, t, live, df, nlive, s_df, s_off, s_tw);
             } else {
                 if (live) s_x[s] = dsigma;          // x is in a register of its lane by now; param_block_sums reads dsigma of the chunk
 #pragma unroll 1
@@ -425,7 +527,7 @@ __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_par
                             const float pre = hidden_pre<C>(w0, b0, k, f);
                             const float dhid = geo ? fmaf(w, s_u[k], dsigma * s_gw1[k]) : w * s_u[64 + k];
                             const float dpre = dhid * sigmoid_fast(pre);
-                            if (gplanes) hidden_back<C>(w0, k, dpre, df);
+                            if (CAM || gplanes) hidden_back<C>(w0, k, dpre, df);
                             s_dp[lane * L::KROW + kk] = dpre;
                             s_hd[lane * L::KROW + kk] = softplus_fast(pre);
                         }
@@ -434,11 +536,25 @@ __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_par
                                             sl + (geo ? PS::GB0 : PS::TB0) + kb, s_sum + br * 64 + kb, geo ? s_sum + 128 + kb : nullptr);
                         wave_lds_sync();
                     }
+                    if constexpr (CAM) point_grad(geo ? geo_img : tex_img, df);
                     if (gplanes) {
                         const int64_t* gs = geo ? gr.grad_geo_stride : gr.grad_tex_stride;
                         scatter_sample_grads<C>(gplanes + n * gs[0], gs, t, live, df, nlive, s_df, s_off, s_tw);
                     }
                 }
+            }
+            if constexpr (CAM) {
+                // ---- camera: dL/dM[r][c] += gp_r q_c (c < 3), dL/dM[r][3] += gp_r, summed over the chunk, into the image's 12 numbers ----
+                const int sc = sample_index();
+                float cq[3], mine = 0.f;
+                ray_camera_point(p, r, p.z_lin[sc], p.jitter ? p.jitter[ray * S + sc] : 0.5f, zstep, cq[0], cq[1], cq[2]);
+#pragma unroll
+                for (int i = 0; i < 12; ++i) {
+                    const float g_r = live ? gp[i >> 2] : 0.f;
+                    const float v = wave_sum((i & 3) < 3 ? g_r * cq[i & 3] : g_r);
+                    if (lane == i) mine = v;
+                }
+                if (lane < 12) csl[(int64_t)n * 12 + lane] += mine;
             }
         }
         wave_lds_sync();
@@ -485,6 +601,12 @@ render_rays_backward_params_kernel(ide3d_render_params p, ide3d_render_grads gr,
     render_rays_backward_body<C, HID, true>(p, gr, sp, slices);
 }
 
+template <int C, int HID, bool PARAMS>
+__global__ void __launch_bounds__(512)
+render_rays_backward_camera_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp, float* slices, float* cam_slices) {
+    render_rays_backward_body<C, HID, PARAMS, true>(p, gr, sp, slices, cam_slices);
+}
+
 // Adds the slices in a fixed order: thread (element e, group g) sums slices g, g + 8, ..., then group 0 adds the 8 partial sums.
 struct ParamOut {
     float* dst[8];
@@ -511,6 +633,28 @@ reduce_param_slices_kernel(const float* __restrict__ slices, int nslices, int st
         for (int q = 1; q < 8; ++q)
             if (e >= out.end[q - 1]) { d = out.dst[q]; first = out.end[q - 1]; }
         d[e - first] = t;
+    }
+}
+
+// The camera sums: slices [nslices][n * 12] -> grad_cam2world [n, 4, 4], the same fixed order (group g sums slices g, g + 8, ..., group 0
+// adds the 8 partial sums); the last row is written as zero.
+__global__ void __launch_bounds__(512)
+reduce_camera_slices_kernel(const float* __restrict__ slices, int nslices, int total, float* __restrict__ out) {
+    __shared__ float part[8][64];
+    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int e = blockIdx.x * 64 + lane;               // (image, row, column) = (e / 12, e % 12 / 4, e % 4)
+    float sum = 0.f;
+    if (e < total)
+        for (int i = g; i < nslices; i += 8) sum += slices[(int64_t)i * total + e];
+    part[g][lane] = sum;
+    __syncthreads();
+    if (g == 0 && e < total) {
+        float t = part[0][lane];
+#pragma unroll
+        for (int q = 1; q < 8; ++q) t += part[q][lane];
+        const int img = e / 12, k = e - img * 12;
+        out[img * 16 + k] = t;
+        if (k < 4) out[img * 16 + 12 + k] = 0.f;
     }
 }
 
@@ -589,6 +733,64 @@ static int launch_render_backward_params(const ide3d_render_params& p, const ide
     return IDE3D_OK;
 }
 
+// One slice [n][12] per wave of whichever form launches (with and without the decoder sums the plans may differ in waves per workgroup).
+template <int C, int HID>
+static int64_t camera_workspace_bytes(const ide3d_render_params& p) {
+    const BwdPlan a = plan_render_backward<C, HID, false>(p), b = plan_render_backward<C, HID, true>(p);
+    if (!a.nw) return 0;
+    const int64_t waves = std::max(a.nblk * a.nw, b.nblk * b.nw);
+    return waves * p.n * 12 * (int64_t)sizeof(float);
+}
+
+template <int C, int HID, bool PARAMS>
+static int launch_render_backward_camera(const ide3d_render_params& p, const ide3d_render_grads& g, const ide3d_render_param_grads* q,
+                                         const ide3d_render_camera_grads& c, hipStream_t st) {
+    using PS = ParamSlice<C, HID>;
+    const BwdPlan pl = plan_render_backward<C, HID, PARAMS>(p);
+    if (!pl.nw) {
+        set_error("render_rays_backward_camera: %d steps per ray need %zu bytes of LDS per workgroup (at most 160 KiB)", p.steps, pl.lds_bytes);
+        return IDE3D_ENOKERNEL;
+    }
+    const int64_t nslices = pl.nblk * pl.nw, cam_floats = (int64_t)p.n * 12;
+    const int64_t cam_need = camera_workspace_bytes<C, HID>(p);
+    IDE3D_CHECK_ARG(cam_floats < 0x7fffffffLL, "render_rays_backward_camera: too many images");
+    IDE3D_CHECK_ARG(c.workspace != nullptr && c.workspace_bytes >= cam_need && (reinterpret_cast<uintptr_t>(c.workspace) & 15) == 0,
+                    "render_rays_backward_camera: camera workspace of %lld bytes (16-byte aligned) required, got %lld", (long long)cam_need,
+                    (long long)c.workspace_bytes);
+    float* cam_slices = static_cast<float*>(c.workspace);
+    float* slices = nullptr;
+    if (PARAMS) {
+        const int64_t need = param_workspace_bytes<C, HID>(p);
+        IDE3D_CHECK_ARG(q->workspace != nullptr && q->workspace_bytes >= need && (reinterpret_cast<uintptr_t>(q->workspace) & 15) == 0,
+                        "render_rays_backward_camera: workspace of %lld bytes (16-byte aligned) required, got %lld", (long long)need,
+                        (long long)q->workspace_bytes);
+        slices = static_cast<float*>(q->workspace);
+        if (hipMemsetAsync(slices, 0, (size_t)need, st) != hipSuccess) { set_error("render_rays_backward_camera: hipMemsetAsync failed"); return IDE3D_ELAUNCH; }
+    }
+    if (hipMemsetAsync(cam_slices, 0, (size_t)(nslices * cam_floats) * sizeof(float), st) != hipSuccess) {
+        set_error("render_rays_backward_camera: hipMemsetAsync failed");
+        return IDE3D_ELAUNCH;
+    }
+    auto kern = render_rays_backward_camera_kernel<C, HID, PARAMS>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.nblk), dim3(64 * pl.nw), pl.lds_bytes, st, p, g, pl.sp, slices, cam_slices);
+    IDE3D_CHECK_LAUNCH("render_rays_backward_camera");
+    if (PARAMS) {
+        ParamOut out;
+        float* const dst[8] = {q->grad_geo_w0, q->grad_tex_w0, q->grad_geo_b0, q->grad_tex_b0, q->grad_geo_w1, q->grad_tex_w1, q->grad_geo_b1, q->grad_tex_b1};
+        const int end[8] = {PS::TW0, PS::GB0, PS::TB0, PS::GW1, PS::tw1(p.seg_ch), PS::gb1(p.seg_ch, p.feat_ch), PS::tb1(p.seg_ch, p.feat_ch),
+                            PS::total(p.seg_ch, p.feat_ch)};
+        for (int i = 0; i < 8; ++i) { out.dst[i] = dst[i]; out.end[i] = end[i]; }
+        hipLaunchKernelGGL(reduce_param_slices_kernel, dim3((unsigned)cdiv64(out.end[7], 64)), dim3(512), 0, st, slices, (int)nslices,
+                           PS::stride(p.seg_ch, p.feat_ch), out);
+        IDE3D_CHECK_LAUNCH("render_rays_backward_camera (slice sums)");
+    }
+    hipLaunchKernelGGL(reduce_camera_slices_kernel, dim3((unsigned)cdiv64(cam_floats, 64)), dim3(512), 0, st, cam_slices, (int)nslices,
+                       (int)cam_floats, c.grad_cam2world);
+    IDE3D_CHECK_LAUNCH("render_rays_backward_camera (camera sums)");
+    return IDE3D_OK;
+}
+
 static bool grads_fit(const ide3d_render_params& p, const ide3d_render_grads& g) {
     auto ok = [&](const int64_t* s) {
         return s[1] == 1 && s[2] >= 0 && s[3] >= 0 && (s[2] * (p.H - 1) + s[3] * (p.W - 1) + 3 * p.C) < 0x7fffffffLL;
@@ -648,5 +850,41 @@ extern "C" int ide3d_render_rays_backward_params(const ide3d_render_params* pp, 
     if (p.C == 32 && p.hidden == 64) return launch_render_backward_params<32, 64>(p, g, q, st);
     if (p.C == 16 && p.hidden == 32) return launch_render_backward_params<16, 32>(p, g, q, st);
     set_error("render_rays_backward_params: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
+    return IDE3D_ENOKERNEL;
+}
+
+extern "C" int64_t ide3d_render_camera_grad_workspace_bytes(const ide3d_render_params* pp) {
+    using namespace ide3d;
+    if (pp == nullptr || pp->n <= 0 || pp->rays_per_img <= 0 || pp->steps <= 0) return 0;
+    if (pp->C == 32 && pp->hidden == 64) return camera_workspace_bytes<32, 64>(*pp);
+    if (pp->C == 16 && pp->hidden == 32) return camera_workspace_bytes<16, 32>(*pp);
+    return 0;
+}
+
+extern "C" int ide3d_render_rays_backward_camera(const ide3d_render_params* pp, const ide3d_render_grads* gg, const ide3d_render_param_grads* qq,
+                                                 const ide3d_render_camera_grads* cc, void* stream) {
+    using namespace ide3d;
+    IDE3D_CHECK_ARG(pp != nullptr && gg != nullptr, "render_rays_backward_camera: null params");
+    IDE3D_CHECK_ARG(qq != nullptr || cc != nullptr || gg->grad_tex_planes || gg->grad_geo_planes, "render_rays_backward_camera: no gradient requested");
+    if (cc == nullptr) return qq ? ide3d_render_rays_backward_params(pp, gg, qq, stream) : ide3d_render_rays_backward(pp, gg, stream);
+    const ide3d_render_params& p = *pp;
+    const ide3d_render_grads& g = *gg;
+    int rc = check_render_params(p, "render_rays_backward_camera", false);
+    if (rc) return rc;
+    IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world, "render_rays_backward_camera: null ray pointer");
+    IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "render_rays_backward_camera: bad ray shape");
+    IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "render_rays_backward_camera: Need to choose clamp mode");
+    IDE3D_CHECK_ARG(cc->grad_cam2world != nullptr, "render_rays_backward_camera: null camera-gradient output");
+    IDE3D_CHECK_ARG(!qq || (qq->grad_geo_w0 && qq->grad_geo_b0 && qq->grad_geo_w1 && qq->grad_geo_b1 && qq->grad_tex_w0 && qq->grad_tex_b0 &&
+                            qq->grad_tex_w1 && qq->grad_tex_b1), "render_rays_backward_camera: null parameter-gradient output");
+    if (p.last_back) { set_error("render_rays_backward_camera: last_back is not fused; use the step-wise ops"); return IDE3D_ENOKERNEL; }
+    if (!planes_fast(p)) { set_error("render_rays_backward_camera: tri-planes must be channels_last, 16-byte aligned"); return IDE3D_ENOKERNEL; }
+    if (!grads_fit(p, g)) { set_error("render_rays_backward_camera: gradient buffers must be channels_last (channel stride 1)"); return IDE3D_ENOKERNEL; }
+    hipStream_t st = (hipStream_t)stream;
+    if (p.C == 32 && p.hidden == 64)
+        return qq ? launch_render_backward_camera<32, 64, true>(p, g, qq, *cc, st) : launch_render_backward_camera<32, 64, false>(p, g, qq, *cc, st);
+    if (p.C == 16 && p.hidden == 32)
+        return qq ? launch_render_backward_camera<16, 32, true>(p, g, qq, *cc, st) : launch_render_backward_camera<16, 32, false>(p, g, qq, *cc, st);
+    set_error("render_rays_backward_camera: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
     return IDE3D_ENOKERNEL;
 }

@@ -21,8 +21,24 @@ __device__ __forceinline__ float ray_sample_depth(const ide3d_render_params& p, 
     return p.jitter ? __fadd_rn(z, __fmul_rn(__fsub_rn(p.jitter[ray * p.steps + s], 0.5f), zstep)) : z;
 }
 
+// Camera-space point of the sample at linear depth zl with jitter draw jl on ray r: direction times depth, then the jitter offset,
+// rounded like the reference's fp32 tensor ops (get_initial_rays_trig, perturb_points).  What ray_world_point sends through cam2world;
+// the backward's camera gradient needs it on its own.
+__device__ __forceinline__ void ray_camera_point(const ide3d_render_params& p, int r, float zl, float jl, float zstep,
+                                                 float& px, float& py, float& pz) {
+    const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];
+    px = __fmul_rn(dx, zl); py = __fmul_rn(dy, zl); pz = __fmul_rn(dz, zl);
+    if (p.jitter) {
+        const float off = __fmul_rn(__fsub_rn(jl, 0.5f), zstep);
+        px = __fadd_rn(px, __fmul_rn(off, dx));
+        py = __fadd_rn(py, __fmul_rn(off, dy));
+        pz = __fadd_rn(pz, __fmul_rn(off, dz));
+    }
+}
+
 // World point of the sample at linear depth zl with jitter draw jl on ray r of image n: camera space -> jitter -> world, rounded
-// like the reference's fp32 tensor ops (get_initial_rays_trig, perturb_points, transform_sampled_points).
+// like the reference's fp32 tensor ops (get_initial_rays_trig, perturb_points, transform_sampled_points).  The camera-space part is
+// ray_camera_point's, written out (the forward's and the backward's instruction streams are pinned).
 __device__ __forceinline__ void ray_world_point(const ide3d_render_params& p, int n, int r, float zl, float jl, float zstep,
                                                 float& wx, float& wy, float& wz) {
     const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];

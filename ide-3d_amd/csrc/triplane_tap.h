@@ -50,6 +50,23 @@ __device__ __forceinline__ Tap2 make_tap(float cx, float cy, int W, int H) {
     return t;
 }
 
+// The per-axis factors of make_tap's weights (w00 = ax * ay, w01 = bx * ay, w10 = ax * by, w11 = bx * by), formed by the same
+// operations: bx / by are the fractional parts, ax / ay one minus them.  The derivative of the blend with respect to the tap position
+// needs them one axis at a time (raymarch_bwd.hip, camera gradient).
+struct TapFrac {
+    float ax, bx, ay, by;
+};
+
+__device__ __forceinline__ TapFrac make_tap_frac(float cx, float cy, int W, int H) {
+    TapFrac f;
+    const float u = unnormalize(cx, W), v = unnormalize(cy, H);
+    const float fu = floorf(u), fv = floorf(v);
+    const float x1 = __fadd_rn(fu, 1.0f), y1 = __fadd_rn(fv, 1.0f);
+    f.ax = __fsub_rn(x1, u); f.bx = __fsub_rn(u, fu);
+    f.ay = __fsub_rn(y1, v); f.by = __fsub_rn(v, fv);
+    return f;
+}
+
 // Clamped offsets + masked weights.  sH / sW are element strides (they fit 32 bits: checked on the host).
 __device__ __forceinline__ TapAddr tap_addr(const Tap2& t, int W, int H, int sH, int sW) {
     TapAddr a;

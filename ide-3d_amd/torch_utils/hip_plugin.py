@@ -115,6 +115,11 @@ class _RenderParamGrads(ctypes.Structure):
     ]
 
 
+class _RenderCameraGrads(ctypes.Structure):
+    """ide3d_render_camera_grads (include/ide3d_hip.h): the camera gradient of ide3d_render_rays_backward_camera."""
+    _fields_ = [('grad_cam2world', ctypes.c_void_p), ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_int64)]
+
+
 class _Lattice(ctypes.Structure):
     _fields_ = [('n', ctypes.c_int32), ('voxel_size', ctypes.c_float), ('corner', ctypes.c_float * 3), ('scale', ctypes.c_float)]
 
@@ -323,6 +328,9 @@ def load():
             'ide3d_render_rays_backward': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_RenderGrads), vp],
             'ide3d_render_param_grad_workspace_bytes': [ctypes.POINTER(_RenderParams)],
             'ide3d_render_rays_backward_params': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_RenderGrads), ctypes.POINTER(_RenderParamGrads), vp],
+            'ide3d_render_camera_grad_workspace_bytes': [ctypes.POINTER(_RenderParams)],
+            'ide3d_render_rays_backward_camera': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_RenderGrads), ctypes.POINTER(_RenderParamGrads),
+                                                  ctypes.POINTER(_RenderCameraGrads), vp],
             'ide3d_sample_voxel': [ctypes.POINTER(_RenderParams), vp, i64, vp, vp, ctypes.c_int, vp],
             'ide3d_lattice_points': [ctypes.POINTER(_Lattice), i64, i64, vp, vp],
             'ide3d_density_lattice': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_Lattice), i64, i64, vp, vp],
@@ -385,6 +393,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_bias_noise_grad', 'ide3d_render_param_grad_workspace_bytes', 'ide3d_render_rays_backward_params',
     'ide3d_noise_reg_workspace_bytes', 'ide3d_noise_reg_levels', 'ide3d_noise_reg', 'ide3d_noise_reg_backward',
     'ide3d_noise_normalize_workspace_bytes', 'ide3d_noise_normalize',
+    'ide3d_render_camera_grad_workspace_bytes', 'ide3d_render_rays_backward_camera',
 )
 
 
@@ -858,7 +867,7 @@ class TriplanePlugin:
 
 
 class VolumeRenderPlugin:
-    _ws = _Workspaces()          # (bytes, device index, launch domain) -> the per-wave partial sums of render_rays_backward_params
+    _ws = _Workspaces()          # (kind, bytes, device index, launch domain) -> the per-wave partial sums of render_rays_backward_params / _camera
 
     @staticmethod
     def composite(rgb_sigma, z_vals, dir_norm, noise, clamp_mode, last_back, white_back, max_depth, fill_mode,
@@ -1059,6 +1068,63 @@ class VolumeRenderPlugin:
             return None
         _check(rc, 'render_rays_backward_params')
         return dtex, dgeo, grads
+
+    @staticmethod
+    def render_rays_backward_camera(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_mode, last_back,
+                                    white_back, max_depth, grad_feat, grad_depth, grad_wsum, plane_grads=True, param_grads=False):
+        """The backward of `render_rays` with the gradient of the camera pose (ide3d_render_rays_backward_camera) -> (dL/dtex_planes | None,
+        dL/dgeo_planes | None, {key of mlp: gradient} | None, dL/dcam2world [n, 4, 4] with a zero last row); None when the library has no
+        kernel for the configuration.  `plane_grads=False`: no plane buffer is allocated, the tap scatter is skipped; `param_grads=True`:
+        the eight decoder gradients as well.  The camera gradient (like the decoder's) is summed in a fixed order: bit-reproducible from
+        run to run, and the same whatever else the call computes.  Both workspaces come from this plugin's cache."""
+        dev = tex_planes.device
+        p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
+                                                 clamp_mode, last_back, white_back, max_depth)
+        n, R, nch = p.n, p.rays_per_img, p.feat_ch + p.seg_ch
+        g = _RenderGrads()
+        for name, t, shape in (('grad_feat', grad_feat, (n, nch, R)), ('grad_depth', grad_depth, (n, R)), ('grad_wsum', grad_wsum, (n, R))):
+            if t is not None:
+                _require(t.numel() == math.prod(shape), f'render_rays_backward_camera: {name} must hold {list(shape)} values, got {list(t.shape)}')
+                t = t.to(device=dev, dtype=torch.float32).contiguous()
+                keep.append(t)
+                setattr(g, name, t.data_ptr())
+        dtex = dgeo = None
+        if plane_grads:
+            dtex = torch.empty(tex_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
+            dgeo = torch.empty(geo_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
+            g.grad_tex_planes, g.grad_geo_planes = dtex.data_ptr(), dgeo.data_ptr()
+            g.grad_tex_stride, g.grad_geo_stride = _i64x4(dtex.stride()), _i64x4(dgeo.stride())
+        lib = load()
+
+        def workspace(kind, nbytes):
+            key = (kind, nbytes, dev.index, _ws_domain(dev))
+            return VolumeRenderPlugin._ws.entry(key, lambda: torch.empty([nbytes // 4], dtype=torch.float32, device=dev))[0]
+
+        cbytes = lib.ide3d_render_camera_grad_workspace_bytes(ctypes.byref(p))
+        if cbytes <= 0:        # no compiled form for (C, hidden), or too many steps: what the launch would answer with IDE3D_ENOKERNEL
+            return None
+        c = _RenderCameraGrads()
+        dcam = torch.empty([n, 4, 4], dtype=torch.float32, device=dev)
+        cws = workspace('render_camera_grad', cbytes)
+        c.grad_cam2world, c.workspace, c.workspace_bytes = dcam.data_ptr(), cws.data_ptr(), cbytes
+        q, grads = None, None
+        if param_grads:
+            nbytes = lib.ide3d_render_param_grad_workspace_bytes(ctypes.byref(p))
+            if nbytes <= 0:
+                return None
+            q = _RenderParamGrads()
+            grads = {k: torch.empty_like(mlp[k]) for k in VolumeRenderPlugin.MLP_KEYS}
+            for k, t in grads.items():
+                setattr(q, 'grad_' + k, t.data_ptr())
+            ws = workspace('render_param_grad', nbytes)
+            q.workspace, q.workspace_bytes = ws.data_ptr(), nbytes
+        with _dev_guard(dev):
+            rc = lib.ide3d_render_rays_backward_camera(ctypes.byref(p), ctypes.byref(g), ctypes.byref(q) if q is not None else None,
+                                                       ctypes.byref(c), _stream(tex_planes))
+        if rc == -2:        # IDE3D_ENOKERNEL
+            return None
+        _check(rc, 'render_rays_backward_camera')
+        return dtex, dgeo, grads, dcam
 
     @staticmethod
     def sample_voxel(tex_planes, geo_planes, mlp, pts, sigma_only=False):

@@ -222,7 +222,7 @@ def _run_locked(cache, module, impl, ws, c, render_params, noise_mode, flags, fo
         """None when a replay is what the eager call would compute, else the reason it is not."""
         if hooked or _global_hooks():
             return 'forward hook'
-        if torch.is_grad_enabled() and (requires_grad or ws.requires_grad):
+        if torch.is_grad_enabled() and (requires_grad or ws.requires_grad or (c is not None and c.requires_grad)):
             return 'autograd'
         if cache.stamp != stamp:
             return 'parameters changed'
@@ -231,7 +231,7 @@ def _run_locked(cache, module, impl, ws, c, render_params, noise_mode, flags, fo
     ent = cache.entries.get(sig)
     # cheap rejections BEFORE the optimistic replay: with autograd the static input would join the caller's graph, and a hook on the root
     # (the common place) needs no tree walk to be seen
-    replayable = not (torch.is_grad_enabled() and ws.requires_grad) and not module._forward_hooks and not module._forward_pre_hooks and not _global_hooks()
+    replayable = not (torch.is_grad_enabled() and (ws.requires_grad or (c is not None and c.requires_grad))) and not module._forward_hooks and not module._forward_pre_hooks and not _global_hooks()
     if ent is not None and replayable and ent.untouched():
         # Optimistic replay: the launch goes out first, the ~0.1 ms walk over the module tree (hooks, requires_grad, every parameter's
         # version and address) runs while the GPU works, and the copies are handed out only if the walk finds nothing.  In the drivers'

@@ -114,7 +114,7 @@ class Projector:
 
     def __init__(self, G, target, c, *, num_steps=1000, w_avg_samples=10000, initial_learning_rate=0.01, initial_noise_factor=0.05,
                  lr_rampdown_length=0.25, lr_rampup_length=0.05, noise_ramp_length=0.75, regularize_noise_weight=1e5,
-                 distance=None, initial_w=None, device=None):
+                 distance=None, initial_w=None, device=None, camera_lr=None, camera_project=None):
         assert tuple(target.shape) == (G.img_channels, G.img_resolution, G.img_resolution)
         if device is None:
             device = next(G.parameters()).device
@@ -142,6 +142,12 @@ class Projector:
         for n in self.maps:
             n.requires_grad_(True)
         self.optimizer = torch.optim.Adam([self.w_opt] + self.maps, betas=(0.9, 0.999), lr=initial_learning_rate)
+        self.camera_lr, self.camera_project, self.cam_opt = camera_lr, camera_project, None
+        if camera_lr is not None:
+            # the 16 extrinsic entries of c train in a parameter group of their own; the 9 intrinsics stay what the caller passed
+            self.cam_opt = c[:, :16].detach().clone().requires_grad_(True)
+            self.intrinsics = c[:, 16:].detach()
+            self.optimizer.add_param_group(dict(params=[self.cam_opt], lr=camera_lr))
         self.distance = distance if distance is not None else l2_distance(target[None].to(device=device, dtype=torch.float32))
 
     def step(self, step):
@@ -151,6 +157,8 @@ class Projector:
         lr_ramp = min(1.0, (1.0 - t) / self.lr_rampdown_length)
         lr_ramp = 0.5 - 0.5 * np.cos(lr_ramp * np.pi)
         lr_ramp = lr_ramp * min(1.0, t / self.lr_rampup_length)
+        if self.cam_opt is not None:
+            return self._step_with_camera(w_noise_scale, lr_ramp)
         for group in self.optimizer.param_groups:
             group['lr'] = self.initial_learning_rate * lr_ramp
 
@@ -167,6 +175,35 @@ class Projector:
         normalize_noise_(self.maps)
         return loss.detach()
 
+    def camera(self):
+        """The camera label [1, 25] as it stands: the refined extrinsics beside the caller's intrinsics (`c` itself without `camera_lr`)."""
+        return self.c if self.cam_opt is None else torch.cat([self.cam_opt.detach(), self.intrinsics], 1)
+
+    def _step_with_camera(self, w_noise_scale, lr_ramp):
+        """`step` with the pose as a second parameter group (learning rate `camera_lr` under the same ramp).  The renderer's camera switch
+        (triplane.fused_render_camera_grad) is on for the pass and restored after it."""
+        from training import triplane
+        self.optimizer.param_groups[0]['lr'] = self.initial_learning_rate * lr_ramp
+        self.optimizer.param_groups[1]['lr'] = self.camera_lr * lr_ramp
+        ws = self.w_opt + torch.randn_like(self.w_opt) * w_noise_scale
+        if ws.shape[1] == 1:
+            ws = ws.repeat([1, self.num_ws, 1])
+        old, triplane.fused_render_camera_grad = triplane.fused_render_camera_grad, True
+        try:
+            images = self.G.synthesis(ws, c=torch.cat([self.cam_opt, self.intrinsics], 1), noise_mode='const', force_fp32=True)
+            images = (images + 1) * (255 / 2)
+            loss = self.distance(images) + self.regularize_noise_weight * noise_regularization(self.maps)
+            self.optimizer.zero_grad(set_to_none=True)
+            loss.backward()
+        finally:
+            triplane.fused_render_camera_grad = old
+        self.optimizer.step()
+        normalize_noise_(self.maps)
+        if self.camera_project is not None:
+            with torch.no_grad():
+                self.cam_opt.copy_(self.camera_project(self.cam_opt.detach().clone()))
+        return loss.detach()
+
     def pivot(self):
         w = self.w_opt.detach()
         return w.repeat([1, self.num_ws, 1]) if w.shape[1] == 1 else w.clone()
@@ -174,7 +211,7 @@ class Projector:
 
 def project(G, target, c, *, num_steps=1000, w_avg_samples=10000, initial_learning_rate=0.01, initial_noise_factor=0.05,
             lr_rampdown_length=0.25, lr_rampup_length=0.05, noise_ramp_length=0.75, regularize_noise_weight=1e5,
-            distance=None, initial_w=None, device=None, return_info=False):
+            distance=None, initial_w=None, device=None, return_info=False, camera_lr=None, camera_project=None):
     """Project `target` ([C, H, W], 0..255, the generator's output resolution) seen from camera label `c` ([1, 25]) into W with trainable
     noise maps: the schedule of the reference's w_projector_ide3d.py:50-145.  Returns the pivot [1, num_ws, w_dim].
 
@@ -197,12 +234,23 @@ def project(G, target, c, *, num_steps=1000, w_avg_samples=10000, initial_learni
     The other projectors of the reference differ only in the latent: an `initial_w` of shape [1, num_ws, w_dim] is optimised per layer
     (w_plus_projector*.py); for the join-view variant pass a `distance` that renders and compares the second view itself.
 
-    return_info: also return a dict with `losses` (one float per step), `noise_maps` (the copy's maps after the last step) and `w_std`."""
+    camera_lr: None (default) = `c` is fixed, the reference's schedule statement for statement.  A number = the 16 extrinsic entries of `c`
+    (the flattened cam2world) are refined beside w: a second Adam parameter group with this learning rate under the same ramp; the 9
+    intrinsics stay fixed.  On the GPU the renderer's gradient for the pose is ide3d_render_rays_backward_camera
+    (`triplane.fused_render_camera_grad`, set for the duration of each pass and restored).  All 16 entries move freely: the rotation block
+    is NOT re-orthonormalised and the last row is not pinned (its gradient is zero, so it stays).  `camera_project`: callable([1, 16]) ->
+    [1, 16] applied under no_grad after every step (default: identity), e.g. a projection of the 3 x 3 block onto the nearest rotation.
+
+    return_info: also return a dict with `losses` (one float per step), `noise_maps` (the copy's maps after the last step) and `w_std`;
+    with `camera_lr`, also `c` (the refined camera label [1, 25])."""
     p = Projector(G, target, c, num_steps=num_steps, w_avg_samples=w_avg_samples, initial_learning_rate=initial_learning_rate,
                   initial_noise_factor=initial_noise_factor, lr_rampdown_length=lr_rampdown_length, lr_rampup_length=lr_rampup_length,
                   noise_ramp_length=noise_ramp_length, regularize_noise_weight=regularize_noise_weight, distance=distance,
-                  initial_w=initial_w, device=device)
+                  initial_w=initial_w, device=device, camera_lr=camera_lr, camera_project=camera_project)
     losses = [p.step(step) for step in range(num_steps)]
     if return_info:
-        return p.pivot(), dict(losses=[float(v) for v in losses], noise_maps=[n.detach() for n in p.maps], w_std=p.w_std)
+        info = dict(losses=[float(v) for v in losses], noise_maps=[n.detach() for n in p.maps], w_std=p.w_std)
+        if camera_lr is not None:
+            info['c'] = p.camera()
+        return p.pivot(), info
     return p.pivot()

@@ -50,6 +50,11 @@ fused_render_grad = True
 # networks.hip_param_grad, and set next to it by a coach before its tuning loop; False = a trainable decoder renders step-wise.
 fused_render_param_grad = False
 
+# Also take that path when the camera pose needs a gradient (pose refinement beside w in a projector, training/projection.py's
+# `camera_lr`): its backward then is ide3d_render_rays_backward_camera, which returns dL/dcam2world beside whatever else the call needs.
+# Opt-in; False = a cam2world that requires grad renders step-wise.
+fused_render_camera_grad = False
+
 
 @dataclasses.dataclass
 class GeneratorSpec:
@@ -198,26 +203,32 @@ class TriplaneRenderer(torch.nn.Module):
 
     def _fused_grad_ok(self, img_v, seg_v, cam2world, jitter, sigma_noise):
         """The fused renderer with its backward kernel: fp32 CUDA planes of which at least one needs a gradient, and nothing else it
-        reads (decoder parameters, camera, jitter, density noise) does — the backward kernel differentiates the planes only."""
+        reads (decoder parameters, camera, jitter, density noise) does — the backward kernel differentiates the planes only.  Under
+        `fused_render_camera_grad` the camera may need one too, and is then reason enough."""
         if fused_render_param_grad:
             return self._fused_param_grad_ok(img_v, seg_v, cam2world, jitter, sigma_noise)
-        if not torch.is_grad_enabled() or not (img_v.requires_grad or seg_v.requires_grad):
+        cam_grad = fused_render_camera_grad and cam2world.requires_grad
+        if not torch.is_grad_enabled() or not (img_v.requires_grad or seg_v.requires_grad or cam_grad):
             return False
         if any(t.device.type != 'cuda' or t.dtype != torch.float32 for t in (img_v, seg_v, cam2world)):
             return False
-        if cam2world.requires_grad or any(p.requires_grad for p in self.decoder.parameters()):
+        if (cam2world.requires_grad and not cam_grad) or any(p.requires_grad for p in self.decoder.parameters()):
             return False
         return not any(t is not None and t.requires_grad for t in (jitter, sigma_noise))
 
     def _fused_param_grad_ok(self, img_v, seg_v, cam2world, jitter, sigma_noise):
         """`_fused_grad_ok` under `fused_render_param_grad`: the decoder's parameters may need a gradient too (fp32 CUDA, all of them), and
-        one of them needing it is reason enough; the camera, the jitter and the density noise still may not."""
+        one of them needing it is reason enough; the jitter and the density noise still may not, nor the camera unless
+        `fused_render_camera_grad` is on."""
         params = list(self.decoder.parameters())
-        if not torch.is_grad_enabled() or not (img_v.requires_grad or seg_v.requires_grad or any(p.requires_grad for p in params)):
+        cam_grad = fused_render_camera_grad and cam2world.requires_grad
+        if not torch.is_grad_enabled() or not (img_v.requires_grad or seg_v.requires_grad or cam_grad or any(p.requires_grad for p in params)):
             return False
         if any(t.device.type != 'cuda' or t.dtype != torch.float32 for t in (img_v, seg_v, cam2world, *params)):
             return False
-        return not any(t is not None and t.requires_grad for t in (cam2world, jitter, sigma_noise))
+        if cam2world.requires_grad and not cam_grad:
+            return False
+        return not any(t is not None and t.requires_grad for t in (jitter, sigma_noise))
 
     # -- full rendering -----------------------------------------------------------------------------------
     def forward(self, img_v, seg_v, cam2world, fov=None, num_steps=None, ray_start=None, ray_end=None, img_size=None,

@@ -346,8 +346,9 @@ class _RenderRaysFused(torch.autograd.Function):
     """`ide3d_render_rays` with a gradient for the two tri-planes (`ide3d_render_rays_backward`) and for the eight decoder tensors
     (`ide3d_render_rays_backward_params`, csrc/raymarch_bwd.hip).  The forward is the inference launch unchanged; what is saved is its
     inputs (planes, decoder weights, camera, jitter, noise), nothing per sample: the backward kernel rebuilds the samples.  The backward
-    is one call: the parameter entry point when a decoder tensor needs a gradient (without the tap scatter when no plane does), the
-    tri-plane-only one otherwise.  No gradient for the camera, the jitter or the noise."""
+    is one call: the camera entry point (`ide3d_render_rays_backward_camera`) when `cam2world` needs a gradient, else the parameter entry
+    point when a decoder tensor needs one (both without the tap scatter when no plane does), the tri-plane-only one otherwise.  No gradient
+    for the jitter or the noise."""
 
     @staticmethod
     def forward(ctx, tex_planes, geo_planes, rays_d_cam, z_lin, cam2world, jitter, sigma_noise, clamp_code, white_back, max_depth, *mlp_tensors):
@@ -358,6 +359,7 @@ class _RenderRaysFused(torch.autograd.Function):
             raise _NoFusedKernel()
         ctx.save_for_backward(tex_planes, geo_planes, *mlp_tensors)
         ctx.args = args[:5] + args[8:]
+        ctx.cam_shape = cam2world.shape
         return res
 
     @staticmethod
@@ -367,7 +369,14 @@ class _RenderRaysFused(torch.autograd.Function):
         mlp = dict(zip(_MLP_KEYS, mlp_tensors))
         a = ctx.args
         need = ctx.needs_input_grad
-        if any(need[10:]):
+        dcam = None
+        if need[4]:
+            res = _plugin.render_rays_backward_camera(*a[:5], tex_planes, geo_planes, mlp, *a[5:], grad_feat, grad_depth, grad_wsum,
+                                                      plane_grads=need[0] or need[1], param_grads=any(need[10:]))
+            if res is not None:
+                dcam = res[3].reshape(ctx.cam_shape)
+                res = res[:3] if res[2] is not None else res[:2]
+        elif any(need[10:]):
             res = _plugin.render_rays_backward_params(*a[:5], tex_planes, geo_planes, mlp, *a[5:], grad_feat, grad_depth, grad_wsum,
                                                       plane_grads=need[0] or need[1])
         else:
@@ -378,7 +387,7 @@ class _RenderRaysFused(torch.autograd.Function):
                                + hip_plugin.load().ide3d_last_error().decode('utf-8', 'replace'))
         dtex, dgeo = res[:2]
         dmlp = res[2] if len(res) > 2 else {}
-        return (dtex if need[0] else None, dgeo if need[1] else None) + (None,) * 8 + tuple(
+        return (dtex if need[0] else None, dgeo if need[1] else None, None, None, dcam) + (None,) * 5 + tuple(
             dmlp[k] if need[10 + i] else None for i, k in enumerate(_MLP_KEYS))
 
 
@@ -398,9 +407,11 @@ def render_triplane_fused(tex_planes, geo_planes, mlp, cam2world, fov, resolutio
 
     Gradients: when grad mode is on and a tri-plane or a tensor of `mlp` requires grad, the outputs are differentiable with respect to
     tex_planes, geo_planes and the eight tensors of `mlp` (one backward call: `ide3d_render_rays_backward`, or
-    `ide3d_render_rays_backward_params` when a tensor of `mlp` needs a gradient; first order only).  No gradient is returned for
-    `cam2world`, `jitter` or `sigma_noise`, whether or not they require grad: a caller that needs those must run the step-wise
-    definition (TriplaneRenderer.forward does, and it only sends a trainable decoder here under `triplane.fused_render_param_grad`).
+    `ide3d_render_rays_backward_params` when a tensor of `mlp` needs a gradient; first order only), and with respect to `cam2world` when
+    it requires grad (`ide3d_render_rays_backward_camera`, all 12 entries of the top three rows; the last row gets zero).  No gradient is
+    returned for `jitter` or `sigma_noise`, whether or not they require grad: a caller that needs those must run the step-wise
+    definition (TriplaneRenderer.forward does; it only sends a trainable decoder here under `triplane.fused_render_param_grad` and a
+    trainable camera under `triplane.fused_render_camera_grad`).
     The forward values are those of the no-grad call, bit for bit.
     """
     assert clamp_mode in ('softplus', 'relu')
@@ -413,7 +424,8 @@ def render_triplane_fused(tex_planes, geo_planes, mlp, cam2world, fov, resolutio
     if geo_planes.stride(1) != 1:
         geo_planes = geo_planes.contiguous(memory_format=torch.channels_last)
     clamp_code = 0 if clamp_mode == 'softplus' else 1
-    if torch.is_grad_enabled() and (tex_planes.requires_grad or geo_planes.requires_grad or any(mlp[k].requires_grad for k in _MLP_KEYS)):
+    if torch.is_grad_enabled() and (tex_planes.requires_grad or geo_planes.requires_grad or cam2world.requires_grad
+                                    or any(mlp[k].requires_grad for k in _MLP_KEYS)):
         try:
             res = _RenderRaysFused.apply(tex_planes, geo_planes, rays_d_cam, z_lin, cam2world, jitter, sigma_noise, clamp_code,
                                          white_back, max_depth, *(mlp[k] for k in _MLP_KEYS))

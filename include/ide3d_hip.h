@@ -343,6 +343,31 @@ int64_t ide3d_render_param_grad_workspace_bytes(const ide3d_render_params* p);
 int ide3d_render_rays_backward_params(const ide3d_render_params* p, const ide3d_render_grads* g, const ide3d_render_param_grads* q, void* stream);
 
 /*
+ * The same backward with the gradient of the camera pose: dL/dcam2world [n, 4, 4], what autograd computes through
+ * transform_sampled_points (volumetric_rendering.py:108-136) and the two grid_sample gathers (zeros padding, align_corners=False).  The
+ * outputs depend on cam2world only through the sample points p = M[:3,:3] q + M[:3,3] (q the camera-space point): with gp = dL/dp of a
+ * sample (the feature gradient of both branches dotted with the derivative of the bilinear blend of the three planes, times size / 2),
+ * dL/dM[r][c] = sum_samples gp_r q_c (c < 3), dL/dM[r][3] = sum_samples gp_r; the last row is written as zero.  All 12 entries are free:
+ * no rotation structure is assumed.  Taps outside a plane and non-finite coordinates contribute nothing, like the forward.
+ * p and g as for ide3d_render_rays_backward_params (g's plane pointers may each be NULL); q: the decoder gradients as well, or NULL;
+ * c: the camera gradient, or NULL.  Without c the call is ide3d_render_rays_backward_params (q given) or ide3d_render_rays_backward (q
+ * NULL); q NULL, c NULL and both plane pointers NULL is IDE3D_EINVAL.  grad_cam2world is WRITTEN, fp32, contiguous.  workspace:
+ * ide3d_render_camera_grad_workspace_bytes(p) bytes, 16-byte aligned, owned by this call until the stream has passed it: 12 sums per image
+ * per wave, added in a fixed order by a second launch (no atomics), so the camera gradient is bit-reproducible from run to run and equal
+ * whatever else the call computes.  IDE3D_ENOKERNEL in the cases of ide3d_render_rays_backward.  The workspace query reads n,
+ * rays_per_img, steps, C and hidden; 0 = no kernel.
+ */
+typedef struct ide3d_render_camera_grads {
+    float* grad_cam2world;      /* [n, 4, 4], written, last row zero */
+    void* workspace;
+    int64_t workspace_bytes;
+} ide3d_render_camera_grads;
+
+int64_t ide3d_render_camera_grad_workspace_bytes(const ide3d_render_params* p);
+int ide3d_render_rays_backward_camera(const ide3d_render_params* p, const ide3d_render_grads* g, const ide3d_render_param_grads* q,
+                                      const ide3d_render_camera_grads* c, void* stream);
+
+/*
  * `renderer.sample_voxel(img_v, seg_v, pts)` (call site extract_shapes.py:146): the same two
  * gathers + MLPs for arbitrary points, no compositing.  out: [n*m, feat_ch + seg_ch + 1]
  * (sigma last).  If sigma_only != 0 only out_sigma [n*m] is written (the 256^3 density-cube
