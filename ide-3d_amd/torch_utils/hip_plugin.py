@@ -257,6 +257,17 @@ class _MappingParams(ctypes.Structure):
     ]
 
 
+LPIPS_MAX_TAPS = 8          # IDE3D_LPIPS_MAX_TAPS
+
+
+class _LpipsTap(ctypes.Structure):
+    """Mirror of ide3d_lpips_tap."""
+    _fields_ = [
+        ('a', ctypes.c_void_p), ('t', ctypes.c_void_p), ('lin', ctypes.c_void_p), ('out', ctypes.c_void_p),
+        ('c', ctypes.c_int32), ('h', ctypes.c_int32), ('w', ctypes.c_int32), ('reserved', ctypes.c_int32),
+    ]
+
+
 def _hip_runtimes_mapped():
     """Paths of every libamdhip64 mapped into this process (there must be exactly one)."""
     paths = set()
@@ -353,6 +364,13 @@ def load():
             'ide3d_noise_reg_backward': [vp, ctypes.POINTER(i32), i32, vp, i64, vp, vp, vp, vp],
             'ide3d_noise_normalize_workspace_bytes': [ctypes.POINTER(i32), i32],
             'ide3d_noise_normalize': [vp, ctypes.POINTER(i32), i32, vp, i64, vp],
+            'ide3d_lpips_prep': [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp],
+            'ide3d_lpips_prep_backward': [vp, vp, vp, i32, i32, i32, i32, f32, vp],
+            'ide3d_maxpool2': [vp, vp, i64, i32, i32, vp],
+            'ide3d_lpips_stage_backward': [vp, vp, vp, vp, i64, i32, i32, vp],
+            'ide3d_lpips_head_workspace_bytes': [ctypes.POINTER(_LpipsTap), i32, i32],
+            'ide3d_lpips_head': [ctypes.POINTER(_LpipsTap), i32, i32, vp, i64, vp, vp],
+            'ide3d_lpips_head_backward': [ctypes.POINTER(_LpipsTap), i32, i32, vp, vp],
             'ide3d_set_conv_arithmetic': [i32],
             'ide3d_get_conv_arithmetic': [],
             'ide3d_frame_u8': [vp, vp, vp, i32, i32, i32, i32, vp, vp],
@@ -394,6 +412,8 @@ EXPORTED_SYMBOLS = (
     'ide3d_noise_reg_workspace_bytes', 'ide3d_noise_reg_levels', 'ide3d_noise_reg', 'ide3d_noise_reg_backward',
     'ide3d_noise_normalize_workspace_bytes', 'ide3d_noise_normalize',
     'ide3d_render_camera_grad_workspace_bytes', 'ide3d_render_rays_backward_camera',
+    'ide3d_lpips_prep', 'ide3d_lpips_prep_backward', 'ide3d_maxpool2', 'ide3d_lpips_stage_backward', 'ide3d_lpips_head_workspace_bytes',
+    'ide3d_lpips_head', 'ide3d_lpips_head_backward',
 )
 
 
@@ -1559,10 +1579,131 @@ class NoisePlugin:
         return maps
 
 
+class LpipsPlugin:
+    """The streaming passes of the VGG16 LPIPS distance and its image gradient (csrc/lpips.hip).  Every tensor is a
+    contiguous float32 CUDA tensor on one device."""
+
+    @staticmethod
+    def _f32(t, name, dev=None, shape=None):
+        _require(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and (dev is None or t.device == dev),
+                 f'lpips: {name} must be a contiguous float32 CUDA tensor on the device of the other arguments')
+        if shape is not None:
+            _require(tuple(t.shape) == tuple(shape), f'lpips: {name} must be {list(shape)}, got {list(t.shape)}')
+        return t
+
+    @staticmethod
+    def prep(x, mean, std, f=1, in_scale=1.0, in_shift=0.0):
+        """ide3d_lpips_prep: x [n, 3, H, W] -> ((f x f area mean) * in_scale + in_shift - mean) / std, [n, 3, H / f, W / f]."""
+        LpipsPlugin._f32(x, 'x')
+        _require(x.ndim == 4 and x.shape[1] == 3 and f >= 1 and x.shape[2] % f == 0 and x.shape[3] % f == 0, 'lpips prep: x [n, 3, H, W], f divides H and W')
+        mean = LpipsPlugin._f32(mean.reshape(-1), 'mean', x.device, (3,))
+        std = LpipsPlugin._f32(std.reshape(-1), 'std', x.device, (3,))
+        n, _, H, W = x.shape
+        y = torch.empty([n, 3, H // f, W // f], dtype=torch.float32, device=x.device)
+        with _dev_guard(x.device):
+            rc = load().ide3d_lpips_prep(_ptr(x), _ptr(y), _ptr(mean), _ptr(std), n, H, W, int(f), float(in_scale), float(in_shift), _stream(x))
+        _check(rc, 'lpips_prep')
+        return y
+
+    @staticmethod
+    def prep_backward(dy, std, f=1, in_scale=1.0):
+        """ide3d_lpips_prep_backward: dy [n, 3, h, w] -> dx [n, 3, h f, w f]."""
+        LpipsPlugin._f32(dy, 'dy')
+        _require(dy.ndim == 4 and dy.shape[1] == 3 and f >= 1, 'lpips prep_backward: dy [n, 3, h, w]')
+        std = LpipsPlugin._f32(std.reshape(-1), 'std', dy.device, (3,))
+        n, _, h, w = dy.shape
+        dx = torch.empty([n, 3, h * f, w * f], dtype=torch.float32, device=dy.device)
+        with _dev_guard(dy.device):
+            rc = load().ide3d_lpips_prep_backward(_ptr(dy), _ptr(dx), _ptr(std), n, h * f, w * f, int(f), float(in_scale), _stream(dy))
+        _check(rc, 'lpips_prep_backward')
+        return dx
+
+    @staticmethod
+    def maxpool2(x):
+        """ide3d_maxpool2: [n, c, h, w] -> [n, c, h // 2, w // 2], bit-equal to F.max_pool2d(x, 2)."""
+        LpipsPlugin._f32(x, 'x')
+        _require(x.ndim == 4 and x.shape[2] >= 2 and x.shape[3] >= 2, 'maxpool2: x [n, c, h, w] with h, w >= 2')
+        n, c, h, w = x.shape
+        y = torch.empty([n, c, h // 2, w // 2], dtype=torch.float32, device=x.device)
+        with _dev_guard(x.device):
+            rc = load().ide3d_maxpool2(_ptr(x), _ptr(y), n * c, h, w, _stream(x))
+        _check(rc, 'maxpool2')
+        return y
+
+    @staticmethod
+    def stage_backward(y, dpool, dtap):
+        """ide3d_lpips_stage_backward -> dz = (route(dpool) + dtap) where y > 0, else 0; dpool [n, c, h // 2, w // 2] or None."""
+        LpipsPlugin._f32(y, 'y')
+        _require(y.ndim == 4, 'lpips stage_backward: y [n, c, h, w]')
+        n, c, h, w = y.shape
+        LpipsPlugin._f32(dtap, 'dtap', y.device, y.shape)
+        if dpool is not None:
+            LpipsPlugin._f32(dpool, 'dpool', y.device, (n, c, h // 2, w // 2))
+        dz = torch.empty_like(y)
+        with _dev_guard(y.device):
+            rc = load().ide3d_lpips_stage_backward(_ptr(y), _ptr(dpool), _ptr(dtap), _ptr(dz), n * c, h, w, _stream(y))
+        _check(rc, 'lpips_stage_backward')
+        return dz
+
+    @staticmethod
+    def _taps(acts, targets, lins, outs):
+        k = len(acts)
+        _require(1 <= k <= LPIPS_MAX_TAPS, f'lpips: 1..{LPIPS_MAX_TAPS} taps')
+        dev, n = acts[0].device, acts[0].shape[0]
+        taps = (_LpipsTap * k)()
+        for i, a in enumerate(acts):
+            LpipsPlugin._f32(a, 'tap', dev)
+            _require(a.ndim == 4 and a.shape[0] == n, 'lpips: every tap must be [n, c, h, w]')
+            taps[i].a, (taps[i].c, taps[i].h, taps[i].w) = a.data_ptr(), a.shape[1:]
+            if targets is not None:
+                taps[i].t = LpipsPlugin._f32(targets[i], 'target', dev, a.shape).data_ptr()
+                taps[i].lin = LpipsPlugin._f32(lins[i], 'lin', dev, (a.shape[1],)).data_ptr()
+            if outs is not None:
+                taps[i].out = outs[i].data_ptr()
+        return taps, k, n, dev
+
+    @staticmethod
+    def normalize(acts):
+        """The normalise-only form of ide3d_lpips_head: [a / (sqrt(sum_c a^2) + 1e-10) for a in acts]."""
+        outs = [torch.empty_like(a) for a in acts]
+        taps, k, n, dev = LpipsPlugin._taps(acts, None, None, outs)
+        with _dev_guard(dev):
+            rc = load().ide3d_lpips_head(taps, k, n, None, 0, None, _stream(acts[0]))
+        _check(rc, 'lpips_head')
+        return outs
+
+    @staticmethod
+    def head(acts, targets, lins):
+        """ide3d_lpips_head -> loss [] float32: sum over taps and images of mean_{h,w} sum_c lin[c] (u - t)^2, over n.  lins: [c] each."""
+        taps, k, n, dev = LpipsPlugin._taps(acts, targets, lins, None)
+        lib = load()
+        nbytes = lib.ide3d_lpips_head_workspace_bytes(taps, k, n)
+        _require(nbytes > 0, 'lpips head: unsupported taps')
+        ws = torch.empty([nbytes // 8], dtype=torch.float64, device=dev)
+        loss = torch.empty([], dtype=torch.float32, device=dev)
+        with _dev_guard(dev):
+            rc = lib.ide3d_lpips_head(taps, k, n, _ptr(ws), nbytes, _ptr(loss), _stream(acts[0]))
+        _check(rc, 'lpips_head')
+        return loss
+
+    @staticmethod
+    def head_backward(acts, targets, lins, dloss):
+        """ide3d_lpips_head_backward -> [d loss / d a for a in acts]; dloss: a one-element float32 tensor on the device."""
+        outs = [torch.empty_like(a) for a in acts]
+        taps, k, n, dev = LpipsPlugin._taps(acts, targets, lins, outs)
+        _require(dloss.is_cuda and dloss.dtype == torch.float32 and dloss.device == dev and dloss.numel() == 1, 'lpips head_backward: dloss must be one float32 on the device')
+        dloss = dloss.contiguous()
+        with _dev_guard(dev):
+            rc = load().ide3d_lpips_head_backward(taps, k, n, _ptr(dloss), _stream(acts[0]))
+        _check(rc, 'lpips_head_backward')
+        return outs
+
+
 def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epilogue='conv', x_amax=False):
     """Host-only (works without a GPU): the kernel family, tile and grid `modconv2d` would launch for this shape -> dict of the
     ide3d_modconv_plan_info fields, `kind` as a name from PLAN_KINDS.  epilogue: 'conv' (noise, bias, lrelu, gain sqrt(2): the 3x3 layers),
-    'plain' (demodulation only: the up-sampling layers, whose FIR carries the rest) or 'head' (bias, clamp 256, linear).  x_amax: the
+    'plain' (demodulation only: the up-sampling layers, whose FIR carries the rest), 'head' (bias, clamp 256, linear), 'relu' (an unmodulated
+    convolution + bias + ReLU: the feature nets) or 'grad' (unmodulated, no epilogue: the input gradient of one).  x_amax: the
     caller passes the producer's bound on |x| (what the f16x3 arithmetic needs)."""
     p = _ModconvParams()
     p.n, p.cin, p.cout, p.h, p.w_, p.k, p.mode = n, cin, cout, h, w, k, mode
@@ -1570,9 +1711,13 @@ def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epil
     p.w_batch_stride = cout * cin * k * k if per_image else 0
     dummy = 256                                  # non-null, 16-byte aligned, never dereferenced
     p.x = p.w = p.y = dummy
-    if not per_image:
+    if not per_image and epilogue not in ('relu', 'grad'):
         p.styles = p.dcoefs = dummy
-    if epilogue == 'conv':
+    if epilogue == 'relu':               # an unmodulated convolution + bias + ReLU (training/lpips.py, training/face_parsing.py)
+        p.bias, p.act, p.alpha, p.gain, p.clamp = dummy, 3, 0.0, 1.0, -1.0
+    elif epilogue == 'grad':             # the input gradient of one: unmodulated, no epilogue
+        p.act, p.gain, p.clamp = 1, 1.0, -1.0
+    elif epilogue == 'conv':
         p.noise, p.bias, p.noise_strength, p.act, p.alpha, p.gain, p.clamp = dummy, dummy, 1.0, 3, 0.2, math.sqrt(2.0), -1.0
     elif epilogue == 'plain':
         p.act, p.gain, p.clamp = 1, 1.0, -1.0
@@ -2019,4 +2164,5 @@ PLUGINS = {
     'style_plugin': StylePlugin,
     'resample_plugin': ResamplePlugin,
     'mapping_plugin': MappingPlugin,
+    'lpips_plugin': LpipsPlugin,
 }

@@ -230,6 +230,7 @@ def project(G, target, c, *, num_steps=1000, w_avg_samples=10000, initial_learni
     area-down-sampled images (:66-75, 104-111); those weights are a download this project does not make, so the default is `l2_distance`
     (squared L2 of the same down-sampled images) and a caller with the feature network passes its LPIPS closure, e.g.
     `lambda img: (target_features - vgg16(F.interpolate(img, (256, 256), mode='area'), resize_images=False, return_lpips=True)).square().sum()`.
+    With this package's feature network: `distance=training.lpips.lpips_distance(target[None], training.lpips.LPIPS('vgg'))` (weights loaded by the caller).
 
     The other projectors of the reference differ only in the latent: an `initial_w` of shape [1, num_ws, w_dim] is optimised per layer
     (w_plus_projector*.py); for the join-view variant pass a `distance` that renders and compares the second view itself.

@@ -827,6 +827,53 @@ int64_t ide3d_noise_normalize_workspace_bytes(const int32_t* sides, int32_t k);
 int ide3d_noise_normalize(const ide3d_noise_map* table, const int32_t* sides, int32_t k, float* workspace, int64_t workspace_bytes,
                           void* stream);
 
+/*
+ * ABI 8 (entry points added).  The VGG16 LPIPS distance of the reference's projectors and coaches and its image gradient: everything that
+ * is not a convolution (csrc/lpips.hip; the convolutions are ide3d_modconv2d, the interior ReLU gradients
+ * ide3d_modconv_act_backward).  All tensors dense NCHW fp32 in device memory.  No atomics, fixed-order sums, bit-reproducible; no host
+ * synchronisation.
+ *
+ * ide3d_lpips_prep — what stands in front of the feature net (inversion/training/projectors/w_projector_ide3d.py:104-107: 0..255 images
+ *   area-down-sampled to 256 x 256; inversion/criteria/lpips/networks.py:49-50: the z-score): x [n, 3, H, W] -> y [n, 3, H / f, W / f],
+ *   y = ((mean of the f x f block) * in_scale + in_shift - mean[c]) / std[c]; f >= 1 divides H and W; mean, std: 3 floats each (DEVICE).
+ * ide3d_lpips_prep_backward — its adjoint (autograd's walk back through the same lines): dx = dy[.., Y / f, X / f] * in_scale / (f^2 std[c]).
+ * ide3d_maxpool2 — torchvision's `MaxPool2d(2, 2)` between the stages (networks.py:91, layers 4, 9, 16, 23): [planes, h, w] ->
+ *   [planes, h / 2, w / 2], floor on odd sides, bit-equal to ATen's.
+ * ide3d_lpips_stage_backward — at the last layer of a stage (networks.py:56-59: the activation feeds the tap AND the next stage), what
+ *   autograd does in three passes (max-pool backward, add, ReLU backward): dz = (route(dpool) + dtap) where y > 0, else 0.  y, dtap, dz
+ *   [planes, h, w]; dpool [planes, h / 2, w / 2] or NULL (the last stage); `route` sends a pooled gradient to the first maximum of its
+ *   window; a row / column that the floor dropped receives dtap only.  The result does not depend on the tie rule: y >= 0, a tie at a
+ *   positive maximum needs two equal convolution outputs, and a tie at 0 is masked.
+ * ide3d_lpips_head — the distance from the taps (inversion/criteria/lpips/utils.py:6-8, lpips.py:32-35): per tap u = a / (sqrt(sum_c a^2) +
+ *   1e-10), d = mean_{h,w} sum_c lin[c] (u - t)^2 against the cached normalised target t; loss[0] = sum over taps and images of d / n.
+ *   k launches (per-workgroup partial sums -> workspace of ide3d_lpips_head_workspace_bytes()) + 1 finishing launch.  loss == NULL: the
+ *   normalise-only form, out = u of every tap (k launches; t, lin, workspace unused).
+ * ide3d_lpips_head_backward — d loss / d a of the same in closed form, written to `out` of every tap (k launches): s = 2 dloss / (n h w),
+ *   g_c = s lin[c] (u_c - t_c), da_c = g_c / (|a| + eps) - a_c (sum_k g_k a_k) / (|a| (|a| + eps)^2), the second term 0 where |a| = 0 (the
+ *   reference's autograd yields NaN there: sqrt at 0).  dloss: DEVICE pointer to the upstream scalar gradient.
+ */
+#define IDE3D_LPIPS_MAX_TAPS 8
+typedef struct ide3d_lpips_tap {
+    const float* a;        /* [n, c, h, w] the tap's activation */
+    const float* t;        /* [n, c, h, w] normalised target features */
+    const float* lin;      /* [c] */
+    float*       out;      /* [n, c, h, w]: u (normalise-only form) or d loss / d a (backward) */
+    int32_t      c, h, w;
+    int32_t      reserved;
+} ide3d_lpips_tap;
+
+int ide3d_lpips_prep(const float* x, float* y, const float* mean, const float* std_, int32_t n, int32_t H, int32_t W, int32_t f,
+                     float in_scale, float in_shift, void* stream);
+int ide3d_lpips_prep_backward(const float* dy, float* dx, const float* std_, int32_t n, int32_t H, int32_t W, int32_t f,
+                              float in_scale, void* stream);
+int ide3d_maxpool2(const float* x, float* y, int64_t planes, int32_t h, int32_t w, void* stream);
+int ide3d_lpips_stage_backward(const float* y, const float* dpool, const float* dtap, float* dz, int64_t planes, int32_t h, int32_t w,
+                               void* stream);
+int64_t ide3d_lpips_head_workspace_bytes(const ide3d_lpips_tap* taps, int32_t k, int32_t n);
+int ide3d_lpips_head(const ide3d_lpips_tap* taps, int32_t k, int32_t n, float* workspace, int64_t workspace_bytes, float* loss,
+                     void* stream);
+int ide3d_lpips_head_backward(const ide3d_lpips_tap* taps, int32_t k, int32_t n, const float* dloss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
