@@ -268,6 +268,26 @@ class _LpipsTap(ctypes.Structure):
     ]
 
 
+PARSE_JOIN_TERMS = 3          # IDE3D_PARSE_JOIN_TERMS
+
+
+class _ParseTerm(ctypes.Structure):
+    """Mirror of ide3d_parse_term."""
+    _fields_ = [
+        ('p', ctypes.c_void_p), ('batch_stride', ctypes.c_int64), ('plane_stride', ctypes.c_int64), ('row_pitch', ctypes.c_int32),
+        ('half', ctypes.c_int32),
+    ]
+
+
+class _ParseJoinParams(ctypes.Structure):
+    """Mirror of ide3d_parse_join_params."""
+    _fields_ = [
+        ('term', _ParseTerm * PARSE_JOIN_TERMS), ('scale', ctypes.c_void_p), ('bias', ctypes.c_void_p), ('y', ctypes.c_void_p),
+        ('out', ctypes.c_void_p), ('n', ctypes.c_int32), ('c', ctypes.c_int32), ('h', ctypes.c_int32), ('w', ctypes.c_int32),
+        ('post', ctypes.c_int32), ('bias_gain', ctypes.c_float),
+    ]
+
+
 def _hip_runtimes_mapped():
     """Paths of every libamdhip64 mapped into this process (there must be exactly one)."""
     paths = set()
@@ -371,6 +391,16 @@ def load():
             'ide3d_lpips_head_workspace_bytes': [ctypes.POINTER(_LpipsTap), i32, i32],
             'ide3d_lpips_head': [ctypes.POINTER(_LpipsTap), i32, i32, vp, i64, vp, vp],
             'ide3d_lpips_head_backward': [ctypes.POINTER(_LpipsTap), i32, i32, vp, vp],
+            'ide3d_resize_bilinear': [vp, vp, i64, i32, i32, i32, i32, vp],
+            'ide3d_resize_bilinear_backward': [vp, vp, i64, i32, i32, i32, i32, vp],
+            'ide3d_parse_ce_workspace_bytes': [i32, i32, i32, i32, i32, i32],
+            'ide3d_parse_ce': [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp, vp],
+            'ide3d_parse_ce_backward': [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+            'ide3d_maxpool3s2': [vp, vp, vp, i64, i32, i32, vp],
+            'ide3d_maxpool3s2_backward': [vp, vp, vp, vp, i64, i32, i32, vp],
+            'ide3d_parse_join': [ctypes.POINTER(_ParseJoinParams), vp],
+            'ide3d_plane_sums': [vp, vp, vp, i64, i64, f32, vp],
+            'ide3d_parse_stem_backward': [vp, vp, vp, i32, i32, i32, i32, vp],
             'ide3d_set_conv_arithmetic': [i32],
             'ide3d_get_conv_arithmetic': [],
             'ide3d_frame_u8': [vp, vp, vp, i32, i32, i32, i32, vp, vp],
@@ -414,6 +444,8 @@ EXPORTED_SYMBOLS = (
     'ide3d_render_camera_grad_workspace_bytes', 'ide3d_render_rays_backward_camera',
     'ide3d_lpips_prep', 'ide3d_lpips_prep_backward', 'ide3d_maxpool2', 'ide3d_lpips_stage_backward', 'ide3d_lpips_head_workspace_bytes',
     'ide3d_lpips_head', 'ide3d_lpips_head_backward',
+    'ide3d_resize_bilinear', 'ide3d_resize_bilinear_backward', 'ide3d_parse_ce_workspace_bytes', 'ide3d_parse_ce', 'ide3d_parse_ce_backward',
+    'ide3d_maxpool3s2', 'ide3d_maxpool3s2_backward', 'ide3d_parse_join', 'ide3d_plane_sums', 'ide3d_parse_stem_backward',
 )
 
 
@@ -1699,11 +1731,181 @@ class LpipsPlugin:
         return outs
 
 
+class ParseLossPlugin:
+    """The passes between the convolutions of the face parser's cross-entropy loss and its image gradient (csrc/parse_loss.hip, DESIGN.md
+    section 5.16).  Tensors are float32 CUDA tensors; dense NCHW unless a method says otherwise."""
+
+    @staticmethod
+    def _f32(t, name, dev=None, shape=None):
+        _require(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and (dev is None or t.device == dev),
+                 f'parse_loss: {name} must be a contiguous float32 CUDA tensor on the device of the other arguments')
+        if shape is not None:
+            _require(tuple(t.shape) == tuple(shape), f'parse_loss: {name} must be {list(shape)}, got {list(t.shape)}')
+        return t
+
+    @staticmethod
+    def resize(x, size):
+        """ide3d_resize_bilinear: F.interpolate(x, size, mode='bilinear', align_corners=True) for x [n, c, h, w]."""
+        ParseLossPlugin._f32(x, 'x')
+        _require(x.ndim == 4, 'resize: x [n, c, h, w]')
+        n, c, h, w = x.shape
+        H, W = int(size[0]), int(size[1])
+        y = torch.empty([n, c, H, W], dtype=torch.float32, device=x.device)
+        with _dev_guard(x.device):
+            rc = load().ide3d_resize_bilinear(_ptr(x), _ptr(y), n * c, h, w, H, W, _stream(x))
+        _check(rc, 'resize_bilinear')
+        return y
+
+    @staticmethod
+    def resize_backward(dy, size):
+        """ide3d_resize_bilinear_backward: dy [n, c, H, W] -> the gradient of `resize`'s input of spatial `size`."""
+        ParseLossPlugin._f32(dy, 'dy')
+        _require(dy.ndim == 4, 'resize_backward: dy [n, c, H, W]')
+        n, c, H, W = dy.shape
+        h, w = int(size[0]), int(size[1])
+        dx = torch.empty([n, c, h, w], dtype=torch.float32, device=dy.device)
+        with _dev_guard(dy.device):
+            rc = load().ide3d_resize_bilinear_backward(_ptr(dy), _ptr(dx), n * c, h, w, H, W, _stream(dy))
+        _check(rc, 'resize_bilinear_backward')
+        return dx
+
+    @staticmethod
+    def _ce_args(logits, labels):
+        ParseLossPlugin._f32(logits, 'logits')
+        _require(logits.ndim == 4 and labels.ndim == 3 and labels.shape[0] == logits.shape[0], 'parse_ce: logits [n, C, h, w], labels [n, H, W]')
+        _require(labels.is_cuda and labels.device == logits.device and labels.dtype == torch.int64 and labels.is_contiguous(),
+                 'parse_ce: labels must be a contiguous int64 tensor on the device of the logits')
+        return (*logits.shape, labels.shape[1], labels.shape[2])
+
+    @staticmethod
+    def ce(logits, labels):
+        """ide3d_parse_ce -> (loss [] float32, lse [n, H, W] float64): CrossEntropyLoss()(resize(logits, labels.shape[1:]), labels)."""
+        n, C, h, w, H, W = ParseLossPlugin._ce_args(logits, labels)
+        lib = load()
+        nbytes = lib.ide3d_parse_ce_workspace_bytes(n, C, h, w, H, W)
+        _require(nbytes > 0, 'parse_ce: unsupported shape')
+        dev = logits.device
+        ws = torch.empty([nbytes // 8], dtype=torch.float64, device=dev)
+        lse = torch.empty([n, H, W], dtype=torch.float64, device=dev)
+        loss = torch.empty([], dtype=torch.float32, device=dev)
+        with _dev_guard(dev):
+            rc = lib.ide3d_parse_ce(_ptr(logits), _ptr(labels), n, C, h, w, H, W, _ptr(lse), _ptr(ws), nbytes, _ptr(loss), _stream(logits))
+        _check(rc, 'parse_ce')
+        return loss, lse
+
+    @staticmethod
+    def ce_backward(logits, labels, lse, dloss):
+        """ide3d_parse_ce_backward -> dlogits; dloss: a one-element float32 tensor on the device."""
+        n, C, h, w, H, W = ParseLossPlugin._ce_args(logits, labels)
+        dev = logits.device
+        _require(lse.is_cuda and lse.device == dev and lse.dtype == torch.float64 and lse.is_contiguous() and tuple(lse.shape) == (n, H, W),
+                 'parse_ce_backward: lse must be the float64 [n, H, W] tensor ce() returned')
+        _require(dloss.is_cuda and dloss.dtype == torch.float32 and dloss.device == dev and dloss.numel() == 1, 'parse_ce_backward: dloss must be one float32 on the device')
+        dl = torch.empty_like(logits)
+        with _dev_guard(dev):
+            rc = load().ide3d_parse_ce_backward(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(dloss), _ptr(dl), n, C, h, w, H, W, _stream(logits))
+        _check(rc, 'parse_ce_backward')
+        return dl
+
+    @staticmethod
+    def maxpool(x, want_index=True):
+        """ide3d_maxpool3s2 -> (F.max_pool2d(x, 3, 2, 1), winner bytes [n, c, oh, ow] uint8 or None)."""
+        ParseLossPlugin._f32(x, 'x')
+        _require(x.ndim == 4, 'maxpool3s2: x [n, c, h, w]')
+        n, c, h, w = x.shape
+        oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        y = torch.empty([n, c, oh, ow], dtype=torch.float32, device=x.device)
+        idx = torch.empty([n, c, oh, ow], dtype=torch.uint8, device=x.device) if want_index else None
+        with _dev_guard(x.device):
+            rc = load().ide3d_maxpool3s2(_ptr(x), _ptr(y), _ptr(idx), n * c, h, w, _stream(x))
+        _check(rc, 'maxpool3s2')
+        return y, idx
+
+    @staticmethod
+    def maxpool_backward(dy, idx, size, mask=None):
+        """ide3d_maxpool3s2_backward -> dx [n, c, *size]; mask [n, c, *size]: the gradient is zeroed where mask <= 0."""
+        ParseLossPlugin._f32(dy, 'dy')
+        _require(dy.ndim == 4, 'maxpool3s2_backward: dy [n, c, oh, ow]')
+        n, c, oh, ow = dy.shape
+        h, w = int(size[0]), int(size[1])
+        _require((oh, ow) == ((h - 1) // 2 + 1, (w - 1) // 2 + 1), 'maxpool3s2_backward: dy does not belong to an input of that size')
+        _require(idx.is_cuda and idx.device == dy.device and idx.dtype == torch.uint8 and idx.is_contiguous() and idx.shape == dy.shape,
+                 'maxpool3s2_backward: idx must be the uint8 tensor maxpool() returned')
+        if mask is not None:
+            ParseLossPlugin._f32(mask, 'mask', dy.device, (n, c, h, w))
+        dx = torch.empty([n, c, h, w], dtype=torch.float32, device=dy.device)
+        with _dev_guard(dy.device):
+            rc = load().ide3d_maxpool3s2_backward(_ptr(dy), _ptr(idx), _ptr(mask), _ptr(dx), n * c, h, w, _stream(dy))
+        _check(rc, 'maxpool3s2_backward')
+        return dx
+
+    @staticmethod
+    def join(terms, scale=None, bias=None, bias_gain=1.0, y=None, post=0):
+        """ide3d_parse_join -> post(terms[0] * scale[n, c] + terms[1] + terms[2] + bias[n, c] * bias_gain), dense [n, c, h, w].
+        terms: 1..3 entries, each a [n, c, h, w] tensor or view with contiguous rows, or (tensor [n, c, (h+1)//2, (w+1)//2], True) for a
+        half-resolution map added at the even positions; terms[0] is full size.  post: 0 none, 1 relu, 2 zero where y <= 0."""
+        terms = [t if isinstance(t, tuple) else (t, False) for t in terms]
+        _require(1 <= len(terms) <= PARSE_JOIN_TERMS and not terms[0][1], f'parse_join: 1..{PARSE_JOIN_TERMS} terms, the first at full size')
+        t0 = terms[0][0]
+        _require(t0.ndim == 4, 'parse_join: terms are [n, c, h, w]')
+        n, c, h, w = t0.shape
+        dev = t0.device
+        p = _ParseJoinParams()
+        for i, (t, half) in enumerate(terms):
+            want = (n, c, (h + 1) // 2, (w + 1) // 2) if half else (n, c, h, w)
+            _require(t.is_cuda and t.device == dev and t.dtype == torch.float32 and tuple(t.shape) == want and (t.stride(3) == 1 or want[3] == 1),
+                     f'parse_join: term {i} must be a float32 CUDA tensor {list(want)} with contiguous rows')
+            q = p.term[i]
+            q.p, q.batch_stride, q.plane_stride, q.row_pitch, q.half = t.data_ptr(), t.stride(0), t.stride(1), max(t.stride(2), want[3]), int(half)
+        for name, t in (('scale', scale), ('bias', bias)):
+            if t is not None:
+                ParseLossPlugin._f32(t, name, dev)
+                _require(t.numel() == n * c, f'parse_join: {name} must hold n * c values')
+                setattr(p, name, t.data_ptr())
+        if y is not None:
+            p.y = ParseLossPlugin._f32(y, 'y', dev, (n, c, h, w)).data_ptr()
+        out = torch.empty([n, c, h, w], dtype=torch.float32, device=dev)
+        p.out, p.n, p.c, p.h, p.w, p.post, p.bias_gain = out.data_ptr(), n, c, h, w, int(post), float(bias_gain)
+        with _dev_guard(dev):
+            rc = load().ide3d_parse_join(ctypes.byref(p), _stream(t0))
+        _check(rc, 'parse_join')
+        return out
+
+    @staticmethod
+    def plane_sums(a, b=None, gain=1.0):
+        """ide3d_plane_sums -> [n, c, 1, 1]: gain * sum over the pixels of a (* b)."""
+        ParseLossPlugin._f32(a, 'a')
+        _require(a.ndim == 4, 'plane_sums: a [n, c, h, w]')
+        if b is not None:
+            ParseLossPlugin._f32(b, 'b', a.device, a.shape)
+        n, c, h, w = a.shape
+        out = torch.empty([n, c, 1, 1], dtype=torch.float32, device=a.device)
+        with _dev_guard(a.device):
+            rc = load().ide3d_plane_sums(_ptr(a), _ptr(b), _ptr(out), n * c, h * w, float(gain), _stream(a))
+        _check(rc, 'plane_sums')
+        return out
+
+    @staticmethod
+    def stem_backward(dz, weight, size):
+        """ide3d_parse_stem_backward: the input gradient [n, 3, *size] of conv2d(x, weight [cout, 3, 7, 7], stride=2, padding=3)."""
+        ParseLossPlugin._f32(dz, 'dz')
+        H, W = int(size[0]), int(size[1])
+        _require(dz.ndim == 4 and tuple(dz.shape[2:]) == ((H - 1) // 2 + 1, (W - 1) // 2 + 1), 'stem_backward: dz [n, cout, (H-1)//2+1, (W-1)//2+1]')
+        n, cout = dz.shape[:2]
+        ParseLossPlugin._f32(weight, 'weight', dz.device, (cout, 3, 7, 7))
+        dx = torch.empty([n, 3, H, W], dtype=torch.float32, device=dz.device)
+        with _dev_guard(dz.device):
+            rc = load().ide3d_parse_stem_backward(_ptr(dz), _ptr(weight), _ptr(dx), n, cout, H, W, _stream(dz))
+        _check(rc, 'parse_stem_backward')
+        return dx
+
+
 def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epilogue='conv', x_amax=False):
     """Host-only (works without a GPU): the kernel family, tile and grid `modconv2d` would launch for this shape -> dict of the
     ide3d_modconv_plan_info fields, `kind` as a name from PLAN_KINDS.  epilogue: 'conv' (noise, bias, lrelu, gain sqrt(2): the 3x3 layers),
     'plain' (demodulation only: the up-sampling layers, whose FIR carries the rest), 'head' (bias, clamp 256, linear), 'relu' (an unmodulated
-    convolution + bias + ReLU: the feature nets) or 'grad' (unmodulated, no epilogue: the input gradient of one).  x_amax: the
+    convolution + bias + ReLU: the feature nets), 'bias' (unmodulated + bias, linear: a convolution with its BatchNorm folded in) or 'grad'
+    (unmodulated, no epilogue: the input gradient of one).  x_amax: the
     caller passes the producer's bound on |x| (what the f16x3 arithmetic needs)."""
     p = _ModconvParams()
     p.n, p.cin, p.cout, p.h, p.w_, p.k, p.mode = n, cin, cout, h, w, k, mode
@@ -1711,10 +1913,12 @@ def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epil
     p.w_batch_stride = cout * cin * k * k if per_image else 0
     dummy = 256                                  # non-null, 16-byte aligned, never dereferenced
     p.x = p.w = p.y = dummy
-    if not per_image and epilogue not in ('relu', 'grad'):
+    if not per_image and epilogue not in ('relu', 'bias', 'grad'):
         p.styles = p.dcoefs = dummy
     if epilogue == 'relu':               # an unmodulated convolution + bias + ReLU (training/lpips.py, training/face_parsing.py)
         p.bias, p.act, p.alpha, p.gain, p.clamp = dummy, 3, 0.0, 1.0, -1.0
+    elif epilogue == 'bias':
+        p.bias, p.act, p.gain, p.clamp = dummy, 1, 1.0, -1.0
     elif epilogue == 'grad':             # the input gradient of one: unmodulated, no epilogue
         p.act, p.gain, p.clamp = 1, 1.0, -1.0
     elif epilogue == 'conv':
@@ -2165,4 +2369,5 @@ PLUGINS = {
     'resample_plugin': ResamplePlugin,
     'mapping_plugin': MappingPlugin,
     'lpips_plugin': LpipsPlugin,
+    'parse_loss_plugin': ParseLossPlugin,
 }

@@ -874,6 +874,69 @@ int ide3d_lpips_head(const ide3d_lpips_tap* taps, int32_t k, int32_t n, float* w
                      void* stream);
 int ide3d_lpips_head_backward(const ide3d_lpips_tap* taps, int32_t k, int32_t n, const float* dloss, void* stream);
 
+/*
+ * ABI 8 (entry points added).  The cross-entropy of the BiSeNet face parser's logits against integer labels and its image gradient through
+ * the frozen parser (apps/train_hybrid_encoder.py:279-283, 324-328, apps/finetune_hybrid_encoder.py:170-174): everything between the
+ * convolutions (csrc/parse_loss.hip; the convolutions and all but one of their input gradients are
+ * ide3d_modconv2d, the plain ReLU gradients ide3d_modconv_act_backward).  NCHW fp32 in device memory.  No atomics, fixed-order sums,
+ * bit-reproducible; no host synchronisation.
+ *
+ * ide3d_resize_bilinear — `F.interpolate(x, (H, W), mode='bilinear', align_corners=True)` (inversion/BiSeNet.py:112-121): [planes, h, w] ->
+ *   [planes, H, W], H, W >= 2; interpolated in float64, rounded once.  ide3d_resize_bilinear_backward — its adjoint in gather form: each
+ *   input pixel sums, rows then columns ascending, over the output pixels whose footprint holds it.
+ * ide3d_parse_ce — `CrossEntropyLoss()(interpolate(logits, (H, W), bilinear, align_corners=True), labels)`: logits [n, C, h, w], labels
+ *   int64 [n, H, W] (a label outside 0..C-1 contributes its log-sum-exp only); the resize is evaluated per image pixel, the
+ *   max-subtracted log-sum-exp and the mean are carried in float64: one launch of per-workgroup partial sums (workspace of
+ *   ide3d_parse_ce_workspace_bytes()) + one finishing launch.  lse [n, H, W] float64 receives every pixel's log-sum-exp for the backward.
+ * ide3d_parse_ce_backward — dlogits [n, C, h, w] = the adjoint of that resize applied to (softmax - onehot) dloss / (n H W), gather form,
+ *   softmax recomputed from the saved lse.  dloss: DEVICE pointer to the upstream scalar gradient.
+ * ide3d_maxpool3s2 — `MaxPool2d(3, 2, 1)` (inversion/resnet.py:63): [planes, h, w] -> [planes, (h-1)/2+1, (w-1)/2+1], bit-equal to ATen's
+ *   (the first maximum in row-major window order wins, NaN wins); idx (may be NULL): one byte per output, the winner as ky * 3 + kx.
+ * ide3d_maxpool3s2_backward — gather form: dx[y, x] = the sum of dy over the <= 4 windows whose winner is (y, x), window rows then columns
+ *   ascending (bit-equal to ATen's); mask (may be NULL) [planes, h, w]: dx = 0 where mask <= 0 (the ReLU in front of the pool).
+ * ide3d_parse_join — out[n, c, y, x] = post(t0 * scale[n, c] + t1 + t2 + bias[n, c] * bias_gain).  Forward: the residual join relu(a + b)
+ *   (resnet.py:46), the gates feat * g + broadcast / + map (BiSeNet.py:79-81, 115-120) and feat * g + feat (:206-207).  Backward: the sum
+ *   of the gradients that meet at a tensor, the gate's scale, a spatial mean's broadcast gradient and the ReLU mask in one pass.  A term is a
+ *   strided view (rows contiguous): a cropped transposed-convolution result, a channel slice; `half` = 1: a [n, c, (h+1)/2, (w+1)/2] map
+ *   added at the even rows and columns only (the gradient of a stride-2 1x1 shortcut).  16-byte accesses when every operand allows it.
+ * ide3d_plane_sums — out[plane] = gain * sum_p a[plane, p] (* b[plane, p] when b != NULL), summed in float64 in a fixed order, one
+ *   workgroup per plane: the global averages (BiSeNet.py:77, 111, 203) and the gates' gradients.
+ * ide3d_parse_stem_backward — the input gradient of `conv2d(x [n, 3, H, W], weight [cout <= 64, 3, 7, 7], stride 2, padding 3)`
+ *   (resnet.py:61): dz [n, cout, (H-1)/2+1, (W-1)/2+1] -> dx [n, 3, H, W], direct: <= 16 taps x cout channels per pixel.
+ */
+#define IDE3D_PARSE_JOIN_TERMS 3
+typedef struct ide3d_parse_term {
+    const float* p;             /* NULL: absent (term 0 must be present) */
+    int64_t      batch_stride;  /* in floats */
+    int64_t      plane_stride;
+    int32_t      row_pitch;
+    int32_t      half;
+} ide3d_parse_term;
+typedef struct ide3d_parse_join_params {
+    ide3d_parse_term term[IDE3D_PARSE_JOIN_TERMS];
+    const float* scale;         /* [n, c] or NULL: multiplies term 0 */
+    const float* bias;          /* [n, c] or NULL */
+    const float* y;             /* [n, c, h, w] dense: the mask of post 2 */
+    float*       out;           /* [n, c, h, w] dense */
+    int32_t      n, c, h, w;
+    int32_t      post;          /* 0: none, 1: ReLU, 2: 0 where y <= 0 */
+    float        bias_gain;
+} ide3d_parse_join_params;
+
+int ide3d_resize_bilinear(const float* x, float* y, int64_t planes, int32_t h, int32_t w, int32_t H, int32_t W, void* stream);
+int ide3d_resize_bilinear_backward(const float* dy, float* dx, int64_t planes, int32_t h, int32_t w, int32_t H, int32_t W, void* stream);
+int64_t ide3d_parse_ce_workspace_bytes(int32_t n, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W);
+int ide3d_parse_ce(const float* logits, const int64_t* labels, int32_t n, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W,
+                   double* lse, float* workspace, int64_t workspace_bytes, float* loss, void* stream);
+int ide3d_parse_ce_backward(const float* logits, const int64_t* labels, const double* lse, const float* dloss, float* dlogits,
+                            int32_t n, int32_t C, int32_t h, int32_t w, int32_t H, int32_t W, void* stream);
+int ide3d_maxpool3s2(const float* x, float* y, uint8_t* idx, int64_t planes, int32_t h, int32_t w, void* stream);
+int ide3d_maxpool3s2_backward(const float* dy, const uint8_t* idx, const float* mask, float* dx, int64_t planes, int32_t h, int32_t w,
+                              void* stream);
+int ide3d_parse_join(const ide3d_parse_join_params* p, void* stream);
+int ide3d_plane_sums(const float* a, const float* b, float* out, int64_t planes, int64_t hw, float gain, void* stream);
+int ide3d_parse_stem_backward(const float* dz, const float* weight, float* dx, int32_t n, int32_t cout, int32_t H, int32_t W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,123 @@
+"""The face parser's cross-entropy loss (training/parse_loss.py) at the parser's resolution, the HIP path (`parse_loss.fused = True`) against
+the ATen path of the same module (`fused = False`: the plain PyTorch definition through `BiSeNet.forward`), alternated in one process:
+
+    parse_b1, parse_b4    `cross_entropy` + the image gradient, 512 x 512, batch 1 and batch 4
+    projector_step        one `Projector.step` of the full spec (512 x 512 images) with `parse_distance(..., base=l2_distance(...))`
+
+    python scripts/bench_parse_loss.py [--blocks 5] [--iters 10] [--warmup 3] [--no-projector]
+
+prints one JSON line: per case and path the device-event median over blocks of the time per call, the spread of the blocks (max - min), the
+block times, and the peak memory of one call (torch.cuda.max_memory_allocated minus what was allocated before it).  The parser has
+random weights (the timing does not depend on them)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'ide-3d_amd')); sys.path.insert(0, ROOT)
+
+PATHS = {'hip': True, 'aten': False}
+
+
+def measure(cases, blocks, iters, warmup):
+    """cases: {name: callable()}; every callable is run under both paths -> {name: {path: figures}}."""
+    import torch
+    from training import parse_loss
+    from torch_utils import hip_plugin
+    for name, fn in cases.items():
+        for fused in PATHS.values():
+            parse_loss.fused = fused
+            before = hip_plugin.CALLS.get('parse_ce', 0)
+            for _ in range(warmup):
+                fn()
+            took_hip = hip_plugin.CALLS.get('parse_ce', 0) > before
+            assert took_hip == fused, f'{name}: fused = {fused} but the HIP loss head ' + ('ran' if took_hip else 'did not run')
+    torch.cuda.synchronize()
+    times = {(c, p): [] for c in cases for p in PATHS}
+    for _ in range(blocks):
+        for c, fn in cases.items():
+            for p, fused in PATHS.items():
+                parse_loss.fused = fused
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[(c, p)].append(e0.elapsed_time(e1) / iters)
+    out = {}
+    for c, fn in cases.items():
+        out[c] = {}
+        for p, fused in PATHS.items():
+            parse_loss.fused = fused
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            fn()
+            torch.cuda.synchronize()
+            t = times[(c, p)]
+            out[c][p] = dict(ms=round(statistics.median(t), 3), spread_ms=round(max(t) - min(t), 3), blocks_ms=[round(v, 3) for v in t],
+                             peak_mib=round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1))
+        out[c]['hip_over_aten'] = round(out[c]['hip']['ms'] / out[c]['aten']['ms'], 3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--blocks', type=int, default=5)
+    ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--size', type=int, default=512)
+    ap.add_argument('--no-projector', action='store_true')
+    ap.add_argument('--w-avg-samples', type=int, default=1000)
+    args = ap.parse_args()
+
+    import torch
+    from training import face_parsing, parse_loss, projection, triplane
+    dev = torch.device('cuda', 0)
+    torch.manual_seed(0)
+    default = parse_loss.fused
+    net = face_parsing.initFaceParsing(device=dev)
+    cases = {}
+    for n in (1, 4):
+        g = torch.Generator().manual_seed(n)
+        x = (torch.rand(n, 3, args.size, args.size, generator=g) * 2 - 1).to(dev).requires_grad_(True)
+        target = torch.randint(0, 20, (n, args.size, args.size), generator=g).to(dev)
+
+        def call(x=x, target=target):
+            x.grad = None
+            parse_loss.cross_entropy(net, x, target).backward()
+        cases[f'parse_b{n}'] = call
+    result = dict(bench='parse_loss', size=args.size, blocks=args.blocks, iters=args.iters)
+    try:
+        result.update(measure(cases, args.blocks, args.iters, args.warmup))
+        if not args.no_projector:
+            sp = triplane.GeneratorSpec()
+            G = triplane.TriPlaneGenerator(sp).eval().requires_grad_(False)
+            with torch.no_grad():
+                for name, p in G.synthesis.named_parameters():
+                    if name.endswith('noise_strength'):
+                        p.fill_(0.1)                      # random init has 0; a trained generator does not
+            G = G.to(dev)
+            c = triplane.camera_label(0.2).to(dev)
+            target = torch.rand(3, sp.img_resolution, sp.img_resolution, generator=torch.Generator().manual_seed(7)).to(dev) * 255
+            labels = torch.randint(0, 20, (1, sp.img_resolution, sp.img_resolution), generator=torch.Generator().manual_seed(8)).to(dev)
+            P = projection.Projector(G, target, c, num_steps=1000, w_avg_samples=args.w_avg_samples,
+                                     distance=parse_loss.parse_distance(labels, net, base=projection.l2_distance(target[None])))
+            del G
+            counter = [100]                               # past the learning-rate ramp-up, inside the w-noise ramp
+
+            def step():
+                counter[0] += 1
+                P.step(counter[0])
+            result.update(measure({'projector_step': step}, args.blocks, max(args.iters // 5, 1), max(args.warmup - 1, 1)))
+            result['projector_resolution'] = sp.img_resolution
+    finally:
+        parse_loss.fused = default
+    print(json.dumps(result))
+
+
+if __name__ == '__main__':
+    main()
