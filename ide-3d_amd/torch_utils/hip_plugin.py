@@ -401,6 +401,18 @@ def load():
             'ide3d_parse_join': [ctypes.POINTER(_ParseJoinParams), vp],
             'ide3d_plane_sums': [vp, vp, vp, i64, i64, f32, vp],
             'ide3d_parse_stem_backward': [vp, vp, vp, i32, i32, i32, i32, vp],
+            'ide3d_id_prep': [vp, vp, i32, i32, vp],
+            'ide3d_id_prep_backward': [vp, vp, i32, i32, vp],
+            'ide3d_prelu': [vp, vp, vp, i32, i32, i32, i32, vp],
+            'ide3d_prelu_backward': [vp, i64, i64, i32, vp, vp, vp, i32, i32, i32, i32, vp],
+            'ide3d_se_gate': [vp, vp, vp, vp, i32, i32, i32, vp],
+            'ide3d_se_gate_backward': [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+            'ide3d_linear_workspace_bytes': [i32, i32, i32],
+            'ide3d_linear_backward_input_workspace_bytes': [i32, i32, i32],
+            'ide3d_linear': [vp, vp, vp, vp, i32, i32, i32, vp, i64, vp],
+            'ide3d_linear_backward_input': [vp, vp, vp, i32, i32, i32, vp, i64, vp],
+            'ide3d_id_head': [vp, vp, vp, vp, vp, i32, i32, vp],
+            'ide3d_id_head_backward': [vp, vp, vp, vp, vp, i32, i32, vp],
             'ide3d_set_conv_arithmetic': [i32],
             'ide3d_get_conv_arithmetic': [],
             'ide3d_frame_u8': [vp, vp, vp, i32, i32, i32, i32, vp, vp],
@@ -446,6 +458,9 @@ EXPORTED_SYMBOLS = (
     'ide3d_lpips_head', 'ide3d_lpips_head_backward',
     'ide3d_resize_bilinear', 'ide3d_resize_bilinear_backward', 'ide3d_parse_ce_workspace_bytes', 'ide3d_parse_ce', 'ide3d_parse_ce_backward',
     'ide3d_maxpool3s2', 'ide3d_maxpool3s2_backward', 'ide3d_parse_join', 'ide3d_plane_sums', 'ide3d_parse_stem_backward',
+    'ide3d_id_prep', 'ide3d_id_prep_backward', 'ide3d_prelu', 'ide3d_prelu_backward', 'ide3d_se_gate', 'ide3d_se_gate_backward',
+    'ide3d_linear_workspace_bytes', 'ide3d_linear_backward_input_workspace_bytes', 'ide3d_linear', 'ide3d_linear_backward_input',
+    'ide3d_id_head', 'ide3d_id_head_backward',
 )
 
 
@@ -1900,6 +1915,177 @@ class ParseLossPlugin:
         return dx
 
 
+class IdLossPlugin:
+    """The passes of the ArcFace identity loss and its image gradient that are not convolutions, joins or plane sums (csrc/id_loss.hip,
+    DESIGN.md section 5.17).  Tensors are contiguous float32 CUDA tensors unless a method says otherwise."""
+
+    LINEAR_MAX_ROWS = 8          # kLinMaxN: images per launch of the linear layer (more are launched in groups)
+
+    @staticmethod
+    def _f32(t, name, dev=None, shape=None):
+        _require(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and (dev is None or t.device == dev),
+                 f'id_loss: {name} must be a contiguous float32 CUDA tensor on the device of the other arguments')
+        if shape is not None:
+            _require(tuple(t.shape) == tuple(shape), f'id_loss: {name} must be {list(shape)}, got {list(t.shape)}')
+        return t
+
+    @staticmethod
+    def _factor(shape):
+        _require(len(shape) == 4 and shape[1] == 3 and shape[2] == shape[3] and shape[2] >= 256 and shape[2] % 256 == 0,
+                 'id_prep: images are [n, 3, 256 f, 256 f] with an integer f >= 1')
+        return shape[2] // 256
+
+    @staticmethod
+    def prep(x):
+        """ide3d_id_prep: x [n, 3, 256 f, 256 f] -> [n, 3, 112, 112]: average pooling by f, the crop [35:223, 32:220], adaptive pooling to 112."""
+        IdLossPlugin._f32(x, 'x')
+        f = IdLossPlugin._factor(x.shape)
+        y = torch.empty([x.shape[0], 3, 112, 112], dtype=torch.float32, device=x.device)
+        with _dev_guard(x.device):
+            rc = load().ide3d_id_prep(_ptr(x), _ptr(y), x.shape[0], f, _stream(x))
+        _check(rc, 'id_prep')
+        return y
+
+    @staticmethod
+    def prep_backward(dy, size):
+        """ide3d_id_prep_backward: dy [n, 3, 112, 112] -> the gradient of `prep`'s input of spatial `size`."""
+        n = dy.shape[0]
+        IdLossPlugin._f32(dy, 'dy', None, (n, 3, 112, 112))
+        f = IdLossPlugin._factor((n, 3, int(size[0]), int(size[1])))
+        dx = torch.empty([n, 3, 256 * f, 256 * f], dtype=torch.float32, device=dy.device)
+        with _dev_guard(dy.device):
+            rc = load().ide3d_id_prep_backward(_ptr(dy), _ptr(dx), n, f, _stream(dy))
+        _check(rc, 'id_prep_backward')
+        return dx
+
+    @staticmethod
+    def prelu(x, slope):
+        """ide3d_prelu: F.prelu(x, slope) for x [n, c, h, w], slope [c]."""
+        IdLossPlugin._f32(x, 'x')
+        _require(x.ndim == 4, 'prelu: x [n, c, h, w]')
+        n, c, h, w = x.shape
+        IdLossPlugin._f32(slope, 'slope', x.device, (c,))
+        y = torch.empty_like(x)
+        with _dev_guard(x.device):
+            rc = load().ide3d_prelu(_ptr(x), _ptr(slope), _ptr(y), n, c, h, w, _stream(x))
+        _check(rc, 'prelu')
+        return y
+
+    @staticmethod
+    def prelu_backward(dy, x, slope):
+        """ide3d_prelu_backward -> dx; x: the pre-activation; dy: [n, c, h, w], possibly a view with contiguous rows."""
+        IdLossPlugin._f32(x, 'x')
+        _require(x.ndim == 4, 'prelu_backward: x [n, c, h, w]')
+        n, c, h, w = x.shape
+        IdLossPlugin._f32(slope, 'slope', x.device, (c,))
+        _require(dy.is_cuda and dy.device == x.device and dy.dtype == torch.float32 and dy.shape == x.shape and (dy.stride(3) == 1 or w == 1),
+                 'prelu_backward: dy must be a float32 CUDA tensor of the shape of x with contiguous rows')
+        dx = torch.empty_like(x)
+        with _dev_guard(x.device):
+            rc = load().ide3d_prelu_backward(ctypes.c_void_p(dy.data_ptr()), dy.stride(0), dy.stride(1), max(dy.stride(2), w), _ptr(x), _ptr(slope),
+                                             _ptr(dx), n, c, h, w, _stream(x))
+        _check(rc, 'prelu_backward')
+        return dx
+
+    @staticmethod
+    def _se_args(s, w1, w2):
+        IdLossPlugin._f32(s, 's')
+        n, c = s.shape[0], s.numel() // max(s.shape[0], 1)
+        r = w1.shape[0]
+        IdLossPlugin._f32(w1, 'w1', s.device)
+        IdLossPlugin._f32(w2, 'w2', s.device)
+        _require(w1.numel() == r * c and w2.numel() == c * r and w2.shape[0] == c, 'se_gate: s [n, c], w1 [r, c], w2 [c, r]')
+        return n, c, r
+
+    @staticmethod
+    def se_gate(s, w1, w2):
+        """ide3d_se_gate: s [n, c(, 1, 1)] spatial means, w1 [r, c(, 1, 1)], w2 [c, r(, 1, 1)] -> sigmoid(w2 relu(w1 s)) in the shape of s."""
+        n, c, r = IdLossPlugin._se_args(s, w1, w2)
+        g = torch.empty_like(s)
+        with _dev_guard(s.device):
+            rc = load().ide3d_se_gate(_ptr(s), _ptr(w1), _ptr(w2), _ptr(g), n, c, r, _stream(s))
+        _check(rc, 'se_gate')
+        return g
+
+    @staticmethod
+    def se_gate_backward(s, w1, w2, g, dg):
+        """ide3d_se_gate_backward: dg (the gradient of `se_gate`'s result g) -> ds, in the shape of s."""
+        n, c, r = IdLossPlugin._se_args(s, w1, w2)
+        IdLossPlugin._f32(g, 'g', s.device)
+        IdLossPlugin._f32(dg, 'dg', s.device)
+        _require(g.numel() == n * c and dg.numel() == n * c, 'se_gate_backward: g and dg hold n * c values')
+        ds = torch.empty_like(s)
+        with _dev_guard(s.device):
+            rc = load().ide3d_se_gate_backward(_ptr(s), _ptr(w1), _ptr(w2), _ptr(g), _ptr(dg), _ptr(ds), n, c, r, _stream(s))
+        _check(rc, 'se_gate_backward')
+        return ds
+
+    @staticmethod
+    def _linear(x, weight, bias, backward):
+        lib = load()
+        IdLossPlugin._f32(x, 'dy' if backward else 'x')
+        IdLossPlugin._f32(weight, 'weight', x.device)
+        _require(x.ndim == 2 and weight.ndim == 2 and x.shape[1] == weight.shape[0 if backward else 1], 'linear: x [n, K], weight [M, K], dy [n, M]')
+        M, K = weight.shape
+        if bias is not None:
+            IdLossPlugin._f32(bias, 'bias', x.device, (M,))
+        out = torch.empty([x.shape[0], K if backward else M], dtype=torch.float32, device=x.device)
+        query = lib.ide3d_linear_backward_input_workspace_bytes if backward else lib.ide3d_linear_workspace_bytes
+        what = 'linear_backward_input' if backward else 'linear'
+        step = IdLossPlugin.LINEAR_MAX_ROWS
+        for i in range(0, x.shape[0], step):
+            xs, ys = x[i:i + step], out[i:i + step]
+            nbytes = query(xs.shape[0], K, M)
+            _require(nbytes > 0, f'{what}: unsupported shape n = {xs.shape[0]}, K = {K}, M = {M} (K must be a multiple of 4)')
+            ws = torch.empty([nbytes // 4], dtype=torch.float32, device=x.device)
+            with _dev_guard(x.device):
+                if backward:
+                    rc = lib.ide3d_linear_backward_input(_ptr(xs), _ptr(weight), _ptr(ys), xs.shape[0], K, M, _ptr(ws), nbytes, _stream(x))
+                else:
+                    rc = lib.ide3d_linear(_ptr(xs), _ptr(weight), _ptr(bias), _ptr(ys), xs.shape[0], K, M, _ptr(ws), nbytes, _stream(x))
+            _check(rc, what)
+        return out
+
+    @staticmethod
+    def linear(x, weight, bias=None):
+        """ide3d_linear: F.linear(x [n, K], weight [M, K], bias [M]); the weight is read once per 8 images."""
+        return IdLossPlugin._linear(x, weight, bias, False)
+
+    @staticmethod
+    def linear_backward_input(dy, weight):
+        """ide3d_linear_backward_input: dy [n, M] @ weight [M, K]."""
+        return IdLossPlugin._linear(dy, weight, None, True)
+
+    @staticmethod
+    def head(f, target=None):
+        """ide3d_id_head -> (e [n, M] = f / |f|, norm [n], loss [] or None): loss = mean_i (1 - e_i . target_i) when target [n, M] is given."""
+        IdLossPlugin._f32(f, 'f')
+        _require(f.ndim == 2, 'id_head: f [n, M]')
+        n, M = f.shape
+        if target is not None:
+            IdLossPlugin._f32(target, 'target', f.device, (n, M))
+        e, norm = torch.empty_like(f), torch.empty([n], dtype=torch.float32, device=f.device)
+        loss = torch.empty([], dtype=torch.float32, device=f.device) if target is not None else None
+        with _dev_guard(f.device):
+            rc = load().ide3d_id_head(_ptr(f), _ptr(target), _ptr(e), _ptr(norm), _ptr(loss), n, M, _stream(f))
+        _check(rc, 'id_head')
+        return e, norm, loss
+
+    @staticmethod
+    def head_backward(e, target, norm, dloss):
+        """ide3d_id_head_backward -> df; dloss: a one-element float32 tensor on the device."""
+        IdLossPlugin._f32(e, 'e')
+        n, M = e.shape
+        IdLossPlugin._f32(target, 'target', e.device, (n, M))
+        IdLossPlugin._f32(norm, 'norm', e.device, (n,))
+        _require(dloss.is_cuda and dloss.dtype == torch.float32 and dloss.device == e.device and dloss.numel() == 1, 'id_head_backward: dloss must be one float32 on the device')
+        df = torch.empty_like(e)
+        with _dev_guard(e.device):
+            rc = load().ide3d_id_head_backward(_ptr(e), _ptr(target), _ptr(norm), _ptr(dloss), _ptr(df), n, M, _stream(e))
+        _check(rc, 'id_head_backward')
+        return df
+
+
 def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epilogue='conv', x_amax=False):
     """Host-only (works without a GPU): the kernel family, tile and grid `modconv2d` would launch for this shape -> dict of the
     ide3d_modconv_plan_info fields, `kind` as a name from PLAN_KINDS.  epilogue: 'conv' (noise, bias, lrelu, gain sqrt(2): the 3x3 layers),
@@ -2370,4 +2556,5 @@ PLUGINS = {
     'mapping_plugin': MappingPlugin,
     'lpips_plugin': LpipsPlugin,
     'parse_loss_plugin': ParseLossPlugin,
+    'id_loss_plugin': IdLossPlugin,
 }

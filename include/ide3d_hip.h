@@ -937,6 +937,50 @@ int ide3d_parse_join(const ide3d_parse_join_params* p, void* stream);
 int ide3d_plane_sums(const float* a, const float* b, float* out, int64_t planes, int64_t hw, float gain, void* stream);
 int ide3d_parse_stem_backward(const float* dz, const float* weight, float* dx, int32_t n, int32_t cout, int32_t H, int32_t W, void* stream);
 
+/*
+ * ABI 8 (entry points added).  The ArcFace identity loss of the hybrid encoder's training step (inversion/criteria/id_loss.py,
+ * apps/train_hybrid_encoder.py:235-237, 305-335): one minus the cosine between IR-SE50 embeddings (inversion/psp/encoders/model_irse.py,
+ * helpers.py), and its image gradient through the frozen net: everything that is not a convolution, a per-channel affine pass, a gated
+ * join or a spatial mean (those are ide3d_modconv2d, ide3d_parse_join, ide3d_plane_sums); csrc/id_loss.hip, DESIGN.md section 5.17.
+ * Dense NCHW fp32 in device memory.  No atomics, fixed-order sums, bit-reproducible; no host synchronisation.
+ *
+ * ide3d_id_prep — `face_pool(pool(x)[:, :, 35:223, 32:220])` (id_loss.py:19-23) in one launch: x [n, 3, 256 f, 256 f] -> y [n, 3, 112, 112];
+ *   output (i, j) is the mean over rows floor(188 i / 112) .. ceil(188 (i + 1) / 112) - 1 (+ 35) and the columns likewise (+ 32) of the
+ *   f x f block means, window edges in integer arithmetic, summed in float64.  ide3d_id_prep_backward — the adjoint in gather form: each
+ *   input pixel inside the crop sums over the <= 2 x 2 output windows that hold it, rows then columns ascending; an exact 0 outside.
+ * ide3d_prelu — `PReLU(c)`: y = x > 0 ? x : slope[c] x, bit-equal to ATen.  ide3d_prelu_backward — dx = x > 0 ? dy : slope[c] dy (ATen's
+ *   rule at x = 0; x is the PRE-activation: slopes may be 0 or negative); dy is [n, c, h, w] with contiguous rows and the given strides
+ *   in floats (a cropped view), x and dx are dense.  16-byte accesses when h w is a multiple of 4 and every operand dense and aligned.
+ * ide3d_se_gate — `SEModule` past its average pool (helpers.py:61-78): s [n, c <= 512] spatial means, w1 [r <= 32, c], w2 [c, r] ->
+ *   g [n, c] = sigmoid(w2 relu(w1 s)), one workgroup per image, float64 sums.  ide3d_se_gate_backward — dg [n, c] -> ds [n, c]; the hidden
+ *   units are recomputed from s.
+ * ide3d_linear — y [n, M] = x [n, K] weight^T + bias (bias may be NULL) for n <= 8, K a multiple of 4, x and weight 16-byte aligned: the
+ *   weight matrix is read once for all n; one launch writes the sums of every 2048-wide slice of K to the workspace
+ *   (ide3d_linear_workspace_bytes(); -1: not covered), a finishing launch adds them in ascending order in float64.
+ * ide3d_linear_backward_input — dx [n, K] = dy [n, M] weight under the same limits: partial sums per 64 rows of the weight
+ *   (ide3d_linear_backward_input_workspace_bytes(), 16-byte aligned) + the same finishing launch.
+ * ide3d_id_head — `l2_norm` and the loss (helpers.py:14-17, id_loss.py:26-47): e [n, M] = f / |f|, norm [n] = |f|, and, when target (unit
+ *   vectors [n, M]) is not NULL, loss[0] = sum_i (1 - e_i . target_i) / n.  |f| = 0 divides by zero as the reference does.
+ * ide3d_id_head_backward — df = (g - e (e . g)) / |f| with g = -dloss target / n.  dloss: DEVICE pointer to the upstream scalar gradient.
+ */
+int ide3d_id_prep(const float* x, float* y, int32_t n, int32_t f, void* stream);
+int ide3d_id_prep_backward(const float* dy, float* dx, int32_t n, int32_t f, void* stream);
+int ide3d_prelu(const float* x, const float* slope, float* y, int32_t n, int32_t c, int32_t h, int32_t w, void* stream);
+int ide3d_prelu_backward(const float* dy, int64_t dy_batch_stride, int64_t dy_plane_stride, int32_t dy_row_pitch, const float* x,
+                         const float* slope, float* dx, int32_t n, int32_t c, int32_t h, int32_t w, void* stream);
+int ide3d_se_gate(const float* s, const float* w1, const float* w2, float* g, int32_t n, int32_t c, int32_t r, void* stream);
+int ide3d_se_gate_backward(const float* s, const float* w1, const float* w2, const float* g, const float* dg, float* ds, int32_t n,
+                           int32_t c, int32_t r, void* stream);
+int64_t ide3d_linear_workspace_bytes(int32_t n, int32_t K, int32_t M);
+int64_t ide3d_linear_backward_input_workspace_bytes(int32_t n, int32_t K, int32_t M);
+int ide3d_linear(const float* x, const float* weight, const float* bias, float* y, int32_t n, int32_t K, int32_t M, float* workspace,
+                 int64_t workspace_bytes, void* stream);
+int ide3d_linear_backward_input(const float* dy, const float* weight, float* dx, int32_t n, int32_t K, int32_t M, float* workspace,
+                                int64_t workspace_bytes, void* stream);
+int ide3d_id_head(const float* f, const float* target, float* e, float* norm, float* loss, int32_t n, int32_t M, void* stream);
+int ide3d_id_head_backward(const float* e, const float* target, const float* norm, const float* dloss, float* df, int32_t n, int32_t M,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
