@@ -589,22 +589,11 @@ __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_par
     }
 }
 
-template <int C, int HID>
+// The kernel of every form: the pointers a form does not use are passed as null.
+template <int C, int HID, bool PARAMS, bool CAM>
 __global__ void __launch_bounds__(512)
-render_rays_backward_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp) {
-    render_rays_backward_body<C, HID, false>(p, gr, sp, nullptr);
-}
-
-template <int C, int HID>
-__global__ void __launch_bounds__(512)
-render_rays_backward_params_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp, float* slices) {
-    render_rays_backward_body<C, HID, true>(p, gr, sp, slices);
-}
-
-template <int C, int HID, bool PARAMS>
-__global__ void __launch_bounds__(512)
-render_rays_backward_camera_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp, float* slices, float* cam_slices) {
-    render_rays_backward_body<C, HID, PARAMS, true>(p, gr, sp, slices, cam_slices);
+render_rays_backward_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp, float* slices, float* cam_slices) {
+    render_rays_backward_body<C, HID, PARAMS, CAM>(p, gr, sp, slices, cam_slices);
 }
 
 // Adds the slices in a fixed order: thread (element e, group g) sums slices g, g + 8, ..., then group 0 adds the 8 partial sums.
@@ -684,53 +673,9 @@ static BwdPlan plan_render_backward(const ide3d_render_params& p) {
 }
 
 template <int C, int HID>
-static int launch_render_backward(const ide3d_render_params& p, const ide3d_render_grads& g, hipStream_t st) {
-    const BwdPlan pl = plan_render_backward<C, HID, false>(p);
-    if (!pl.nw) {
-        set_error("render_rays_backward: %d steps per ray need %zu bytes of LDS per workgroup (at most 160 KiB)", p.steps, pl.lds_bytes);
-        return IDE3D_ENOKERNEL;
-    }
-    auto kern = render_rays_backward_kernel<C, HID>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
-    hipLaunchKernelGGL(kern, dim3((unsigned)pl.nblk), dim3(64 * pl.nw), pl.lds_bytes, st, p, g, pl.sp);
-    IDE3D_CHECK_LAUNCH("render_rays_backward");
-    return IDE3D_OK;
-}
-
-template <int C, int HID>
 static int64_t param_workspace_bytes(const ide3d_render_params& p) {
     const BwdPlan pl = plan_render_backward<C, HID, true>(p);
     return pl.nw ? pl.nblk * pl.nw * (int64_t)ParamSlice<C, HID>::stride(p.seg_ch, p.feat_ch) * (int64_t)sizeof(float) : 0;
-}
-
-template <int C, int HID>
-static int launch_render_backward_params(const ide3d_render_params& p, const ide3d_render_grads& g, const ide3d_render_param_grads& q,
-                                         hipStream_t st) {
-    using PS = ParamSlice<C, HID>;
-    const BwdPlan pl = plan_render_backward<C, HID, true>(p);
-    if (!pl.nw) {
-        set_error("render_rays_backward_params: %d steps per ray need %zu bytes of LDS per workgroup (at most 160 KiB)", p.steps, pl.lds_bytes);
-        return IDE3D_ENOKERNEL;
-    }
-    const int64_t need = param_workspace_bytes<C, HID>(p);
-    IDE3D_CHECK_ARG(q.workspace != nullptr && q.workspace_bytes >= need && (reinterpret_cast<uintptr_t>(q.workspace) & 15) == 0,
-                    "render_rays_backward_params: workspace of %lld bytes (16-byte aligned) required, got %lld", (long long)need,
-                    (long long)q.workspace_bytes);
-    float* slices = static_cast<float*>(q.workspace);
-    if (hipMemsetAsync(slices, 0, (size_t)need, st) != hipSuccess) { set_error("render_rays_backward_params: hipMemsetAsync failed"); return IDE3D_ELAUNCH; }
-    auto kern = render_rays_backward_params_kernel<C, HID>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
-    hipLaunchKernelGGL(kern, dim3((unsigned)pl.nblk), dim3(64 * pl.nw), pl.lds_bytes, st, p, g, pl.sp, slices);
-    IDE3D_CHECK_LAUNCH("render_rays_backward_params");
-    ParamOut out;
-    float* const dst[8] = {q.grad_geo_w0, q.grad_tex_w0, q.grad_geo_b0, q.grad_tex_b0, q.grad_geo_w1, q.grad_tex_w1, q.grad_geo_b1, q.grad_tex_b1};
-    const int end[8] = {PS::TW0, PS::GB0, PS::TB0, PS::GW1, PS::tw1(p.seg_ch), PS::gb1(p.seg_ch, p.feat_ch), PS::tb1(p.seg_ch, p.feat_ch),
-                        PS::total(p.seg_ch, p.feat_ch)};
-    for (int i = 0; i < 8; ++i) { out.dst[i] = dst[i]; out.end[i] = end[i]; }
-    hipLaunchKernelGGL(reduce_param_slices_kernel, dim3((unsigned)cdiv64(out.end[7], 64)), dim3(512), 0, st, slices, (int)(pl.nblk * pl.nw),
-                       PS::stride(p.seg_ch, p.feat_ch), out);
-    IDE3D_CHECK_LAUNCH("render_rays_backward_params (slice sums)");
-    return IDE3D_OK;
 }
 
 // One slice [n][12] per wave of whichever form launches (with and without the decoder sums the plans may differ in waves per workgroup).
@@ -742,53 +687,71 @@ static int64_t camera_workspace_bytes(const ide3d_render_params& p) {
     return waves * p.n * 12 * (int64_t)sizeof(float);
 }
 
-template <int C, int HID, bool PARAMS>
-static int launch_render_backward_camera(const ide3d_render_params& p, const ide3d_render_grads& g, const ide3d_render_param_grads* q,
-                                         const ide3d_render_camera_grads& c, hipStream_t st) {
+// "<entry point> (<stage>)" for the error text of a follow-up launch (only formed when that launch fails).
+static const char* stage_name(const char* what, const char* stage) {
+    thread_local char buf[96];
+    snprintf(buf, sizeof buf, "%s (%s)", what, stage);
+    return buf;
+}
+
+// The launch of every form (q is read when PARAMS, c when CAM): the kernel, then one launch per kind of slices that adds them up.
+// `what` is the entry point that was called, for the error texts.
+template <int C, int HID, bool PARAMS, bool CAM>
+static int launch_render_backward(const ide3d_render_params& p, const ide3d_render_grads& g, const ide3d_render_param_grads* q,
+                                  const ide3d_render_camera_grads* c, hipStream_t st, const char* what) {
     using PS = ParamSlice<C, HID>;
     const BwdPlan pl = plan_render_backward<C, HID, PARAMS>(p);
     if (!pl.nw) {
-        set_error("render_rays_backward_camera: %d steps per ray need %zu bytes of LDS per workgroup (at most 160 KiB)", p.steps, pl.lds_bytes);
+        set_error("%s: %d steps per ray need %zu bytes of LDS per workgroup (at most 160 KiB)", what, p.steps, pl.lds_bytes);
         return IDE3D_ENOKERNEL;
     }
     const int64_t nslices = pl.nblk * pl.nw, cam_floats = (int64_t)p.n * 12;
-    const int64_t cam_need = camera_workspace_bytes<C, HID>(p);
-    IDE3D_CHECK_ARG(cam_floats < 0x7fffffffLL, "render_rays_backward_camera: too many images");
-    IDE3D_CHECK_ARG(c.workspace != nullptr && c.workspace_bytes >= cam_need && (reinterpret_cast<uintptr_t>(c.workspace) & 15) == 0,
-                    "render_rays_backward_camera: camera workspace of %lld bytes (16-byte aligned) required, got %lld", (long long)cam_need,
-                    (long long)c.workspace_bytes);
-    float* cam_slices = static_cast<float*>(c.workspace);
-    float* slices = nullptr;
-    if (PARAMS) {
+    float *slices = nullptr, *cam_slices = nullptr;
+    if constexpr (PARAMS) {
         const int64_t need = param_workspace_bytes<C, HID>(p);
         IDE3D_CHECK_ARG(q->workspace != nullptr && q->workspace_bytes >= need && (reinterpret_cast<uintptr_t>(q->workspace) & 15) == 0,
-                        "render_rays_backward_camera: workspace of %lld bytes (16-byte aligned) required, got %lld", (long long)need,
-                        (long long)q->workspace_bytes);
+                        "%s: workspace of %lld bytes (16-byte aligned) required, got %lld", what, (long long)need, (long long)q->workspace_bytes);
         slices = static_cast<float*>(q->workspace);
-        if (hipMemsetAsync(slices, 0, (size_t)need, st) != hipSuccess) { set_error("render_rays_backward_camera: hipMemsetAsync failed"); return IDE3D_ELAUNCH; }
+        if (hipMemsetAsync(slices, 0, (size_t)need, st) != hipSuccess) { set_error("%s: hipMemsetAsync failed", what); return IDE3D_ELAUNCH; }
     }
-    if (hipMemsetAsync(cam_slices, 0, (size_t)(nslices * cam_floats) * sizeof(float), st) != hipSuccess) {
-        set_error("render_rays_backward_camera: hipMemsetAsync failed");
-        return IDE3D_ELAUNCH;
+    if constexpr (CAM) {
+        const int64_t need = camera_workspace_bytes<C, HID>(p);
+        IDE3D_CHECK_ARG(cam_floats < 0x7fffffffLL, "%s: too many images", what);
+        IDE3D_CHECK_ARG(c->workspace != nullptr && c->workspace_bytes >= need && (reinterpret_cast<uintptr_t>(c->workspace) & 15) == 0,
+                        "%s: camera workspace of %lld bytes (16-byte aligned) required, got %lld", what, (long long)need,
+                        (long long)c->workspace_bytes);
+        cam_slices = static_cast<float*>(c->workspace);
+        if (hipMemsetAsync(cam_slices, 0, (size_t)(nslices * cam_floats) * sizeof(float), st) != hipSuccess) {
+            set_error("%s: hipMemsetAsync failed", what);
+            return IDE3D_ELAUNCH;
+        }
     }
-    auto kern = render_rays_backward_camera_kernel<C, HID, PARAMS>;
+    auto kern = render_rays_backward_kernel<C, HID, PARAMS, CAM>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
     hipLaunchKernelGGL(kern, dim3((unsigned)pl.nblk), dim3(64 * pl.nw), pl.lds_bytes, st, p, g, pl.sp, slices, cam_slices);
-    IDE3D_CHECK_LAUNCH("render_rays_backward_camera");
-    if (PARAMS) {
-        ParamOut out;
-        float* const dst[8] = {q->grad_geo_w0, q->grad_tex_w0, q->grad_geo_b0, q->grad_tex_b0, q->grad_geo_w1, q->grad_tex_w1, q->grad_geo_b1, q->grad_tex_b1};
-        const int end[8] = {PS::TW0, PS::GB0, PS::TB0, PS::GW1, PS::tw1(p.seg_ch), PS::gb1(p.seg_ch, p.feat_ch), PS::tb1(p.seg_ch, p.feat_ch),
-                            PS::total(p.seg_ch, p.feat_ch)};
-        for (int i = 0; i < 8; ++i) { out.dst[i] = dst[i]; out.end[i] = end[i]; }
+    IDE3D_CHECK_LAUNCH(what);
+    if constexpr (PARAMS) {
+        const ParamOut out = {{q->grad_geo_w0, q->grad_tex_w0, q->grad_geo_b0, q->grad_tex_b0, q->grad_geo_w1, q->grad_tex_w1, q->grad_geo_b1, q->grad_tex_b1},
+                              {PS::TW0, PS::GB0, PS::TB0, PS::GW1, PS::tw1(p.seg_ch), PS::gb1(p.seg_ch, p.feat_ch), PS::tb1(p.seg_ch, p.feat_ch),
+                               PS::total(p.seg_ch, p.feat_ch)}};
         hipLaunchKernelGGL(reduce_param_slices_kernel, dim3((unsigned)cdiv64(out.end[7], 64)), dim3(512), 0, st, slices, (int)nslices,
                            PS::stride(p.seg_ch, p.feat_ch), out);
-        IDE3D_CHECK_LAUNCH("render_rays_backward_camera (slice sums)");
+        IDE3D_CHECK_LAUNCH(stage_name(what, "slice sums"));
     }
-    hipLaunchKernelGGL(reduce_camera_slices_kernel, dim3((unsigned)cdiv64(cam_floats, 64)), dim3(512), 0, st, cam_slices, (int)nslices,
-                       (int)cam_floats, c.grad_cam2world);
-    IDE3D_CHECK_LAUNCH("render_rays_backward_camera (camera sums)");
+    if constexpr (CAM) {
+        hipLaunchKernelGGL(reduce_camera_slices_kernel, dim3((unsigned)cdiv64(cam_floats, 64)), dim3(512), 0, st, cam_slices, (int)nslices,
+                           (int)cam_floats, c->grad_cam2world);
+        IDE3D_CHECK_LAUNCH(stage_name(what, "camera sums"));
+    }
     return IDE3D_OK;
+}
+
+// The instantiation for what was asked for.
+template <int C, int HID>
+static int launch_render_backward_form(const ide3d_render_params& p, const ide3d_render_grads& g, const ide3d_render_param_grads* q,
+                                       const ide3d_render_camera_grads* c, hipStream_t st, const char* what) {
+    if (q) return c ? launch_render_backward<C, HID, true, true>(p, g, q, c, st, what) : launch_render_backward<C, HID, true, false>(p, g, q, c, st, what);
+    return c ? launch_render_backward<C, HID, false, true>(p, g, q, c, st, what) : launch_render_backward<C, HID, false, false>(p, g, q, c, st, what);
 }
 
 static bool grads_fit(const ide3d_render_params& p, const ide3d_render_grads& g) {
@@ -798,27 +761,34 @@ static bool grads_fit(const ide3d_render_params& p, const ide3d_render_grads& g)
     return (!g.grad_tex_planes || ok(g.grad_tex_stride)) && (!g.grad_geo_planes || ok(g.grad_geo_stride));
 }
 
+// The checks and the (C, hidden) dispatch of all three entry points.  q = NULL: no decoder gradients; c = NULL: no camera gradient.
+static int render_backward(const ide3d_render_params& p, const ide3d_render_grads& g, const ide3d_render_param_grads* q,
+                           const ide3d_render_camera_grads* c, void* stream, const char* what) {
+    int rc = check_render_params(p, what, false);
+    if (rc) return rc;
+    IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world, "%s: null ray pointer", what);
+    IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "%s: bad ray shape", what);
+    IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "%s: Need to choose clamp mode", what);
+    // the tri-plane-only kernel scatters to both planes unconditionally
+    IDE3D_CHECK_ARG(q || c || (g.grad_tex_planes && g.grad_geo_planes), "%s: null gradient output", what);
+    IDE3D_CHECK_ARG(!c || c->grad_cam2world != nullptr, "%s: null camera-gradient output", what);
+    IDE3D_CHECK_ARG(!q || (q->grad_geo_w0 && q->grad_geo_b0 && q->grad_geo_w1 && q->grad_geo_b1 && q->grad_tex_w0 && q->grad_tex_b0 &&
+                           q->grad_tex_w1 && q->grad_tex_b1), "%s: null parameter-gradient output", what);
+    if (p.last_back) { set_error("%s: last_back is not fused; use the step-wise ops", what); return IDE3D_ENOKERNEL; }
+    if (!planes_fast(p)) { set_error("%s: tri-planes must be channels_last, 16-byte aligned", what); return IDE3D_ENOKERNEL; }
+    if (!grads_fit(p, g)) { set_error("%s: gradient buffers must be channels_last (channel stride 1)", what); return IDE3D_ENOKERNEL; }
+    hipStream_t st = (hipStream_t)stream;
+    if (p.C == 32 && p.hidden == 64) return launch_render_backward_form<32, 64>(p, g, q, c, st, what);
+    if (p.C == 16 && p.hidden == 32) return launch_render_backward_form<16, 32>(p, g, q, c, st, what);
+    set_error("%s: no fused kernel for C=%d hidden=%d", what, p.C, p.hidden);
+    return IDE3D_ENOKERNEL;
+}
+
 }  // namespace ide3d
 
 extern "C" int ide3d_render_rays_backward(const ide3d_render_params* pp, const ide3d_render_grads* gg, void* stream) {
-    using namespace ide3d;
     IDE3D_CHECK_ARG(pp != nullptr && gg != nullptr, "render_rays_backward: null params");
-    const ide3d_render_params& p = *pp;
-    const ide3d_render_grads& g = *gg;
-    int rc = check_render_params(p, "render_rays_backward", false);
-    if (rc) return rc;
-    IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world, "render_rays_backward: null ray pointer");
-    IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "render_rays_backward: bad ray shape");
-    IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "render_rays_backward: Need to choose clamp mode");
-    IDE3D_CHECK_ARG(g.grad_tex_planes && g.grad_geo_planes, "render_rays_backward: null gradient output");
-    if (p.last_back) { set_error("render_rays_backward: last_back is not fused; use the step-wise ops"); return IDE3D_ENOKERNEL; }
-    if (!planes_fast(p)) { set_error("render_rays_backward: tri-planes must be channels_last, 16-byte aligned"); return IDE3D_ENOKERNEL; }
-    if (!grads_fit(p, g)) { set_error("render_rays_backward: gradient buffers must be channels_last (channel stride 1)"); return IDE3D_ENOKERNEL; }
-    hipStream_t st = (hipStream_t)stream;
-    if (p.C == 32 && p.hidden == 64) return launch_render_backward<32, 64>(p, g, st);
-    if (p.C == 16 && p.hidden == 32) return launch_render_backward<16, 32>(p, g, st);
-    set_error("render_rays_backward: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
-    return IDE3D_ENOKERNEL;
+    return ide3d::render_backward(*pp, *gg, nullptr, nullptr, stream, "render_rays_backward");
 }
 
 extern "C" int64_t ide3d_render_param_grad_workspace_bytes(const ide3d_render_params* pp) {
@@ -831,26 +801,8 @@ extern "C" int64_t ide3d_render_param_grad_workspace_bytes(const ide3d_render_pa
 
 extern "C" int ide3d_render_rays_backward_params(const ide3d_render_params* pp, const ide3d_render_grads* gg, const ide3d_render_param_grads* qq,
                                                  void* stream) {
-    using namespace ide3d;
     IDE3D_CHECK_ARG(pp != nullptr && gg != nullptr && qq != nullptr, "render_rays_backward_params: null params");
-    const ide3d_render_params& p = *pp;
-    const ide3d_render_grads& g = *gg;
-    const ide3d_render_param_grads& q = *qq;
-    int rc = check_render_params(p, "render_rays_backward_params", false);
-    if (rc) return rc;
-    IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world, "render_rays_backward_params: null ray pointer");
-    IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "render_rays_backward_params: bad ray shape");
-    IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "render_rays_backward_params: Need to choose clamp mode");
-    IDE3D_CHECK_ARG(q.grad_geo_w0 && q.grad_geo_b0 && q.grad_geo_w1 && q.grad_geo_b1 && q.grad_tex_w0 && q.grad_tex_b0 && q.grad_tex_w1 && q.grad_tex_b1,
-                    "render_rays_backward_params: null parameter-gradient output");
-    if (p.last_back) { set_error("render_rays_backward_params: last_back is not fused; use the step-wise ops"); return IDE3D_ENOKERNEL; }
-    if (!planes_fast(p)) { set_error("render_rays_backward_params: tri-planes must be channels_last, 16-byte aligned"); return IDE3D_ENOKERNEL; }
-    if (!grads_fit(p, g)) { set_error("render_rays_backward_params: gradient buffers must be channels_last (channel stride 1)"); return IDE3D_ENOKERNEL; }
-    hipStream_t st = (hipStream_t)stream;
-    if (p.C == 32 && p.hidden == 64) return launch_render_backward_params<32, 64>(p, g, q, st);
-    if (p.C == 16 && p.hidden == 32) return launch_render_backward_params<16, 32>(p, g, q, st);
-    set_error("render_rays_backward_params: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
-    return IDE3D_ENOKERNEL;
+    return ide3d::render_backward(*pp, *gg, qq, nullptr, stream, "render_rays_backward_params");
 }
 
 extern "C" int64_t ide3d_render_camera_grad_workspace_bytes(const ide3d_render_params* pp) {
@@ -863,28 +815,7 @@ extern "C" int64_t ide3d_render_camera_grad_workspace_bytes(const ide3d_render_p
 
 extern "C" int ide3d_render_rays_backward_camera(const ide3d_render_params* pp, const ide3d_render_grads* gg, const ide3d_render_param_grads* qq,
                                                  const ide3d_render_camera_grads* cc, void* stream) {
-    using namespace ide3d;
     IDE3D_CHECK_ARG(pp != nullptr && gg != nullptr, "render_rays_backward_camera: null params");
     IDE3D_CHECK_ARG(qq != nullptr || cc != nullptr || gg->grad_tex_planes || gg->grad_geo_planes, "render_rays_backward_camera: no gradient requested");
-    if (cc == nullptr) return qq ? ide3d_render_rays_backward_params(pp, gg, qq, stream) : ide3d_render_rays_backward(pp, gg, stream);
-    const ide3d_render_params& p = *pp;
-    const ide3d_render_grads& g = *gg;
-    int rc = check_render_params(p, "render_rays_backward_camera", false);
-    if (rc) return rc;
-    IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world, "render_rays_backward_camera: null ray pointer");
-    IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "render_rays_backward_camera: bad ray shape");
-    IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "render_rays_backward_camera: Need to choose clamp mode");
-    IDE3D_CHECK_ARG(cc->grad_cam2world != nullptr, "render_rays_backward_camera: null camera-gradient output");
-    IDE3D_CHECK_ARG(!qq || (qq->grad_geo_w0 && qq->grad_geo_b0 && qq->grad_geo_w1 && qq->grad_geo_b1 && qq->grad_tex_w0 && qq->grad_tex_b0 &&
-                            qq->grad_tex_w1 && qq->grad_tex_b1), "render_rays_backward_camera: null parameter-gradient output");
-    if (p.last_back) { set_error("render_rays_backward_camera: last_back is not fused; use the step-wise ops"); return IDE3D_ENOKERNEL; }
-    if (!planes_fast(p)) { set_error("render_rays_backward_camera: tri-planes must be channels_last, 16-byte aligned"); return IDE3D_ENOKERNEL; }
-    if (!grads_fit(p, g)) { set_error("render_rays_backward_camera: gradient buffers must be channels_last (channel stride 1)"); return IDE3D_ENOKERNEL; }
-    hipStream_t st = (hipStream_t)stream;
-    if (p.C == 32 && p.hidden == 64)
-        return qq ? launch_render_backward_camera<32, 64, true>(p, g, qq, *cc, st) : launch_render_backward_camera<32, 64, false>(p, g, qq, *cc, st);
-    if (p.C == 16 && p.hidden == 32)
-        return qq ? launch_render_backward_camera<16, 32, true>(p, g, qq, *cc, st) : launch_render_backward_camera<16, 32, false>(p, g, qq, *cc, st);
-    set_error("render_rays_backward_camera: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
-    return IDE3D_ENOKERNEL;
+    return ide3d::render_backward(*pp, *gg, qq, cc, stream, "render_rays_backward_camera");
 }

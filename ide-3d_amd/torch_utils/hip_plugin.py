@@ -935,6 +935,7 @@ class TriplanePlugin:
 
 class VolumeRenderPlugin:
     _ws = _Workspaces()          # (kind, bytes, device index, launch domain) -> the per-wave partial sums of render_rays_backward_params / _camera
+    MLP_KEYS = ('geo_w0', 'geo_b0', 'geo_w1', 'geo_b1', 'tex_w0', 'tex_b0', 'tex_w1', 'tex_b1')        # the decoder tensors of `mlp`, in the order of the C structs
 
     @staticmethod
     def composite(rgb_sigma, z_vals, dir_norm, noise, clamp_mode, last_back, white_back, max_depth, fill_mode,
@@ -979,7 +980,7 @@ class VolumeRenderPlugin:
     def _fill_render_params(p, tex_planes, geo_planes, mlp):
         p.tex_planes, p.geo_planes = tex_planes.data_ptr(), geo_planes.data_ptr()
         p.tex_stride, p.geo_stride = _i64x4(tex_planes.stride()), _i64x4(geo_planes.stride())
-        for k in ('geo_w0', 'geo_b0', 'geo_w1', 'geo_b1', 'tex_w0', 'tex_b0', 'tex_w1', 'tex_b1'):
+        for k in VolumeRenderPlugin.MLP_KEYS:
             t = mlp[k]
             _require(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), f'{k} must be contiguous float32 on GPU')
             setattr(p, k, t.data_ptr())
@@ -1064,98 +1065,22 @@ class VolumeRenderPlugin:
         return feat, depth, wsum
 
     @staticmethod
-    def render_rays_backward(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_mode, last_back,
-                             white_back, max_depth, grad_feat, grad_depth, grad_wsum):
-        """Gradients of `render_rays` with respect to the two tri-planes: the same arguments as the forward, then dL/dfeat [n, feat+seg,
-        rays], dL/ddepth [n, rays], dL/dwsum [n, rays] (each may be None = zero) -> (dL/dtex_planes, dL/dgeo_planes), channels_last
-        float32 of the planes' shape; None when the library has no backward kernel for the configuration (IDE3D_ENOKERNEL)."""
+    def _render_backward(what, ray_args, upstream, plane_grads, param_grads, camera_grad):
+        """The one backward call behind the three public methods: `what` names the entry point (C symbol `ide3d_<what>`, error texts,
+        `CALLS`), `ray_args` are the forward's twelve arguments, `upstream` is (grad_feat, grad_depth, grad_wsum) -> (dtex, dgeo, grads,
+        dcam) with None for what was not asked; None when the library has no kernel for the configuration (IDE3D_ENOKERNEL)."""
+        tex_planes, geo_planes, mlp = ray_args[5:8]
         dev = tex_planes.device
-        p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
-                                                 clamp_mode, last_back, white_back, max_depth)
+        p, keep = VolumeRenderPlugin._ray_params(*ray_args)
         n, R, nch = p.n, p.rays_per_img, p.feat_ch + p.seg_ch
         g = _RenderGrads()
-        for name, t, shape in (('grad_feat', grad_feat, (n, nch, R)), ('grad_depth', grad_depth, (n, R)), ('grad_wsum', grad_wsum, (n, R))):
+        for name, t, shape in zip(('grad_feat', 'grad_depth', 'grad_wsum'), upstream, ((n, nch, R), (n, R), (n, R))):
             if t is not None:
-                _require(t.numel() == math.prod(shape), f'render_rays_backward: {name} must hold {list(shape)} values, got {list(t.shape)}')
+                _require(t.numel() == math.prod(shape), f'{what}: {name} must hold {list(shape)} values, got {list(t.shape)}')
                 t = t.to(device=dev, dtype=torch.float32).contiguous()
                 keep.append(t)
                 setattr(g, name, t.data_ptr())
-        dtex = torch.empty(tex_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
-        dgeo = torch.empty(geo_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
-        g.grad_tex_planes, g.grad_geo_planes = dtex.data_ptr(), dgeo.data_ptr()
-        g.grad_tex_stride, g.grad_geo_stride = _i64x4(dtex.stride()), _i64x4(dgeo.stride())
-        with _dev_guard(dev):
-            rc = load().ide3d_render_rays_backward(ctypes.byref(p), ctypes.byref(g), _stream(tex_planes))
-        if rc == -2:        # IDE3D_ENOKERNEL
-            return None
-        _check(rc, 'render_rays_backward')
-        return dtex, dgeo
-
-    MLP_KEYS = ('geo_w0', 'geo_b0', 'geo_w1', 'geo_b1', 'tex_w0', 'tex_b0', 'tex_w1', 'tex_b1')
-
-    @staticmethod
-    def render_rays_backward_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_mode, last_back,
-                                    white_back, max_depth, grad_feat, grad_depth, grad_wsum, plane_grads=True):
-        """`render_rays_backward` with the gradients of the eight decoder tensors of `mlp` as well (ide3d_render_rays_backward_params) ->
-        (dL/dtex_planes | None, dL/dgeo_planes | None, {key of mlp: gradient of that gain-folded tensor}); None when the library has no
-        kernel for the configuration.  `plane_grads=False`: no plane buffer is allocated and the kernel skips the tap scatter (decoder-only
-        training on detached planes).  The decoder gradients are bit-reproducible from run to run; the per-wave partial sums live in a
-        workspace of this plugin's cache (one per shape and launch domain, see `workspace_scope`)."""
-        dev = tex_planes.device
-        p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
-                                                 clamp_mode, last_back, white_back, max_depth)
-        n, R, nch = p.n, p.rays_per_img, p.feat_ch + p.seg_ch
-        g = _RenderGrads()
-        for name, t, shape in (('grad_feat', grad_feat, (n, nch, R)), ('grad_depth', grad_depth, (n, R)), ('grad_wsum', grad_wsum, (n, R))):
-            if t is not None:
-                _require(t.numel() == math.prod(shape), f'render_rays_backward_params: {name} must hold {list(shape)} values, got {list(t.shape)}')
-                t = t.to(device=dev, dtype=torch.float32).contiguous()
-                keep.append(t)
-                setattr(g, name, t.data_ptr())
-        dtex = dgeo = None
-        if plane_grads:
-            dtex = torch.empty(tex_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
-            dgeo = torch.empty(geo_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
-            g.grad_tex_planes, g.grad_geo_planes = dtex.data_ptr(), dgeo.data_ptr()
-            g.grad_tex_stride, g.grad_geo_stride = _i64x4(dtex.stride()), _i64x4(dgeo.stride())
-        lib = load()
-        nbytes = lib.ide3d_render_param_grad_workspace_bytes(ctypes.byref(p))
-        if nbytes <= 0:        # no compiled form for (C, hidden), or too many steps: what the launch would answer with IDE3D_ENOKERNEL
-            return None
-        q = _RenderParamGrads()
-        grads = {k: torch.empty_like(mlp[k]) for k in VolumeRenderPlugin.MLP_KEYS}
-        for k, t in grads.items():
-            setattr(q, 'grad_' + k, t.data_ptr())
-        key = ('render_param_grad', nbytes, dev.index, _ws_domain(dev))
-        ws = VolumeRenderPlugin._ws.entry(key, lambda: torch.empty([nbytes // 4], dtype=torch.float32, device=dev))[0]
-        q.workspace, q.workspace_bytes = ws.data_ptr(), nbytes
-        with _dev_guard(dev):
-            rc = lib.ide3d_render_rays_backward_params(ctypes.byref(p), ctypes.byref(g), ctypes.byref(q), _stream(tex_planes))
-        if rc == -2:        # IDE3D_ENOKERNEL
-            return None
-        _check(rc, 'render_rays_backward_params')
-        return dtex, dgeo, grads
-
-    @staticmethod
-    def render_rays_backward_camera(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_mode, last_back,
-                                    white_back, max_depth, grad_feat, grad_depth, grad_wsum, plane_grads=True, param_grads=False):
-        """The backward of `render_rays` with the gradient of the camera pose (ide3d_render_rays_backward_camera) -> (dL/dtex_planes | None,
-        dL/dgeo_planes | None, {key of mlp: gradient} | None, dL/dcam2world [n, 4, 4] with a zero last row); None when the library has no
-        kernel for the configuration.  `plane_grads=False`: no plane buffer is allocated, the tap scatter is skipped; `param_grads=True`:
-        the eight decoder gradients as well.  The camera gradient (like the decoder's) is summed in a fixed order: bit-reproducible from
-        run to run, and the same whatever else the call computes.  Both workspaces come from this plugin's cache."""
-        dev = tex_planes.device
-        p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
-                                                 clamp_mode, last_back, white_back, max_depth)
-        n, R, nch = p.n, p.rays_per_img, p.feat_ch + p.seg_ch
-        g = _RenderGrads()
-        for name, t, shape in (('grad_feat', grad_feat, (n, nch, R)), ('grad_depth', grad_depth, (n, R)), ('grad_wsum', grad_wsum, (n, R))):
-            if t is not None:
-                _require(t.numel() == math.prod(shape), f'render_rays_backward_camera: {name} must hold {list(shape)} values, got {list(t.shape)}')
-                t = t.to(device=dev, dtype=torch.float32).contiguous()
-                keep.append(t)
-                setattr(g, name, t.data_ptr())
-        dtex = dgeo = None
+        dtex = dgeo = grads = dcam = None
         if plane_grads:
             dtex = torch.empty(tex_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
             dgeo = torch.empty(geo_planes.shape, dtype=torch.float32, device=dev, memory_format=torch.channels_last).zero_()
@@ -1165,33 +1090,70 @@ class VolumeRenderPlugin:
 
         def workspace(kind, nbytes):
             key = (kind, nbytes, dev.index, _ws_domain(dev))
-            return VolumeRenderPlugin._ws.entry(key, lambda: torch.empty([nbytes // 4], dtype=torch.float32, device=dev))[0]
+            return VolumeRenderPlugin._ws.entry(key, lambda: torch.empty([nbytes // 4], dtype=torch.float32, device=dev))[0].data_ptr()
 
-        cbytes = lib.ide3d_render_camera_grad_workspace_bytes(ctypes.byref(p))
-        if cbytes <= 0:        # no compiled form for (C, hidden), or too many steps: what the launch would answer with IDE3D_ENOKERNEL
-            return None
-        c = _RenderCameraGrads()
-        dcam = torch.empty([n, 4, 4], dtype=torch.float32, device=dev)
-        cws = workspace('render_camera_grad', cbytes)
-        c.grad_cam2world, c.workspace, c.workspace_bytes = dcam.data_ptr(), cws.data_ptr(), cbytes
-        q, grads = None, None
+        q_ref = c_ref = None
+        if camera_grad:
+            cbytes = lib.ide3d_render_camera_grad_workspace_bytes(ctypes.byref(p))
+            if cbytes <= 0:        # no compiled form for (C, hidden), or too many steps: what the launch would answer with IDE3D_ENOKERNEL
+                return None
+            c = _RenderCameraGrads()
+            dcam = torch.empty([n, 4, 4], dtype=torch.float32, device=dev)
+            c.grad_cam2world, c.workspace, c.workspace_bytes = dcam.data_ptr(), workspace('render_camera_grad', cbytes), cbytes
+            c_ref = ctypes.byref(c)
         if param_grads:
             nbytes = lib.ide3d_render_param_grad_workspace_bytes(ctypes.byref(p))
-            if nbytes <= 0:
+            if nbytes <= 0:        # as above
                 return None
             q = _RenderParamGrads()
             grads = {k: torch.empty_like(mlp[k]) for k in VolumeRenderPlugin.MLP_KEYS}
             for k, t in grads.items():
                 setattr(q, 'grad_' + k, t.data_ptr())
-            ws = workspace('render_param_grad', nbytes)
-            q.workspace, q.workspace_bytes = ws.data_ptr(), nbytes
+            q.workspace, q.workspace_bytes = workspace('render_param_grad', nbytes), nbytes
+            q_ref = ctypes.byref(q)
+        extra = {'render_rays_backward': (), 'render_rays_backward_params': (q_ref,), 'render_rays_backward_camera': (q_ref, c_ref)}[what]
         with _dev_guard(dev):
-            rc = lib.ide3d_render_rays_backward_camera(ctypes.byref(p), ctypes.byref(g), ctypes.byref(q) if q is not None else None,
-                                                       ctypes.byref(c), _stream(tex_planes))
+            rc = getattr(lib, 'ide3d_' + what)(ctypes.byref(p), ctypes.byref(g), *extra, _stream(tex_planes))
         if rc == -2:        # IDE3D_ENOKERNEL
             return None
-        _check(rc, 'render_rays_backward_camera')
+        _check(rc, what)
         return dtex, dgeo, grads, dcam
+
+    @staticmethod
+    def render_rays_backward(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_mode, last_back,
+                             white_back, max_depth, grad_feat, grad_depth, grad_wsum):
+        """Gradients of `render_rays` with respect to the two tri-planes: the same arguments as the forward, then dL/dfeat [n, feat+seg,
+        rays], dL/ddepth [n, rays], dL/dwsum [n, rays] (each may be None = zero) -> (dL/dtex_planes, dL/dgeo_planes), channels_last
+        float32 of the planes' shape; None when the library has no backward kernel for the configuration (IDE3D_ENOKERNEL)."""
+        res = VolumeRenderPlugin._render_backward('render_rays_backward', (rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes,
+                                                  geo_planes, mlp, clamp_mode, last_back, white_back, max_depth),
+                                                  (grad_feat, grad_depth, grad_wsum), True, False, False)
+        return None if res is None else res[:2]
+
+    @staticmethod
+    def render_rays_backward_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_mode, last_back,
+                                    white_back, max_depth, grad_feat, grad_depth, grad_wsum, plane_grads=True):
+        """`render_rays_backward` with the gradients of the eight decoder tensors of `mlp` as well (ide3d_render_rays_backward_params) ->
+        (dL/dtex_planes | None, dL/dgeo_planes | None, {key of mlp: gradient of that gain-folded tensor}); None when the library has no
+        kernel for the configuration.  `plane_grads=False`: no plane buffer is allocated and the kernel skips the tap scatter (decoder-only
+        training on detached planes).  The decoder gradients are bit-reproducible from run to run; the per-wave partial sums live in a
+        workspace of this plugin's cache (one per shape and launch domain, see `workspace_scope`)."""
+        res = VolumeRenderPlugin._render_backward('render_rays_backward_params', (rays_d_cam, z_lin, cam2world, jitter, sigma_noise,
+                                                  tex_planes, geo_planes, mlp, clamp_mode, last_back, white_back, max_depth),
+                                                  (grad_feat, grad_depth, grad_wsum), plane_grads, True, False)
+        return None if res is None else res[:3]
+
+    @staticmethod
+    def render_rays_backward_camera(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_mode, last_back,
+                                    white_back, max_depth, grad_feat, grad_depth, grad_wsum, plane_grads=True, param_grads=False):
+        """The backward of `render_rays` with the gradient of the camera pose (ide3d_render_rays_backward_camera) -> (dL/dtex_planes | None,
+        dL/dgeo_planes | None, {key of mlp: gradient} | None, dL/dcam2world [n, 4, 4] with a zero last row); None when the library has no
+        kernel for the configuration.  `plane_grads=False`: no plane buffer is allocated, the tap scatter is skipped; `param_grads=True`:
+        the eight decoder gradients as well.  The camera gradient (like the decoder's) is summed in a fixed order: bit-reproducible from
+        run to run, and the same whatever else the call computes.  Both workspaces come from this plugin's cache."""
+        return VolumeRenderPlugin._render_backward('render_rays_backward_camera', (rays_d_cam, z_lin, cam2world, jitter, sigma_noise,
+                                                   tex_planes, geo_planes, mlp, clamp_mode, last_back, white_back, max_depth),
+                                                   (grad_feat, grad_depth, grad_wsum), plane_grads, param_grads, True)
 
     @staticmethod
     def sample_voxel(tex_planes, geo_planes, mlp, pts, sigma_only=False):

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from torch_utils import custom_ops
+from torch_utils import custom_ops, hip_plugin
 
 _plugin = None
 
@@ -339,7 +339,7 @@ class _NoFusedKernel(Exception):
     """The library has no fused kernel for the configuration (IDE3D_ENOKERNEL)."""
 
 
-_MLP_KEYS = ('geo_w0', 'geo_b0', 'geo_w1', 'geo_b1', 'tex_w0', 'tex_b0', 'tex_w1', 'tex_b1')
+_MLP_KEYS = hip_plugin.VolumeRenderPlugin.MLP_KEYS
 
 
 class _RenderRaysFused(torch.autograd.Function):
@@ -369,26 +369,19 @@ class _RenderRaysFused(torch.autograd.Function):
         mlp = dict(zip(_MLP_KEYS, mlp_tensors))
         a = ctx.args
         need = ctx.needs_input_grad
-        dcam = None
+        planes, ups = need[0] or need[1], (grad_feat, grad_depth, grad_wsum)
         if need[4]:
-            res = _plugin.render_rays_backward_camera(*a[:5], tex_planes, geo_planes, mlp, *a[5:], grad_feat, grad_depth, grad_wsum,
-                                                      plane_grads=need[0] or need[1], param_grads=any(need[10:]))
-            if res is not None:
-                dcam = res[3].reshape(ctx.cam_shape)
-                res = res[:3] if res[2] is not None else res[:2]
+            res = _plugin.render_rays_backward_camera(*a[:5], tex_planes, geo_planes, mlp, *a[5:], *ups, plane_grads=planes, param_grads=any(need[10:]))
         elif any(need[10:]):
-            res = _plugin.render_rays_backward_params(*a[:5], tex_planes, geo_planes, mlp, *a[5:], grad_feat, grad_depth, grad_wsum,
-                                                      plane_grads=need[0] or need[1])
+            res = _plugin.render_rays_backward_params(*a[:5], tex_planes, geo_planes, mlp, *a[5:], *ups, plane_grads=planes)
         else:
-            res = _plugin.render_rays_backward(*a[:5], tex_planes, geo_planes, mlp, *a[5:], grad_feat, grad_depth, grad_wsum)
+            res = _plugin.render_rays_backward(*a[:5], tex_planes, geo_planes, mlp, *a[5:], *ups)
         if res is None:
-            from torch_utils import hip_plugin
             raise RuntimeError('render_rays_backward: no backward kernel for this configuration: '
                                + hip_plugin.load().ide3d_last_error().decode('utf-8', 'replace'))
-        dtex, dgeo = res[:2]
-        dmlp = res[2] if len(res) > 2 else {}
-        return (dtex if need[0] else None, dgeo if need[1] else None, None, None, dcam) + (None,) * 5 + tuple(
-            dmlp[k] if need[10 + i] else None for i, k in enumerate(_MLP_KEYS))
+        dtex, dgeo, dmlp, dcam = res + (None,) * (4 - len(res))        # the entry points without a decoder / camera gradient return fewer
+        return (dtex if need[0] else None, dgeo if need[1] else None, None, None, dcam if dcam is None else dcam.reshape(ctx.cam_shape)) \
+            + (None,) * 5 + tuple(dmlp[k] if need[10 + i] else None for i, k in enumerate(_MLP_KEYS))
 
 
 def render_triplane_fused(tex_planes, geo_planes, mlp, cam2world, fov, resolution, num_steps, ray_start, ray_end,

@@ -350,8 +350,8 @@ int ide3d_render_rays_backward_params(const ide3d_render_params* p, const ide3d_
  * dL/dM[r][c] = sum_samples gp_r q_c (c < 3), dL/dM[r][3] = sum_samples gp_r; the last row is written as zero.  All 12 entries are free:
  * no rotation structure is assumed.  Taps outside a plane and non-finite coordinates contribute nothing, like the forward.
  * p and g as for ide3d_render_rays_backward_params (g's plane pointers may each be NULL); q: the decoder gradients as well, or NULL;
- * c: the camera gradient, or NULL.  Without c the call is ide3d_render_rays_backward_params (q given) or ide3d_render_rays_backward (q
- * NULL); q NULL, c NULL and both plane pointers NULL is IDE3D_EINVAL.  grad_cam2world is WRITTEN, fp32, contiguous.  workspace:
+ * c: the camera gradient, or NULL.  Without c the call does what ide3d_render_rays_backward_params (q given) or ide3d_render_rays_backward
+ * (q NULL, both plane pointers required) does, with this entry point's name in its error texts; q NULL, c NULL and both plane pointers NULL is IDE3D_EINVAL.  grad_cam2world is WRITTEN, fp32, contiguous.  workspace:
  * ide3d_render_camera_grad_workspace_bytes(p) bytes, 16-byte aligned, owned by this call until the stream has passed it: 12 sums per image
  * per wave, added in a fixed order by a second launch (no atomics), so the camera gradient is bit-reproducible from run to run and equal
  * whatever else the call computes.  IDE3D_ENOKERNEL in the cases of ide3d_render_rays_backward.  The workspace query reads n,
