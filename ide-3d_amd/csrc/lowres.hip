@@ -1,4 +1,4 @@
-// lowres.hip — the low-resolution block group of the tri-plane backbone (4^2 .. 16^2 / 32^2) in ONE launch.
+// lowres.hip — the low-resolution block group of the tri-plane backbone (4^2 .. 16^2 / 32^2) in ONE call.
 //
 // Replaces, for the StyleGAN2 dual-path blocks of inversion/networks.py:966-1139 whose maps are so small that every per-layer kernel of
 // modconv.hip / upfirdn2d.hip is a latency chain ("persistent low-resolution backbone"):
@@ -8,13 +8,12 @@
 // The per-layer path costs 2-4 launches per layer + 3 per head (26 launches for 4^2 .. 32^2 at batch 1, 0.64 ms of a 1.67 ms pass for ~3 % of its
 // FLOPs): each launch pays its own fill, prologue (weights + patch round trip), split-K partial round trip and drain.
 //
-// Structure (one 8-wave workgroup per CU, 160 KB LDS each, a grid barrier between phases):
+// Structure (one 8-wave workgroup per CU, 160 KB LDS each, one launch per phase):
 //   * GEMM view per layer: D[pixel, cout] = sum_{tap, cin} X[pixel + tap, cin] * W[tap, cin, cout] on v_mfma_f32_32x32x16_bf16 with every fp32
 //     operand as PARTS bf16 pieces (bf16x6 / bf16x3) — M = pixels of ALL images (<= ~512), N = 32 output channels, K = 32 input
 //     channels x 9 taps per work item: item (cb, s) = (output-channel block, K slice), C/32 x C/32 = 256 items at C = 512.
 //   * WEIGHT-STATIONARY: an item's whole weight slice (9 x PARTS x 4 x 32 units of 16 B = 55 KB, pre-split and packed once per weight version in
-//     exactly the LDS image) is copied to LDS in one burst; in the persistent form the NEXT layer's slice is requested while the workgroup
-//     sits in the reduction phase / the grid barrier (it depends on nothing computed here).
+//     exactly the LDS image) is copied to LDS in one burst.
 //   * Activations travel between layers PRE-MODULATED by the consumer's styles and PRE-SPLIT into bf16 pieces, channel-slice major with a zero
 //     halo: act[n][slice][piece][k octet][(res + 2)^2] units of 16 B (8 channels of one pixel): an item's input is one contiguous run per image
 //     and, in LDS, the A operand of the MFMA is one ds_read_b128 per (tap, piece, k half) at slot + tap offset — no bounds checks, no conversion
@@ -27,12 +26,11 @@
 //     8 outputs, lanes split the channels, the 64 partial sums meet in a 6-step transposing butterfly (63 shuffles instead of 64 x 6); bias,
 //     clamp and `+ upsample2d(previous skip)` (4 taps of the 2 x 2 polyphase) are applied by the lane that ends up with the sum.  Run as side
 //     work behind the GEMM of the next layer's G phase (same dependency, off the critical path).
-// Two launch forms of the SAME phase functions: `persistent = 1` one cooperative-style launch (co-residency checked against the occupancy
-// query, bounded spins), `persistent = 0` one launch per phase (what MI355X_MICROARCH.md's price list favours for GEMM -> GEMM seams: a kernel
-// boundary is 1.5-1.9 us, a 256-workgroup barrier 4-7 us).  Both are measured in profiles/round6/lowres_ab.txt.
+// One launch per phase, a workgroup per item: what MI355X_MICROARCH.md's price list favours for GEMM -> GEMM seams (a kernel boundary is
+// 1.5-1.9 us, a 256-workgroup barrier 4-7 us).  One launch for all phases with a grid barrier between them was built and measured slower:
+// profiles/round6/lowres_ab.txt, DESIGN.md 5.8.
 #include "common.h"
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 #include <utility>
 
@@ -86,7 +84,6 @@ struct GroupDev {
     const float* x0; long long x0_bs;
     const float* fir;           // [4][4] resample filter (device)
     float* partial;
-    unsigned* counter;          // [0] barrier, [1] error word
     int n, C, S, CB, nlayers, nheads, nphases, res0;
 };
 
@@ -139,30 +136,6 @@ pack_kernel(const float* __restrict__ w, int C, u32x4* __restrict__ out) {
     }
 }
 
-// ---- grid barrier (mapping.hip's, MI355X_MICROARCH.md "Workgroup dispatch ..."): monotonic counter, release -> relaxed arrive, relaxed poll
-// with s_sleep, one acquire; bounded spin that traps with the error word set ----------------------------------------------------
-constexpr unsigned SPIN_LIMIT = 1u << 22;
-template <class F>
-__device__ __forceinline__ void grid_barrier(unsigned* counter, unsigned target, F&& between) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    between();
-    if (threadIdx.x == 0) {
-        unsigned spins = 0;
-        while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > SPIN_LIMIT) { __hip_atomic_store(counter + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __builtin_trap(); }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-}
-
 // ---- staging --------------------------------------------------------------------------------------------------------------
 // LDS-DMA (global_load_lds, 16 B per lane): a wave copies 64 consecutive 16-byte units = 1 KB to a wave-uniform LDS address; every copy of a
 // phase is in flight at once, no registers, no ds_write (the first version staged through registers, 4 loads per thread in flight: a
@@ -188,7 +161,7 @@ __device__ __forceinline__ void stage_weights(const LayerDev& L, int item, unsig
 __host__ __device__ inline int waves_per_tile(int) { return 1; }
 
 template <int PARTS, int UP>
-__device__ __forceinline__ void g_item(const GroupDev& g, const LayerDev& L, int item, unsigned char* smem, bool weights_ready) {
+__device__ __forceinline__ void g_item(const GroupDev& g, const LayerDev& L, int item, unsigned char* smem) {
     constexpr int NACC = UP ? 4 : 2;
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l32 = lane & 31, khalf = lane >> 5;
@@ -198,7 +171,7 @@ __device__ __forceinline__ void g_item(const GroupDev& g, const LayerDev& L, int
     int* const s_tab = reinterpret_cast<int*>(smem + LDS_BYTES - TAB_BYTES);
     const int nslot = L.nslot_in, img_pad = L.img_pad_in;
     const int R = L.res, rin = L.rin, G = rin + 1, T = 2 * rin + 1, pitch = rin + 2;
-    if (!weights_ready) stage_weights<PARTS>(L, item, smem);
+    stage_weights<PARTS>(L, item, smem);
     if (L.first) {
         // the group's input x0 [C, rin, rin] (+ n * x0_bs) x this layer's styles, split, straight into the LDS image (halo zeroed first)
         const u32x4 z = {0u, 0u, 0u, 0u};
@@ -505,59 +478,29 @@ __device__ __forceinline__ void r_item(const GroupDev& g, const LayerDev& L, int
             L.x_out[((long long)n * g.C + cg * BC + c) * R * R + y0 * R + pix] = outs[pix * 33 + c];
         }
     }
-    __syncthreads();
 }
 
-template <int PARTS>
-__device__ __forceinline__ void run_phase(const GroupDev& g, const Phase& ph, unsigned char* smem, int wg, int nwg, bool weights_ready) {
-    const LayerDev& L = g.L[ph.idx < MAX_LAYERS ? ph.idx : 0];
-    if (ph.kind == PH_G) {
-        const int items = g.CB * g.S;
-        for (int it = wg; it < items; it += nwg) {
-            if (L.up == 2) g_item<PARTS, 1>(g, L, it, smem, weights_ready && it == wg);
-            else g_item<PARTS, 0>(g, L, it, smem, weights_ready && it == wg);
-            if (it + nwg < items) __syncthreads();
-        }
-        if (L.head_side >= 0) head_items(g, g.H[L.head_side], wg * WAVES + (threadIdx.x >> 6), nwg * WAVES);
-    } else if (ph.kind == PH_H) {
-        head_items(g, g.H[ph.idx], wg * WAVES + (threadIdx.x >> 6), nwg * WAVES);
-    } else {
-        const int items = g.n * g.CB * L.bands;
-        // R scratch sits BEHIND the weight region: in the persistent form the next layer's weights land there meanwhile
-        for (int it = wg; it < items; it += nwg) r_item<PARTS>(g, L, it, smem + w_units(PARTS) * 16);
-    }
-}
-
-// one launch per phase
+// one launch per phase: a G phase's grid is CB * S items, an R phase's n * CB * bands, a stand-alone H phase's its wave-items / WAVES rounded up
 template <int PARTS>
 __global__ void __launch_bounds__(THREADS, 2)
 phase_kernel(const GroupDev g, int phase) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     asm volatile("" ::: "v255");                       // 8 waves x 256 registers: the workgroup owns its CU's register files
-    run_phase<PARTS>(g, g.ph[phase], smem, blockIdx.x, gridDim.x, false);
-    __syncthreads();                                   // no wave leaves while a partner on its SIMD still multiplies
-}
-
-// all phases in one launch: grid = min(items, co-resident workgroups); the next G phase's weight slice is requested inside the barrier
-template <int PARTS>
-__global__ void __launch_bounds__(THREADS, 2)
-persistent_kernel(const GroupDev g) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    asm volatile("" ::: "v255");
-    const int wg = blockIdx.x, nwg = gridDim.x;
-    bool ready = false;
-    for (int p = 0; p < g.nphases; ++p) {
-        run_phase<PARTS>(g, g.ph[p], smem, wg, nwg, ready);
-        ready = false;
-        if (p + 1 == g.nphases) break;
-        grid_barrier(g.counter, (unsigned)(p + 1) * nwg, [&] {
-            // the weight slice of the NEXT phase, when that is a G phase, depends on nothing computed in this launch: it is requested between
-            // this workgroup's arrival and its first poll (this phase was PREP / R: its scratch sits behind the weight region, and every
-            // wave has passed the barrier's first __syncthreads)
-            if (g.ph[p + 1].kind == PH_G && wg < g.CB * g.S) { stage_weights<PARTS>(g.L[g.ph[p + 1].idx], wg, smem); ready = true; }
-        });
+    const Phase ph = g.ph[phase];
+    const LayerDev& L = g.L[ph.idx < MAX_LAYERS ? ph.idx : 0];
+    const int item = blockIdx.x, wave = item * WAVES + (threadIdx.x >> 6);
+    if (ph.kind == PH_G) {
+        if (L.up == 2) g_item<PARTS, 1>(g, L, item, smem);
+        else g_item<PARTS, 0>(g, L, item, smem);
+        if (L.head_side >= 0) head_items(g, g.H[L.head_side], wave, gridDim.x * WAVES);
+    } else if (ph.kind == PH_H) {
+        head_items(g, g.H[ph.idx], wave, gridDim.x * WAVES);
+    } else {
+        // R's scratch starts behind the weight region, which nothing occupies during R: the offset only keeps the planning (r_scratch_bytes,
+        // r_bands, the LDS check in launch_group) and with it every layer's bands where they were measured
+        r_item<PARTS>(g, L, item, smem + w_units(PARTS) * 16);
     }
-    __syncthreads();
+    __syncthreads();                                   // no wave leaves while a partner on its SIMD still multiplies
 }
 
 }  // namespace lr
@@ -571,7 +514,7 @@ using namespace ide3d::lr;
 inline int64_t align256(int64_t v) { return (v + 255) & ~int64_t(255); }
 
 struct Layout {
-    int64_t wq[MAX_LAYERS], act[MAX_LAYERS], xf[MAX_LAYERS], partial, counter, total;
+    int64_t wq[MAX_LAYERS], act[MAX_LAYERS], xf[MAX_LAYERS], partial, total;
     int rin[MAX_LAYERS];
 };
 
@@ -635,7 +578,6 @@ bool make_layout(const ide3d_lowres_params& p, int parts, Layout& lo) {
         res = rout;
     }
     lo.partial = off; off = align256(off + part_max);
-    lo.counter = off; off = align256(off + 256);
     lo.total = off;
     return true;
 }
@@ -643,25 +585,6 @@ bool make_layout(const ide3d_lowres_params& p, int parts, Layout& lo) {
 int resolve_parts(int arith) {
     const int a = arith ? arith : ide3d_get_conv_arithmetic();
     return a == 6 ? 3 : (a == 3 ? 2 : 0);
-}
-
-// co-resident workgroups of the persistent kernel on the current device (one per CU by LDS); cached per device
-template <int PARTS>
-int persistent_grid() {
-    static std::atomic<int> cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    int c = cache[dev].load(std::memory_order_relaxed);
-    if (c) return c > 0 ? c : 0;
-    int per_cu = 0;
-    hipDeviceProp_t prop;
-    int grid = -1;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(persistent_kernel<PARTS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_kernel<PARTS>, THREADS, LDS_BYTES) == hipSuccess && per_cu == 1)
-        grid = prop.multiProcessorCount;
-    cache[dev].store(grid > 0 ? grid : -1, std::memory_order_relaxed);
-    return grid > 0 ? grid : 0;
 }
 
 template <int PARTS>
@@ -674,7 +597,6 @@ int launch_group(const ide3d_lowres_params& p, hipStream_t st) {
     g.n = p.n; g.C = p.C; g.S = p.C / KS; g.CB = p.C / BC; g.nlayers = p.nlayers; g.nheads = p.nheads; g.res0 = p.res0;
     g.x0 = p.x0; g.x0_bs = p.x0_batch_stride; g.fir = p.fir;
     g.partial = reinterpret_cast<float*>(ws + lo.partial);
-    g.counter = reinterpret_cast<unsigned*>(ws + lo.counter);
     const int items = g.CB * g.S;
     int np = 0;
     int pending_head = -1;                                  // a head whose block output exists and that has not run yet
@@ -724,15 +646,6 @@ int launch_group(const ide3d_lowres_params& p, hipStream_t st) {
     if (pending_head >= 0) g.ph[np++] = Phase{PH_H, pending_head};
     g.nphases = np;
     IDE3D_CHECK_ARG(p.x_out != nullptr, "lowres_group: null x_out");
-    const bool persistent = p.persistent != 0;
-    if (persistent) {
-        const int grid = std::min(persistent_grid<PARTS>(), std::max(items, 1));
-        if (grid <= 0) { set_error("lowres_group: the persistent form needs one resident workgroup per CU on this device"); return IDE3D_ENOKERNEL; }
-        if (hipMemsetAsync(g.counter, 0, 2 * sizeof(unsigned), st) != hipSuccess) { set_error("lowres_group: hipMemsetAsync failed"); return IDE3D_ELAUNCH; }
-        IDE3D_EXCL_LAUNCH((persistent_kernel<PARTS>), dim3(grid), THREADS, LDS_BYTES, st, g);
-        IDE3D_CHECK_LAUNCH("lowres_group (persistent)");
-        return IDE3D_OK;
-    }
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(phase_kernel<PARTS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     for (int ph = 0; ph < np; ++ph) {
         const Phase& P = g.ph[ph];

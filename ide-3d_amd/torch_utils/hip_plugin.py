@@ -239,7 +239,7 @@ class _LowresParams(ctypes.Structure):
     _fields_ = [('x0', ctypes.c_void_p), ('x0_batch_stride', ctypes.c_int64), ('fir', ctypes.c_void_p), ('x_out', ctypes.c_void_p),
                 ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_int64),
                 ('n', ctypes.c_int32), ('C', ctypes.c_int32), ('res0', ctypes.c_int32), ('nlayers', ctypes.c_int32), ('nheads', ctypes.c_int32),
-                ('arith', ctypes.c_int32), ('persistent', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('arith', ctypes.c_int32), ('reserved0', ctypes.c_int32), ('reserved', ctypes.c_int32),
                 ('layers', _LowresLayer * LOWRES_MAX_LAYERS), ('heads', _LowresHead * LOWRES_MAX_HEADS)]
 
 
@@ -2428,11 +2428,7 @@ class LowresPlugin:
         return [(int(bands[l]), int(scratch[l])) for l in range(fit)]
 
     @staticmethod
-    def persistent_default():
-        return os.environ.get('IDE3D_LOWRES_PERSISTENT', '0') == '1'
-
-    @staticmethod
-    def group(x0, layers, heads, fir, persistent=None, arith=0):
+    def group(x0, layers, heads, fir, arith=0):
         """x0 [C, r, r] (shared by the batch) or [n, C, r, r]; layers: dicts(weight [C, C, 3, 3], styles [n, C], dcoefs [n, C], noise [res, res] | None
         (x noise_strength already), bias [C] | None, act_gain, clamp (< 0: none), up (1 | 2), head (index | -1)); heads: dicts(w [n, O, C], bias [O] |
         None, clamp).  Returns (x_out [n, C, res, res], [skip_k [n, O, res_k, res_k]])."""
@@ -2447,7 +2443,6 @@ class LowresPlugin:
         p.x0, p.x0_batch_stride = x0.data_ptr(), (x0.stride(0) if x0.ndim == 4 else 0)
         p.fir = fir.data_ptr()
         p.n, p.C, p.res0, p.nlayers, p.nheads, p.arith = n, C, x0.shape[-1], len(layers), len(heads), arith
-        p.persistent = int(LowresPlugin.persistent_default() if persistent is None else bool(persistent))
         keep, res, head_res = [], x0.shape[-1], {}
         for l, L in enumerate(layers):
             q = p.layers[l]

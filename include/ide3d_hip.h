@@ -652,13 +652,13 @@ typedef struct ide3d_fold_job {
 int ide3d_style_demod_batch(const ide3d_style_job* jobs, int32_t njobs, int32_t n, int32_t wdim, void* stream);
 int ide3d_fold_heads_batch(const ide3d_fold_job* jobs, int32_t njobs, int32_t n, int32_t wdim, void* stream);
 
-/* ---- the low-resolution block group of the backbone in one launch (round 6, ABI 7) ------------------- */
+/* ---- the low-resolution block group of the backbone in one call (round 6, ABI 7) ------------------- */
 /*
  * The first blocks of the dual-path StyleGAN2 backbone (inversion/networks.py:966-1139: 4^2, 8^2, 16^2 ... while all images' maps of a layer
  * fit one CU's LDS beside a weight slice) — every 3x3 / up-sampling SynthesisLayer (networks.py:330-514) with its noise, bias, lrelu,
  * gain and clamp, the 4x4 FIR of the up-sampling layers (conv2d_resample.py:112-129), the toRGB + toSeg heads (networks.py:670-713) and the
- * skip accumulation `img = upsample2d(img) + y` (networks.py:1100,1121) — as ONE launch (persistent != 0: phases separated by a grid barrier)
- * or one launch per phase (persistent == 0).  All layers have C input and C output channels (C % 32 == 0); fp32 in / fp32 out; products in
+ * skip accumulation `img = upsample2d(img) + y` (networks.py:1100,1121) — in ONE call, one launch per phase (a layer's GEMM, its reduction
+ * + epilogue, the heads).  All layers have C input and C output channels (C % 32 == 0); fp32 in / fp32 out; products in
  * the bf16x6 (or bf16x3) arithmetic of ide3d_set_conv_arithmetic, heads in plain fp32 FMAs.  Inference only.
  *   layer l: up = 1: y = lrelu(d * conv3x3(x * s) + noise + b, 0.2) * act_gain, clamped;   up = 2: the same with
  *            conv_transpose2d(stride 2) -> upfirdn2d(f, pad 1, gain 4) in place of the convolution (output 2 x the input resolution);
@@ -696,7 +696,7 @@ typedef struct ide3d_lowres_params {
     void* workspace; int64_t workspace_bytes;
     int32_t n, C, res0, nlayers, nheads;
     int32_t arith;            /* 0 = process default; only 6 (bf16x6) and 3 (bf16x3) have this form */
-    int32_t persistent;
+    int32_t reserved0;        /* not read: it selected a launch form that no longer exists; keeps the struct layout */
     int32_t reserved;
     ide3d_lowres_layer layers[IDE3D_LOWRES_MAX_LAYERS];
     ide3d_lowres_head heads[IDE3D_LOWRES_MAX_HEADS];

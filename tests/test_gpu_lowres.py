@@ -39,16 +39,14 @@ def _split(blocks, ws):
     return out
 
 
-def _run(blocks, ws_list, group, persistent=None, start_state=None):
+def _run(blocks, ws_list, group, start_state=None):
     """-> (x, img, seg) after all blocks, with / without the group launch; also how many blocks the group covered"""
     from training import networks
-    old = {k: os.environ.get(k) for k in ('IDE3D_NO_LOWRES_GROUP', 'IDE3D_LOWRES_PERSISTENT')}
+    old = os.environ.get('IDE3D_NO_LOWRES_GROUP')
     try:
         os.environ.pop('IDE3D_NO_LOWRES_GROUP', None)
         if not group:
             os.environ['IDE3D_NO_LOWRES_GROUP'] = '1'
-        if persistent is not None:
-            os.environ['IDE3D_LOWRES_PERSISTENT'] = '1' if persistent else '0'
         x = img = seg = None
         start, resume, info = 0, False, None
         with torch.no_grad():
@@ -63,11 +61,10 @@ def _run(blocks, ws_list, group, persistent=None, start_state=None):
                 x, img, seg = b(x, img, w, condition_img=seg, noise_mode='const', **extra)
         return x, img, seg, info
     finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+        if old is None:
+            os.environ.pop('IDE3D_NO_LOWRES_GROUP', None)
+        else:
+            os.environ['IDE3D_NO_LOWRES_GROUP'] = old
 
 
 def _rel(a, b):
@@ -75,8 +72,7 @@ def _rel(a, b):
 
 
 @pytest.mark.parametrize('C,nblocks,n', [(64, 3, 1), (64, 4, 3), (512, 4, 1), (512, 3, 4), (512, 3, 2), (128, 2, 8)])
-@pytest.mark.parametrize('persistent', [False, True])
-def test_group_equals_per_layer_path(gpu_device, C, nblocks, n, persistent):
+def test_group_equals_per_layer_path(gpu_device, C, nblocks, n):
     from torch_utils import hip_plugin
     assert hip_plugin.conv_arithmetic() == 'bf16x6'
     w_dim = 64
@@ -84,7 +80,7 @@ def test_group_equals_per_layer_path(gpu_device, C, nblocks, n, persistent):
     ws = torch.randn([n, sum(b.num_conv for b in blocks) + 1, w_dim], device=gpu_device)
     ws_list = _split(blocks, ws)
     before = hip_plugin.CALLS.get('lowres_group', 0)
-    xg, ig, sg, info = _run(blocks, ws_list, True, persistent)
+    xg, ig, sg, info = _run(blocks, ws_list, True)
     assert info is not None, 'the group launch did not apply'
     assert hip_plugin.CALLS.get('lowres_group', 0) == before + 1
     xr, ir, sr, none = _run(blocks, ws_list, False)
@@ -153,7 +149,7 @@ def test_group_against_float64_definition(gpu_device):
 
 def test_backbone_uses_the_group_and_replays_bit_equal(gpu_device):
     """Full-size backbone: the group launch is taken (batch 1 and 4), agrees with the per-layer path, and a hipGraph replay of it is bit-equal
-    to the eager launches (persistent and per-phase forms)."""
+    to the eager launches."""
     from torch_utils import hip_plugin
     from training import triplane, graph_cache
     torch.manual_seed(0)
@@ -161,29 +157,26 @@ def test_backbone_uses_the_group_and_replays_bit_equal(gpu_device):
     syn = G.synthesis
     for n in (1, 4):
         ws = torch.randn([n, G.num_ws, G.w_dim], device=gpu_device)
-        for persistent in ('1', '0'):
-            os.environ['IDE3D_LOWRES_PERSISTENT'] = persistent
-            try:
-                graph_cache.reset(syn)
-                graph_cache.STATS.clear()
-                before = hip_plugin.CALLS.get('lowres_group', 0)
-                with graph_cache.disabled():
-                    a = syn.planes(ws)
-                assert hip_plugin.CALLS.get('lowres_group', 0) == before + 1
-                os.environ['IDE3D_NO_LOWRES_GROUP'] = '1'
-                with graph_cache.disabled():
-                    b = syn.planes(ws)
-                os.environ.pop('IDE3D_NO_LOWRES_GROUP')
-                for u, v in zip(a, b):
-                    assert _rel(u, v) < 1e-5
-                outs = [syn.planes(ws) for _ in range(4)]          # eager, capture, replay, replay
-                assert graph_cache.STATS['replay'] >= 2
-                for o in outs:
-                    for u, v in zip(o, a):
-                        assert torch.equal(u, v)
-            finally:
-                os.environ.pop('IDE3D_NO_LOWRES_GROUP', None)
-                os.environ.pop('IDE3D_LOWRES_PERSISTENT', None)
+        try:
+            graph_cache.reset(syn)
+            graph_cache.STATS.clear()
+            before = hip_plugin.CALLS.get('lowres_group', 0)
+            with graph_cache.disabled():
+                a = syn.planes(ws)
+            assert hip_plugin.CALLS.get('lowres_group', 0) == before + 1
+            os.environ['IDE3D_NO_LOWRES_GROUP'] = '1'
+            with graph_cache.disabled():
+                b = syn.planes(ws)
+            os.environ.pop('IDE3D_NO_LOWRES_GROUP')
+            for u, v in zip(a, b):
+                assert _rel(u, v) < 1e-5
+            outs = [syn.planes(ws) for _ in range(4)]          # eager, capture, replay, replay
+            assert graph_cache.STATS['replay'] >= 2
+            for o in outs:
+                for u, v in zip(o, a):
+                    assert torch.equal(u, v)
+        finally:
+            os.environ.pop('IDE3D_NO_LOWRES_GROUP', None)
 
 
 def test_hooks_and_other_arithmetics_keep_the_per_layer_path(gpu_device):
@@ -213,14 +206,14 @@ def _stop_of(fit):
     return (bi, True) if conv0 else (bi + 1, False)
 
 
-def _group_both_forms(run):
-    """run(persistent) twice: per-phase and persistent launches of the same phase functions on the same items must be bit-equal"""
+def _group_twice(run):
+    """run() twice: the group sums in a fixed order, so two launches on the same inputs must be bit-equal"""
     from torch_utils import hip_plugin
     before = hip_plugin.CALLS.get('lowres_group', 0)
-    a, b = run(False), run(True)
+    a, b = run(), run()
     assert hip_plugin.CALLS.get('lowres_group', 0) == before + 2, 'the group launch did not run'
     for u, v in zip(a, b):
-        assert torch.equal(u, v), 'persistent and per-phase forms differ'
+        assert torch.equal(u, v), 'two runs of the group differ'
     assert hip_plugin.exclusive_violations() == (0, '')
     return a
 
@@ -240,7 +233,7 @@ def _case_id(c):
 @pytest.mark.parametrize('case', _SERIES, ids=[_case_id(c) for c in _SERIES])
 def test_group_edges_against_float64(gpu_device, case):
     """x, img and seg where the group stops — at the stop point `ide3d_lowres_layers_supported` gives for the case — against the float64
-    definition.  Both launch forms, bit-equal to each other."""
+    definition.  Run twice, bit-equal run to run."""
     from torch_utils import hip_plugin
     from training import networks
     C, nblocks, n = case['C'], case['nblocks'], case['n']
@@ -264,19 +257,15 @@ def test_group_edges_against_float64(gpu_device, case):
     if C == 512 and nblocks == 4:          # tests/test_plan_cpu.py::test_lowres_group_extent_by_batch_size
         assert want_stop == ((3, True) if n == 1 or (n == 2 and arith == 'bf16x3') else (2, True) if n <= 5 or arith == 'bf16x3' else (1, True))
 
-    def run(persistent):
-        os.environ['IDE3D_LOWRES_PERSISTENT'] = '1' if persistent else '0'
-        try:
-            with torch.no_grad():
-                grp = networks.lowres_group_forward(blocks, ws_list, noise_mode=noise_mode)
-        finally:
-            os.environ.pop('IDE3D_LOWRES_PERSISTENT')
+    def run():
+        with torch.no_grad():
+            grp = networks.lowres_group_forward(blocks, ws_list, noise_mode=noise_mode)
         assert grp is not None
         assert grp[3:] == want_stop, (grp[3:], want_stop)
         return grp[:3]
     hip_plugin.conv_arithmetic(arith)
     try:
-        xg, ig, sg = _group_both_forms(run)
+        xg, ig, sg = _group_twice(run)
     finally:
         hip_plugin.conv_arithmetic('default')
     with torch.no_grad():
@@ -324,7 +313,7 @@ def test_group_with_a_per_image_input_through_the_abi(gpu_device, n, arith):
         assert hip_plugin.LowresPlugin.layers_supported(n, C, 8, [1, 2, 1], 6 if arith == 'bf16x6' else 3) == 3
         hip_plugin.conv_arithmetic(arith)
         try:
-            xg, k0, k1 = _group_both_forms(lambda persistent: _flat(hip_plugin.LowresPlugin.group(x0, layers, heads, b0.resample_filter, persistent=persistent)))
+            xg, k0, k1 = _group_twice(lambda: _flat(hip_plugin.LowresPlugin.group(x0, layers, heads, b0.resample_filter)))
         finally:
             hip_plugin.conv_arithmetic('default')
         x, img, seg = _blocks64(blocks, ws_list, x0=x0)
@@ -434,7 +423,7 @@ def test_wide_up_layer_whose_fill_rule_band_would_overflow_lds(gpu_device, n, C,
         x64 = _layer64(lay, x0, w)
         hip_plugin.conv_arithmetic(arith)
         try:
-            (xg,) = _group_both_forms(lambda persistent: _flat(hip_plugin.LowresPlugin.group(x0, layers, [], lay.resample_filter, persistent=persistent)))
+            (xg,) = _group_twice(lambda: _flat(hip_plugin.LowresPlugin.group(x0, layers, [], lay.resample_filter)))
         finally:
             hip_plugin.conv_arithmetic('default')
     tol = 2e-4 if arith == 'bf16x3' else 1e-5
