@@ -229,7 +229,9 @@ head_wgrad_sum_kernel(const float* __restrict__ partial, int splits, int64_t per
 // ---- K4: the direct weight gradient of a modulated 3x3 convolution -----------------------------------------
 // dW[o, i, k] = sum_n d[n, o] s[n, i] sum_q A_k[n, o, q] B_k[n, i, q]: a GEMM with M = cout, N = cin x 9 taps, K = n x pixels,
 //   mode 0 (stride-1 layer, g = dz [n, co, h, w]): q = output pixel, A = g[q], B = x[q + (ky - 1, kx - 1)] (zero outside the map);
-//   mode 2 (up-sampling layer, g = g_t [n, co, 2h + 1, 2w + 1]): q = input pixel, A = g_t[2 q + (ky, kx)], B = x[q].
+//   mode 2 (up-sampling layer, g = g_t [n, co, 2h + 1, 2w + 1]): q = input pixel, A = g_t[2 q + (ky, kx)], B = x[q];
+//   mode 1 (stride-2 unpadded layer, x [n, ci, h, w], g = dz [n, co, (h - 3) / 2 + 1, (w - 3) / 2 + 1]): q = output pixel, A = g[q],
+//     B = x[2 q + (ky, kx)]: mode 2 with the operands' roles exchanged, the strided read on the B side of the same staging code.
 // One workgroup: one image, one tap, one 64 (o) x 64 (i) tile, one range of pixels; 4 waves of one 32 x 32 accumulator tile each.  The
 // operands are scaled (d on A, s on B) and split while they are staged, 32 pixels per stage: the next stage's global loads are in flight
 // while the current one feeds the matrix cores.  bf16x6 (three bf16 pieces per operand, the six products above 2^-24 on
@@ -240,6 +242,7 @@ constexpr int kWtM = 64, kWtN = 64, kWtK = 32;
 
 struct WtGeom { int tiles_o, tiles_i, splits, pix_per_split, kpix; };
 
+// (h, w): the grid of K pixels q (modes 0 and 2: the size of x; mode 1: the size of g)
 static WtGeom wt_geom(int n, int cout, int cin, int h, int w) {
     WtGeom g;
     g.tiles_o = cdiv(cout, kWtM); g.tiles_i = cdiv(cin, kWtN); g.kpix = h * w;
@@ -275,7 +278,7 @@ __device__ __forceinline__ void wt_split3(float a, float b, unsigned (&out)[3]) 
 template <int MODE>
 __device__ __forceinline__ void wt_load(const ide3d_wgrad_params& p, const float* __restrict__ A, const float* __restrict__ B, int o, int i,
                                         float da, float sb, int ky, int kx, int q0, int q1, float (&av)[8], float (&bv)[8]) {
-    const int w = p.w, h = p.h;
+    const int h = p.h, w = (MODE == 1) ? (p.w - 3) / 2 + 1 : p.w;        // w: the row length of the K-pixel grid
     int y = q0 / w, xx = q0 - y * w;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -284,6 +287,9 @@ __device__ __forceinline__ void wt_load(const ide3d_wgrad_params& p, const float
             av[e] = (in && o < p.cout) ? A[q0 + e] * da : 0.f;
             const int sy = y + ky - 1, sx = xx + kx - 1;
             bv[e] = (in && i < p.cin && sy >= 0 && sy < h && sx >= 0 && sx < w) ? B[sy * w + sx] * sb : 0.f;
+        } else if (MODE == 1) {
+            av[e] = (in && o < p.cout) ? A[q0 + e] * da : 0.f;
+            bv[e] = (in && i < p.cin) ? B[(2 * y + ky) * p.w + 2 * xx + kx] * sb : 0.f;      // 2 y + ky <= h - 1, 2 xx + kx <= p.w - 1 for q < q1
         } else {
             av[e] = (in && o < p.cout) ? A[(2 * y + ky) * (2 * w + 1) + 2 * xx + kx] * da : 0.f;
             bv[e] = (in && i < p.cin) ? B[q0 + e] * sb : 0.f;
@@ -312,7 +318,7 @@ modconv_wgrad_kernel(ide3d_wgrad_params p, WtGeom g, float* __restrict__ partial
     // staging role: row r of both operands, pixels 8 sq .. 8 sq + 7 of the stage
     const int r = tid >> 2, sq = tid & 3;
     const int o = o0 + r, i = i0 + r;
-    const int64_t gplane = (MODE == 0) ? (int64_t)p.h * p.w : (int64_t)(2 * p.h + 1) * (2 * p.w + 1);
+    const int64_t gplane = (MODE == 0) ? (int64_t)p.h * p.w : (MODE == 1) ? (int64_t)g.kpix : (int64_t)(2 * p.h + 1) * (2 * p.w + 1);
     const float* __restrict__ A = p.g + ((int64_t)n * p.cout + min(o, p.cout - 1)) * gplane;
     const float* __restrict__ B = p.x + ((int64_t)n * p.cin + min(i, p.cin - 1)) * p.h * p.w;
     const float da = (o < p.cout && p.dcoefs) ? p.dcoefs[(int64_t)n * p.cout + o] : 1.f;
@@ -524,7 +530,7 @@ extern "C" int ide3d_head_weight_grad(const float* dy, const float* x, float* dw
 }
 
 extern "C" int64_t ide3d_wgrad_workspace_bytes(int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w) {
-    if (n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return -1;
+    if (n <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || (int64_t)h * w >= 0x7fffffffLL) return -1;
     const WtGeom g = wt_geom(n, cout, cin, h, w);
     return (int64_t)n * g.splits * cout * cin * 9 * (int64_t)sizeof(float);
 }
@@ -534,11 +540,18 @@ extern "C" int ide3d_modconv_weight_grad(const ide3d_wgrad_params* pp, void* str
     const ide3d_wgrad_params& p = *pp;
     IDE3D_CHECK_ARG(p.g && p.x && p.dw && p.workspace, "modconv_weight_grad: null g / x / dw / workspace");
     IDE3D_CHECK_ARG(p.n > 0 && p.cin > 0 && p.cout > 0 && p.h > 0 && p.w > 0, "modconv_weight_grad: bad shape");
-    IDE3D_CHECK_ARG(p.mode == 0 || p.mode == 2, "modconv_weight_grad: mode must be 0 (3x3, stride 1) or 2 (transposed 3x3, stride 2)");
-    const int64_t gplane = p.mode == 0 ? (int64_t)p.h * p.w : (int64_t)(2 * p.h + 1) * (2 * p.w + 1);
-    IDE3D_CHECK_ARG((int64_t)p.n * p.cin * p.h * p.w < 0x7fffffffLL && (int64_t)p.n * p.cout * gplane < 0x7fffffffLL,
+    IDE3D_CHECK_ARG(p.mode == 0 || p.mode == 1 || p.mode == 2,
+                    "modconv_weight_grad: mode must be 0 (3x3, stride 1), 1 (3x3, stride 2, no padding) or 2 (transposed 3x3, stride 2)");
+    IDE3D_CHECK_ARG(p.mode != 1 || (p.h >= 3 && p.w >= 3), "modconv_weight_grad: mode 1 needs an input of at least 3 x 3");
+    // the grid of K pixels: the size of x in modes 0 and 2, of g in mode 1
+    const int qh = p.mode == 1 ? (p.h - 3) / 2 + 1 : p.h, qw = p.mode == 1 ? (p.w - 3) / 2 + 1 : p.w;
+    const int64_t gplane = p.mode == 2 ? (int64_t)(2 * p.h + 1) * (2 * p.w + 1) : (int64_t)qh * qw;
+    // (factor by factor: the products below must not leave 64 bits either)
+    IDE3D_CHECK_ARG((int64_t)p.h * p.w < 0x7fffffffLL && gplane < 0x7fffffffLL && (int64_t)p.n * p.cin < 0x7fffffffLL && (int64_t)p.n * p.cout < 0x7fffffffLL,
                     "modconv_weight_grad: operands too large for 32-bit indexing");
-    const WtGeom g = wt_geom(p.n, p.cout, p.cin, p.h, p.w);
+    IDE3D_CHECK_ARG((int64_t)p.n * p.cin * ((int64_t)p.h * p.w) < 0x7fffffffLL && (int64_t)p.n * p.cout * gplane < 0x7fffffffLL,
+                    "modconv_weight_grad: operands too large for 32-bit indexing");
+    const WtGeom g = wt_geom(p.n, p.cout, p.cin, qh, qw);
     const int64_t per = (int64_t)p.cout * p.cin * 9, slices = (int64_t)p.n * g.splits;
     IDE3D_CHECK_ARG(p.workspace_bytes >= slices * per * (int64_t)sizeof(float), "modconv_weight_grad: workspace too small");
     const int64_t wgs = slices * 9 * g.tiles_o * g.tiles_i;
@@ -548,11 +561,13 @@ extern "C" int ide3d_modconv_weight_grad(const ide3d_wgrad_params* pp, void* str
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)wgs);
     if (arith == 1) {
-        if (p.mode == 0) IDE3D_EXCL_LAUNCH((modconv_wgrad_kernel<0, false>), grid, kBwdThreads, 0, st, p, g, p.workspace);
-        else             IDE3D_EXCL_LAUNCH((modconv_wgrad_kernel<2, false>), grid, kBwdThreads, 0, st, p, g, p.workspace);
+        if (p.mode == 0)      IDE3D_EXCL_LAUNCH((modconv_wgrad_kernel<0, false>), grid, kBwdThreads, 0, st, p, g, p.workspace);
+        else if (p.mode == 1) IDE3D_EXCL_LAUNCH((modconv_wgrad_kernel<1, false>), grid, kBwdThreads, 0, st, p, g, p.workspace);
+        else                  IDE3D_EXCL_LAUNCH((modconv_wgrad_kernel<2, false>), grid, kBwdThreads, 0, st, p, g, p.workspace);
     } else {
-        if (p.mode == 0) IDE3D_EXCL_LAUNCH((modconv_wgrad_kernel<0, true>), grid, kBwdThreads, 0, st, p, g, p.workspace);
-        else             IDE3D_EXCL_LAUNCH((modconv_wgrad_kernel<2, true>), grid, kBwdThreads, 0, st, p, g, p.workspace);
+        if (p.mode == 0)      IDE3D_EXCL_LAUNCH((modconv_wgrad_kernel<0, true>), grid, kBwdThreads, 0, st, p, g, p.workspace);
+        else if (p.mode == 1) IDE3D_EXCL_LAUNCH((modconv_wgrad_kernel<1, true>), grid, kBwdThreads, 0, st, p, g, p.workspace);
+        else                  IDE3D_EXCL_LAUNCH((modconv_wgrad_kernel<2, true>), grid, kBwdThreads, 0, st, p, g, p.workspace);
     }
     IDE3D_CHECK_LAUNCH("modconv_weight_grad");
     hipLaunchKernelGGL(head_wgrad_sum_kernel, dim3((unsigned)cdiv64(per, kBwdThreads)), dim3(kBwdThreads), 0, st, p.workspace, (int)slices, per, 1, p.dw);

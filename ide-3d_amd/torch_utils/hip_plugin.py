@@ -411,6 +411,8 @@ def load():
             'ide3d_linear_backward_input_workspace_bytes': [i32, i32, i32],
             'ide3d_linear': [vp, vp, vp, vp, i32, i32, i32, vp, i64, vp],
             'ide3d_linear_backward_input': [vp, vp, vp, i32, i32, i32, vp, i64, vp],
+            'ide3d_linear_weight_grad': [vp, vp, vp, i32, i32, i32, vp],
+            'ide3d_residual_join': [vp, vp, vp, i64, f32, vp],
             'ide3d_id_head': [vp, vp, vp, vp, vp, i32, i32, vp],
             'ide3d_id_head_backward': [vp, vp, vp, vp, vp, i32, i32, vp],
             'ide3d_set_conv_arithmetic': [i32],
@@ -460,7 +462,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_maxpool3s2', 'ide3d_maxpool3s2_backward', 'ide3d_parse_join', 'ide3d_plane_sums', 'ide3d_parse_stem_backward',
     'ide3d_id_prep', 'ide3d_id_prep_backward', 'ide3d_prelu', 'ide3d_prelu_backward', 'ide3d_se_gate', 'ide3d_se_gate_backward',
     'ide3d_linear_workspace_bytes', 'ide3d_linear_backward_input_workspace_bytes', 'ide3d_linear', 'ide3d_linear_backward_input',
-    'ide3d_id_head', 'ide3d_id_head_backward',
+    'ide3d_linear_weight_grad', 'ide3d_residual_join', 'ide3d_id_head', 'ide3d_id_head_backward',
 )
 
 
@@ -1442,14 +1444,17 @@ class ModconvGradPlugin:
     def weight_grad(g, x, styles, dcoefs, mode=0, arith=0):
         """ide3d_modconv_weight_grad -> dw [cout, cin, 3, 3], the direct weight gradient of a modulated 3x3 convolution.
         mode 0: g [n, cout, h, w] (dz of a stride-1 layer); mode 2: g [n, cout, 2h + 1, 2w + 1] (the FIR adjoint g_t of an up-sampling layer);
+        mode 1: g [n, cout, (h - 3) // 2 + 1, (w - 3) // 2 + 1] (dz of a stride-2 unpadded layer, section 5.19);
         x [n, cin, h, w]; styles [n, cin], dcoefs [n, cout] or None.  arith: 0 = the process arithmetic, 1 fp32, 6 bf16x6."""
         dev = g.device
         ModconvGradPlugin._f32(g, 'g', dev)
         _require(g.ndim == 4 and x.ndim == 4 and x.shape[0] == g.shape[0], 'weight_grad: g [n, cout, gh, gw], x [n, cin, h, w]')
-        _require(mode in (0, 2), 'weight_grad: mode must be 0 or 2')
+        _require(mode in (0, 1, 2), 'weight_grad: mode must be 0, 1 or 2')
         n, cout = g.shape[:2]
         cin, h, w = x.shape[1:]
-        _require(tuple(g.shape[2:]) == ((h, w) if mode == 0 else (2 * h + 1, 2 * w + 1)), f'weight_grad: g must be {"h x w" if mode == 0 else "(2h+1) x (2w+1)"} of x')
+        _require(mode != 1 or (h >= 3 and w >= 3), 'weight_grad: mode 1 needs an x of at least 3 x 3')
+        gshape = {0: (h, w), 1: ((h - 3) // 2 + 1, (w - 3) // 2 + 1), 2: (2 * h + 1, 2 * w + 1)}[mode]
+        _require(tuple(g.shape[2:]) == gshape, f'weight_grad: g must be {gshape[0]} x {gshape[1]} for mode {mode} and an x of {h} x {w}')
         g = g.contiguous()
         x = ModconvGradPlugin._f32(x, 'x', dev).contiguous()
         if styles is not None:
@@ -1457,7 +1462,7 @@ class ModconvGradPlugin:
         if dcoefs is not None:
             dcoefs = ModconvGradPlugin._f32(dcoefs, 'dcoefs', dev, (n, cout)).contiguous()
         lib = load()
-        nbytes = lib.ide3d_wgrad_workspace_bytes(n, cin, cout, h, w)
+        nbytes = lib.ide3d_wgrad_workspace_bytes(n, cin, cout, *(gshape if mode == 1 else (h, w)))      # (the grid the sum runs over)
         _require(nbytes > 0, 'weight_grad: unsupported shape')
         ws = torch.empty([nbytes // 4], dtype=torch.float32, device=dev)
         dw = torch.empty([cout, cin, 3, 3], dtype=torch.float32, device=dev)
@@ -2017,6 +2022,36 @@ class IdLossPlugin:
     def linear_backward_input(dy, weight):
         """ide3d_linear_backward_input: dy [n, M] @ weight [M, K]."""
         return IdLossPlugin._linear(dy, weight, None, True)
+
+    @staticmethod
+    def linear_weight_grad(dy, x):
+        """ide3d_linear_weight_grad: dy [n, M]^T @ x [n, K] -> [M, K], summed over the images in ascending order (n <= 8, K % 4 == 0)."""
+        IdLossPlugin._f32(dy, 'dy')
+        IdLossPlugin._f32(x, 'x', dy.device)
+        _require(dy.ndim == 2 and x.ndim == 2 and dy.shape[0] == x.shape[0], 'linear_weight_grad: dy [n, M], x [n, K]')
+        dy, x = dy.contiguous(), x.contiguous()
+        (n, M), K = dy.shape, x.shape[1]
+        dw = torch.empty([M, K], dtype=torch.float32, device=dy.device)
+        with _dev_guard(dy.device):
+            rc = load().ide3d_linear_weight_grad(_ptr(dy), _ptr(x), _ptr(dw), n, K, M, _stream(dy))
+        _check(rc, 'linear_weight_grad')
+        return dw
+
+    @staticmethod
+    def residual_join(a, b, gain):
+        """ide3d_residual_join -> (a + b) * gain, or a * gain when b is None, in the shape of a: one launch, bit-equal to the element-wise definition."""
+        IdLossPlugin._f32(a, 'a')
+        _require(a.numel() > 0, 'residual_join: empty operand')
+        a = a.contiguous()
+        if b is not None:
+            IdLossPlugin._f32(b, 'b', a.device)
+            _require(b.shape == a.shape, 'residual_join: a and b must have one shape')
+            b = b.contiguous()
+        out = torch.empty(a.shape, dtype=torch.float32, device=a.device)
+        with _dev_guard(a.device):
+            rc = load().ide3d_residual_join(_ptr(a), _ptr(b), _ptr(out), a.numel(), float(gain), _stream(a))
+        _check(rc, 'residual_join')
+        return out
 
     @staticmethod
     def head(f, target=None):

@@ -11,8 +11,11 @@ bias / activation on csrc/bias_act.hip; module and parameter names equal the ref
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
+from torch_utils import custom_ops
 from torch_utils import persistence
+from training import networks
 from training.networks import Conv2dLayer
 
 
@@ -32,8 +35,63 @@ class EncoderResBlock(torch.nn.Module):
         self.skip = Conv2dLayer(in_channel, out_channel, 1, down=2, activation='linear', bias=False)
 
     def forward(self, x):
-        y = self.conv2(self.conv1(x))
-        return (y + self.skip(x)) * (1 / math.sqrt(2))
+        y, s = self.conv2(self.conv1(x)), self.skip(x)
+        if (networks.hip_plain_conv_grad and networks.use_hip_modconv and torch.is_grad_enabled() and (y.requires_grad or s.requires_grad) and y.shape == s.shape
+                and 0 < y.numel() < 2 ** 40 and all(t.is_cuda and t.dtype == torch.float32 for t in (y, s)) and y.device == s.device):
+            return _ResidualJoin.apply(y, s, 1 / math.sqrt(2))
+        return (y + s) * (1 / math.sqrt(2))
+
+
+class _ResidualJoin(torch.autograd.Function):
+    """(a + b) * gain as one launch (ide3d_residual_join), bit-equal to the two element-wise operators; both branches
+    receive dy * gain, one launch and one tensor."""
+
+    @staticmethod
+    def forward(ctx, a, b, gain):
+        ctx.gain = gain
+        return _id_plugin().residual_join(a.contiguous(), b.contiguous(), gain)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        d = _id_plugin().residual_join(dy.contiguous(), None, ctx.gain) if any(ctx.needs_input_grad[:2]) else None
+        return (d if ctx.needs_input_grad[0] else None), (d if ctx.needs_input_grad[1] else None), None
+
+
+def _id_plugin():
+    return custom_ops.get_plugin(module_name='id_loss_plugin', sources=['id_loss.hip', 'linear_wgrad.hip', 'res_join.hip'])
+
+
+class _ProjectorGrad(torch.autograd.Function):
+    """An `EqualConv2d` whose kernel covers its whole input, as the linear layer it is: y = x2 ws^T with
+    x2 = x.reshape(n, -1) and ws = (weight * scale).reshape(M, -1) (ide3d_linear); dx2 = dy ws (ide3d_linear_backward_input),
+    d weight = scale * dy^T x2 (ide3d_linear_weight_grad)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, scale):
+        P = _id_plugin()
+        x2 = x.reshape(x.shape[0], -1).contiguous()
+        ws = networks._scaled_weight(weight, scale).reshape(weight.shape[0], -1)
+        y = P.linear(x2, ws)
+        ctx.save_for_backward(x2)
+        ctx.ws, ctx.scale, ctx.x_shape, ctx.w_shape = ws, scale, tuple(x.shape), tuple(weight.shape)
+        return y.reshape(x.shape[0], weight.shape[0], 1, 1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        P = _id_plugin()
+        x2, = ctx.saved_tensors
+        dy2 = dy.reshape(x2.shape[0], -1).contiguous()
+        dx = P.linear_backward_input(dy2, ctx.ws).reshape(ctx.x_shape) if ctx.needs_input_grad[0] else None
+        dw = (P.linear_weight_grad(dy2, x2) * ctx.scale).reshape(ctx.w_shape) if ctx.needs_input_grad[1] else None
+        return dx, dw, None
+
+
+def _linear_covers(n, K, M):
+    """The limits of ide3d_linear, ide3d_linear_backward_input and ide3d_linear_weight_grad (csrc/id_loss.hip `id_linear_ok`, csrc/linear_wgrad.hip
+    `linear_wgrad_ok`), restated so that a projector outside them keeps F.conv2d instead of raising."""
+    return 1 <= n <= 8 and K >= 4 and K % 4 == 0 and K <= 2 ** 24 and 1 <= M <= 65535 * 8 and K * M < 2 ** 40
 
 
 @persistence.persistent_class
@@ -48,6 +106,13 @@ class EqualConv2d(torch.nn.Module):
         self.bias = torch.nn.Parameter(torch.zeros(out_channel)) if bias else None
 
     def forward(self, x):
+        k = self.weight.shape[-1]
+        if (networks.hip_plain_conv_grad and networks.use_hip_modconv and torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad)
+                and self.bias is None and self.padding == 0 and self.stride == 1 and x.ndim == 4 and tuple(x.shape[2:]) == (k, k)
+                and x.shape[1] == self.weight.shape[1] and _linear_covers(x.shape[0], x.shape[1] * k * k, self.weight.shape[0])
+                and x.is_cuda and x.dtype == torch.float32 and self.weight.is_cuda and self.weight.dtype == torch.float32
+                and x.device == self.weight.device):
+            return _ProjectorGrad.apply(x, self.weight, self.scale)
         return torch.nn.functional.conv2d(x, self.weight * self.scale, bias=self.bias, stride=self.stride, padding=self.padding)
 
     def extra_repr(self):

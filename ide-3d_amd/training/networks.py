@@ -845,6 +845,124 @@ class FullyConnectedLayer(torch.nn.Module):
         return bias_act.bias_act(x, b, act=self.activation)
 
 
+# ---- trainable plain convolutions (the hybrid encoder's training step) -------------------------------------------
+# With this switch on (opt-in, like `hip_param_grad`; a training loop sets it before its first step), a `Conv2dLayer` whose input or
+# parameters require grad runs its inference launches inside an autograd Function whose backward is HIP too, instead of falling back to
+# conv2d_resample + bias_act through ATen.  Off: every path is what it is without the switch.
+hip_plain_conv_grad = False
+
+
+def _plain_fir_pads(lay, k):
+    """(p0, p1) of the low-pass filter in front of a down-sampling layer's convolution (conv2d_resample.py:73-78,95-103)."""
+    fw = lay.resample_filter.shape[-1]
+    return lay.padding + (fw - lay.down + 1) // 2, lay.padding + (fw - lay.down) // 2
+
+
+def _plain_conv_form(lay, x):
+    """The form of `_PlainConvGrad` that serves this call of a Conv2dLayer: 'conv' (stride 1), 'fir_conv1' (1x1, down 2: FIR with decimation, then
+    the 1x1 convolution) or 'fir_conv3' (3x3, down 2: FIR, then the stride-2 convolution); None when the layer keeps the ATen definition."""
+    k = lay.weight.shape[-1]
+    params = (lay.weight, lay.bias)
+    if not (hip_plain_conv_grad and use_hip_modconv and torch.is_grad_enabled() and x.ndim == 4 and x.is_cuda and x.dtype == torch.float32
+            and all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in params)
+            and (x.requires_grad or any(t is not None and t.requires_grad for t in params))
+            and lay.up == 1 and lay.down in (1, 2) and k in (1, 3) and lay.weight.shape[-2] == k and lay.activation in ('linear', 'lrelu')):
+        return None
+    # bias_act's linear activation passes the gradient through the clamp unmasked (it keeps no y), ide3d_modconv_act_backward masks it
+    if lay.conv_clamp is not None and lay.activation == 'linear':
+        return None
+    n, cin, h, w = x.shape
+    cout = lay.weight.shape[0]
+    if lay.down == 1:
+        form, fh, fw_, oh, ow = 'conv', h, w, h, w
+    else:
+        f = lay.resample_filter
+        if f.ndim != 2 or f.requires_grad or f.shape[0] != f.shape[1] or h % 2 or w % 2:
+            return None
+        p0, p1 = _plain_fir_pads(lay, k)
+        if k == 1:
+            form = 'fir_conv1'
+            fh, fw_ = (h + p0 + p1 - f.shape[0]) // 2 + 1, (w + p0 + p1 - f.shape[0]) // 2 + 1
+            oh, ow = fh, fw_
+            if 2 * fh != h or 2 * fw_ != w:
+                return None
+        else:
+            form = 'fir_conv3'
+            fh, fw_ = h + p0 + p1 - f.shape[0] + 1, w + p0 + p1 - f.shape[0] + 1
+            # the input gradient is the transposed convolution's (2 oh + 1) x (2 ow + 1) map: it must be the FIR output's size
+            if fh < 3 or fw_ < 3 or fh % 2 == 0 or fw_ % 2 == 0:
+                return None
+            oh, ow = (fh - 3) // 2 + 1, (fw_ - 3) // 2 + 1
+    # the launches index with 32 bits
+    if max(x.numel(), n * cin * fh * fw_, n * cout * oh * ow, n * cout * fh * fw_) >= 2 ** 31:
+        return None
+    if not (_modconv_init() and _modconv_grad_init()):
+        return None
+    return form
+
+
+class _PlainConvGrad(torch.autograd.Function):
+    """A trainable Conv2dLayer (up 1, down 1 or 2, k 1 or 3, linear / lrelu): forward = the launches of the layer's inference branches, so
+    that it equals them bit for bit; gradients for x, weight and bias, with ws = weight * weight_gain what the launches read.
+      y = clamp(act(conv(ws, f) + b) * gain),  f = x ('conv'), FIR(x) decimated by 2 ('fir_conv1'), FIR(x) ('fir_conv3', conv of stride 2)
+      dz = dy * act'(.) (K1; skipped where it is the identity),
+      df = conv(ws^T flipped, dz) (ide3d_modconv2d mode 0), or convT(ws^T, dz) (mode 2) for the stride-2 3x3; dx = the FIR adjoint of df
+      (upfirdn2d: flipped filter, the adjoint's padding; zero insertion for the decimating form),
+      dws = the weight gradient: ide3d_modconv_weight_grad mode 0 / mode 1 for 3x3, ide3d_head_weight_grad summed over the images for 1x1;
+      d weight = dws * weight_gain,  d bias = sum_{n,p} dz (K5)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, form, fir, pads, weight_gain, act, gain, clamp):
+        spec = bias_act.activation_funcs[act]
+        ws = _scaled_weight(weight, weight_gain)
+        p0, p1 = pads
+        if form == 'conv':
+            f, mode = x.contiguous(), 0
+        elif form == 'fir_conv1':
+            f, mode = upfirdn2d.upfirdn2d(x, fir, down=2, padding=[p0, p1, p0, p1]).contiguous(), 0
+        else:
+            f, mode = upfirdn2d.upfirdn2d(x, fir, padding=[p0, p1, p0, p1]).contiguous(), 1
+        y = _modconv_plugin.modconv2d(f, ws, None, None, None, 0.0, bias, spec.cuda_idx, spec.def_alpha, gain,
+                                      -1.0 if clamp is None else clamp, mode=mode)
+        ctx.save_for_backward(f, y)
+        ctx.ws, ctx.form, ctx.fir, ctx.pads, ctx.weight_gain, ctx.act, ctx.gain, ctx.clamp = ws, form, fir, pads, weight_gain, act, gain, clamp
+        ctx.x_size, ctx.w_shape = tuple(x.shape[2:]), tuple(weight.shape)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        f, y = ctx.saved_tensors
+        spec = bias_act.activation_funcs[ctx.act]
+        dz = dy.contiguous()
+        if not (ctx.act == 'linear' and ctx.gain == 1 and ctx.clamp is None):
+            dz, _ = _modconv_grad_plugin.act_backward(dz, y, spec.cuda_idx, spec.def_alpha, ctx.gain, -1.0 if ctx.clamp is None else ctx.clamp)
+        form, k = ctx.form, ctx.w_shape[-1]
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            if form == 'fir_conv3':
+                df = _modconv_plugin.modconv2d(dz, _grad_weight(ctx.ws, False), None, None, None, 0.0, None, 1, 0.0, 1.0, -1.0, mode=2)
+            else:
+                df = _modconv_plugin.modconv2d(dz, _grad_weight(ctx.ws, True), None, None, None, 0.0, None, 1, 0.0, 1.0, -1.0)
+            if form == 'conv':
+                dx = df
+            else:
+                # the adjoint of upfirdn2d(x, fir, down, padding) (torch_utils/ops/upfirdn2d.py, _Upfirdn2dHip.backward): up and down exchanged, the filter flipped
+                down = 2 if form == 'fir_conv1' else 1
+                fw, (p0, p1) = ctx.fir.shape[-1], ctx.pads
+                q = [fw - p0 - 1, ctx.x_size[1] - df.shape[3] * down + p0, fw - p0 - 1, ctx.x_size[0] - df.shape[2] * down + p0]
+                dx = upfirdn2d.upfirdn2d(df, ctx.fir, up=down, padding=q, flip_filter=True)
+        if ctx.needs_input_grad[1]:
+            if k == 1:
+                dws = _modconv_grad_plugin.head_weight_grad(dz, f).sum(dim=0)
+            else:
+                dws = _modconv_grad_plugin.weight_grad(dz, f, None, None, mode=(1 if form == 'fir_conv3' else 0))
+            dw = (dws * ctx.weight_gain).reshape(ctx.w_shape)
+        if ctx.needs_input_grad[2]:
+            db = _modconv_grad_plugin.bias_noise_grad(dz)[0]
+        return dx, dw, db, None, None, None, None, None, None, None
+
+
 @persistence.persistent_class
 class Conv2dLayer(torch.nn.Module):
     """Plain (un-modulated) convolution with optional resampling (reference networks.py:170-226)."""
@@ -875,6 +993,11 @@ class Conv2dLayer(torch.nn.Module):
 
     def forward(self, x, gain=1):
         k = self.weight.shape[-1]
+        form = _plain_conv_form(self, x) if hip_plain_conv_grad else None
+        if form is not None:
+            act_clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
+            return _PlainConvGrad.apply(x, self.weight, self.bias, form, self.resample_filter, _plain_fir_pads(self, k) if self.down == 2 else (0, 0),
+                                        self.weight_gain, self.activation, self.act_gain * gain, act_clamp)
         if (self.up == 1 and self.down == 1 and k in (1, 3) and self.activation in ('linear', 'lrelu') and use_hip_modconv
                 and _inference_on_gpu(x, self.weight, self.bias) and _modconv_init()):
             # MI355X inference: conv + bias + activation in ONE launch of the MFMA kernel (csrc/modconv.hip, no modulation)

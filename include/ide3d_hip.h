@@ -522,11 +522,17 @@ int ide3d_head_weight_grad(const float* dy, const float* x, float* dw, int32_t n
  *   mode 0 (stride 1, pad 1, correlation; ide3d_modconv2d mode 0): g [n, cout, h, w],
  *          dw[o, i, ky, kx] = sum_n dcoefs[n, o] styles[n, i] sum_{y,x} g[n, o, y, x] x[n, i, y + ky - 1, x + kx - 1];
  *   mode 2 (transposed, stride 2, pad 0; ide3d_modconv2d mode 2): g [n, cout, 2h + 1, 2w + 1],
- *          dw[o, i, ky, kx] = sum_n dcoefs[n, o] styles[n, i] sum_{y,x} g[n, o, 2y + ky, 2x + kx] x[n, i, y, x].
+ *          dw[o, i, ky, kx] = sum_n dcoefs[n, o] styles[n, i] sum_{y,x} g[n, o, 2y + ky, 2x + kx] x[n, i, y, x];
+ *   mode 1 (stride 2, pad 0, correlation; ide3d_modconv2d mode 1; the encoders' down-sampling layers):
+ *          g [n, cout, gh, gw] with gh = (h - 3) / 2 + 1, gw = (w - 3) / 2 + 1 (h, w >= 3, else IDE3D_EINVAL),
+ *          dw[o, i, ky, kx] = sum_n dcoefs[n, o] styles[n, i] sum_{y,x} g[n, o, y, x] x[n, i, 2y + ky, 2x + kx];
+ *          the last row (column) of x is never read when h (w) is even.
  * x [n, cin, h, w]; all dense.  arith: 0 = the process arithmetic (ide3d_get_conv_arithmetic), 1 = exact fp32 products
  * (v_mfma_f32_32x32x2_f32), 6 = bf16x6; 3 (bf16x3) and 16 (f16x3) run bf16x6.  Split-K partial slices per (image, pixel range) in the
- * workspace (ide3d_wgrad_workspace_bytes(), the same for both modes), added in a fixed order by a second launch: bit-reproducible, no
- * atomics.  Exclusive residency (its matrix loop is LDS-fed bf16).
+ * workspace, added in a fixed order by a second launch: bit-reproducible, no atomics.  Exclusive residency (its matrix loop is LDS-fed
+ * bf16).  ide3d_wgrad_workspace_bytes(n, cin, cout, h, w): (h, w) is the grid of pixels the sum runs over, which is the size of x in
+ * modes 0 and 2 (the same value for both) and the size of g, (gh, gw), in mode 1; a workspace sized for another grid is refused with
+ * IDE3D_EINVAL when it is too small, never indexed past its end.
  */
 typedef struct ide3d_wgrad_params {
     const float* g;
@@ -959,6 +965,12 @@ int ide3d_parse_stem_backward(const float* dz, const float* weight, float* dx, i
  *   (ide3d_linear_workspace_bytes(); -1: not covered), a finishing launch adds them in ascending order in float64.
  * ide3d_linear_backward_input — dx [n, K] = dy [n, M] weight under the same limits: partial sums per 64 rows of the weight
  *   (ide3d_linear_backward_input_workspace_bytes(), 16-byte aligned) + the same finishing launch.
+ * ide3d_linear_weight_grad — dw [M, K] = dy [n, M]^T x [n, K], summed over the images in ascending order, under the same limits (x and dw
+ *   16-byte aligned): one launch, no workspace (the encoders' trainable projectors; csrc/linear_wgrad.hip).
+ * ide3d_residual_join — out[i] = (a[i] + b[i]) * gain over `count` dense floats, or a[i] * gain when b is NULL: the join of the encoders'
+ *   residual blocks, (conv2(conv1(x)) + skip(x)) / sqrt(2) (inversion/networks.py:1507-1521), and with b NULL the gradient dy * gain that
+ *   both of its branches receive.  One fp32 addition, then one fp32 multiplication: bit-equal to the element-wise definition.  count in
+ *   [1, 2^40); out overlaps neither input; 16-byte accesses when every operand is 16-byte aligned (csrc/res_join.hip).
  * ide3d_id_head — `l2_norm` and the loss (helpers.py:14-17, id_loss.py:26-47): e [n, M] = f / |f|, norm [n] = |f|, and, when target (unit
  *   vectors [n, M]) is not NULL, loss[0] = sum_i (1 - e_i . target_i) / n.  |f| = 0 divides by zero as the reference does.
  * ide3d_id_head_backward — df = (g - e (e . g)) / |f| with g = -dloss target / n.  dloss: DEVICE pointer to the upstream scalar gradient.
@@ -977,6 +989,8 @@ int ide3d_linear(const float* x, const float* weight, const float* bias, float* 
                  int64_t workspace_bytes, void* stream);
 int ide3d_linear_backward_input(const float* dy, const float* weight, float* dx, int32_t n, int32_t K, int32_t M, float* workspace,
                                 int64_t workspace_bytes, void* stream);
+int ide3d_linear_weight_grad(const float* dy, const float* x, float* dw, int32_t n, int32_t K, int32_t M, void* stream);
+int ide3d_residual_join(const float* a, const float* b, float* out, int64_t count, float gain, void* stream);
 int ide3d_id_head(const float* f, const float* target, float* e, float* norm, float* loss, int32_t n, int32_t M, void* stream);
 int ide3d_id_head_backward(const float* e, const float* target, const float* norm, const float* dloss, float* df, int32_t n, int32_t M,
                            void* stream);
