@@ -391,6 +391,10 @@ def load():
             'ide3d_lpips_head_workspace_bytes': [ctypes.POINTER(_LpipsTap), i32, i32],
             'ide3d_lpips_head': [ctypes.POINTER(_LpipsTap), i32, i32, vp, i64, vp, vp],
             'ide3d_lpips_head_backward': [ctypes.POINTER(_LpipsTap), i32, i32, vp, vp],
+            'ide3d_unfold2d': [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+            'ide3d_fold2d': [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+            'ide3d_maxpool3s2p0': [vp, vp, vp, i64, i32, i32, vp],
+            'ide3d_lpips_tap_backward': [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
             'ide3d_resize_bilinear': [vp, vp, i64, i32, i32, i32, i32, vp],
             'ide3d_resize_bilinear_backward': [vp, vp, i64, i32, i32, i32, i32, vp],
             'ide3d_parse_ce_workspace_bytes': [i32, i32, i32, i32, i32, i32],
@@ -458,6 +462,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_render_camera_grad_workspace_bytes', 'ide3d_render_rays_backward_camera',
     'ide3d_lpips_prep', 'ide3d_lpips_prep_backward', 'ide3d_maxpool2', 'ide3d_lpips_stage_backward', 'ide3d_lpips_head_workspace_bytes',
     'ide3d_lpips_head', 'ide3d_lpips_head_backward',
+    'ide3d_unfold2d', 'ide3d_fold2d', 'ide3d_maxpool3s2p0', 'ide3d_lpips_tap_backward',
     'ide3d_resize_bilinear', 'ide3d_resize_bilinear_backward', 'ide3d_parse_ce_workspace_bytes', 'ide3d_parse_ce', 'ide3d_parse_ce_backward',
     'ide3d_maxpool3s2', 'ide3d_maxpool3s2_backward', 'ide3d_parse_join', 'ide3d_plane_sums', 'ide3d_parse_stem_backward',
     'ide3d_id_prep', 'ide3d_id_prep_backward', 'ide3d_prelu', 'ide3d_prelu_backward', 'ide3d_se_gate', 'ide3d_se_gate_backward',
@@ -1713,6 +1718,81 @@ class LpipsPlugin:
         return outs
 
 
+class LpipsAlexPlugin:
+    """The streaming passes of the AlexNet LPIPS distance and its image gradient beside `LpipsPlugin` (csrc/lpips_alex.hip, DESIGN.md
+    section 5.20).  Every tensor is a contiguous float32 CUDA tensor on one device (the winner bytes: uint8)."""
+
+    @staticmethod
+    def _geometry(h, w, k, stride, pad):
+        _require(1 <= k <= 16 and 1 <= stride <= k and 0 <= pad < k and h + 2 * pad >= k and w + 2 * pad >= k,
+                 'lpips_alex: 1 <= k <= 16, 1 <= stride <= k, 0 <= pad < k and at least one window per side')
+        return (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+
+    @staticmethod
+    def unfold2d(x, k, stride, pad):
+        """ide3d_unfold2d: x [n, c, h, w] -> [n, c k k, ho, wo], bit-equal to F.unfold(x, k, padding=pad, stride=stride).reshape(...)."""
+        LpipsPlugin._f32(x, 'x')
+        _require(x.ndim == 4, 'unfold2d: x [n, c, h, w]')
+        n, c, h, w = x.shape
+        ho, wo = LpipsAlexPlugin._geometry(h, w, k, stride, pad)
+        col = torch.empty([n, c * k * k, ho, wo], dtype=torch.float32, device=x.device)
+        with _dev_guard(x.device):
+            rc = load().ide3d_unfold2d(_ptr(x), _ptr(col), n, c, h, w, int(k), int(stride), int(pad), _stream(x))
+        _check(rc, 'unfold2d')
+        return col
+
+    @staticmethod
+    def fold2d(dcol, size, k, stride, pad):
+        """ide3d_fold2d: dcol [n, c k k, ho, wo] -> dx [n, c, h, w] for size = (h, w): the adjoint of `unfold2d`."""
+        LpipsPlugin._f32(dcol, 'dcol')
+        h, w = (int(v) for v in size)
+        ho, wo = LpipsAlexPlugin._geometry(h, w, k, stride, pad)
+        _require(dcol.ndim == 4 and dcol.shape[1] % (k * k) == 0 and tuple(dcol.shape[2:]) == (ho, wo),
+                 f'fold2d: dcol must be [n, c * {k * k}, {ho}, {wo}], got {list(dcol.shape)}')
+        n, c = dcol.shape[0], dcol.shape[1] // (k * k)
+        dx = torch.empty([n, c, h, w], dtype=torch.float32, device=dcol.device)
+        with _dev_guard(dcol.device):
+            rc = load().ide3d_fold2d(_ptr(dcol), _ptr(dx), n, c, h, w, int(k), int(stride), int(pad), _stream(dcol))
+        _check(rc, 'fold2d')
+        return dx
+
+    @staticmethod
+    def maxpool3s2p0(x, want_idx=True):
+        """ide3d_maxpool3s2p0: [n, c, h, w] -> (y [n, c, (h-3)//2+1, (w-3)//2+1] bit-equal to F.max_pool2d(x, 3, 2), winner bytes or None)."""
+        LpipsPlugin._f32(x, 'x')
+        _require(x.ndim == 4 and x.shape[2] >= 3 and x.shape[3] >= 3, 'maxpool3s2p0: x [n, c, h, w] with h, w >= 3')
+        n, c, h, w = x.shape
+        y = torch.empty([n, c, (h - 3) // 2 + 1, (w - 3) // 2 + 1], dtype=torch.float32, device=x.device)
+        idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device) if want_idx else None
+        with _dev_guard(x.device):
+            rc = load().ide3d_maxpool3s2p0(_ptr(x), _ptr(y), _ptr(idx), n * c, h, w, _stream(x))
+        _check(rc, 'maxpool3s2p0')
+        return y, idx
+
+    @staticmethod
+    def tap_backward(y, g, idx, dtap):
+        """ide3d_lpips_tap_backward -> dz = (route(g) + dtap) where y > 0, else 0.  idx given: g is the gradient of the 3x3 stride-2 pool of
+        y, routed through the winner bytes; idx None: g has y's shape and is added as it is, or is None."""
+        LpipsPlugin._f32(y, 'y')
+        _require(y.ndim == 4, 'lpips tap_backward: y [n, c, h, w]')
+        n, c, h, w = y.shape
+        LpipsPlugin._f32(dtap, 'dtap', y.device, y.shape)
+        pooled = idx is not None
+        if pooled:
+            _require(g is not None and h >= 3 and w >= 3, 'lpips tap_backward: winner bytes need a pooled gradient and h, w >= 3')
+            ps = (n, c, (h - 3) // 2 + 1, (w - 3) // 2 + 1)
+            LpipsPlugin._f32(g, 'g', y.device, ps)
+            _require(idx.is_cuda and idx.dtype == torch.uint8 and idx.is_contiguous() and idx.device == y.device and tuple(idx.shape) == ps,
+                     f'lpips tap_backward: idx must be a contiguous uint8 CUDA tensor {list(ps)}')
+        elif g is not None:
+            LpipsPlugin._f32(g, 'g', y.device, y.shape)
+        dz = torch.empty_like(y)
+        with _dev_guard(y.device):
+            rc = load().ide3d_lpips_tap_backward(_ptr(y), _ptr(g), _ptr(idx), _ptr(dtap), _ptr(dz), n * c, h, w, int(pooled), _stream(y))
+        _check(rc, 'lpips_tap_backward')
+        return dz
+
+
 class ParseLossPlugin:
     """The passes between the convolutions of the face parser's cross-entropy loss and its image gradient (csrc/parse_loss.hip, DESIGN.md
     section 5.16).  Tensors are float32 CUDA tensors; dense NCHW unless a method says otherwise."""
@@ -2547,6 +2627,7 @@ PLUGINS = {
     'resample_plugin': ResamplePlugin,
     'mapping_plugin': MappingPlugin,
     'lpips_plugin': LpipsPlugin,
+    'lpips_alex_plugin': LpipsAlexPlugin,
     'parse_loss_plugin': ParseLossPlugin,
     'id_loss_plugin': IdLossPlugin,
 }

@@ -13,8 +13,9 @@ Reference: `inversion/criteria/lpips/{lpips,networks,utils}.py` (the class the c
 Parameter and buffer names equal the reference class's (`net.layers.{0,2,5,...,28}.{weight,bias}`, `net.mean`, `net.std`,
 `lin.{0..4}.1.weight`), so a `state_dict` saved from its `LPIPS('vgg')` loads as is; `load_torchvision_state_dict` takes torchvision's
 `features.N.*` keys and the five `lin` tensors.  Nothing here downloads: WITHOUT LOADED WEIGHTS THE NET IS RANDOMLY INITIALISED and the
-value is not LPIPS.  Only 'vgg' exists: AlexNet and SqueezeNet need 11x11, 5x5 and strided convolutions, which the convolution kernel of
-this library does not have.
+value is not LPIPS.  Only 'vgg' exists in this module: AlexNet and SqueezeNet need 11x11, 5x5 and strided convolutions, which the
+convolution kernel of this library does not have.  The AlexNet form (the reference's default) is `training.lpips_alex.LPIPS()`, which runs
+those convolutions as 1x1 launches over unfolded patches.
 
 One deliberate difference from the reference: at a pixel whose tap is zero in every channel, the reference's autograd returns NaN (the
 derivative of sqrt at 0).  Here the gradient of that pixel's norm is DEFINED as 0 — in the kernels and in the torch definition below alike,

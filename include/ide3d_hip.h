@@ -881,6 +881,40 @@ int ide3d_lpips_head(const ide3d_lpips_tap* taps, int32_t k, int32_t n, float* w
 int ide3d_lpips_head_backward(const ide3d_lpips_tap* taps, int32_t k, int32_t n, const float* dloss, void* stream);
 
 /*
+ * ABI 8 (entry points added).  The AlexNet LPIPS distance — the reference's default, `LPIPS(net_type='alex')`
+ * (inversion/criteria/lpips/lpips.py:16, networks.py:76-84: torchvision's alexnet().features, taps behind layers 1, 4, 7, 9, 11;
+ * apps/train_hybrid_encoder.py:235, inversion/configs/hyperparameters.py `lpips_type`, base_coach.py:44) — and its image gradient: what it
+ * needs beside the VGG16 block above (csrc/lpips_alex.hip).  Prep, head and their gradients are the entry points
+ * above; all five convolutions and their input gradients are ide3d_modconv2d, the 11x11 stride-4 stem and the 5x5 layer at k = 1 over
+ * unfolded patches.  All tensors dense NCHW fp32 in device memory.  No atomics, fixed-order sums, bit-reproducible; no host synchronisation.
+ *
+ * ide3d_unfold2d — `F.unfold(x, k, padding=pad, stride=stride)` as [n, c k k, ho, wo], ho = (h + 2 pad - k) / stride + 1 (floor), wo
+ *   likewise: channel (ci k + ky) k + kx at (oy, ox) is x[ci, oy stride + ky - pad, ox stride + kx - pad], 0 outside the image.  That is the
+ *   order of weight.reshape(cout, c k k, 1, 1), so `Conv2d(3, 64, 11, 4, 2)` and `Conv2d(64, 192, 5, 1, 2)` (torchvision alexnet features
+ *   0 and 3) are 1x1 convolutions over col.  1 <= k <= 16, 1 <= stride <= k, 0 <= pad < k, ho, wo >= 1, fewer than 2^31 elements in x and
+ *   in col.
+ * ide3d_fold2d — its adjoint (autograd's walk back through the unfolding) in gather form: dx[ci, y, x] = the sum over ky then kx ascending
+ *   of dcol[(ci k + ky) k + kx, (y + pad - ky) / stride, (x + pad - kx) / stride] where both divisions are exact and the position lies
+ *   inside ho x wo (<= ceil(k / stride)^2 terms, summed in float64 and rounded once); a row or column that no window reaches gets an
+ *   exact 0.  The same limits.
+ * ide3d_maxpool3s2p0 — `MaxPool2d(3, 2)` (torchvision alexnet features 2 and 5): [planes, h, w] -> [planes, (h-3)/2+1, (w-3)/2+1],
+ *   h, w >= 3, bit-equal to ATen's (the first maximum in row-major window order wins, NaN wins); idx (may be NULL): one byte per output,
+ *   the winner as ky * 3 + kx.  (ide3d_maxpool3s2 is the padding-1 geometry.)
+ * ide3d_lpips_tap_backward — at a tap (networks.py:56-59: the activation feeds the tap AND the next layer), what autograd does in three
+ *   passes: dz = (route(g) + dtap) where y > 0, else 0; y, dtap, dz [planes, h, w].  pooled = 1: g [planes, (h-3)/2+1, (w-3)/2+1] and idx
+ *   the forward's winner bytes; each pixel sums g over the <= 4 windows whose winner it is, window rows then columns ascending; a row or
+ *   column that the floor dropped receives dtap only.  pooled = 0: g [planes, h, w] is added as it is (a tap that feeds the next
+ *   convolution directly), or g == NULL: the last tap, dtap alone.
+ */
+int ide3d_unfold2d(const float* x, float* col, int32_t n, int32_t c, int32_t h, int32_t w, int32_t k, int32_t stride, int32_t pad,
+                   void* stream);
+int ide3d_fold2d(const float* dcol, float* dx, int32_t n, int32_t c, int32_t h, int32_t w, int32_t k, int32_t stride, int32_t pad,
+                 void* stream);
+int ide3d_maxpool3s2p0(const float* x, float* y, uint8_t* idx, int64_t planes, int32_t h, int32_t w, void* stream);
+int ide3d_lpips_tap_backward(const float* y, const float* g, const uint8_t* idx, const float* dtap, float* dz, int64_t planes, int32_t h,
+                             int32_t w, int32_t pooled, void* stream);
+
+/*
  * ABI 8 (entry points added).  The cross-entropy of the BiSeNet face parser's logits against integer labels and its image gradient through
  * the frozen parser (apps/train_hybrid_encoder.py:279-283, 324-328, apps/finetune_hybrid_encoder.py:170-174): everything between the
  * convolutions (csrc/parse_loss.hip; the convolutions and all but one of their input gradients are
