@@ -593,6 +593,7 @@ filtered_lrelu_act_kernel(T* __restrict__ x, uint8_t* __restrict__ s, int n, int
                           int64_t sn, int64_t sc, int64_t sh, int64_t sw_,
                           int s_w, int s_h, int s_ofs_x, int s_ofs_y, float gain, float slope, float clamp) {
     // One thread handles 4 horizontally consecutive elements = one sign byte.
+    using M = typename Elem<T>::math_t;
     const int gw = SIGN == 1 ? s_w : w;                 // logical launch width
     const int gh = SIGN == 1 ? s_h : h;
     const int gw4 = (gw + 3) / 4;
@@ -610,24 +611,24 @@ filtered_lrelu_act_kernel(T* __restrict__ x, uint8_t* __restrict__ s, int n, int
         for (int j = 0; j < 4; ++j) {
             const int xx = x4 + j;
             if (xx < w && yy < h) {
-                float v = (float)Elem<T>::ld(row + xx * sw_) * gain;
+                M v = (M)Elem<T>::ld(row + xx * sw_) * (M)gain;          // (math type of T: the float64 route of the generic path stays float64)
                 if (SIGN == 1) {
                     unsigned code = 0;
-                    if (v < 0.f) { v *= slope; code = 1; }
-                    if (fabsf(v) > clamp) { v = copysignf(clamp, v); code = 2; }
+                    if (v < (M)0) { v *= (M)slope; code = 1; }
+                    if ((v < (M)0 ? -v : v) > (M)clamp) { v = v < (M)0 ? -(M)clamp : (M)clamp; code = 2; }
                     packed |= code << (2 * j);
                 } else if (SIGN == 2) {
                     const int sx = xx + s_ofs_x, sy = yy + s_ofs_y;
                     if (sx >= 0 && sx < s_w && sy >= 0 && sy < s_h) {
                         const unsigned code = (s[(q * s_h + sy) * (int64_t)(s_w >> 2) + (sx >> 2)] >> ((sx & 3) << 1)) & 3u;
-                        if (code & 1u) v *= slope;
-                        if (code & 2u) v = 0.f;
+                        if (code & 1u) v *= (M)slope;
+                        if (code & 2u) v = (M)0;
                     }
                 } else {
-                    if (v < 0.f) v *= slope;
-                    if (fabsf(v) > clamp) v = copysignf(clamp, v);
+                    if (v < (M)0) v *= (M)slope;
+                    if ((v < (M)0 ? -v : v) > (M)clamp) v = v < (M)0 ? -(M)clamp : (M)clamp;
                 }
-                Elem<T>::st(row + xx * sw_, (typename Elem<T>::math_t)v);
+                Elem<T>::st(row + xx * sw_, v);
             }
         }
         if (SIGN == 1 && x4 < s_w)

@@ -117,6 +117,7 @@ class _FilteredLReluHip(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, fu, fd, b, signs, sx, sy, cfg):
         assert isinstance(x, torch.Tensor) and x.ndim == 4
+        fu_none, fd_none = fu is None, fd is None
         fu = _as_2d_filter(fu, cfg.up, x.device)
         fd = _as_2d_filter(fd, cfg.down, x.device)
         have_signs = signs is not None and signs.numel() > 0
@@ -132,8 +133,11 @@ class _FilteredLReluHip(torch.autograd.Function):
         pads = (cfg.px0, cfg.px1, cfg.py0, cfg.py1)
         rc = -1
         if x.dtype in (torch.float16, torch.float32, torch.bfloat16):
-            # the HIP kernel keeps both filters in LDS (no global constant buffer): safe on concurrent streams
-            y, codes, rc = _plugin.filtered_lrelu(x, fu, fd, b, signs, cfg.up, cfg.down, *pads, sx, sy,
+            # the HIP kernel keeps both filters in LDS (no global constant buffer): safe on concurrent streams.  An absent filter goes to it as ONE
+            # separable tap of 1, not as the 2-D [[1]] of the other paths: the kernel's compile-time instances are separable, and (2, 1, 12, 1) /
+            # (1, 2, 1, 12) - the layers without a down- / up-sampling filter and their gradients - are reached by nothing else
+            ku, kd = (f2.reshape(1) if none else f2 for f2, none in ((fu, fu_none), (fd, fd_none)))
+            y, codes, rc = _plugin.filtered_lrelu(x, ku, kd, b, signs, cfg.up, cfg.down, *pads, sx, sy,
                                                   cfg.gain, cfg.slope, cfg.clamp, cfg.flip, record)
         if rc < 0:
             warnings.warn('filtered_lrelu called with parameters that have no fused HIP kernel, using generic path', RuntimeWarning)
@@ -144,6 +148,7 @@ class _FilteredLReluHip(torch.autograd.Function):
 
         ctx.save_for_backward(fu, fd, signs if have_signs else codes)
         ctx.cfg, ctx.in_hw, ctx.out_hw, ctx.sign_ofs = cfg, tuple(x.shape[2:]), tuple(y.shape[2:]), (sx, sy)
+        ctx.absent = (fu_none, fd_none)
         return y
 
     @staticmethod
@@ -163,7 +168,7 @@ class _FilteredLReluHip(torch.autograd.Function):
                            px0=taps_x - cfg.px0, px1=xw * cfg.up - yw * cfg.down + cfg.px0 - (cfg.up - 1),
                            py0=taps_y - cfg.py0, py1=xh * cfg.up - yh * cfg.down + cfg.py0 - (cfg.up - 1),
                            gain=cfg.gain * cfg.up ** 2 / cfg.down ** 2, slope=cfg.slope, clamp=float('inf'), flip=not cfg.flip)
-            dx = _FilteredLReluHip.apply(dy, fd, fu, None, codes, sx - (fu.shape[-1] - 1) + cfg.px0, sy - (fu.shape[0] - 1) + cfg.py0, back)
+            dx = _FilteredLReluHip.apply(dy, None if ctx.absent[1] else fd, None if ctx.absent[0] else fu, None, codes, sx - (fu.shape[-1] - 1) + cfg.px0, sy - (fu.shape[0] - 1) + cfg.py0, back)
             if need_b:
                 db = dx.sum([0, 2, 3])
         return dx, None, None, db, None, None, None, None
