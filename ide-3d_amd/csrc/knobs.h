@@ -5,7 +5,6 @@
 //
 //   read ONCE per process (`knobs()`, first use):
 //     IDE3D_CONV_ARITH = fp32 | bf16x6 | bf16x3 | f16x3        process default of ide3d_set_conv_arithmetic (include/ide3d_hip.h)
-//     IDE3D_GATHER_PC=4|8|0                                    ray-grid tri-plane gather: producer / consumer kernel with 4 or 8 blending waves, or the 4-wave kernel (triplane_tile.hip)
 //     IDE3D_MAPPING_PER_LAYER                                  mapping network as one launch per layer (the form of devices where the one-launch kernel is not co-resident)
 //   read PER CALL (`knob_live`): the six fallbacks that tests/ flip inside one process to compare a lean kernel with the form it replaced
 //     IDE3D_FIR_NO_LEAN  IDE3D_FIR_NO_CELL  IDE3D_BIAS_ACT_NO_PLANES  IDE3D_MODCONV_NO_STRIP  IDE3D_MODCONV_PAIR=0|2
@@ -18,7 +17,6 @@ namespace ide3d {
 
 struct Knobs {
     int conv_arith;                                   // 1 / 3 / 6 / 16
-    int gather_pc;
     bool mapping_per_layer;
 };
 
@@ -28,8 +26,6 @@ inline const Knobs& knobs() {
         const char* a = getenv("IDE3D_CONV_ARITH");
         k.conv_arith = !a ? 6 : (!strcmp(a, "fp32") || !strcmp(a, "1")) ? 1 : (!strcmp(a, "bf16x3") || !strcmp(a, "3")) ? 3
                      : (!strcmp(a, "f16x3") || !strcmp(a, "16")) ? 16 : 6;
-        const char* pc = getenv("IDE3D_GATHER_PC");
-        k.gather_pc = pc ? atoi(pc) : 8;
         k.mapping_per_layer = getenv("IDE3D_MAPPING_PER_LAYER") != nullptr;
         return k;
     }();

@@ -84,21 +84,6 @@ int main(int argc, char** argv) {
         }
         // phase trace of libraries built with -DIDE3D_TT_TRACE (cycle stamps of one wave, see triplane_tile.hip)
         typedef int (*dbg_fn)(unsigned long long*);
-        if (dbg_fn dbg = (dbg_fn)dlsym(lib, "ide3d_debug_tt")) {
-            unsigned long long v[256];
-            if (dbg(v) == 0) {
-                printf("  chunk: cycles between stamps [0-1 bbox reduce, 1-2 barrier 1, 2-3 region table + issue A/B, 3-4 tap table + fetch + LDS fill, 4-5 barrier 2, 5-6 blend], total\n");
-                for (int ch = 0; ch < 24; ++ch) {
-                    const unsigned long long* r = v + ch * 8;
-                    if (!r[0]) continue;
-                    printf("  %2d:", ch);
-                    for (int i = 0; i < 6; ++i) printf(" %6llu", r[i + 1] - r[i]);
-                    printf("  total %6llu", r[6] - r[0]);
-                    if (ch > 0 && v[(ch - 1) * 8]) printf("  (start-to-start %6llu)", r[0] - v[(ch - 1) * 8]);
-                    printf("\n");
-                }
-            }
-        }
         // producer / consumer kernel (round 3): stamps of wave 0 of each role of one workgroup, per iteration
         if (dbg_fn dbgp = (dbg_fn)dlsym(lib, "ide3d_debug_tt_pc")) {
             static unsigned long long v[3][32][8];
@@ -114,19 +99,6 @@ int main(int argc, char** argv) {
                     printf("  total %6lld |", (long long)(f[3] - f[0]));
                     for (int i = 0; i < 2; ++i) printf(" %6lld", (long long)(b[i + 1] - b[i]));
                     printf("  total %6lld\n", (long long)(b[2] - b[0]));
-                }
-            }
-        }
-        if (dbg_fn dbgr = (dbg_fn)dlsym(lib, "ide3d_debug_tt_pc_r")) {
-            static unsigned long long v[32][8];
-            if (dbgr(&v[0][0]) == 0 && v[1][0]) {
-                printf("  region-builder wave (IDE3D_PC_RWAVE builds): [copy + issue next loads, index arithmetic, reduce, table, barrier wait] total\n");
-                for (int it = 0; it < 24; ++it) {
-                    const unsigned long long* r = v[it];
-                    if (!r[0]) continue;
-                    printf("  %2d:", it);
-                    for (int i = 0; i < 5; ++i) printf(" %6lld", (long long)(r[i + 1] - r[i]));
-                    printf("  total %6lld\n", (long long)(r[5] - r[0]));
                 }
             }
         }
