@@ -268,6 +268,14 @@ class _LpipsTap(ctypes.Structure):
     ]
 
 
+class _FeatL1Tap(ctypes.Structure):
+    """Mirror of ide3d_feat_l1_tap."""
+    _fields_ = [
+        ('a', ctypes.c_void_p), ('t', ctypes.c_void_p), ('weight', ctypes.c_float),
+        ('c', ctypes.c_int32), ('h', ctypes.c_int32), ('w', ctypes.c_int32),
+    ]
+
+
 PARSE_JOIN_TERMS = 3          # IDE3D_PARSE_JOIN_TERMS
 
 
@@ -395,6 +403,10 @@ def load():
             'ide3d_fold2d': [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
             'ide3d_maxpool3s2p0': [vp, vp, vp, i64, i32, i32, vp],
             'ide3d_lpips_tap_backward': [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
+            'ide3d_feat_l1_workspace_bytes': [ctypes.POINTER(_FeatL1Tap), i32, i32],
+            'ide3d_feat_l1': [ctypes.POINTER(_FeatL1Tap), i32, i32, vp, i64, vp, vp],
+            'ide3d_feat_l1_tap_backward': [vp, vp, vp, vp, vp, f32, i64, i32, i32, i64, vp],
+            'ide3d_maxpool2_relu_backward': [vp, vp, vp, i64, i32, i32, vp],
             'ide3d_resize_bilinear': [vp, vp, i64, i32, i32, i32, i32, vp],
             'ide3d_resize_bilinear_backward': [vp, vp, i64, i32, i32, i32, i32, vp],
             'ide3d_parse_ce_workspace_bytes': [i32, i32, i32, i32, i32, i32],
@@ -463,6 +475,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_lpips_prep', 'ide3d_lpips_prep_backward', 'ide3d_maxpool2', 'ide3d_lpips_stage_backward', 'ide3d_lpips_head_workspace_bytes',
     'ide3d_lpips_head', 'ide3d_lpips_head_backward',
     'ide3d_unfold2d', 'ide3d_fold2d', 'ide3d_maxpool3s2p0', 'ide3d_lpips_tap_backward',
+    'ide3d_feat_l1_workspace_bytes', 'ide3d_feat_l1', 'ide3d_feat_l1_tap_backward', 'ide3d_maxpool2_relu_backward',
     'ide3d_resize_bilinear', 'ide3d_resize_bilinear_backward', 'ide3d_parse_ce_workspace_bytes', 'ide3d_parse_ce', 'ide3d_parse_ce_backward',
     'ide3d_maxpool3s2', 'ide3d_maxpool3s2_backward', 'ide3d_parse_join', 'ide3d_plane_sums', 'ide3d_parse_stem_backward',
     'ide3d_id_prep', 'ide3d_id_prep_backward', 'ide3d_prelu', 'ide3d_prelu_backward', 'ide3d_se_gate', 'ide3d_se_gate_backward',
@@ -611,7 +624,7 @@ class _Workspaces:
 
 def _drop_owner(domain):
     _scope_finalizers.pop(domain, None)
-    for plugin in (ModconvPlugin, MappingPlugin, LowresPlugin, VolumeRenderPlugin):
+    for plugin in (ModconvPlugin, MappingPlugin, LowresPlugin, VolumeRenderPlugin, VggLossPlugin):
         plugin._ws.drop(domain)
 
 
@@ -1793,6 +1806,68 @@ class LpipsAlexPlugin:
         return dz
 
 
+class VggLossPlugin:
+    """The streaming passes of the VGG19 feature loss and its image gradient beside `LpipsPlugin` (csrc/vgg_loss.hip, DESIGN.md section
+    5.22).  Every tensor is a contiguous float32 CUDA tensor on one device."""
+
+    _ws = _Workspaces()          # (bytes, device index, launch domain) -> the per-workgroup partial sums of feat_l1
+
+    @staticmethod
+    def feat_l1(acts, targets, weights):
+        """ide3d_feat_l1 -> loss [] float32: sum_k weights[k] * mean |acts[k] - targets[k]|."""
+        k = len(acts)
+        _require(1 <= k <= LPIPS_MAX_TAPS and len(targets) == k and len(weights) == k, f'feat_l1: 1..{LPIPS_MAX_TAPS} taps, a target and a weight for each')
+        dev, n = acts[0].device, acts[0].shape[0]
+        taps = (_FeatL1Tap * k)()
+        for i, (a, t, wt) in enumerate(zip(acts, targets, weights)):
+            LpipsPlugin._f32(a, 'tap', dev)
+            _require(a.ndim == 4 and a.shape[0] == n, 'feat_l1: every tap must be [n, c, h, w]')
+            taps[i].a, taps[i].t = a.data_ptr(), LpipsPlugin._f32(t, 'target', dev, a.shape).data_ptr()
+            taps[i].weight, (taps[i].c, taps[i].h, taps[i].w) = float(wt), a.shape[1:]
+        lib = load()
+        nbytes = lib.ide3d_feat_l1_workspace_bytes(taps, k, n)
+        _require(nbytes > 0, 'feat_l1: unsupported taps')
+        ws = VggLossPlugin._ws.entry((nbytes, dev.index, _ws_domain(dev)), lambda: torch.empty([nbytes // 8], dtype=torch.float64, device=dev))[0]
+        loss = torch.empty([], dtype=torch.float32, device=dev)
+        with _dev_guard(dev):
+            rc = lib.ide3d_feat_l1(taps, k, n, _ptr(ws), nbytes, _ptr(loss), _stream(acts[0]))
+        _check(rc, 'feat_l1')
+        return loss
+
+    @staticmethod
+    def feat_l1_tap_backward(a, t, g, dloss, weight):
+        """ide3d_feat_l1_tap_backward -> dz = (g + s sign(a - t)) where a > 0, else 0, s = fp32(double(dloss) * weight / a.numel()); g: the
+        next convolution's input gradient, or None at the last tap; dloss: a one-element float32 tensor on the device."""
+        LpipsPlugin._f32(a, 'a')
+        _require(a.ndim == 4, 'feat_l1_tap_backward: a [n, c, h, w]')
+        n, c, h, w = a.shape
+        LpipsPlugin._f32(t, 't', a.device, a.shape)
+        if g is not None:
+            LpipsPlugin._f32(g, 'g', a.device, a.shape)
+        _require(dloss.is_cuda and dloss.dtype == torch.float32 and dloss.device == a.device and dloss.numel() == 1,
+                 'feat_l1_tap_backward: dloss must be one float32 on the device')
+        dloss = dloss.contiguous()
+        dz = torch.empty_like(a)
+        with _dev_guard(a.device):
+            rc = load().ide3d_feat_l1_tap_backward(_ptr(a), _ptr(t), _ptr(g), _ptr(dz), _ptr(dloss), float(weight), n * c, h, w, a.numel(), _stream(a))
+        _check(rc, 'feat_l1_tap_backward')
+        return dz
+
+    @staticmethod
+    def maxpool2_relu_backward(y, dpool):
+        """ide3d_maxpool2_relu_backward -> dz = dpool routed to the first maximum of its 2x2 window where y > 0, else 0; y a ReLU output
+        [n, c, h, w], dpool [n, c, h // 2, w // 2]."""
+        LpipsPlugin._f32(y, 'y')
+        _require(y.ndim == 4 and y.shape[2] >= 2 and y.shape[3] >= 2, 'maxpool2_relu_backward: y [n, c, h, w] with h, w >= 2')
+        n, c, h, w = y.shape
+        LpipsPlugin._f32(dpool, 'dpool', y.device, (n, c, h // 2, w // 2))
+        dz = torch.empty_like(y)
+        with _dev_guard(y.device):
+            rc = load().ide3d_maxpool2_relu_backward(_ptr(y), _ptr(dpool), _ptr(dz), n * c, h, w, _stream(y))
+        _check(rc, 'maxpool2_relu_backward')
+        return dz
+
+
 class ParseLossPlugin:
     """The passes between the convolutions of the face parser's cross-entropy loss and its image gradient (csrc/parse_loss.hip, DESIGN.md
     section 5.16).  Tensors are float32 CUDA tensors; dense NCHW unless a method says otherwise."""
@@ -2628,6 +2703,7 @@ PLUGINS = {
     'mapping_plugin': MappingPlugin,
     'lpips_plugin': LpipsPlugin,
     'lpips_alex_plugin': LpipsAlexPlugin,
+    'vgg_loss_plugin': VggLossPlugin,
     'parse_loss_plugin': ParseLossPlugin,
     'id_loss_plugin': IdLossPlugin,
 }

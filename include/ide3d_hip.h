@@ -1029,6 +1029,41 @@ int ide3d_id_head(const float* f, const float* target, float* e, float* norm, fl
 int ide3d_id_head_backward(const float* e, const float* target, const float* norm, const float* dloss, float* df, int32_t n, int32_t M,
                            void* stream);
 
+/*
+ * ABI 8 (entry points added).  The VGG19 feature loss of the hybrid encoder's training step (apps/train_hybrid_encoder.py:120-152, used at
+ * :305: a weighted L1 distance between the relu1_1 .. relu5_1 activations of torchvision's vgg19().features of two images mapped by
+ * (x + 1) / 2) and its image gradient: what it needs beside the entry points above (csrc/vgg_loss.hip).  The 13
+ * convolutions and their input gradients are ide3d_modconv2d, the interior ReLU gradients ide3d_modconv_act_backward, (x + 1) / 2 and its
+ * adjoint ide3d_lpips_prep / _prep_backward at f = 1, in_scale = in_shift = 0.5, mean = 0, std = 1, the pools ide3d_maxpool2.  All tensors
+ * dense NCHW fp32 in device memory.  No atomics, fixed-order sums in float64, bit-reproducible; no host synchronisation.
+ *
+ * ide3d_feat_l1 — the loss from the taps (train_hybrid_encoder.py:141, 146-150: `weight * L1Loss()(source, target)` summed over the
+ *   slices): loss[0] = sum_k weight_k * (sum |a_k - t_k|) / (n c_k h_k w_k), 1 <= k <= IDE3D_LPIPS_MAX_TAPS taps [n, c_k, h_k, w_k].
+ *   k launches (per-workgroup partial sums -> workspace of ide3d_feat_l1_workspace_bytes()) + 1 finishing launch.
+ * ide3d_feat_l1_tap_backward — at a tap (train_hybrid_encoder.py:147-150: the slice's output feeds the criterion AND the next slice), what
+ *   autograd does in three passes (L1 backward, add of the next convolution's input gradient, ReLU backward):
+ *   dz = (g + s sign(a - t)) where a > 0, else 0, with s = fp32(double(dloss[0]) * weight / count) and sign(0) = 0 as in ATen's L1
+ *   backward.  a, t, g, dz [planes, h, w]; g == NULL: the last tap, the sign term alone.  dloss: DEVICE pointer to the upstream scalar
+ *   gradient; count: the elements the tap's mean runs over (n c h w).
+ * ide3d_maxpool2_relu_backward — behind a pool that follows a ReLU which is no tap (vgg19 features 3-4, 8-9, 17-18, 26-27; in VGG19 no tap
+ *   sits in front of a pool), what autograd does in two passes: dz = dpool routed to the first maximum of its 2x2 window where y > 0, else
+ *   0.  y, dz [planes, h, w] (y a ReLU output), dpool [planes, h / 2, w / 2], h, w >= 2; a row or column that the floor dropped gets an
+ *   exact 0.  The result does not depend on the tie rule, for the reason given at ide3d_lpips_stage_backward.
+ */
+typedef struct ide3d_feat_l1_tap {
+    const float* a;        /* [n, c, h, w] the tap's activation */
+    const float* t;        /* [n, c, h, w] the target's activation at the same tap */
+    float        weight;
+    int32_t      c, h, w;
+} ide3d_feat_l1_tap;
+
+int64_t ide3d_feat_l1_workspace_bytes(const ide3d_feat_l1_tap* taps, int32_t k, int32_t n);
+int ide3d_feat_l1(const ide3d_feat_l1_tap* taps, int32_t k, int32_t n, float* workspace, int64_t workspace_bytes, float* loss,
+                  void* stream);
+int ide3d_feat_l1_tap_backward(const float* a, const float* t, const float* g, float* dz, const float* dloss, float weight,
+                               int64_t planes, int32_t h, int32_t w, int64_t count, void* stream);
+int ide3d_maxpool2_relu_backward(const float* y, const float* dpool, float* dz, int64_t planes, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

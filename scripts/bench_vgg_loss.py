@@ -1,0 +1,111 @@
+"""The VGG19 feature loss (training/vgg_loss.py) at the resolutions the hybrid encoder trains at, the HIP path (`vgg_loss.fused = True`)
+against the ATen path of the same module (`fused = False`), alternated in one process:
+
+    vgg_loss_256_b1, vgg_loss_256_b4, vgg_loss_512_b1, vgg_loss_512_b4
+                                    `distance_to` against cached target features + the image gradient, 256 x 256 and 512 x 512, batch 1
+                                    and batch 4
+
+    python scripts/bench_vgg_loss.py [--blocks 5] [--iters 5] [--warmup 2] [--sizes 256 512] [--out profiles/vgg_loss/bench_vgg_loss.json]
+
+prints one JSON line and writes it to --out: per case and path the device-event median over blocks of the time per call, the spread of the
+blocks (max - min), the block times, the peak memory of one call (torch.cuda.max_memory_allocated minus what was allocated before it) and
+the library launches of one call by entry point.  `fused_default_by_rule`: the HIP path is faster than the ATen path at every one of the
+four points (the rule by which `vgg_loss.fused` ships True).  The net is VGG19 with random weights (the timing does not depend on them)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'ide-3d_amd')); sys.path.insert(0, ROOT)
+
+PATHS = {'hip': True, 'aten': False}
+
+
+def measure(cases, blocks, iters, warmup):
+    """cases: {name: callable()}; every callable is run under both paths -> {name: {path: figures}}."""
+    import torch
+    from torch_utils import hip_plugin
+    from training import vgg_loss
+    for fn in cases.values():
+        for fused in PATHS.values():
+            vgg_loss.fused = fused
+            for _ in range(warmup):
+                fn()
+    torch.cuda.synchronize()
+    times = {(c, p): [] for c in cases for p in PATHS}
+    for _ in range(blocks):
+        for c, fn in cases.items():
+            for p, fused in PATHS.items():
+                vgg_loss.fused = fused
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[(c, p)].append(e0.elapsed_time(e1) / iters)
+    out = {}
+    for c, fn in cases.items():
+        out[c] = {}
+        for p, fused in PATHS.items():
+            vgg_loss.fused = fused
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            before = dict(hip_plugin.CALLS)
+            fn()
+            torch.cuda.synchronize()
+            t = times[(c, p)]
+            out[c][p] = dict(ms=round(statistics.median(t), 3), spread_ms=round(max(t) - min(t), 3), blocks_ms=[round(v, 3) for v in t],
+                             peak_mib=round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1),
+                             launches={k: v - before.get(k, 0) for k, v in hip_plugin.CALLS.items() if v != before.get(k, 0)})
+        out[c]['hip_over_aten'] = round(out[c]['hip']['ms'] / out[c]['aten']['ms'], 3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--blocks', type=int, default=5)
+    ap.add_argument('--iters', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--sizes', type=int, nargs='+', default=[256, 512])
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'vgg_loss', 'bench_vgg_loss.json'))
+    args = ap.parse_args()
+
+    import torch
+    from training import vgg_loss
+    dev = torch.device('cuda', 0)
+    torch.manual_seed(0)
+    default = vgg_loss.fused
+    net = vgg_loss.VGGLoss(dev)
+    cases = {}
+    for size in args.sizes:
+        for n in (1, 4):
+            g = torch.Generator().manual_seed(n)
+            x = (torch.rand(n, 3, size, size, generator=g) * 2 - 1).to(dev).requires_grad_(True)
+            y = (torch.rand(n, 3, size, size, generator=g) * 2 - 1).to(dev)
+            vgg_loss.fused = False
+            feats = net.features(y)
+
+            def call(x=x, feats=feats):
+                x.grad = None
+                net.distance_to(x, feats).backward()
+            cases[f'vgg_loss_{size}_b{n}'] = call
+    result = dict(bench='vgg_loss', sizes=args.sizes, blocks=args.blocks, iters=args.iters, fused_shipped=default)
+    try:
+        result.update(measure(cases, args.blocks, args.iters, args.warmup))
+    finally:
+        vgg_loss.fused = default
+    result['fused_default_by_rule'] = all(result[c]['hip']['ms'] < result[c]['aten']['ms'] for c in cases)
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()
