@@ -373,6 +373,9 @@ def load():
             'ide3d_sample_voxel': [ctypes.POINTER(_RenderParams), vp, i64, vp, vp, ctypes.c_int, vp],
             'ide3d_lattice_points': [ctypes.POINTER(_Lattice), i64, i64, vp, vp],
             'ide3d_density_lattice': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_Lattice), i64, i64, vp, vp],
+            'ide3d_mesh_workspace_bytes': [i32, i32, i32],
+            'ide3d_mesh_count': [vp, i32, i32, i32, f32, vp, vp, i64, vp],
+            'ide3d_mesh_emit': [vp, i32, i32, i32, f32, vp, ctypes.POINTER(_Lattice), i32, vp, i64, i64, i64, vp, vp, vp, vp],
             'ide3d_modconv2d': [ctypes.POINTER(_ModconvParams), vp],
             'ide3d_modconv2d_heads': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), vp],
             'ide3d_modconv_plan': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvPlanInfo)],
@@ -481,6 +484,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_id_prep', 'ide3d_id_prep_backward', 'ide3d_prelu', 'ide3d_prelu_backward', 'ide3d_se_gate', 'ide3d_se_gate_backward',
     'ide3d_linear_workspace_bytes', 'ide3d_linear_backward_input_workspace_bytes', 'ide3d_linear', 'ide3d_linear_backward_input',
     'ide3d_linear_weight_grad', 'ide3d_residual_join', 'ide3d_id_head', 'ide3d_id_head_backward',
+    'ide3d_mesh_workspace_bytes', 'ide3d_mesh_count', 'ide3d_mesh_emit',
 )
 
 
@@ -624,7 +628,7 @@ class _Workspaces:
 
 def _drop_owner(domain):
     _scope_finalizers.pop(domain, None)
-    for plugin in (ModconvPlugin, MappingPlugin, LowresPlugin, VolumeRenderPlugin, VggLossPlugin):
+    for plugin in (ModconvPlugin, MappingPlugin, LowresPlugin, VolumeRenderPlugin, VggLossPlugin, MeshPlugin):
         plugin._ws.drop(domain)
 
 
@@ -1868,6 +1872,67 @@ class VggLossPlugin:
         return dz
 
 
+class MeshPlugin:
+    """Marching cubes on a float32 CUDA volume (csrc/mesh.hip): `mcubes.marching_cubes` of render_mesh.py:31 /
+    dnnlib/geometry.py:286.  The one host read is the pair of totals that sizes the outputs."""
+
+    _ws = _Workspaces()          # (bytes, device index, launch domain) -> totals + per-workgroup pairs + one int32 per grid point
+    _tables = {}                 # device index -> the case table on that device
+
+    @staticmethod
+    def _table(table, dev):
+        t = MeshPlugin._tables.get(dev.index)
+        if t is None:
+            _require(tuple(table.shape) == (256, 16) and table.dtype == torch.uint8, 'marching_cubes: the case table is uint8 [256, 16]')
+            t = MeshPlugin._tables[dev.index] = table.to(dev).contiguous()
+        return t
+
+    @staticmethod
+    def _grid(volume):
+        _require(volume.is_cuda and volume.dtype == torch.float32 and volume.ndim == 3 and volume.is_contiguous(),
+                 'marching_cubes: volume must be a contiguous [X, Y, Z] float32 CUDA tensor')
+        dev = volume.device if volume.device.index is not None else torch.device('cuda', torch.cuda.current_device())
+        return dev, tuple(volume.shape)
+
+    @staticmethod
+    def count(volume, threshold, table):
+        """ide3d_mesh_count -> (workspace, number of vertices, number of triangles).  Reading the two totals is the only synchronisation."""
+        dev, (X, Y, Z) = MeshPlugin._grid(volume)
+        lib = load()
+        nbytes = lib.ide3d_mesh_workspace_bytes(X, Y, Z)
+        _require(nbytes > 0, f'marching_cubes: unsupported grid {X} x {Y} x {Z} (1..1024 points per axis)')
+        ws = MeshPlugin._ws.entry((nbytes, dev.index, _ws_domain(dev)), lambda: torch.empty([(nbytes + 7) // 8], dtype=torch.int64, device=dev))[0]
+        with _dev_guard(dev):
+            rc = lib.ide3d_mesh_count(_ptr(volume), X, Y, Z, float(threshold), _ptr(MeshPlugin._table(table, dev)), _ptr(ws), ws.numel() * 8, _stream(volume))
+        _check(rc, 'mesh_count')
+        nv, nt = (int(v) for v in ws[:2].tolist())
+        _require(nv < 2 ** 31 and nt < 2 ** 31, f'marching_cubes: {nv} vertices / {nt} triangles do not fit int32 indices')
+        return ws, nv, nt
+
+    @staticmethod
+    def emit(volume, threshold, table, ws, nv, nt, normals=False, flip=False, lattice=None):
+        """ide3d_mesh_emit with the workspace and totals of `count` on the same volume and threshold -> (vertices, triangles, normals or None)."""
+        dev, (X, Y, Z) = MeshPlugin._grid(volume)
+        lat = VolumeRenderPlugin._lattice(max(X, Y, Z), *lattice) if lattice is not None else None
+        vertices = torch.empty([nv, 3], dtype=torch.float32, device=dev)
+        triangles = torch.empty([nt, 3], dtype=torch.int32, device=dev)
+        nrm = torch.empty([nv, 3], dtype=torch.float32, device=dev) if normals else None
+        with _dev_guard(dev):
+            rc = load().ide3d_mesh_emit(_ptr(volume), X, Y, Z, float(threshold), _ptr(MeshPlugin._table(table, dev)),
+                                        ctypes.byref(lat) if lat is not None else None, int(bool(flip)), _ptr(ws), ws.numel() * 8, nv, nt,
+                                        _ptr(vertices), _ptr(triangles), _ptr(nrm), _stream(volume))
+        _check(rc, 'mesh_emit')
+        return vertices, triangles, nrm
+
+    @staticmethod
+    def marching_cubes(volume, threshold, table, normals=False, flip=False, lattice=None):
+        """-> (vertices [V, 3] float32, triangles [T, 3] int32, normals [V, 3] float32 or None); `table`: mesh_extraction.case_table_bytes() as a
+        tensor, `lattice`: None (index units) or (voxel_size, corner[3], scale) as in ide3d_lattice."""
+        volume = volume.detach().contiguous()
+        ws, nv, nt = MeshPlugin.count(volume, threshold, table)
+        return MeshPlugin.emit(volume, threshold, table, ws, nv, nt, normals=normals, flip=flip, lattice=lattice)
+
+
 class ParseLossPlugin:
     """The passes between the convolutions of the face parser's cross-entropy loss and its image gradient (csrc/parse_loss.hip, DESIGN.md
     section 5.16).  Tensors are float32 CUDA tensors; dense NCHW unless a method says otherwise."""
@@ -2688,6 +2753,7 @@ class LowresPlugin:
 
 
 PLUGINS = {
+    'mesh_plugin': MeshPlugin,
     'lowres_plugin': LowresPlugin,
     'bias_act_plugin': BiasActPlugin,
     'upfirdn2d_plugin': Upfirdn2dPlugin,

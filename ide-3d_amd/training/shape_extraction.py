@@ -10,8 +10,8 @@ using the reference's fp32 arithmetic operation by operation (including its floa
 
 `save_density_cube` writes the two files of extract_shapes.py:191-194 — `<name>.npy` and an MRC2014 volume
 (`mrcfile.new_mmap(..., mrc_mode=2)` there; here a dependency-free writer of the same 1024-byte header + float32
-voxels, since `mrcfile` is not installed).  Marching cubes / .ply export (extract_shapes.py:27-70,195-219) is a further
-host-side consumer of the cube: out of scope.
+voxels, since `mrcfile` is not installed).  Marching cubes and .ply export (extract_shapes.py:27-70,195-219; render_mesh.py:31) consume
+the cube on the device in `training/mesh_extraction.py` (`extract_mesh`, `marching_cubes`, `save_mesh`).
 """
 
 import os

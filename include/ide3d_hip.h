@@ -404,6 +404,40 @@ int ide3d_lattice_points(const ide3d_lattice* lat, int64_t first, int64_t count,
 int ide3d_density_lattice(const ide3d_render_params* p, const ide3d_lattice* lat, int64_t first, int64_t count,
                           float* out_sigma, void* stream);
 
+/* ---- iso-surface mesh of a density cube ----------------------------------------------------- */
+/*
+ * `vertices, triangles = mcubes.marching_cubes(volume, threshold)` (render_mesh.py:31,
+ * dnnlib/geometry.py:286 `extract_geometry`) on the device, in two calls around the one read the
+ * caller needs to size the outputs.
+ *
+ * volume [X, Y, Z] float32 contiguous (Z fastest), 1..1024 points per axis.  A corner is inside
+ * when value > iso (strict).  table: device copy of the 256 x 16 byte case table of
+ * training/mesh_extraction.py::case_table_bytes() (byte 0: triangles of the case, then their edge
+ * ids; cell corner c = x + 2y + 4z, edges = corner pairs differing in one bit, ascending).
+ * workspace: ide3d_mesh_workspace_bytes(X, Y, Z) bytes (-1: unsupported grid), 16-byte aligned,
+ * owned by the pair of calls: 2 x int64 totals, one (vertices, triangles) pair per workgroup of
+ * 1024 points, and one int32 per point (the id of the first vertex the point owns).
+ *
+ * ide3d_mesh_count: two launches (count per workgroup; scan).  When the stream has passed them
+ *   the first 16 bytes of the workspace hold {number of vertices, number of triangles} as int64.
+ * ide3d_mesh_emit: with those two numbers (each < 2^31, else IDE3D_EINVAL) and the same volume,
+ *   iso, table and workspace: vertices [V, 3] float32 = p_a + t (p_b - p_a) on every crossing
+ *   grid edge, t = (iso - v_a) / (v_b - v_a) in fp32 with IEEE division, in index units, or with
+ *   lat != NULL (lat->n is ignored) axis k of the volume mapped like ide3d_lattice_points:
+ *   (index * voxel_size + corner[2 - k]) * scale; triangles [T, 3] int32; normals [V, 3] or NULL:
+ *   the negated central-difference gradient (one-sided at the border) of both edge ends,
+ *   interpolated with t and normalised, zero where it vanishes.  Triangle normals point toward
+ *   lower values; flip != 0 reverses the winding and the normals.  No atomics: vertex order
+ *   (owning point in memory order, x before y before z) and triangle order (cell in memory order,
+ *   then table order) depend on the grid shape and the data only.
+ */
+int64_t ide3d_mesh_workspace_bytes(int32_t X, int32_t Y, int32_t Z);
+int ide3d_mesh_count(const float* volume, int32_t X, int32_t Y, int32_t Z, float iso, const uint8_t* table,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+int ide3d_mesh_emit(const float* volume, int32_t X, int32_t Y, int32_t Z, float iso, const uint8_t* table,
+                    const ide3d_lattice* lat, int32_t flip, void* workspace, int64_t workspace_bytes,
+                    int64_t num_vertices, int64_t num_triangles, float* vertices, int32_t* triangles, float* normals, void* stream);
+
 /* ---- modulated 3x3 / 1x1 convolution (MFMA implicit GEMM) --------------------------------- */
 /*
  * Replaces the ATen conv behind `conv2d_gradfix.conv2d` for the StyleGAN2 modulated
