@@ -37,6 +37,8 @@
 //     [n, feat+seg, rays] image, depth and weight sum is written.
 //   * Persistent workgroups (2 per CU) take contiguous ray ranges; the range order is XCD-remapped so neighbouring rays
 //     (neighbouring plane lines) share one XCD L2.
+//   * The hierarchical (importance) pass is the same walk split in two around ide3d_sample_pdf and a per-ray depth merge:
+//     render_ray_weights_kernel, merge_depths_kernel, render_rays_merged_kernel at the end of this file.
 // Compulsory HBM traffic per image: 2 tri-planes + jitter/noise in + (feat+seg+2)*rays*4 out.  The planes are cache resident
 // (L2 4 MiB/XCD + 256 MiB MALL); the kernel is bound by its vector instructions (~70 % of the VALU pipe at 2 waves per SIMD), not by HBM
 // or the matrix pipe — see DESIGN.md.
@@ -945,16 +947,23 @@ density_kernel(ide3d_render_params p, const Src src, int64_t m, float* __restric
     if constexpr (SPLIT) __syncthreads();          // exclusive residency (see render_rays_kernel)
 }
 
+// grid of the ray marchers (render_rays_kernel and the two of the hierarchical pass): 8 waves per CU either way, contiguous ray ranges
+template <bool SPLIT>
+static void ray_grid(int64_t total_rays, int64_t& nblk, int64_t& rpb) {
+    constexpr int NW = RmWaves<SPLIT>::value;
+    nblk = kNumCU * 8 / NW;
+    rpb = cdiv64(cdiv64(total_rays, nblk), NW) * NW;
+    if (rpb < NW) rpb = NW;
+    nblk = cdiv64(total_rays, rpb);
+}
+
 template <int C, int HID, bool SPLIT = false>
 static int launch_render(const ide3d_render_params& p, hipStream_t st) {
     using R = RmRender<C, HID, SPLIT>;
     const size_t lds_bytes = (size_t)2 * R::BYTES + (size_t)R::ROW * sizeof(float);
-    const int64_t total_rays = (int64_t)p.n * p.rays_per_img;
     constexpr int NW = RmWaves<SPLIT>::value;
-    int64_t nblk = kNumCU * 8 / NW;                                // 8 waves per CU either way
-    int64_t rpb = cdiv64(cdiv64(total_rays, nblk), NW) * NW;
-    if (rpb < NW) rpb = NW;
-    nblk = cdiv64(total_rays, rpb);
+    int64_t nblk, rpb;
+    ray_grid<SPLIT>((int64_t)p.n * p.rays_per_img, nblk, rpb);
     auto kern = render_rays_kernel<C, HID, SPLIT>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if constexpr (SPLIT) IDE3D_EXCL_LAUNCH(kern, dim3((unsigned)nblk), 64 * NW, lds_bytes, st, p, rpb);
@@ -1001,6 +1010,397 @@ static int launch_voxel(const ide3d_render_params& p, const Src& src, int64_t m,
     if constexpr (SPLIT) IDE3D_EXCL_LAUNCH(kern, dim3((unsigned)nblk), 64 * NW, lds_bytes, st, p, src, m, out, tpb);
     else hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * NW), lds_bytes, st, p, src, m, out, tpb);
     IDE3D_CHECK_LAUNCH("sample_voxel");
+    return IDE3D_OK;
+}
+
+// ---- the hierarchical (importance) pass: first-pass weights, depth merge, merged march ---------------------------
+// TriplaneRenderer.forward(hierarchical=True) as four launches: render_ray_weights_kernel -> ide3d_sample_pdf (sample_pdf.hip) ->
+// merge_depths_kernel -> render_rays_merged_kernel.  Per sample nothing but depths and weights is ever written: the first pass keeps the
+// geometry branch only (gather, hidden layer, sigma row, transmittance scan), the merged march is render_rays_kernel's walk over the 2 S
+// depth-ordered samples of a ray, each rebuilt from where it came from (`src`): a coarse sample from z_lin / jitter exactly as the first pass
+// placed it, a fine one as origin + direction * depth.
+// Both marchers prefetch two tiles deep: a tile's taps hang on its depths (first pass) or on what its `src` entries select (merged march:
+// a load that depends on a load), so those small loads are issued one tile before the taps they feed, and a tile's `src` one tile before that.
+
+// the tile after (ray, n, r, s0) of a wave that takes every NW-th ray and walks `steps` samples per ray in tiles of 16
+template <int NW>
+__device__ __forceinline__ void next_tile(int steps, int rays_per_img, int64_t& ray, int& n, int& r, int& s0) {
+    s0 += 16;
+    if (s0 >= steps) {
+        s0 = 0; ray += NW; r += NW;
+        while (r >= rays_per_img) { r -= rays_per_img; ++n; }
+    }
+}
+
+// First pass: the compositing weights of the S linear (jittered) samples of every ray, their depths, and the pdf that ide3d_sample_pdf draws
+// the fine depths from (bins = depth mid-points, weights = inner samples' weights + 1e-5), any of them optional.
+template <int C, int HID, bool SPLIT>
+__global__ void __launch_bounds__(64 * RmWaves<SPLIT>::value, 2)
+render_ray_weights_kernel(ide3d_render_params p, float* __restrict__ out_w, float* __restrict__ out_z, float* __restrict__ out_bins,
+                          float* __restrict__ out_pw, int64_t rays_per_block) {
+    using K = RmCfg<C, HID>;
+    using R = RmRender<C, HID, SPLIT>;
+    constexpr int NW = RmWaves<SPLIT>::value;
+    rm_claim_half_simd<SPLIT>();
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    unsigned char* s_geo = reinterpret_cast<unsigned char*>(lds);
+    float* const s_row = reinterpret_cast<float*>(s_geo + R::BYTES);           // row 0 of geo_w1 + its bias
+    stage_render_branch<C, HID, SPLIT>(s_geo, p.geo_w0, p.geo_b0, p.geo_w1, p.geo_b1, 1 + p.seg_ch);
+    for (int i = threadIdx.x; i <= HID; i += blockDim.x) s_row[i] = (i < HID) ? p.geo_w1[i] : p.geo_b1[0];
+    __syncthreads();
+
+    const int lane = lane_id(), wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = lane >> 4, j = lane & 15, gl = gather_block(lane);
+    const int64_t total_rays = (int64_t)p.n * p.rays_per_img;
+    const int blk = xcd_remap(blockIdx.x, gridDim.x);
+    const int64_t ray_begin = (int64_t)blk * rays_per_block;
+    int64_t ray_end = ray_begin + rays_per_block;
+    if (ray_end > total_rays) ray_end = total_rays;
+    const int S = p.steps;
+    const int sH = (int)p.geo_stride[2], sW = (int)p.geo_stride[3];
+    const float zstep = p.z_lin[1] - p.z_lin[0];              // S >= 3 (host)
+
+    auto tile_depth = [&](int64_t ray, int s0, float& zl, float& jl) {
+        const int sl = min(s0 + gather_sample(lane), S - 1);
+        zl = p.z_lin[sl];
+        jl = p.jitter ? p.jitter[ray * S + sl] : 0.5f;
+    };
+    auto tile_taps = [&](int n, int r, float zl, float jl, TapAddr (&t)[3]) {
+        float wx, wy, wz;
+        ray_world_point(p, n, r, zl, jl, zstep, wx, wy, wz);
+        t[0] = make_tap_addr(wx, wy, p.W, p.H, sH, sW);
+        t[1] = make_tap_addr(wy, wz, p.W, p.H, sH, sW);
+        t[2] = make_tap_addr(wx, wz, p.W, p.H, sH, sW);
+    };
+
+    int64_t ray = ray_begin + wid;
+    int n = __builtin_amdgcn_readfirstlane((int)(ray / p.rays_per_img));
+    int r = __builtin_amdgcn_readfirstlane((int)(ray - (int64_t)n * p.rays_per_img));
+    int s0 = 0;
+    bool have = ray < ray_end;
+    TapAddr t[3];
+    TapBuf<C> buf;
+    float zl1 = 0.f, jl1 = 0.5f;                            // depths of the tile after this one (gather layout), loaded one tile ahead
+    if (have) {
+        float zl, jl;
+        tile_depth(ray, 0, zl, jl);
+        tile_taps(n, r, zl, jl, t);
+        issue_taps<C>(uniform_ptr(p.geo_planes + n * p.geo_stride[0]), t, gl, buf);
+        int64_t ray1 = ray; int n1 = n, r1 = r, s1 = s0;
+        next_tile<NW>(S, p.rays_per_img, ray1, n1, r1, s1);
+        if (ray1 < ray_end) tile_depth(ray1, s1, zl1, jl1); else tile_depth(ray, s0, zl1, jl1);
+    }
+    float carry = 1.0f;
+
+    while (have) {
+        // the next tile and the one after it; past the last tile the prefetches re-read the last one (see render_rays_kernel)
+        int64_t rayn = ray; int nn = n, rn = r, s0n = s0;
+        next_tile<NW>(S, p.rays_per_img, rayn, nn, rn, s0n);
+        const bool haven = rayn < ray_end;
+        const int64_t rayp = haven ? rayn : ray;
+        const int np = haven ? nn : n, rp = haven ? rn : r, s0p = haven ? s0n : s0;
+        int64_t ray2 = rayn; int n2 = nn, r2 = rn, s2 = s0n;
+        next_tile<NW>(S, p.rays_per_img, ray2, n2, r2, s2);
+        const bool have2 = haven && ray2 < ray_end;
+        const int64_t rayq = have2 ? ray2 : rayp;
+        const int s0q = have2 ? s2 : s0p;
+
+        // matrix layout: depth of sample s0 + lane % 16, the one after it, its density noise
+        const int s = s0 + j;
+        const bool live = s < S;
+        const int sc = live ? s : S - 1;
+        const float z = ray_sample_depth(p, ray, sc, zstep);
+        const float znext = (sc + 1 < S) ? ray_sample_depth(p, ray, sc + 1, zstep) : 0.f;
+        const float noise = p.sigma_noise ? p.sigma_noise[ray * S + sc] : 0.f;
+
+        float fg[K::NF];
+        f32x4 hg[K::MT1];
+        blend_taps<C>(buf, t, fg);
+        to_matrix_lanes(fg);
+        tile_taps(np, rp, zl1, jl1, t);                                          // next tile's taps: in flight during this tile's MLP
+        issue_taps<C>(uniform_ptr(p.geo_planes + np * p.geo_stride[0]), t, gl, buf);
+        tile_depth(rayq, s0q, zl1, jl1);
+        hidden_branch<C, HID, SPLIT>(s_geo, fg, hg);
+
+        float sigma = sigma_row0<HID>(s_row, hg);             // in every lane of sample j
+        sigma += noise;
+        const float dens = p.clamp_mode == 0 ? softplus_fast(sigma) : fmaxf(sigma, 0.f);
+        float dnorm;
+        {
+            const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];
+            dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
+        }
+        const float delta = (sc + 1 < S) ? (znext - z) * dnorm : 1e10f;
+        const float alpha = live ? 1.0f - __expf(-delta * dens) : 0.f;
+        const float fac = live ? (1.0f - alpha + 1e-10f) : 1.0f;
+        float tot;
+        const float excl = seg16_excl_prod(fac, tot);
+        const float w = alpha * (carry * excl);
+        carry = (s0n == 0) ? 1.0f : carry * tot;
+
+        // the four lanes of a sample hold the same values: one output each
+        if (live) {
+            if (g == 0 && out_w) out_w[ray * S + s] = w;
+            if (g == 1 && out_z) out_z[ray * S + s] = z;
+            if (g == 2 && out_bins && s + 1 < S) out_bins[ray * (S - 1) + s] = __fmul_rn(0.5f, __fadd_rn(z, znext));
+            if (g == 3 && out_pw && s >= 1 && s + 1 < S) out_pw[ray * (S - 2) + s - 1] = __fadd_rn(w, 1e-5f);
+        }
+        ray = rayn; n = nn; r = rn; s0 = s0n; have = haven;
+    }
+    if constexpr (SPLIT) __syncthreads();          // exclusive residency (see render_rays_kernel)
+}
+
+// Monotone integer image of a depth: a < b as floats <=> key(a) < key(b) as unsigned, -0 == +0, every NaN above +inf.  With the index as
+// the second key the order is total for any input bits.
+__device__ __forceinline__ unsigned depth_key(float v) {
+    unsigned b = __float_as_uint(v);
+    if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+constexpr int kMergeWaves = 4;             // rays per workgroup and step
+constexpr int kMergeMaxT = 2048;           // merged samples per ray: 4 * 2048 keys = 32 KB of LDS
+
+// Stable ascending order of [z_fine | z_coarse] per ray (torch.sort(torch.cat([z_fine, z_coarse]), stable=True)): one wave per ray, the T
+// keys in LDS, the rank of an element = how many precede it in (key, index) order, counted by every lane for its elements from broadcast
+// reads.  T^2 comparisons: T <= 192 at the workload's size, ~25 us for 16384 rays.  The ranks of a row are a permutation of 0 .. T-1
+// whatever the data, so every element of z_all / src is written exactly once and nothing outside the row is.
+__global__ void __launch_bounds__(kMergeWaves * kWave)
+merge_depths_kernel(const float* __restrict__ z_fine, const float* __restrict__ z_coarse, int64_t rays, int sf, int sc,
+                    float* __restrict__ z_all, int* __restrict__ src) {
+    extern __shared__ unsigned s_keys[];                   // [kMergeWaves][T]
+    const int lane = lane_id(), wid = threadIdx.x / kWave;
+    const int T = sf + sc;
+    unsigned* keys = s_keys + (size_t)wid * T;
+    for (int64_t base = (int64_t)blockIdx.x * kMergeWaves; base < rays; base += (int64_t)gridDim.x * kMergeWaves) {
+        const int64_t ray = base + wid;
+        const bool live = ray < rays;
+        if (live)
+            for (int i = lane; i < T; i += kWave) keys[i] = depth_key(i < sf ? z_fine[ray * sf + i] : z_coarse[ray * sc + (i - sf)]);
+        __syncthreads();
+        if (live) {
+            for (int i = lane; i < T; i += kWave) {
+                const unsigned ki = keys[i];
+                int rank = 0;
+                for (int k = 0; k < T; ++k) {
+                    const unsigned kk = keys[k];
+                    rank += (kk < ki || (kk == ki && k < i)) ? 1 : 0;
+                }
+                const float v = i < sf ? z_fine[ray * sf + i] : z_coarse[ray * sc + (i - sf)];
+                z_all[ray * T + rank] = v;
+                src[ray * T + rank] = i;
+            }
+        }
+        __syncthreads();                                   // the keys are rewritten by the next ray of this wave
+    }
+}
+
+// Merged march: render_rays_kernel's walk over the T = 2 S samples of a ray in z_all order.  Sample s of a ray is entry src[ray, s] of the
+// concatenation [fine | coarse]: a coarse one is rebuilt by ray_world_point from z_lin / jitter (the point the first pass weighed), a fine one
+// is origin + dir_world * z_fine.  No density noise; delta from neighbouring z_all.
+template <int C, int HID, bool SPLIT>
+__global__ void __launch_bounds__(64 * RmWaves<SPLIT>::value, 2)
+render_rays_merged_kernel(ide3d_render_params p, const float* __restrict__ z_all, const int* __restrict__ src,
+                          const float* __restrict__ z_fine, int64_t rays_per_block) {
+    using K = RmCfg<C, HID>;
+    constexpr int NW = RmWaves<SPLIT>::value;
+    rm_claim_half_simd<SPLIT>();
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    using R = RmRender<C, HID, SPLIT>;
+    constexpr int NA = HID / 4;                            // hidden units per lane and branch
+    unsigned char* s_geo = reinterpret_cast<unsigned char*>(lds);
+    unsigned char* s_tex = s_geo + R::BYTES;
+    float* const s_row = reinterpret_cast<float*>(s_tex + R::BYTES);           // row 0 of geo_w1 + its bias
+    stage_render_branch<C, HID, SPLIT>(s_geo, p.geo_w0, p.geo_b0, p.geo_w1, p.geo_b1, 1 + p.seg_ch);
+    stage_render_branch<C, HID, SPLIT>(s_tex, p.tex_w0, p.tex_b0, p.tex_w1, p.tex_b1, p.feat_ch);
+    for (int i = threadIdx.x; i <= HID; i += blockDim.x) s_row[i] = (i < HID) ? p.geo_w1[i] : p.geo_b1[0];
+    __syncthreads();
+
+    const int lane = lane_id(), wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = lane >> 4, j = lane & 15, gl = gather_block(lane);
+    const int64_t total_rays = (int64_t)p.n * p.rays_per_img;
+    const int blk = xcd_remap(blockIdx.x, gridDim.x);
+    const int64_t ray_begin = (int64_t)blk * rays_per_block;
+    int64_t ray_end = ray_begin + rays_per_block;
+    if (ray_end > total_rays) ray_end = total_rays;
+    const int S = p.steps, T = 2 * S;
+    const int nch = p.feat_ch + p.seg_ch;
+    const int sH = (int)p.tex_stride[2], sW = (int)p.tex_stride[3];   // host guarantees tex / geo share the layout
+    const float zstep = p.z_lin[1] - p.z_lin[0];             // S >= 3 (host)
+
+    // src of merged sample s0 + lane / 4 of `ray` (gather layout)
+    auto tile_src = [&](int64_t ray, int s0) { return src[ray * T + min(s0 + gather_sample(lane), T - 1)]; };
+    // what that entry selects: a coarse sample's linear depth and jitter draw, or a fine sample's depth (in `a`).  The entry is clamped
+    // into [0, T) first, so no value of it reads outside z_lin / jitter / z_fine.
+    auto tile_sample = [&](int64_t ray, int sv, float& zl, float& a) {
+        sv = min(max(sv, 0), T - 1);
+        const bool fine = sv < S;
+        const int idx = fine ? sv : sv - S;
+        zl = p.z_lin[idx];
+        const float* ap = fine ? z_fine : p.jitter;
+        a = ap ? ap[ray * S + idx] : 0.5f;
+    };
+    auto tile_taps = [&](int n, int r, int sv, float zl, float a, TapAddr (&t)[3]) {
+        float wx, wy, wz;
+        ray_world_point(p, n, r, zl, a, zstep, wx, wy, wz);
+        if (min(max(sv, 0), T - 1) < S) {
+            // origin + dir_world * z, the multiply and the add rounded separately like the tensor expression
+            const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];
+            const float* M = p.cam2world + n * 16;
+            const float ux = fmaf(M[0], dx, fmaf(M[1], dy, __fmul_rn(M[2], dz)));
+            const float uy = fmaf(M[4], dx, fmaf(M[5], dy, __fmul_rn(M[6], dz)));
+            const float uz = fmaf(M[8], dx, fmaf(M[9], dy, __fmul_rn(M[10], dz)));
+            wx = __fadd_rn(M[3], __fmul_rn(ux, a));
+            wy = __fadd_rn(M[7], __fmul_rn(uy, a));
+            wz = __fadd_rn(M[11], __fmul_rn(uz, a));
+        }
+        t[0] = make_tap_addr(wx, wy, p.W, p.H, sH, sW);
+        t[1] = make_tap_addr(wy, wz, p.W, p.H, sH, sW);
+        t[2] = make_tap_addr(wx, wz, p.W, p.H, sH, sW);
+    };
+
+    int64_t ray = ray_begin + wid;
+    int n = __builtin_amdgcn_readfirstlane((int)(ray / p.rays_per_img));
+    int r = __builtin_amdgcn_readfirstlane((int)(ray - (int64_t)n * p.rays_per_img));
+    int s0 = 0;
+    bool have = ray < ray_end;
+    TapAddr t[3];
+    TapBuf<C> buf;
+    int src1 = 0;                                          // src of the tile after this one (gather layout), loaded one tile ahead
+    if (have) {
+        const int sv = tile_src(ray, 0);
+        float zl, a;
+        tile_sample(ray, sv, zl, a);
+        tile_taps(n, r, sv, zl, a, t);
+        issue_taps<C>(uniform_ptr(p.geo_planes + n * p.geo_stride[0]), t, gl, buf);
+        int64_t ray1 = ray; int n1 = n, r1 = r, s1 = s0;
+        next_tile<NW>(T, p.rays_per_img, ray1, n1, r1, s1);
+        src1 = (ray1 < ray_end) ? tile_src(ray1, s1) : sv;
+    }
+    float acc_t[NA], acc_g[NA];                           // sum_i w_i h_i of the units 16 mt + 4 g + r, over this lane's samples
+#pragma unroll
+    for (int i = 0; i < NA; ++i) { acc_t[i] = 0.f; acc_g[i] = 0.f; }
+    float carry = 1.0f, wsum = 0.f, dsum = 0.f;
+
+    while (have) {
+        // the next tile and the one after it; past the last tile the prefetches re-read the last one (see render_rays_kernel)
+        int64_t rayn = ray; int nn = n, rn = r, s0n = s0;
+        next_tile<NW>(T, p.rays_per_img, rayn, nn, rn, s0n);
+        const bool haven = rayn < ray_end;
+        const int64_t rayp = haven ? rayn : ray;
+        const int np = haven ? nn : n, rp = haven ? rn : r;
+        int64_t ray2 = rayn; int n2 = nn, r2 = rn, s2 = s0n;
+        next_tile<NW>(T, p.rays_per_img, ray2, n2, r2, s2);
+        const bool have2 = haven && ray2 < ray_end;
+        // --- matrix layout: depth of sample s0 + lane % 16 and of the one after it; gather layout: the next tile's samples, the src of the one after ---
+        const int s = s0 + j;
+        const bool live = s < T;
+        const int sc = live ? s : T - 1;
+        const float z = z_all[ray * T + sc];
+        const float znext = (sc + 1 < T) ? z_all[ray * T + sc + 1] : 0.f;
+        float zln, an;
+        tile_sample(rayp, src1, zln, an);
+        const int svn = src1;
+        if (have2) src1 = tile_src(ray2, s2);
+
+        float fg[K::NF], ft[K::NF];
+        f32x4 hg[K::MT1], ht[K::MT1];
+        blend_taps<C>(buf, t, fg);
+        to_matrix_lanes(fg);
+        issue_taps<C>(uniform_ptr(p.tex_planes + n * p.tex_stride[0]), t, gl, buf);          // in flight during the geometry MLP
+        hidden_branch<C, HID, SPLIT>(s_geo, fg, hg);
+
+        // --- compositing weights (before the texture MLP: the geometry hidden vector dies here) ---
+        const float sigma = sigma_row0<HID>(s_row, hg);       // in every lane of sample j
+        const float dens = p.clamp_mode == 0 ? softplus_fast(sigma) : fmaxf(sigma, 0.f);
+        float dnorm;
+        {
+            const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];
+            dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
+        }
+        const float delta = (sc + 1 < T) ? (znext - z) * dnorm : 1e10f;
+        const float alpha = live ? 1.0f - __expf(-delta * dens) : 0.f;
+        const float fac = live ? (1.0f - alpha + 1e-10f) : 1.0f;
+        float tot;
+        const float excl = seg16_excl_prod(fac, tot);
+        const float w = alpha * (carry * excl);
+        carry *= tot;
+        wsum += w; dsum += w * z;
+#pragma unroll
+        for (int mt = 0; mt < K::MT1; ++mt)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) acc_g[mt * 4 + rr] += w * hg[mt][rr];
+
+        blend_taps<C>(buf, t, ft);
+        to_matrix_lanes(ft);
+        tile_taps(np, rp, svn, zln, an, t);                                     // next tile's geometry taps: during the texture MLP
+        issue_taps<C>(uniform_ptr(p.geo_planes + np * p.geo_stride[0]), t, gl, buf);
+        hidden_branch<C, HID, SPLIT>(s_tex, ft, ht);
+#pragma unroll
+        for (int mt = 0; mt < K::MT1; ++mt)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) acc_t[mt * 4 + rr] += w * ht[mt][rr];
+
+        if (s0n == 0) {
+            // --- close the ray (as render_rays_kernel does) ---
+            wsum = row16_sum(wsum); dsum = row16_sum(dsum);
+#pragma unroll
+            for (int i = 0; i < NA; ++i) { acc_g[i] = row16_sum(acc_g[i]); acc_t[i] = row16_sum(acc_t[i]); }
+            float o_t[2], o_g[2];
+            heads_per_ray<C, HID, SPLIT>(s_tex, acc_t, wsum, o_t);
+            heads_per_ray<C, HID, SPLIT>(s_geo, acc_g, wsum, o_g);
+            {
+                const float bg = p.white_back ? (1.0f - wsum) : 0.f;
+                float* of = p.out_feat + (int64_t)n * nch * p.rays_per_img + r;
+                const int idx = j + 16 * (g & 1);
+                const float v = (g & 2) ? ((g & 1) ? o_g[1] : o_g[0]) : ((g & 1) ? o_t[1] : o_t[0]);
+                if (g < 2) {
+                    if (idx < p.feat_ch) of[(int64_t)idx * p.rays_per_img] = v + bg;
+                } else {
+                    if (idx >= 1 && idx <= p.seg_ch) of[(int64_t)(p.feat_ch + idx - 1) * p.rays_per_img] = v + bg;      // row 0 is sigma
+                }
+                if (lane == 0) {
+                    if (p.out_depth) p.out_depth[ray] = dsum + ((p.max_depth != 0.f) ? (1.0f - wsum) * p.max_depth : 0.f);
+                    if (p.out_wsum) p.out_wsum[ray] = wsum;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < NA; ++i) { acc_t[i] = 0.f; acc_g[i] = 0.f; }
+            carry = 1.0f; wsum = 0.f; dsum = 0.f;
+        }
+        ray = rayn; n = nn; r = rn; s0 = s0n; have = haven;
+    }
+    if constexpr (SPLIT) __syncthreads();          // exclusive residency (see render_rays_kernel)
+}
+
+template <int C, int HID, bool SPLIT = false>
+static int launch_ray_weights(const ide3d_render_params& p, float* w, float* z, float* bins, float* pw, hipStream_t st) {
+    using R = RmRender<C, HID, SPLIT>;
+    const size_t lds_bytes = (size_t)R::BYTES + (size_t)R::ROW * sizeof(float);
+    constexpr int NW = RmWaves<SPLIT>::value;
+    int64_t nblk, rpb;
+    ray_grid<SPLIT>((int64_t)p.n * p.rays_per_img, nblk, rpb);
+    auto kern = render_ray_weights_kernel<C, HID, SPLIT>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if constexpr (SPLIT) IDE3D_EXCL_LAUNCH(kern, dim3((unsigned)nblk), 64 * NW, lds_bytes, st, p, w, z, bins, pw, rpb);
+    else hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * NW), lds_bytes, st, p, w, z, bins, pw, rpb);
+    IDE3D_CHECK_LAUNCH("render_ray_weights");
+    return IDE3D_OK;
+}
+
+template <int C, int HID, bool SPLIT = false>
+static int launch_render_merged(const ide3d_render_params& p, const float* z_all, const int* src, const float* z_fine, hipStream_t st) {
+    using R = RmRender<C, HID, SPLIT>;
+    const size_t lds_bytes = (size_t)2 * R::BYTES + (size_t)R::ROW * sizeof(float);
+    constexpr int NW = RmWaves<SPLIT>::value;
+    int64_t nblk, rpb;
+    ray_grid<SPLIT>((int64_t)p.n * p.rays_per_img, nblk, rpb);
+    auto kern = render_rays_merged_kernel<C, HID, SPLIT>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if constexpr (SPLIT) IDE3D_EXCL_LAUNCH(kern, dim3((unsigned)nblk), 64 * NW, lds_bytes, st, p, z_all, src, z_fine, rpb);
+    else hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * NW), lds_bytes, st, p, z_all, src, z_fine, rpb);
+    IDE3D_CHECK_LAUNCH("render_rays_merged");
     return IDE3D_OK;
 }
 
@@ -1084,6 +1484,67 @@ extern "C" int ide3d_density_lattice(const ide3d_render_params* pp, const ide3d_
                                                                   : launch_voxel<32, 64>(p, src, count, nullptr, out_sigma, 1, st);
     if (p.C == 16 && p.hidden == 32) return launch_voxel<16, 32>(p, src, count, nullptr, out_sigma, 1, st);
     set_error("density_lattice: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
+    return IDE3D_ENOKERNEL;
+}
+
+// What the two marchers of the hierarchical pass check alike: ide3d_render_rays' rules without its outputs, then its declines plus the step
+// counts the pass cannot take (an inner pdf needs 3 samples; ide3d_merge_depths holds 2 * steps keys per ray in LDS).
+static int check_hierarchical(const ide3d_render_params& p, const char* who) {
+    using namespace ide3d;
+    int rc = check_render_params(p, who, false);
+    if (rc) return rc;
+    IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world, "%s: null ray pointer", who);
+    IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "%s: bad ray shape", who);
+    IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "%s: Need to choose clamp mode", who);
+    if (p.steps < 3 || 2 * (int64_t)p.steps > kMergeMaxT) { set_error("%s: the hierarchical pass takes 3 .. %d steps, got %d", who, kMergeMaxT / 2, p.steps); return IDE3D_ENOKERNEL; }
+    if (p.last_back) { set_error("%s: last_back is not fused; use the step-wise ops", who); return IDE3D_ENOKERNEL; }
+    if (!planes_fast(p)) { set_error("%s: tri-planes must be channels_last, 16-byte aligned", who); return IDE3D_ENOKERNEL; }
+    return IDE3D_OK;
+}
+
+extern "C" int ide3d_render_ray_weights(const ide3d_render_params* pp, float* weights, float* z_vals, float* pdf_bins, float* pdf_weights,
+                                        void* stream) {
+    using namespace ide3d;
+    IDE3D_CHECK_ARG(pp != nullptr, "render_ray_weights: null params");
+    const ide3d_render_params& p = *pp;
+    int rc = check_hierarchical(p, "render_ray_weights");
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (p.C == 32 && p.hidden == 64) return mlp_split_selected() ? launch_ray_weights<32, 64, true>(p, weights, z_vals, pdf_bins, pdf_weights, st)
+                                                                  : launch_ray_weights<32, 64>(p, weights, z_vals, pdf_bins, pdf_weights, st);
+    if (p.C == 16 && p.hidden == 32) return launch_ray_weights<16, 32>(p, weights, z_vals, pdf_bins, pdf_weights, st);
+    set_error("render_ray_weights: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
+    return IDE3D_ENOKERNEL;
+}
+
+extern "C" int ide3d_merge_depths(const float* z_fine, const float* z_coarse, int64_t rays, int32_t steps_fine, int32_t steps_coarse,
+                                  float* z_all, int32_t* src, void* stream) {
+    using namespace ide3d;
+    IDE3D_CHECK_ARG(rays >= 0 && steps_fine >= 0 && steps_coarse >= 0 && (int64_t)steps_fine + steps_coarse >= 1 &&
+                    (int64_t)steps_fine + steps_coarse <= kMergeMaxT, "merge_depths: bad shape (1 <= steps_fine + steps_coarse <= %d)", kMergeMaxT);
+    IDE3D_CHECK_ARG(z_all && src && (z_fine || steps_fine == 0) && (z_coarse || steps_coarse == 0), "merge_depths: null pointer");
+    if (rays == 0) return IDE3D_OK;
+    const int T = steps_fine + steps_coarse;
+    hipLaunchKernelGGL(merge_depths_kernel, dim3(stream_grid(rays, kMergeWaves)), dim3(kMergeWaves * kWave), (size_t)kMergeWaves * T * sizeof(unsigned),
+                       (hipStream_t)stream, z_fine, z_coarse, rays, (int)steps_fine, (int)steps_coarse, z_all, src);
+    IDE3D_CHECK_LAUNCH("merge_depths");
+    return IDE3D_OK;
+}
+
+extern "C" int ide3d_render_rays_merged(const ide3d_render_params* pp, const float* z_all, const int32_t* src, const float* z_fine,
+                                        int32_t total_steps, void* stream) {
+    using namespace ide3d;
+    IDE3D_CHECK_ARG(pp != nullptr && z_all != nullptr && src != nullptr && z_fine != nullptr, "render_rays_merged: null pointer");
+    const ide3d_render_params& p = *pp;
+    int rc = check_hierarchical(p, "render_rays_merged");
+    if (rc) return rc;
+    IDE3D_CHECK_ARG(p.out_feat != nullptr, "render_rays_merged: null output pointer");
+    IDE3D_CHECK_ARG((int64_t)total_steps == 2 * (int64_t)p.steps, "render_rays_merged: total_steps must be 2 * steps = %d, got %d", 2 * p.steps, total_steps);
+    hipStream_t st = (hipStream_t)stream;
+    if (p.C == 32 && p.hidden == 64) return mlp_split_selected() ? launch_render_merged<32, 64, true>(p, z_all, src, z_fine, st)
+                                                                  : launch_render_merged<32, 64>(p, z_all, src, z_fine, st);
+    if (p.C == 16 && p.hidden == 32) return launch_render_merged<16, 32>(p, z_all, src, z_fine, st);
+    set_error("render_rays_merged: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
     return IDE3D_ENOKERNEL;
 }
 

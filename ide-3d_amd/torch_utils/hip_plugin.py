@@ -364,6 +364,9 @@ def load():
                                 ctypes.c_int, vp, vp, vp, vp],
             'ide3d_sample_pdf': [vp, vp, vp, i64, i64, i32, i32, f32, vp, vp],
             'ide3d_render_rays': [ctypes.POINTER(_RenderParams), vp],
+            'ide3d_render_ray_weights': [ctypes.POINTER(_RenderParams), vp, vp, vp, vp, vp],
+            'ide3d_merge_depths': [vp, vp, i64, i32, i32, vp, vp, vp],
+            'ide3d_render_rays_merged': [ctypes.POINTER(_RenderParams), vp, vp, vp, i32, vp],
             'ide3d_render_rays_backward': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_RenderGrads), vp],
             'ide3d_render_param_grad_workspace_bytes': [ctypes.POINTER(_RenderParams)],
             'ide3d_render_rays_backward_params': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_RenderGrads), ctypes.POINTER(_RenderParamGrads), vp],
@@ -485,6 +488,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_linear_workspace_bytes', 'ide3d_linear_backward_input_workspace_bytes', 'ide3d_linear', 'ide3d_linear_backward_input',
     'ide3d_linear_weight_grad', 'ide3d_residual_join', 'ide3d_id_head', 'ide3d_id_head_backward',
     'ide3d_mesh_workspace_bytes', 'ide3d_mesh_count', 'ide3d_mesh_emit',
+    'ide3d_render_ray_weights', 'ide3d_merge_depths', 'ide3d_render_rays_merged',
 )
 
 
@@ -1086,6 +1090,67 @@ class VolumeRenderPlugin:
         if rc == -2:        # IDE3D_ENOKERNEL: configuration not covered by the fused kernel
             return None
         _check(rc, 'render_rays')
+        return feat, depth, wsum
+
+    @staticmethod
+    def render_ray_weights(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_mode,
+                           want=('weights', 'z_vals', 'pdf_bins', 'pdf_weights'), last_back=False):
+        """First pass of the hierarchical renderer (`ide3d_render_ray_weights`): the geometry branch only.  -> (weights [n*R, S], z_vals
+        [n*R, S], pdf_bins [n*R, S-1], pdf_weights [n*R, S-2]), None in place of what `want` does not name (not computed); None when the
+        library has no kernel for the configuration (IDE3D_ENOKERNEL: what `render_rays` declines, and S < 3 or S > 1024)."""
+        dev = tex_planes.device
+        p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
+                                                 clamp_mode, last_back, False, None)
+        rays, S = p.n * p.rays_per_img, p.steps
+        outs = [torch.empty([rays, max(S - k, 0)], dtype=torch.float32, device=dev) if name in want else None
+                for name, k in (('weights', 0), ('z_vals', 0), ('pdf_bins', 1), ('pdf_weights', 2))]
+        with _dev_guard(dev):
+            rc = load().ide3d_render_ray_weights(ctypes.byref(p), *(_ptr(o) for o in outs), _stream(tex_planes))
+        if rc == -2:        # IDE3D_ENOKERNEL
+            return None
+        _check(rc, 'render_ray_weights')
+        return tuple(outs)
+
+    @staticmethod
+    def merge_depths(z_fine, z_coarse):
+        """z_fine [rays, Sf], z_coarse [rays, Sc] -> (z_all [rays, Sf+Sc] float32, src [rays, Sf+Sc] int32): per ray the stable ascending order
+        of cat([z_fine, z_coarse], 1) (`ide3d_merge_depths`); src indexes the concatenation."""
+        _require(z_fine.is_cuda and z_fine.dtype == torch.float32 and z_fine.ndim == 2, 'merge_depths: z_fine must be 2-D float32 on a CUDA device')
+        _require(z_coarse.dtype == torch.float32 and z_coarse.ndim == 2 and z_coarse.device == z_fine.device and z_coarse.shape[0] == z_fine.shape[0],
+                 'merge_depths: z_coarse must be [rays, steps] float32 next to z_fine')
+        z_fine, z_coarse = z_fine.contiguous(), z_coarse.contiguous()
+        rays, sf, sc = z_fine.shape[0], z_fine.shape[1], z_coarse.shape[1]
+        z_all = torch.empty([rays, sf + sc], dtype=torch.float32, device=z_fine.device)
+        src = torch.empty([rays, sf + sc], dtype=torch.int32, device=z_fine.device)
+        with _dev_guard(z_fine.device):
+            rc = load().ide3d_merge_depths(_ptr(z_fine), _ptr(z_coarse), rays, sf, sc, _ptr(z_all), _ptr(src), _stream(z_fine))
+        _check(rc, 'merge_depths')
+        return z_all, src
+
+    @staticmethod
+    def render_rays_merged(rays_d_cam, z_lin, cam2world, jitter, tex_planes, geo_planes, mlp, clamp_mode, white_back, max_depth,
+                           z_all, src, z_fine, last_back=False):
+        """Merged march of the hierarchical renderer (`ide3d_render_rays_merged`): `render_rays` over the 2 S samples of each ray in the order
+        `merge_depths(z_fine, z_vals)` gave (z_all, src [n*R, 2S]; z_fine [n*R, S]), no density noise.  -> (feat, depth, wsum) like
+        `render_rays`, or None (IDE3D_ENOKERNEL, as `render_ray_weights`)."""
+        dev = tex_planes.device
+        p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, None, tex_planes, geo_planes, mlp,
+                                                 clamp_mode, last_back, white_back, max_depth)
+        n, R, S = p.n, p.rays_per_img, p.steps
+        for name, t_, shape, dt in (('z_all', z_all, (n * R, 2 * S), torch.float32), ('src', src, (n * R, 2 * S), torch.int32),
+                                    ('z_fine', z_fine, (n * R, S), torch.float32)):
+            _require(t_.dtype == dt and t_.device == dev and tuple(t_.shape) == shape,
+                     f'render_rays_merged: {name} must be {list(shape)} {dt} next to the tri-planes, got {list(t_.shape)} {t_.dtype}')
+        z_all, src, z_fine = z_all.contiguous(), src.contiguous(), z_fine.contiguous()
+        feat = torch.empty([n, p.feat_ch + p.seg_ch, R], dtype=torch.float32, device=dev)
+        depth = torch.empty([n, R], dtype=torch.float32, device=dev)
+        wsum = torch.empty([n, R], dtype=torch.float32, device=dev)
+        p.out_feat, p.out_depth, p.out_wsum = feat.data_ptr(), depth.data_ptr(), wsum.data_ptr()
+        with _dev_guard(dev):
+            rc = load().ide3d_render_rays_merged(ctypes.byref(p), _ptr(z_all), _ptr(src), _ptr(z_fine), 2 * S, _stream(tex_planes))
+        if rc == -2:        # IDE3D_ENOKERNEL
+            return None
+        _check(rc, 'render_rays_merged')
         return feat, depth, wsum
 
     @staticmethod

@@ -55,6 +55,11 @@ fused_render_param_grad = False
 # Opt-in; False = a cam2world that requires grad renders step-wise.
 fused_render_camera_grad = False
 
+# Render the importance pass (`hierarchical=True`) as four HIP launches that keep nothing per sample in memory but depths and weights
+# (vr.render_triplane_hierarchical) instead of the step-wise ops, for inference calls without `sigma_noise_fine`.
+# Opt-in: set by a driver that renders with `render_params=dict(hierarchical=True)`; False = the step-wise definition.
+fused_hierarchical = False
+
 
 @dataclasses.dataclass
 class GeneratorSpec:
@@ -272,6 +277,14 @@ class TriplaneRenderer(torch.nn.Module):
             res = vr.render_triplane_fused(_as_channels_last(img_v), _as_channels_last(seg_v), self.decoder.kernel_weights(),
                                            cam2world.float(), fov, (size, size), steps, t0, t1, jitter=jitter,
                                            sigma_noise=sigma_noise, clamp_mode=clamp_mode, white_back=white_back)
+            if res is not None:
+                return res
+        elif hierarchical and fused_hierarchical and sigma_noise_fine is None \
+                and self._hip_ok(img_v, seg_v, cam2world, *(() if importance_u is None else (importance_u,))):
+            res = vr.render_triplane_hierarchical(_as_channels_last(img_v), _as_channels_last(seg_v), self.decoder.kernel_weights(),
+                                                  cam2world.float(), fov, (size, size), steps, t0, t1, jitter=jitter,
+                                                  sigma_noise=sigma_noise, importance_u=importance_u, clamp_mode=clamp_mode,
+                                                  white_back=white_back)
             if res is not None:
                 return res
 

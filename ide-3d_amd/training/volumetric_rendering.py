@@ -7,7 +7,8 @@ Every public name of the reference module is kept with the same arguments: `fanc
 `sample_pdf` (:224), `LookAtPoseSampler` (:268) and the small vector helpers.  On ROCm devices
 `fancy_integration` runs the wave-per-ray HIP compositing kernel (`csrc/composite.hip`) and
 `render_triplane_fused` (new) runs steps ray-setup -> transform -> gathers -> MLPs -> compositing in
-one launch (`csrc/raymarch.hip`).  Two optional keyword arguments were added so that callers (and
+one launch (`csrc/raymarch.hip`); `render_triplane_hierarchical` (new) is that renderer with the importance pass, in four
+launches.  Two optional keyword arguments were added so that callers (and
 parity tests) can supply the random draws instead of having them generated on the device:
 `perturb_points(..., jitter=)` / `transform_sampled_points(..., jitter=)` and
 `fancy_integration(..., noise=)`.
@@ -431,4 +432,46 @@ def render_triplane_fused(tex_planes, geo_planes, mlp, cam2world, fov, resolutio
         return None
     feat, depth, wsum = res
     n = tex_planes.shape[0]
+    return feat.reshape(n, -1, H, W), depth.reshape(n, 1, H, W), wsum.reshape(n, 1, H, W)
+
+
+def render_triplane_hierarchical(tex_planes, geo_planes, mlp, cam2world, fov, resolution, num_steps, ray_start, ray_end,
+                                 jitter=None, sigma_noise=None, importance_u=None, clamp_mode='softplus', white_back=False,
+                                 max_depth=None):
+    """`render_triplane_fused` with the importance pass, in four HIP launches and nothing per sample in memory but depths and
+    weights:
+
+      `ide3d_render_ray_weights`  the first pass's weights (geometry branch only; `sigma_noise` applies here) -> depths, pdf
+      `ide3d_sample_pdf`          `num_steps` more depths per ray from that pdf
+      `ide3d_merge_depths`        both depth sets in ascending order (stable: the order of torch.sort(torch.cat([fine, coarse])))
+      `ide3d_render_rays_merged`  the fused march over the 2 * num_steps samples, no density noise
+
+    Arguments as `render_triplane_fused`; importance_u: the draws of `sample_pdf`, [num_steps] (one row for every ray) or
+    [N * R, num_steps]; None -> torch.rand.  Inference only: no gradients.  Returns the same triple, or None when the library
+    has no kernel for the configuration (what `render_triplane_fused` declines, and num_steps < 3 or > 1024).
+    """
+    assert clamp_mode in ('softplus', 'relu')
+    _init()
+    device = tex_planes.device
+    W, H = resolution
+    rays_d_cam, z_lin = _fused_ray_setup(device, float(fov), tuple(resolution), int(num_steps), float(ray_start), float(ray_end))
+    if tex_planes.stride(1) != 1:
+        tex_planes = tex_planes.contiguous(memory_format=torch.channels_last)
+    if geo_planes.stride(1) != 1:
+        geo_planes = geo_planes.contiguous(memory_format=torch.channels_last)
+    clamp_code = 0 if clamp_mode == 'softplus' else 1
+    n = tex_planes.shape[0]
+    first = _plugin.render_ray_weights(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp, clamp_code,
+                                       want=('z_vals', 'pdf_bins', 'pdf_weights'))
+    if first is None:
+        return None
+    _w, z_vals, bins, pdf_w = first
+    u = torch.rand(n * W * H, num_steps, device=device) if importance_u is None else importance_u
+    z_fine = _plugin.sample_pdf(bins, pdf_w, u.float())
+    z_all, src = _plugin.merge_depths(z_fine, z_vals)
+    res = _plugin.render_rays_merged(rays_d_cam, z_lin, cam2world, jitter, tex_planes, geo_planes, mlp, clamp_code, white_back,
+                                     max_depth, z_all, src, z_fine)
+    if res is None:
+        return None
+    feat, depth, wsum = res
     return feat.reshape(n, -1, H, W), depth.reshape(n, 1, H, W), wsum.reshape(n, 1, H, W)

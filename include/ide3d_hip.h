@@ -368,6 +368,40 @@ int ide3d_render_rays_backward_camera(const ide3d_render_params* p, const ide3d_
                                       const ide3d_render_camera_grads* c, void* stream);
 
 /*
+ * The hierarchical (importance) pass of the renderer as four launches, nothing per sample but depths and weights in memory (DESIGN.md
+ * section 5.24): ide3d_render_ray_weights -> ide3d_sample_pdf -> ide3d_merge_depths -> ide3d_render_rays_merged.  All three take what
+ * ide3d_render_rays takes and return IDE3D_ENOKERNEL for what it declines (last_back, planes not channels_last, (C, hidden) other than
+ * (32, 64) / (16, 32)) and for steps < 3 or steps > 1024 (ide3d_merge_depths keeps the 2 * steps keys of a ray in LDS: at most 2048).
+ * No atomics: results are bit-reproducible.
+ *
+ * ide3d_render_ray_weights: the first pass, geometry branch only.  p as for ide3d_render_rays (sigma_noise honoured, out_* ignored).
+ *   weights     [n * rays_per_img, steps]      fancy_integration's third output
+ *   z_vals      [n * rays_per_img, steps]      the (jittered) sample depths
+ *   pdf_bins    [n * rays_per_img, steps - 1]  0.5 * (z[s] + z[s + 1])
+ *   pdf_weights [n * rays_per_img, steps - 2]  weights[1 .. steps - 2] + 1e-5
+ * each contiguous, each may be NULL (not written); pdf_bins / pdf_weights are ide3d_sample_pdf's bins / weights with k = steps - 2.
+ *
+ * ide3d_merge_depths: per ray the stable ascending order of the concatenation [z_fine | z_coarse] (torch.sort(torch.cat(...)), equal
+ * depths keep concatenation order, -0 == +0, NaN last).  z_fine [rays, steps_fine], z_coarse [rays, steps_coarse], T = steps_fine +
+ * steps_coarse (1 <= T <= 2048, else IDE3D_EINVAL); z_all [rays, T]: the sorted depths, bit-equal to the inputs; src [rays, T]: index
+ * into the concatenation (src < steps_fine: fine sample src, else coarse sample src - steps_fine).  The order is total for any input bits:
+ * every row of src is a permutation of 0 .. T-1.
+ *
+ * ide3d_render_rays_merged: ide3d_render_rays over the total_steps = 2 * p->steps samples of each ray in z_all order, written to p->out_feat
+ * / out_depth / out_wsum (white_back / max_depth as there).  z_all / src [n * rays_per_img, total_steps] from ide3d_merge_depths of
+ * z_fine [n * rays_per_img, steps] (steps_fine = steps_coarse = steps) and ide3d_render_ray_weights' z_vals.  A coarse sample is placed
+ * from z_lin / jitter exactly as the first pass placed it, a fine one at cam2world[:3, 3] + (cam2world[:3, :3] * d_cam) * z_fine; delta =
+ * (z_all[s + 1] - z_all[s]) * |d_cam|, 1e10 for the last sample; p->sigma_noise is ignored (no density noise).  src entries are clamped
+ * into [0, total_steps) before use: no input data makes the kernel read outside its buffers.
+ */
+int ide3d_render_ray_weights(const ide3d_render_params* p, float* weights, float* z_vals, float* pdf_bins, float* pdf_weights,
+                             void* stream);
+int ide3d_merge_depths(const float* z_fine, const float* z_coarse, int64_t rays, int32_t steps_fine, int32_t steps_coarse,
+                       float* z_all, int32_t* src, void* stream);
+int ide3d_render_rays_merged(const ide3d_render_params* p, const float* z_all, const int32_t* src, const float* z_fine,
+                             int32_t total_steps, void* stream);
+
+/*
  * `renderer.sample_voxel(img_v, seg_v, pts)` (call site extract_shapes.py:146): the same two
  * gathers + MLPs for arbitrary points, no compositing.  out: [n*m, feat_ch + seg_ch + 1]
  * (sigma last).  If sigma_only != 0 only out_sigma [n*m] is written (the 256^3 density-cube
