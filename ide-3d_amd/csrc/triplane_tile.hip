@@ -522,6 +522,42 @@ triplane_sample_tile_pc_kernel(const TileArgs p) {
     }
 }
 
+// Parity hook (`ide3d_triplane_tile_masks`): the staged-plane mask of every chunk, from the kernel's own table code.  One wave per
+// (image, ray tile, chunk) does what T wave 0 does for that chunk: its own 64 samples through sample_taps(), the other 192 through
+// axis_index(), wave_reduce_pk4(), build_region_table(); lane 0 writes word 3 of the table's last row.
+__global__ void __launch_bounds__(64)
+triplane_tile_masks_kernel(const float* __restrict__ coords, int H, int W, int rays_w, int rays_per_image, int steps,
+                           int tiles_x, int tiles_per_image, int chunks, int32_t* __restrict__ masks) {
+    __shared__ u32x4 s_table[4];
+    const int lane = threadIdx.x;
+    const unsigned chunk = blockIdx.x % (unsigned)chunks;
+    const unsigned tile_lin = blockIdx.x / (unsigned)chunks;
+    const unsigned img = tile_lin / (unsigned)tiles_per_image;
+    const unsigned tile = tile_lin - img * (unsigned)tiles_per_image;
+    const unsigned ty = tile / (unsigned)tiles_x, tx = tile - ty * (unsigned)tiles_x;
+    const unsigned ray00 = ty * TT_EDGE * (unsigned)rays_w + tx * TT_EDGE;
+    const unsigned step0 = chunk * TT_DS, last_step = (unsigned)steps - 1u;
+    auto coord_ptr = [&](int k) {                  // sample lane + 64 k of the chunk = (ray t >> 2 of the tile, depth t & 3)
+        const unsigned t = (unsigned)lane + 64u * (unsigned)k, rl = t >> 2, ds = t & 3u;
+        const unsigned ray = ray00 + (rl >> 3) * (unsigned)rays_w + (rl & 7u);
+        return coords + (size_t)((img * (unsigned)rays_per_image + ray) * (unsigned)steps + min(step0 + ds, last_step)) * 3;
+    };
+    const float* cp = coord_ptr(0);
+    const SampleTaps t = sample_taps(cp[0], cp[1], cp[2], W, H);
+    unsigned lo0 = t.ax[0], lo1 = t.ax[1], hi0 = t.ax[0], hi1 = t.ax[1];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+        const float* q = coord_ptr(k);
+        const unsigned a0 = axis_index(q[0], W) | (axis_index(q[1], H) << 16);
+        const unsigned a1 = axis_index(q[1], W) | (axis_index(q[2], H) << 16);
+        lo0 = pk_min(lo0, a0); hi0 = pk_max(hi0, a0); lo1 = pk_min(lo1, a1); hi1 = pk_max(hi1, a1);
+    }
+    wave_reduce_pk4(lo0, lo1, hi0, hi1);
+    build_region_table(lo0, lo1, hi0, hi1, W, H, (unsigned)PC_CAP, s_table, lane);
+    __syncthreads();
+    if (lane == 0) masks[blockIdx.x] = (int32_t)s_table[3][3];
+}
+
 }  // namespace
 
 // Returns false when the hint / layout does not fit this kernel (the caller then uses the flat kernel).
@@ -560,6 +596,21 @@ bool launch_triplane_tile(const float* planes, const int64_t* s, int n, int C, i
 }
 
 }  // namespace ide3d
+
+extern "C" int ide3d_triplane_tile_masks(int32_t H, int32_t W, const float* coords, int32_t n,
+                                         int32_t rays_h, int32_t rays_w, int32_t steps, int32_t* masks, void* stream) {
+    using namespace ide3d;
+    IDE3D_CHECK_ARG(coords && masks && n > 0 && H > 0 && W > 0 && H <= 0x7fff && W <= 0x7fff, "triplane_tile_masks: bad argument");
+    IDE3D_CHECK_ARG(rays_h > 0 && rays_w > 0 && steps > 0 && rays_h % TT_EDGE == 0 && rays_w % TT_EDGE == 0 && steps % TT_DS == 0,
+                    "triplane_tile_masks: not a ray grid of 8 x 8-ray tiles and 4-step chunks");
+    const int64_t blocks = (int64_t)n * (rays_h / TT_EDGE) * (rays_w / TT_EDGE) * (steps / TT_DS);
+    IDE3D_CHECK_ARG((int64_t)n * rays_h * rays_w * steps < (1LL << 31) && blocks < (1LL << 31), "triplane_tile_masks: too many samples");
+    hipLaunchKernelGGL(triplane_tile_masks_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream,
+                       coords, (int)H, (int)W, (int)rays_w, (int)(rays_h * rays_w), (int)steps,
+                       (int)(rays_w / TT_EDGE), (int)((rays_h / TT_EDGE) * (rays_w / TT_EDGE)), (int)(steps / TT_DS), masks);
+    IDE3D_CHECK_LAUNCH("triplane_tile_masks");
+    return IDE3D_OK;
+}
 
 #ifdef IDE3D_TT_TRACE
 extern "C" int ide3d_debug_tt_wg(unsigned long long* host) {

@@ -358,6 +358,7 @@ def load():
             'ide3d_triplane_sample': [vp, ctypes.POINTER(i64 * 4), i32, i32, i32, i32, vp, i64, vp, vp],
             'ide3d_triplane_sample_rays': [vp, ctypes.POINTER(i64 * 4), i32, i32, i32, i32, vp, i64, vp, i32, i32, i32, vp],
             'ide3d_triplane_taps': [i32, i32, vp, i64, vp, vp],
+            'ide3d_triplane_tile_masks': [i32, i32, vp, i32, i32, i32, i32, vp, vp],
             'ide3d_triplane_sample_backward': [vp, vp, ctypes.POINTER(i64 * 4), i32, i32, i32, i32, vp, i64,
                                                vp, ctypes.POINTER(i64 * 4), vp, vp],
             'ide3d_composite': [vp, vp, vp, vp, i64, i32, i32, ctypes.c_int, ctypes.c_int, ctypes.c_int, f32,
@@ -465,7 +466,7 @@ def load():
 
 EXPORTED_SYMBOLS = (
     'ide3d_last_error', 'ide3d_abi_version', 'ide3d_build_arch', 'ide3d_build_flags', 'ide3d_exclusive_violations', 'ide3d_exclusive_violation_text', 'ide3d_bias_act', 'ide3d_upfirdn2d', 'ide3d_upfirdn2d_ex',
-    'ide3d_filtered_lrelu', 'ide3d_filtered_lrelu_act', 'ide3d_triplane_sample', 'ide3d_triplane_sample_rays', 'ide3d_triplane_taps',
+    'ide3d_filtered_lrelu', 'ide3d_filtered_lrelu_act', 'ide3d_triplane_sample', 'ide3d_triplane_sample_rays', 'ide3d_triplane_taps', 'ide3d_triplane_tile_masks',
     'ide3d_triplane_sample_backward', 'ide3d_composite', 'ide3d_sample_pdf', 'ide3d_render_rays', 'ide3d_render_rays_backward', 'ide3d_sample_voxel',
     'ide3d_lattice_points', 'ide3d_density_lattice',
     'ide3d_modconv2d', 'ide3d_modconv2d_heads', 'ide3d_modconv_workspace_bytes', 'ide3d_modconv_plan', 'ide3d_set_conv_arithmetic', 'ide3d_get_conv_arithmetic', 'ide3d_frame_u8', 'ide3d_sphere_points', 'ide3d_cam2world', 'ide3d_style_demod', 'ide3d_fold_heads',
@@ -941,6 +942,23 @@ class TriplanePlugin:
                 rc = load().ide3d_triplane_taps(H, W, _ptr(coords), coords.shape[0], _ptr(taps), _stream(coords))
             _check(rc, 'triplane_taps')
         return taps
+
+    @staticmethod
+    def tile_masks(H, W, coords, ray_grid):
+        """coords [n, rays_h * rays_w * steps, 3] -> int32 [n, tiles, steps / 4]: the planes `sample(..., ray_grid=)` stages in LDS per
+        chunk (bit p = plane p), from the gather kernel's own region-table code.  Parity hook for the tests."""
+        rh, rw, steps = (int(v) for v in ray_grid)
+        coords = coords.contiguous()
+        _require(coords.is_cuda and coords.dtype == torch.float32, 'coords must be float32 on a CUDA device')
+        _require(coords.ndim == 3 and coords.shape[2] == 3 and coords.shape[1] == rh * rw * steps, 'coords must be [n, rays_h * rays_w * steps, 3]')
+        _require(rh > 0 and rw > 0 and steps > 0 and rh % 8 == 0 and rw % 8 == 0 and steps % 4 == 0, 'ray_grid must be made of 8 x 8-ray tiles and 4-step chunks')
+        n = coords.shape[0]
+        masks = torch.empty([n, (rh // 8) * (rw // 8), steps // 4], dtype=torch.int32, device=coords.device)
+        if n:
+            with _dev_guard(coords.device):
+                rc = load().ide3d_triplane_tile_masks(H, W, _ptr(coords), n, rh, rw, steps, _ptr(masks), _stream(coords))
+            _check(rc, 'triplane_tile_masks')
+        return masks
 
     @staticmethod
     def sample_backward(grad_out, planes, coords, need_coord_grad):

@@ -222,6 +222,16 @@ int ide3d_triplane_taps(int32_t H, int32_t W, const float* coords, int64_t n_tim
                         int32_t* taps, void* stream);
 
 /*
+ * Debug / parity hook of the ray-grid gather: which planes `ide3d_triplane_sample_rays` stages in LDS
+ * for every chunk (8x8 rays x 4 depth steps) of coords [n, rays_h, rays_w, steps, 3], computed by the
+ * gather kernel's own region-table code.  masks: int32 [n, tiles, steps / 4], tiles row-major over
+ * the (rays_h / 8) x (rays_w / 8) ray tiles; bit p = plane p is staged, the others are read like the
+ * flat kernel reads them.  rays_h, rays_w must be multiples of 8, steps of 4; H, W <= 32767.
+ */
+int ide3d_triplane_tile_masks(int32_t H, int32_t W, const float* coords, int32_t n,
+                              int32_t rays_h, int32_t rays_w, int32_t steps, int32_t* masks, void* stream);
+
+/*
  * Backward of the gather w.r.t. the planes (atomic scatter-add into grad_planes, which the
  * caller zero-fills) and optionally w.r.t. the coordinates (grad_coords may be NULL).
  * Replaces aten::grid_sampler_2d_backward as used by grid_sample_gradfix.py:55-60.

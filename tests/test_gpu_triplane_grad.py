@@ -23,7 +23,6 @@ Rows with NaN / inf coordinates are the only ones ever left out, and only of the
 there is a mix of NaN and 0): each test asserts that the rows the reference marks non-finite are exactly the ones it inserted.
 """
 
-import itertools
 import math
 
 import pytest
@@ -45,29 +44,7 @@ def _uniform(g, n, m):
     return (torch.rand(n, m, 3, generator=g) * 2 - 1) * 1.1
 
 
-def _axis_edges(size):
-    """Coordinates of one axis, by where their tap position u = ((c + 1) * size - 1) / 2 falls."""
-    s = float(size)
-    centres = [(2 * i + 1) / s - 1 for i in sorted({0, size // 2, size - 1})]          # u = i: an exact texel centre where fp32 allows
-    return ([-1.0, 0.0, 1.0]                                   # the plane's edges (u = -0.5, size - 0.5: half a texel outside the outermost centres) and its middle
-            + centres
-            + [-1 - 0.5 / s, 1 + 0.5 / s]                      # u = -0.75, size - 0.25: one tap of the axis in bounds, inside the padding
-            + [-1 - 1 / s, 1 + 1 / s]                          # u = -1, size: the in-bounds tap has weight 0 / no tap in bounds
-            + [-1 - 3 / s, 1 + 3 / s, -1e30, 1e30])            # more than one texel outside, and far outside
-
-
-def _edges(g, n, m, H, W):
-    """Every combination of the per-axis edge values (sides: two taps in bounds, corners: one), shuffled, cycled over the n * m rows."""
-    xs, zs = _axis_edges(W), _axis_edges(H)
-    ys = xs if H == W else xs + zs                              # y is plane 0's v (H) and plane 1's u (W)
-    combos = torch.tensor(list(itertools.product(xs, ys, zs)), dtype=torch.float32)
-    combos = combos[torch.randperm(combos.shape[0], generator=g)]
-    idx = torch.arange(n * m) % combos.shape[0]
-    return combos[idx].reshape(n, m, 3).contiguous()
-
-
-NONFINITE = [[float('nan'), 0.0, 0.0], [0.0, float('nan'), 0.0], [0.0, 0.0, float('nan')], [float('inf'), 0.1, 0.0],
-             [0.0, float('-inf'), 0.2], [0.3, 0.0, float('inf')], [float('nan'), float('inf'), float('-inf')]]
+from triplane_ref import NONFINITE, axis_edges as _axis_edges, edges as _edges          # shared with tests/test_gpu_triplane_fwd.py
 
 
 # ---- comparison --------------------------------------------------------------------------------------------------------------------

@@ -126,3 +126,96 @@ def test_error_scales_and_counts_equal_the_scalar_definition():
         assert bool(((got - want).abs() <= 1e-13 * scale).all()), what
     assert bool((ref.abs_planes >= ref.grad_planes.abs() * (1 - 1e-12)).all()) and bool((ref.abs_coords >= ref.grad_coords.abs() * (1 - 1e-12)).all())
     assert int(kp.max()) > 1 and int((kp == 0).sum()) > 0
+
+
+# ---- the forward definition and the host model of the ray-grid kernel (tests/test_gpu_triplane_fwd.py) ----------------------------------
+
+def test_forward_ref_equals_float64_grid_sample():
+    """`triplane_forward_ref` = three float64 ATen grid_sample look-ups (bilinear, zeros padding, align_corners=False), summed; on the
+    inputs above both sides see one and the same tap position, so every element is compared, to 1e-12 of its A."""
+    co, planes, _ = _inputs()
+    out, A, hit, finite = triplane_ref.triplane_forward_ref(planes, co)
+    assert out.shape == A.shape == (N * M, C) and out.dtype == torch.float64 and hit.shape == finite.shape == (N, M)
+    assert bool(finite.all()) and bool(hit.any()) and not bool(hit.all())
+    want = util._sample_from_triplane_ref(co.double(), planes)
+    assert want.shape == out.shape
+    err = (out - want).abs()
+    print(f'forward: {out.numel()} elements, worst error / A {float((err / A.clamp_min(1e-300)).max()):.2e}')
+    assert bool((err <= 1e-12 * A).all())
+    assert bool((A >= out.abs() * (1 - 1e-12)).all())
+    dead = (~hit).reshape(-1)
+    assert bool((out[dead] == 0).all()) and bool((want[dead] == 0).all()) and bool((A[dead] == 0).all())
+    assert torch.equal(hit, triplane_ref.triplane_backward_ref(torch.ones(N * M, C, dtype=torch.float64), planes, co).hit)
+    # a plane that reads a non-finite coordinate has no tap; the plane that does not read it is untouched
+    bad = co.clone()
+    bad[0, :len(triplane_ref.NONFINITE)] = torch.tensor(triplane_ref.NONFINITE)
+    far = torch.nan_to_num(bad, nan=1e30, posinf=1e30, neginf=-1e30)
+    o_bad, a_bad, hit_bad, fin_bad = triplane_ref.triplane_forward_ref(planes, bad)
+    o_far, a_far, hit_far, fin_far = triplane_ref.triplane_forward_ref(planes, far)
+    assert int((~fin_bad).sum()) == len(triplane_ref.NONFINITE) and bool(fin_far.all())
+    assert torch.equal(o_bad, o_far) and torch.equal(a_bad, a_far) and torch.equal(hit_bad, hit_far)
+    assert not bool(hit_bad[0, 6]) and bool(hit_bad[0, :3].all())          # (nan, inf, -inf): nothing left; (nan, 0, 0): plane 1 is
+
+
+def test_tile_plan_is_the_launchers_rule():
+    assert triplane_ref.tile_plan(2, 16, 16, 8) == (2, 1)            # the variants case: a workgroup per chunk
+    assert triplane_ref.tile_plan(4, 32, 32, 64) == (4, 4)           # the hand-over case: 256 workgroups of four chunks
+    assert triplane_ref.tile_plan(1, 64, 64, 96) == (4, 6)           # the benchmark's shape
+    assert triplane_ref.tile_plan(3, 16, 24, 12) == (3, 1) and triplane_ref.tile_plan(8, 64, 64, 96) == (1, 24)
+    assert triplane_ref.tile_plan(1, 8, 8, 28) == (7, 1)             # only divisors of the chunk count
+
+
+def test_virtual_index_saturates_and_maps_nan_to_zero():
+    c = torch.tensor([float('nan'), float('-inf'), -1e30, -1.5, -1.0, 0.0, 1.0, 1.5, 1e30, float('inf')])
+    assert triplane_ref.virtual_index(c, 8).tolist() == [0, 0, 0, 0, 0, 4, 8, 8, 8, 8]
+    assert triplane_ref.virtual_index(c, 1).tolist() == [0, 0, 0, 0, 0, 1, 1, 1, 1, 1]
+
+
+def test_constructed_ray_grids_take_the_prescribed_variants():
+    """What the GPU suite relies on, from the host model alone: every chunk of every constructed case gets the mask its kind prescribes."""
+    import triplane_cases
+    for name, case in (('variants', triplane_cases.variants_case()), ('hand-over', triplane_cases.handover_case()),
+                       ('8x24', triplane_cases.mixed_case(311, 2, 20, 28, (8, 24, 8))), ('24x8', triplane_cases.mixed_case(312, 2, 20, 28, (24, 8, 8))),
+                       ('channel slice', triplane_cases.mixed_case(313, 2, 20, 28, (16, 16, 8))),
+                       ('edges 5x9', triplane_cases.edge_grid_case(5, 9)), ('edges 9x5', triplane_cases.edge_grid_case(9, 5))):
+        got = triplane_ref.staged_masks(case['coords'], case['H'], case['W'], case['ray_grid'])
+        assert got.shape == case['want'].shape, name
+        assert torch.equal(got, case['want']), (name, got.flatten().tolist(), case['want'].flatten().tolist())
+        print(f'{name}: masks {sorted(set(got.flatten().tolist()))} over {got.numel()} chunks')
+
+
+def test_variants_case_reaches_every_mask_and_the_three_way_tie():
+    import triplane_cases
+    case = triplane_cases.variants_case()
+    masks = triplane_ref.staged_masks(case['coords'], case['H'], case['W'], case['ray_grid']).flatten()
+    assert set(masks.tolist()) == set(range(8))
+    cost = triplane_ref.staged_costs(case['coords'], case['H'], case['W'], case['ray_grid']).reshape(3, -1)
+    tie = case['kinds'].index('tie')
+    l = cost[:, tie].tolist()
+    assert l[0] == l[1] == l[2] == 184 and sum(l) > triplane_ref.TT_CAP and int(masks[tie]) == 3          # usable, over budget, all pairs equal
+    # 'big' is unstaged because of its size, 'out' because it leaves the plane: both with mask 0
+    assert int(masks[case['kinds'].index('big')]) == 0 and int(masks[case['kinds'].index('out')]) == 0
+    _, _, hit, _ = triplane_ref.triplane_forward_ref(torch.zeros(2, 3, 48, 64), case['coords'])
+    per_chunk = hit.reshape(2, 2, 8, 2, 8, 2, 4).permute(0, 1, 3, 5, 2, 4, 6).reshape(16, 256)
+    assert bool(per_chunk[case['kinds'].index('big')].all()) and not bool(per_chunk[case['kinds'].index('out')].any())
+
+
+def test_handover_case_changes_the_mask_inside_workgroups():
+    import triplane_cases
+    case = triplane_cases.handover_case()
+    segs, cps = triplane_ref.tile_plan(case['n'], *case['ray_grid'])
+    assert (segs, cps) == (4, 4) and cps >= 4
+    masks = triplane_ref.staged_masks(case['coords'], case['H'], case['W'], case['ray_grid'])
+    per_wg = masks.reshape(-1, cps)                                 # a workgroup = (image, tile, segment): cps consecutive chunks
+    assert per_wg.shape[0] == 256
+    steps = {(int(a), int(b)) for row in per_wg.tolist() for a, b in zip(row[:-1], row[1:])}
+    assert all(a != b for a, b in steps)                            # neighbouring chunks never share a mask
+    for m_ in (0, 1, 2, 4):
+        assert (7, m_) in steps and (m_, 7) in steps, m_
+    assert any(a in (3, 5, 6) and b in (3, 5, 6) for a, b in steps)
+    # ... nor a box: the plane-0 region of neighbouring chunks differs in origin or size wherever both are staged
+    co = case['coords'].reshape(case['n'], 4, 8, 4, 8, 16, 4, 3).permute(0, 1, 3, 5, 2, 4, 6, 7).reshape(-1, cps, 256, 3)
+    lo = triplane_ref.virtual_index(co[..., 0], case['W']).amin(-1)
+    hi = triplane_ref.virtual_index(co[..., 0], case['W']).amax(-1)
+    same = (lo[:, 1:] == lo[:, :-1]) & (hi[:, 1:] == hi[:, :-1])
+    assert float(same.double().mean()) < 0.05
