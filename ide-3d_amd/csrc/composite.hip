@@ -203,43 +203,65 @@ composite_lds_kernel(const float* __restrict__ rgb_sigma, const float* __restric
     }
 }
 
+// The form decision of ide3d_composite, host arithmetic only: the launch below and the ide3d_composite_plan query both go through it.
+static void composite_plan(const void* rgb_sigma, int64_t rays, int steps, int ch, ide3d_composite_plan_info* out) {
+    // LDS-staged path: contiguous, 16-byte aligned ray blocks that fit four to a workgroup
+    const int64_t block = (int64_t)steps * (ch + 1);
+    const size_t lds = (size_t)4 * (block + ((steps + 3) & ~3)) * sizeof(float);
+    if (block % 4 == 0 && block <= 40 * 256 && lds <= 160 * 1024 && ((reinterpret_cast<uintptr_t>(rgb_sigma) & 15) == 0)) {
+        const int nld = (int)((block / 4 + kWave - 1) / kWave);
+        // one-wave workgroups, one per ray: the LDS footprint is per wave (block + weights), so 64-thread workgroups pack the CU's
+        // 160 KB with as many waves as fit (7 at 96 x 53) instead of one 4-wave workgroup
+        out->form = nld <= 8 ? IDE3D_COMPOSITE_LDS8 : nld <= 20 ? IDE3D_COMPOSITE_LDS20 : IDE3D_COMPOSITE_LDS40;
+        out->workgroup = kWave;
+        out->grid = rays < 0x7fffffff ? rays : 0x7fffffff;
+        out->lds_bytes = (int64_t)(lds / 4);
+        return;
+    }
+    out->form = IDE3D_COMPOSITE_FALLBACK;
+    out->workgroup = 256;
+    out->grid = stream_grid(rays, 4);
+    out->lds_bytes = (int64_t)((size_t)4 * steps * sizeof(float));
+}
+
 }  // namespace ide3d
+
+#define IDE3D_COMPOSITE_CHECK_SHAPE() \
+    IDE3D_CHECK_ARG(rays >= 0 && steps >= 1 && steps <= kMaxSteps && ch >= 1, "composite: bad shape (steps <= %d)", kMaxSteps)
+
+extern "C" int ide3d_composite_plan(const void* rgb_sigma, int64_t rays, int32_t steps, int32_t ch, ide3d_composite_plan_info* out) {
+    using namespace ide3d;
+    IDE3D_CHECK_ARG(out, "composite_plan: null pointer");
+    IDE3D_COMPOSITE_CHECK_SHAPE();
+    composite_plan(rgb_sigma, rays, steps, ch, out);
+    return IDE3D_OK;
+}
 
 extern "C" int ide3d_composite(const float* rgb_sigma, const float* z_vals, const float* dir_norm,
                                const float* noise, int64_t rays, int32_t steps, int32_t ch,
                                int clamp_mode, int last_back, int white_back, float max_depth,
                                int fill_mode, float* rgb, float* depth, float* weights, void* stream) {
     using namespace ide3d;
-    IDE3D_CHECK_ARG(rgb_sigma && z_vals && dir_norm && rgb, "composite: null pointer");
-    IDE3D_CHECK_ARG(rays >= 0 && steps >= 1 && steps <= kMaxSteps && ch >= 1, "composite: bad shape (steps <= %d)", kMaxSteps);
+    IDE3D_COMPOSITE_CHECK_SHAPE();
     IDE3D_CHECK_ARG(clamp_mode == 0 || clamp_mode == 1, "composite: Need to choose clamp mode");
     IDE3D_CHECK_ARG(fill_mode != 1 || ch == 3, "composite: fill_mode 'debug' needs 3 colour channels");
-    if (rays == 0) return IDE3D_OK;
-    const int grid = stream_grid(rays, 4);
-    {
-        // LDS-staged path: contiguous, 16-byte aligned ray blocks that fit four to a workgroup
-        const int64_t block = (int64_t)steps * (ch + 1);
-        const size_t lds = (size_t)4 * (block + ((steps + 3) & ~3)) * sizeof(float);
-        if (block % 4 == 0 && block <= 40 * 256 && lds <= 160 * 1024 && ((reinterpret_cast<uintptr_t>(rgb_sigma) & 15) == 0)) {
-            const int nld = (int)((block / 4 + kWave - 1) / kWave);
-            // one-wave workgroups, one per ray: the LDS footprint is per wave (block + weights), so 64-thread workgroups pack the CU's
-            // 160 KB with as many waves as fit (7 at 96 x 53) instead of one 4-wave workgroup
-            const size_t lds_w = lds / 4;
-            const int64_t pgrid = rays < 0x7fffffff ? rays : 0x7fffffff;
-            auto go = [&](auto kern) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w);
-                hipLaunchKernelGGL(kern, dim3((unsigned)pgrid), dim3(64), lds_w, (hipStream_t)stream,
-                                   rgb_sigma, z_vals, dir_norm, noise, rays, steps, ch, clamp_mode, last_back, white_back,
-                                   max_depth, fill_mode, rgb, depth, weights);
-            };
-            if (nld <= 8) go(composite_lds_kernel<8>); else if (nld <= 20) go(composite_lds_kernel<20>); else go(composite_lds_kernel<40>);
-            IDE3D_CHECK_LAUNCH("composite");
-            return IDE3D_OK;
-        }
+    if (rays == 0) return IDE3D_OK;          // (empty tensors have no address: before the pointer check, as in ide3d_sample_pdf)
+    IDE3D_CHECK_ARG(rgb_sigma && z_vals && dir_norm && rgb, "composite: null pointer");
+    ide3d_composite_plan_info plan;
+    composite_plan(rgb_sigma, rays, steps, ch, &plan);
+    auto go = [&](auto kern) {
+        if (plan.form != IDE3D_COMPOSITE_FALLBACK)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+        hipLaunchKernelGGL(kern, dim3((unsigned)plan.grid), dim3((unsigned)plan.workgroup), (size_t)plan.lds_bytes, (hipStream_t)stream,
+                           rgb_sigma, z_vals, dir_norm, noise, rays, steps, ch, clamp_mode, last_back, white_back,
+                           max_depth, fill_mode, rgb, depth, weights);
+    };
+    switch (plan.form) {
+        case IDE3D_COMPOSITE_LDS8: go(composite_lds_kernel<8>); break;
+        case IDE3D_COMPOSITE_LDS20: go(composite_lds_kernel<20>); break;
+        case IDE3D_COMPOSITE_LDS40: go(composite_lds_kernel<40>); break;
+        default: go(composite_kernel); break;
     }
-    hipLaunchKernelGGL(composite_kernel, dim3(grid), dim3(256), (size_t)4 * steps * sizeof(float), (hipStream_t)stream,
-                       rgb_sigma, z_vals, dir_norm, noise, rays, steps, ch, clamp_mode, last_back, white_back,
-                       max_depth, fill_mode, rgb, depth, weights);
     IDE3D_CHECK_LAUNCH("composite");
     return IDE3D_OK;
 }

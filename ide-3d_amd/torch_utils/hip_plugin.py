@@ -196,6 +196,13 @@ class _ModconvPlanInfo(ctypes.Structure):
     ]
 
 
+class _CompositePlanInfo(ctypes.Structure):
+    """ide3d_composite_plan_info (include/ide3d_hip.h): what ide3d_composite would launch."""
+    _fields_ = [('form', ctypes.c_int32), ('workgroup', ctypes.c_int32), ('grid', ctypes.c_int64), ('lds_bytes', ctypes.c_int64)]
+
+
+COMPOSITE_FORMS = ('fallback', 'lds8', 'lds20', 'lds40')     # IDE3D_COMPOSITE_*
+
 PLAN_KINDS = ('fp32', 'split', 'split_teams', 'head_split', 'head_resident', 'head_small')     # IDE3D_PLAN_*
 
 STYLE_BATCH_MAX = 24        # IDE3D_STYLE_BATCH_MAX
@@ -363,6 +370,7 @@ def load():
                                                vp, ctypes.POINTER(i64 * 4), vp, vp],
             'ide3d_composite': [vp, vp, vp, vp, i64, i32, i32, ctypes.c_int, ctypes.c_int, ctypes.c_int, f32,
                                 ctypes.c_int, vp, vp, vp, vp],
+            'ide3d_composite_plan': [vp, i64, i32, i32, ctypes.POINTER(_CompositePlanInfo)],
             'ide3d_sample_pdf': [vp, vp, vp, i64, i64, i32, i32, f32, vp, vp],
             'ide3d_render_rays': [ctypes.POINTER(_RenderParams), vp],
             'ide3d_render_ray_weights': [ctypes.POINTER(_RenderParams), vp, vp, vp, vp, vp],
@@ -467,7 +475,7 @@ def load():
 EXPORTED_SYMBOLS = (
     'ide3d_last_error', 'ide3d_abi_version', 'ide3d_build_arch', 'ide3d_build_flags', 'ide3d_exclusive_violations', 'ide3d_exclusive_violation_text', 'ide3d_bias_act', 'ide3d_upfirdn2d', 'ide3d_upfirdn2d_ex',
     'ide3d_filtered_lrelu', 'ide3d_filtered_lrelu_act', 'ide3d_triplane_sample', 'ide3d_triplane_sample_rays', 'ide3d_triplane_taps', 'ide3d_triplane_tile_masks',
-    'ide3d_triplane_sample_backward', 'ide3d_composite', 'ide3d_sample_pdf', 'ide3d_render_rays', 'ide3d_render_rays_backward', 'ide3d_sample_voxel',
+    'ide3d_triplane_sample_backward', 'ide3d_composite', 'ide3d_composite_plan', 'ide3d_sample_pdf', 'ide3d_render_rays', 'ide3d_render_rays_backward', 'ide3d_sample_voxel',
     'ide3d_lattice_points', 'ide3d_density_lattice',
     'ide3d_modconv2d', 'ide3d_modconv2d_heads', 'ide3d_modconv_workspace_bytes', 'ide3d_modconv_plan', 'ide3d_set_conv_arithmetic', 'ide3d_get_conv_arithmetic', 'ide3d_frame_u8', 'ide3d_sphere_points', 'ide3d_cam2world', 'ide3d_style_demod', 'ide3d_fold_heads',
     'ide3d_style_demod_batch', 'ide3d_fold_heads_batch',
@@ -2424,6 +2432,21 @@ def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epil
     out = {name: getattr(info, name) for name, _ in _ModconvPlanInfo._fields_ if name != 'reserved'}
     out['kind'] = PLAN_KINDS[info.kind]
     return out
+
+
+def composite_plan(rgb_sigma, rays=None, steps=None, ch=None):
+    """Host-only (works without a GPU): the kernel form `VolumeRenderPlugin.composite` would launch -> dict of the ide3d_composite_plan_info
+    fields, `form` as a name from COMPOSITE_FORMS.  rgb_sigma: a [rays, steps, ch + 1] tensor on any device (its shape and the 16-byte
+    alignment of its address count; `.contiguous()` is applied as the launch does), or an address / alignment as an int next to rays,
+    steps and ch."""
+    if torch.is_tensor(rgb_sigma):
+        rays, steps, row = rgb_sigma.shape
+        ch, rgb_sigma = row - 1, rgb_sigma.contiguous().data_ptr()
+    info = _CompositePlanInfo()
+    rc = load().ide3d_composite_plan(ctypes.c_void_p(int(rgb_sigma)), rays, steps, ch, ctypes.byref(info))       # (not a launch: stays out of CALLS)
+    if rc != 0:
+        raise RuntimeError(f'composite_plan failed (code {rc}): ' + load().ide3d_last_error().decode('utf-8', 'replace'))
+    return dict(form=COMPOSITE_FORMS[info.form], grid=info.grid, workgroup=info.workgroup, lds_bytes=info.lds_bytes)
 
 
 _ARITH_NAMES = {'fp32': 1, 'bf16x3': 3, 'bf16x6': 6, 'f16x3': 16, 'default': 0}

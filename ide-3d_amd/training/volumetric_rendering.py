@@ -94,7 +94,7 @@ def _fancy_integration_torch(rgb_sigma, rays_d_cam, z_vals, noise, last_back, wh
     if max_depth:
         depth_final = depth_final + (1 - weights_sum) * max_depth
     if fill_mode == 'debug':
-        rgb_final[weights_sum.squeeze(-1) < 0.9] = torch.tensor([1., 0, 0], device=rgb_final.device)
+        rgb_final[weights_sum.squeeze(-1) < 0.9] = torch.tensor([1., 0, 0], device=rgb_final.device, dtype=rgb_final.dtype)
     elif fill_mode == 'weight':
         rgb_final = weights_sum.expand_as(rgb_final)
     return rgb_final, depth_final, weights
@@ -116,7 +116,9 @@ def fancy_integration(rgb_sigma, rays_d_cam, z_vals, device, noise_std=0.5, last
 
     on_gpu = rgb_sigma.device.type == 'cuda' and rgb_sigma.dtype == torch.float32
     needs_grad = torch.is_grad_enabled() and (rgb_sigma.requires_grad or z_vals.requires_grad)
-    if on_gpu and not needs_grad and _init():
+    # one sample: the definition below drops it (the only delta is an empty tensor's, so weights come out [N, R, 0, 1]); the kernel would
+    # integrate it with delta 1e10.  Both devices follow the definition
+    if on_gpu and not needs_grad and rgb_sigma.shape[2] >= 2 and _init():
         n, r, s, c1 = rgb_sigma.shape
         dir_norm = torch.norm(rays_d_cam, p=2, dim=-1).reshape(n * r)
         rgb, depth, weights = _plugin.composite(

@@ -257,6 +257,23 @@ int ide3d_composite(const float* rgb_sigma, const float* z_vals, const float* di
                     const float* noise, int64_t rays, int32_t steps, int32_t ch,
                     int clamp_mode, int last_back, int white_back, float max_depth,
                     int fill_mode, float* rgb, float* depth, float* weights, void* stream);
+/* steps == 1 is accepted: one sample, delta 1e10 (the last sample's delta).  `fancy_integration` itself never sends it: the tensor
+ * definition drops the lone sample (weights [N, R, 0, 1]), and the call surface follows the definition there. */
+
+/* Host-only planning query (no launch, no device access): which of the kernel forms ide3d_composite would launch for this shape, with its
+ * grid, workgroup size and dynamic LDS bytes.  `rgb_sigma` counts for its 16-byte alignment only and is never dereferenced.  The launch
+ * goes through the same decision.  Same shape checks as ide3d_composite.  For tests and tooling; not part of the reference's interface. */
+enum { IDE3D_COMPOSITE_FALLBACK = 0, /* composite_kernel: 4 waves per workgroup, rows read from global memory, any shape / alignment */
+       IDE3D_COMPOSITE_LDS8 = 1,     /* composite_lds_kernel<8>:  ray block staged in LDS, steps * (ch + 1) <= 2048 floats */
+       IDE3D_COMPOSITE_LDS20 = 2,    /* composite_lds_kernel<20>: <= 5120 floats */
+       IDE3D_COMPOSITE_LDS40 = 3 };  /* composite_lds_kernel<40>: <= 10240 floats */
+typedef struct ide3d_composite_plan_info {
+    int32_t form;                    /* IDE3D_COMPOSITE_* */
+    int32_t workgroup;               /* threads per workgroup */
+    int64_t grid;                    /* workgroups */
+    int64_t lds_bytes;               /* dynamic LDS per workgroup */
+} ide3d_composite_plan_info;
+int ide3d_composite_plan(const void* rgb_sigma, int64_t rays, int32_t steps, int32_t ch, ide3d_composite_plan_info* out);
 
 /* ---- importance resampling ------------------------------------------------------------- */
 /*

@@ -320,9 +320,10 @@ def lookat_pose(h, v, lookat, radius):
 
 
 def composite(rgb_sigma, rays_d_cam, z_vals, noise=None, last_back=False, white_back=False, max_depth=None,
-              clamp_mode='softplus', fill_mode=None):
+              clamp_mode='softplus', fill_mode=None, keep_double=False):
     """fancy_integration (volumetric_rendering.py:34-74) with an explicit sequential loop over depth in float64.
-    rgb_sigma [N,R,S,C+1], rays_d_cam [N,R,3], z_vals [N,R,S,1], noise (already scaled) [N,R,S,1] or None."""
+    rgb_sigma [N,R,S,C+1], rays_d_cam [N,R,3], z_vals [N,R,S,1], noise (already scaled) [N,R,S,1] or None.
+    keep_double: return the float64 results unrounded (for error measurements below a float32 ulp)."""
     rs = rgb_sigma.double()
     z = z_vals.double()
     N, R, S, C1 = rs.shape
@@ -356,6 +357,8 @@ def composite(rgb_sigma, rays_d_cam, z_vals, noise=None, last_back=False, white_
         rgb[wsum < 0.9] = torch.tensor([1., 0., 0.], dtype=torch.float64)
     elif fill_mode == 'weight':
         rgb = wsum[..., None].expand_as(rgb).clone()
+    if keep_double:
+        return rgb, depth, weights[..., None]
     return rgb.float(), depth.float(), weights[..., None].float()
 
 

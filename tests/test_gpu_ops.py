@@ -14,6 +14,7 @@ import torch
 
 from oracle import fast_ops
 from oracle import ops as oracle_ops
+import pdf_ref
 from util import assert_close, filter_from, t
 
 pytestmark = pytest.mark.gpu
@@ -553,18 +554,7 @@ def test_sample_pdf_kernel(golden, gpu_device):
     # a float64 piece-wise linear cdf; on either branch the deviation is bounded by the mass eps of the bin).
     err = (got.cpu() - want).abs()
     assert float((err > 5e-6).float().mean()) < 1e-4, f'sample_pdf at the benchmark shape: {int((err > 5e-6).sum())} elements differ'
-    def cdf_at(smp):
-        pd = (wts.double() + 1e-5)
-        cd = torch.cat([torch.zeros(rays, 1, dtype=torch.float64), torch.cumsum(pd / pd.sum(-1, keepdim=True), -1)], -1)
-        bd = bins.double()
-        i = (torch.searchsorted(bd, smp.double().contiguous(), right=True) - 1).clamp(0, bd.shape[1] - 2)
-        b0, b1 = torch.gather(bd, 1, i), torch.gather(bd, 1, i + 1)
-        c0, c1 = torch.gather(cd, 1, i), torch.gather(cd, 1, i + 1)
-        # tolerance: the mass eps of a bin on the `denom -> 1` branch + a float32 ulp of the depth (2.4e-7 near 3) times the
-        # steepest cdf slope of the ray
-        steepest = ((cd[:, 1:] - cd[:, :-1]) / (bd[:, 1:] - bd[:, :-1])).max(-1, keepdim=True)[0]
-        return c0 + (smp.double() - b0) / (b1 - b0) * (c1 - c0), 2e-5 + steepest * 5e-7
-    f_got, f_tol = cdf_at(got.cpu())
+    f_got, f_tol = pdf_ref.cdf_at(bins, wts, got.cpu())
     assert bool(((f_got - u.double()).abs() <= f_tol).all()), 'cdf(sample) != u'
     assert bool((got.cpu() >= bins[:, :1] - 1e-6).all() and (got.cpu() <= bins[:, -1:] + 1e-6).all()), 'samples stay inside the bins'
     # size-independent property: sorted draws give sorted samples (the inverse cdf is monotone)
