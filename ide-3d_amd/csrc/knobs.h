@@ -32,6 +32,11 @@ inline const Knobs& knobs() {
     return k;
 }
 
+// Not an environment switch but the one measured constant of raster.hip, kept beside the switches so that it is found: a triangle whose
+// clipped box holds at least this many samples is rasterized by its whole wave instead of its own lane (ide3d_raster_depth's `large_min`
+// argument overrides it; results do not depend on it).  Sweep: scripts/bench_mesh_render.py, DESIGN.md section 5.26.
+constexpr int kRasterLargeMin = 256;
+
 // the switches tests flip inside one process: read when asked
 inline bool knob_live(const char* name) { return getenv(name) != nullptr; }
 inline const char* knob_live_str(const char* name) { return getenv(name); }

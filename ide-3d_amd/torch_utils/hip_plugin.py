@@ -388,6 +388,10 @@ def load():
             'ide3d_mesh_workspace_bytes': [i32, i32, i32],
             'ide3d_mesh_count': [vp, i32, i32, i32, f32, vp, vp, i64, vp],
             'ide3d_mesh_emit': [vp, i32, i32, i32, f32, vp, ctypes.POINTER(_Lattice), i32, vp, i64, i64, i64, vp, vp, vp, vp],
+            'ide3d_raster_workspace_bytes': [i32, i64, i32, i32],
+            'ide3d_raster_project': [vp, i64, vp, i32, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp, i64, vp],
+            'ide3d_raster_depth': [vp, i64, i64, i32, i32, i32, i32, i32, vp, i64, vp],
+            'ide3d_raster_shade': [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, i32, f32, f32, ctypes.POINTER(ctypes.c_float * 3), f32, vp, i64, vp, vp, vp, vp, vp],
             'ide3d_modconv2d': [ctypes.POINTER(_ModconvParams), vp],
             'ide3d_modconv2d_heads': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), vp],
             'ide3d_modconv_plan': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvPlanInfo)],
@@ -498,6 +502,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_linear_weight_grad', 'ide3d_residual_join', 'ide3d_id_head', 'ide3d_id_head_backward',
     'ide3d_mesh_workspace_bytes', 'ide3d_mesh_count', 'ide3d_mesh_emit',
     'ide3d_render_ray_weights', 'ide3d_merge_depths', 'ide3d_render_rays_merged',
+    'ide3d_raster_workspace_bytes', 'ide3d_raster_project', 'ide3d_raster_depth', 'ide3d_raster_shade',
 )
 
 
@@ -641,7 +646,7 @@ class _Workspaces:
 
 def _drop_owner(domain):
     _scope_finalizers.pop(domain, None)
-    for plugin in (ModconvPlugin, MappingPlugin, LowresPlugin, VolumeRenderPlugin, VggLossPlugin, MeshPlugin):
+    for plugin in (ModconvPlugin, MappingPlugin, LowresPlugin, VolumeRenderPlugin, VggLossPlugin, MeshPlugin, RasterPlugin):
         plugin._ws.drop(domain)
 
 
@@ -2024,6 +2029,91 @@ class MeshPlugin:
         return MeshPlugin.emit(volume, threshold, table, ws, nv, nt, normals=normals, flip=flip, lattice=lattice)
 
 
+class RasterPlugin:
+    """Triangle rasterizer on float32 CUDA meshes (csrc/raster.hip): the pyrender step of render_mesh.py:36-61.
+    `training.mesh_render` prepares the arguments (camera inversion in float64, the pixel grid) and holds the host definition."""
+
+    _ws = _Workspaces()          # (bytes, device index, launch domain) -> status word + vertex records + z-buffer
+    CULL = {'none': 0, 'back': 1, 'front': 2}
+
+    @staticmethod
+    def _workspace(dev, N, V, H, W):
+        nbytes = load().ide3d_raster_workspace_bytes(N, V, H, W)
+        _require(nbytes > 0, f'render_mesh: unsupported shape: {N} cameras, {V} vertices, {H} x {W} pixels')
+        return RasterPlugin._ws.entry((nbytes, dev.index, _ws_domain(dev)), lambda: torch.empty([(nbytes + 15) // 16, 2], dtype=torch.int64, device=dev))[0]
+
+    @staticmethod
+    def _mesh(vertices, triangles):
+        _require(vertices.is_cuda and vertices.dtype == torch.float32 and vertices.ndim == 2 and vertices.shape[1] == 3 and vertices.is_contiguous(),
+                 'render_mesh: vertices must be a contiguous [V, 3] float32 CUDA tensor')
+        dev = vertices.device if vertices.device.index is not None else torch.device('cuda', torch.cuda.current_device())
+        if triangles is not None:
+            _require(triangles.dtype == torch.int32 and triangles.ndim == 2 and triangles.shape[1] == 3 and triangles.is_contiguous() and triangles.device == vertices.device,
+                     'render_mesh: triangles must be a contiguous [T, 3] int32 tensor on the vertices\' device')
+        return dev
+
+    @staticmethod
+    def project(vertices, world2cam, H, W, view, near):
+        """ide3d_raster_project -> the workspace; `view` = (fx, fy, sx, ox, sy, oy) as float32 values, world2cam [N, 3, 4] float32 on the device."""
+        dev = RasterPlugin._mesh(vertices, None)
+        N, V = int(world2cam.shape[0]), int(vertices.shape[0])
+        _require(world2cam.dtype == torch.float32 and tuple(world2cam.shape) == (N, 3, 4) and world2cam.is_contiguous() and world2cam.device == vertices.device,
+                 'render_mesh: world2cam must be a contiguous [N, 3, 4] float32 tensor on the vertices\' device')
+        ws = RasterPlugin._workspace(dev, N, V, H, W)
+        with _dev_guard(dev):
+            rc = load().ide3d_raster_project(_ptr(vertices), V, _ptr(world2cam), N, H, W, *[float(v) for v in view], float(near), _ptr(ws), ws.numel() * 8,
+                                             _stream(vertices))
+        _check(rc, 'raster_project')
+        return ws
+
+    @staticmethod
+    def records(ws, N, V):
+        """The projected-vertex records of `project` as an int32 tensor [N, V, 4]: X, Y, float bits of the view depth, flags (a copy)."""
+        return ws.view(torch.int32).reshape(-1)[4:4 + N * V * 4].reshape(N, V, 4).clone()
+
+    @staticmethod
+    def depth(ws, vertices, triangles, N, H, W, cull='none', large_min=None):
+        """ide3d_raster_depth on the records in `ws`: clears and fills the z-buffer."""
+        dev = RasterPlugin._mesh(vertices, triangles)
+        _require(cull in RasterPlugin.CULL, f'render_mesh: cull must be one of {sorted(RasterPlugin.CULL)}')
+        with _dev_guard(dev):
+            rc = load().ide3d_raster_depth(_ptr(triangles), int(triangles.shape[0]), int(vertices.shape[0]), N, H, W, RasterPlugin.CULL[cull],
+                                           -1 if large_min is None else int(large_min), _ptr(ws), ws.numel() * 8, _stream(vertices))
+        _check(rc, 'raster_depth')
+
+    @staticmethod
+    def status(ws):
+        """The status word `depth` left (IDE3D_RASTER_BAD_INDEX | IDE3D_RASTER_DROPPED): one host read."""
+        return int(ws.view(torch.int32).reshape(-1)[0].item())
+
+    @staticmethod
+    def shade(ws, vertices, triangles, N, H, W, light, normals=None, colors=None, labels=None, two_sided=True, ambient=0.3, diffuse=0.7,
+              base_color=(1.0, 1.0, 1.0), bg=1.0):
+        """ide3d_raster_shade -> dict(depth [N, 1, H, W], triangle [N, H, W] int32, image [N, 3, H, W][, label [N, H, W] int32])."""
+        dev = RasterPlugin._mesh(vertices, triangles)
+        V = int(vertices.shape[0])
+        _require(light.dtype == torch.float32 and tuple(light.shape) == (N, 3) and light.is_contiguous() and light.device == vertices.device, 'render_mesh: light must be float32 [N, 3]')
+        for name, t, dt in (('normals', normals, torch.float32), ('colors', colors, torch.uint8)):
+            _require(t is None or (t.dtype == dt and tuple(t.shape) == (V, 3) and t.is_contiguous() and t.device == vertices.device),
+                     f'render_mesh: {name} must be a contiguous [V, 3] {dt} tensor on the vertices\' device')
+        _require(labels is None or (labels.dtype == torch.int32 and tuple(labels.shape) == (V,) and labels.is_contiguous() and labels.device == vertices.device),
+                 'render_mesh: labels must be a contiguous [V] int32 tensor on the vertices\' device')
+        out = {'depth': torch.empty([N, 1, H, W], dtype=torch.float32, device=dev), 'triangle': torch.empty([N, H, W], dtype=torch.int32, device=dev),
+               'image': torch.empty([N, 3, H, W], dtype=torch.float32, device=dev)}
+        if labels is not None:
+            out['label'] = torch.empty([N, H, W], dtype=torch.int32, device=dev)
+        base = (ctypes.c_float * 3)(*[float(v) for v in base_color])
+        if labels is not None and V == 0:          # nothing to look up: every pixel is background
+            out['label'].fill_(-1)
+            labels = None
+        with _dev_guard(dev):
+            rc = load().ide3d_raster_shade(_ptr(vertices), _ptr(triangles), V, N, H, W, _ptr(normals), _ptr(colors), _ptr(labels), _ptr(light),
+                                           int(bool(two_sided)), float(ambient), float(diffuse), ctypes.byref(base), float(bg), _ptr(ws), ws.numel() * 8,
+                                           _ptr(out['depth']), _ptr(out['triangle']), _ptr(out['image']), _ptr(out['label'] if labels is not None else None), _stream(vertices))
+        _check(rc, 'raster_shade')
+        return out
+
+
 class ParseLossPlugin:
     """The passes between the convolutions of the face parser's cross-entropy loss and its image gradient (csrc/parse_loss.hip, DESIGN.md
     section 5.16).  Tensors are float32 CUDA tensors; dense NCHW unless a method says otherwise."""
@@ -2860,6 +2950,7 @@ class LowresPlugin:
 
 PLUGINS = {
     'mesh_plugin': MeshPlugin,
+    'raster_plugin': RasterPlugin,
     'lowres_plugin': LowresPlugin,
     'bias_act_plugin': BiasActPlugin,
     'upfirdn2d_plugin': Upfirdn2dPlugin,

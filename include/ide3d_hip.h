@@ -499,6 +499,60 @@ int ide3d_mesh_emit(const float* volume, int32_t X, int32_t Y, int32_t Z, float 
                     const ide3d_lattice* lat, int32_t flip, void* workspace, int64_t workspace_bytes,
                     int64_t num_vertices, int64_t num_triangles, float* vertices, int32_t* triangles, float* normals, void* stream);
 
+/* ---- triangle rasterizer for the extracted mesh --------------------------------------------- */
+/*
+ * The pyrender / OpenGL step of render_mesh.py:36-61 (perspective camera render_mesh.py:48-56,
+ * one directional light at the camera pose render_mesh.py:57, white background
+ * render_mesh.py:47): N cameras of one mesh in three calls on
+ * one stream.  csrc/raster.hip states the definition; training/mesh_render.py holds the host
+ * definition that reproduces every integer of it.  pyrender's metallic-roughness shading is NOT
+ * reproduced (ambient + diffuse Lambert instead), and there is NO clipping: a triangle with a
+ * vertex behind `near` or outside the guard band |pixel coordinate| <= 16384 is dropped whole.
+ *
+ * vertices [V, 3] float32 world space; triangles [T, 3] int32; V, T < 2^31; 1 <= H, W <= 16384;
+ * 1 <= N <= 65535.  workspace: ide3d_raster_workspace_bytes(N, V, H, W) bytes (-1: unsupported
+ * shape), 16-byte aligned, owned by the three calls: a status word (16 bytes), one 16-byte
+ * record (X, Y, view depth, flags) per camera and vertex, the z-buffer [N, H, W] of uint64 keys
+ * (float_bits(depth) << 32 | triangle index; all ones = background).
+ *
+ * ide3d_raster_project (render_mesh.py:48-56): world2cam [N, 3, 4] float32 = rows of (R | t),
+ *   the inverse of the camera pose, inverted by the caller in float64.  d = -z_cam,
+ *   px = ((fx * x_cam) / d) * sx + ox, py = oy - ((fy * y_cam) / d) * sy, every operation one
+ *   float32 operation in this order, X = rint(256 px), Y = rint(256 py).  fy = 1 / tan(yfov / 2),
+ *   fx = fy / aspect.  The sample of pixel (r, c) is (256 c + 128, 256 r + 128), so sx = W / 2,
+ *   ox = W / 2 puts pixel centres at c + 0.5 as OpenGL (and therefore render_mesh.py:60) does.
+ * ide3d_raster_depth (render_mesh.py:60-61, the depth test): clears the status word and the
+ *   z-buffer, then one 64-bit unsigned atomic minimum per covered sample (top-left rule on the
+ *   integers, perspective-correct float32 depth).  The result does not depend on the order of
+ *   the triangles' arrival; equal depths resolve to the lower index.  cull: IDE3D_RASTER_CULL_*
+ *   (front = the geometric normal (v1 - v0) x (v2 - v0) points toward the camera).  large_min:
+ *   triangles whose clipped box holds at least this many samples are rasterized by a whole
+ *   wave instead of one lane (< 0: the library's measured default); results do not depend on it.
+ *   Status word afterwards: IDE3D_RASTER_BAD_INDEX | IDE3D_RASTER_DROPPED.
+ * ide3d_raster_shade (render_mesh.py:36-42, :47, :57): per pixel depth [N, 1, H, W] (+inf on
+ *   the background), triangle [N, H, W] (-1), image [N, 3, H, W] in [0, 1] =
+ *   clamp(base * (ambient + diffuse * max(0, n . l))) (bg), and, when labels [V] int32 is given,
+ *   label [N, H, W] (-1).  normals [V, 3] float32 or NULL (flat face normals), colors [V, 3]
+ *   uint8 or NULL (base_color: 3 floats in HOST memory), light [N, 3] float32 device memory: the
+ *   camera's +z axis in world space.  two_sided: turn n over on back-facing triangles.
+ */
+#define IDE3D_RASTER_CULL_NONE  0
+#define IDE3D_RASTER_CULL_BACK  1
+#define IDE3D_RASTER_CULL_FRONT 2
+#define IDE3D_RASTER_BEHIND     1   /* vertex flag: d >= near fails                              */
+#define IDE3D_RASTER_OUTSIDE    2   /* vertex flag: outside the guard band                       */
+#define IDE3D_RASTER_BAD_INDEX  1   /* status: a triangle index outside [0, V)                   */
+#define IDE3D_RASTER_DROPPED    2   /* status: a dropped triangle's remaining box met the screen */
+int64_t ide3d_raster_workspace_bytes(int32_t N, int64_t V, int32_t H, int32_t W);
+int ide3d_raster_project(const float* vertices, int64_t V, const float* world2cam, int32_t N, int32_t H, int32_t W, float fx, float fy,
+                         float sx, float ox, float sy, float oy, float near, void* workspace, int64_t workspace_bytes, void* stream);
+int ide3d_raster_depth(const int32_t* triangles, int64_t T, int64_t V, int32_t N, int32_t H, int32_t W, int32_t cull,
+                       int32_t large_min, void* workspace, int64_t workspace_bytes, void* stream);
+int ide3d_raster_shade(const float* vertices, const int32_t* triangles, int64_t V, int32_t N, int32_t H, int32_t W,
+                       const float* normals, const uint8_t* colors, const int32_t* labels, const float* light, int32_t two_sided,
+                       float ambient, float diffuse, const float* base_color, float bg, const void* workspace, int64_t workspace_bytes,
+                       float* depth, int32_t* triangle, float* image, int32_t* label, void* stream);
+
 /* ---- modulated 3x3 / 1x1 convolution (MFMA implicit GEMM) --------------------------------- */
 /*
  * Replaces the ATen conv behind `conv2d_gradfix.conv2d` for the StyleGAN2 modulated
