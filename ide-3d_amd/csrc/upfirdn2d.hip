@@ -5,9 +5,11 @@
 // where U is the zero-upsampled input (U[iy*uy, ix*ux] = x[iy, ix], 0 elsewhere / outside) and
 // g = f flipped in both axes (true convolution) unless `flip` is set.
 //
-// Two kernels:
+// Five kernels in thirteen launchable forms; which one runs is decided by one host function, upfirdn2d_plan (below the kernels), which
+// the launch and the host-only query ide3d_upfirdn2d_plan both go through:
 //  * upfirdn2d_tile<...>: LDS-tiled polyphase kernel for the shapes on the IDE-3D render path
-//    (4x4 [1,3,3,1] filter, up in {1,2}, down in {1,2}) and w-contiguous (NCHW) tensors.  A
+//    (4x4 [1,3,3,1] filter, up in {1,2}, down in {1,2}: four instances) and for one pass of a separable
+//    12-tap filter (fp32; up 2 / down 2 / unit rate along x or y: six instances), w-contiguous (NCHW) tensors.  A
 //    256-thread workgroup stages the input window of its output tile in LDS (zero-filled
 //    outside the image), every lane then owns a register micro-tile and walks only the taps
 //    that hit non-zero samples of its polyphase component.  Filter taps are read once through
@@ -15,6 +17,8 @@
 //  * upfirdn2d_generic: one output element per lane, any (up, down, filter, strides, dtype);
 //    lanes run along the unit-stride axis (w for NCHW, c for channels_last) so global
 //    accesses stay coalesced.
+//  * upfirdn2d_cell<U = 2 | 4>: up U x U through a large filter held in LDS, one thread per output row of a cell.
+//  * fir44_kernel / fir_up2_kernel: lean fp32 forms of the unit-rate and up-2 4x4 tile instances (bit-equal to them).
 #include "common.h"
 #include "knobs.h"
 #include <type_traits>
@@ -257,16 +261,39 @@ struct Axis {
     static constexpr int step = (U > 1) ? 1 : D;
 };
 
+// LDS geometry of one tile instance: the kernel and the host plan (upfirdn2d_plan) read it from here.
+template <int UX, int UY, int DX, int DY, int FW, int FH, int CX, int CY>
+struct TileGeom {
+    using AX = Axis<UX, DX, FW>;
+    using AY = Axis<UY, DY, FH>;
+    static constexpr int TX = 32, TY = 8;                              // thread grid inside the workgroup
+    static constexpr int TCX = TX * CX, TCY = TY * CY;                 // cells per tile
+    static constexpr int LW = ((AX::window(TCX) + 3) & ~3) + 4;        // LDS tile width (padded, see bank note)
+    static constexpr int LH = AY::window(TCY);
+    static constexpr int NLD4 = (LH * (LW / 4) + 255) / 256;           // 16-byte staging loads per thread
+};
+
+// The tile kernel's staging choice, in one place for the kernel and the host plan.  The instance half is a compile-time fact (element
+// size, loads per thread), the plane half a run-time one: 16-byte staging reads whole aligned quads of a row, i.e. up to
+// round_up(in_w, 4) - 1 — only when the rows start on the 16-byte grid (pitch a multiple of 4 floats, plane pointer aligned) and the
+// caller promised that much of every row is readable (x_row_floats: padded rows) or in_w is a multiple of 4 — the last row of the last
+// plane may end the storage.
+__host__ __device__ constexpr bool tile_stage16_instance(int elem_bytes, int nld4) { return elem_bytes == 4 && nld4 <= 16; }
+__host__ __device__ inline bool tile_stage16_plane(int64_t pitch, int in_w, int x_row_floats, uintptr_t plane_addr) {
+    const int w4 = (in_w + 3) & ~3;
+    return (pitch & 3) == 0 && pitch >= w4 && w4 <= (in_w > x_row_floats ? in_w : x_row_floats) && (plane_addr & 15) == 0;
+}
+
 template <class T, int UX, int UY, int DX, int DY, int FW, int FH, int CX, int CY>
 __global__ void __launch_bounds__(256)
 upfirdn2d_tile_kernel(ide3d_upfirdn2d_params p, ide3d_upfirdn2d_epilogue ep, int tiles_x, int tiles_y) {
     using M = typename Elem<T>::math_t;
-    using AX = Axis<UX, DX, FW>;
-    using AY = Axis<UY, DY, FH>;
-    constexpr int TX = 32, TY = 8;                              // thread grid inside the workgroup
-    constexpr int TCX = TX * CX, TCY = TY * CY;                 // cells per tile
-    constexpr int LW = ((AX::window(TCX) + 3) & ~3) + 4;        // LDS tile width (padded, see bank note)
-    constexpr int LH = AY::window(TCY);
+    using G = TileGeom<UX, UY, DX, DY, FW, FH, CX, CY>;
+    using AX = typename G::AX;
+    using AY = typename G::AY;
+    constexpr int TX = G::TX;
+    constexpr int TCX = G::TCX, TCY = G::TCY;
+    constexpr int LW = G::LW, LH = G::LH;
     constexpr int WX = AX::window(CX), WY = AY::window(CY);     // per-thread register window
 
     __shared__ __attribute__((aligned(16))) M s_in[LH * LW];
@@ -308,12 +335,10 @@ upfirdn2d_tile_kernel(ide3d_upfirdn2d_params p, ide3d_upfirdn2d_epilogue ep, int
     // pad columns of a padded row, which hold no data) are zeroed by per-element selects on their true coordinates.
     int xoff = 0;
     bool staged = false;
-    if constexpr (sizeof(T) == 4 && (LH * (LW / 4) + 255) / 256 <= 16) {
+    if constexpr (tile_stage16_instance((int)sizeof(T), G::NLD4)) {
         const int64_t pitch = p.x_stride[2];
-        // 16-byte staging reads whole aligned quads of a row, i.e. up to round_up(in_w, 4) - 1: only when the caller promised that much of
-        // every row is readable (x_row_floats: padded rows) or in_w is a multiple of 4 — the last row of the last plane may end the storage
         const int w4 = (p.in_w + 3) & ~3;
-        if ((pitch & 3) == 0 && pitch >= w4 && w4 <= max(p.in_w, p.x_row_floats) && ((reinterpret_cast<uintptr_t>(xp) & 15) == 0)) {
+        if (tile_stage16_plane(pitch, p.in_w, p.x_row_floats, reinterpret_cast<uintptr_t>(xp))) {
             const int x_al = in_x0 & ~3;                          // floor to the 16-byte grid (two's complement: also for negative origins)
             xoff = in_x0 - x_al;
             constexpr int NV = LW / 4, NLD4 = (LH * NV + 255) / 256;
@@ -563,30 +588,6 @@ fir44_kernel(ide3d_upfirdn2d_params p, ide3d_upfirdn2d_epilogue ep, int tiles_x,
     if (ep.y_amax) amax_raise_block(ep.y_amax, n, amax_t, s_in);
 }
 
-// the conditions of fir44_kernel (see there)
-static bool fir44_applies(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep) {
-    const bool off = knob_live("IDE3D_FIR_NO_LEAN");      // read per call: tests/test_gpu_ops.py flips it inside one process
-    if (off || p.dtype != IDE3D_F32 || p.f_w != 4 || p.f_h != 4 || p.up_x != 1 || p.up_y != 1 || p.down_x != 1 || p.down_y != 1) return false;
-    if (p.x_stride[3] != 1 || p.y_stride[3] != 1 || ep.add || p.out_w <= 64 || (p.out_w & 3)) return false;
-    const int64_t pitch = p.x_stride[2], w4 = (p.in_w + 3) & ~3;
-    if ((pitch & 3) || pitch < w4 || w4 > (p.in_w > p.x_row_floats ? p.in_w : p.x_row_floats)) return false;
-    if ((reinterpret_cast<uintptr_t>(p.x) & 15) || (p.x_stride[0] & 3) || (p.x_stride[1] & 3)) return false;
-    if ((reinterpret_cast<uintptr_t>(p.y) & 15) || (p.y_stride[0] & 3) || (p.y_stride[1] & 3) || (p.y_stride[2] & 3)) return false;
-    if (ep.noise && (reinterpret_cast<uintptr_t>(ep.noise) & 15)) return false;
-    if (pitch * p.in_h >= (1ll << 29) || p.y_stride[2] * (int64_t)p.out_h >= (1ll << 29) || (int64_t)p.out_w * p.out_h >= (1ll << 29)) return false;
-    if (p.x_stride[2] <= 0 || p.y_stride[2] <= 0) return false;
-    return true;
-}
-
-static int launch_fir44(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep, hipStream_t st) {
-    const int tiles_x = cdiv(p.out_w, 128), tiles_y = cdiv(p.out_h, 32);
-    const int64_t nblocks = (int64_t)tiles_x * tiles_y * p.n * p.c;
-    if (nblocks > 0x7fffffff) { set_error("upfirdn2d: grid too large"); return IDE3D_EINVAL; }
-    hipLaunchKernelGGL(fir44_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, p, ep, tiles_x, tiles_y);
-    IDE3D_CHECK_LAUNCH("upfirdn2d (fir44)");
-    return IDE3D_OK;
-}
-
 // fp32 4x4 FIR with 2x zero-upsampling (the skip-image upsampler, upfirdn2d.upsample2d with the [1, 3, 3, 1] filter, optionally + the skip
 // operand), lean form: same polyphase arithmetic in the same order as upfirdn2d_tile_kernel<float, 2, 2, 1, 1, 4, 4, 2, 2> (bit-equal; that
 // kernel spends 386 vector instructions per wave on 64 multiply-adds per lane), bookkeeping as in fir44_kernel.  Tile = 64 x 16 cells
@@ -709,6 +710,26 @@ fir_up2_kernel(ide3d_upfirdn2d_params p, ide3d_upfirdn2d_epilogue ep, int tiles_
     if (ep.y_amax) amax_raise_block(ep.y_amax, n, amax_t, s_in);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Host: one function decides the form and its geometry (upfirdn2d_plan); the launch and the ide3d_upfirdn2d_plan query go through it
+// ------------------------------------------------------------------------------------------------
+
+// the conditions of fir44_kernel (see there)
+static bool fir44_applies(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep) {
+    const bool off = knob_live("IDE3D_FIR_NO_LEAN");      // read per call: tests/test_gpu_ops.py flips it inside one process
+    if (off || p.dtype != IDE3D_F32 || p.f_w != 4 || p.f_h != 4 || p.up_x != 1 || p.up_y != 1 || p.down_x != 1 || p.down_y != 1) return false;
+    if (p.x_stride[3] != 1 || p.y_stride[3] != 1 || ep.add || p.out_w <= 64 || (p.out_w & 3)) return false;
+    const int64_t pitch = p.x_stride[2], w4 = (p.in_w + 3) & ~3;
+    if ((pitch & 3) || pitch < w4 || w4 > (p.in_w > p.x_row_floats ? p.in_w : p.x_row_floats)) return false;
+    if ((reinterpret_cast<uintptr_t>(p.x) & 15) || (p.x_stride[0] & 3) || (p.x_stride[1] & 3)) return false;
+    if ((reinterpret_cast<uintptr_t>(p.y) & 15) || (p.y_stride[0] & 3) || (p.y_stride[1] & 3) || (p.y_stride[2] & 3)) return false;
+    if (ep.noise && (reinterpret_cast<uintptr_t>(ep.noise) & 15)) return false;
+    if (pitch * p.in_h >= (1ll << 29) || p.y_stride[2] * (int64_t)p.out_h >= (1ll << 29) || (int64_t)p.out_w * p.out_h >= (1ll << 29)) return false;
+    if (p.x_stride[2] <= 0 || p.y_stride[2] <= 0) return false;
+    return true;
+}
+
+// the conditions of fir_up2_kernel (see there)
 static bool fir_up2_applies(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep) {
     const bool off = knob_live("IDE3D_FIR_NO_LEAN");      // read per call: tests/test_gpu_ops.py flips it inside one process
     if (off || p.dtype != IDE3D_F32 || p.f_w != 4 || p.f_h != 4 || p.up_x != 2 || p.up_y != 2 || p.down_x != 1 || p.down_y != 1) return false;
@@ -726,56 +747,6 @@ static bool fir_up2_applies(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn
     return true;
 }
 
-static int launch_fir_up2(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep, hipStream_t st) {
-    auto cells = [](int out, int pad0) { return floordiv(out - 1 - pad0, 2) - floordiv(-pad0, 2) + 1; };
-    const int tiles_x = cdiv(cells(p.out_w, p.pad_x0), 64), tiles_y = cdiv(cells(p.out_h, p.pad_y0), 16);
-    const int64_t nblocks = (int64_t)tiles_x * tiles_y * p.n * p.c;
-    if (nblocks > 0x7fffffff) { set_error("upfirdn2d: grid too large"); return IDE3D_EINVAL; }
-    hipLaunchKernelGGL(fir_up2_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, p, ep, tiles_x, tiles_y);
-    IDE3D_CHECK_LAUNCH("upfirdn2d (fir_up2)");
-    return IDE3D_OK;
-}
-
-template <class T, int UX, int UY, int DX, int DY, int FW, int FH, int CX, int CY>
-static int launch_tile(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep, hipStream_t st) {
-    constexpr int TCX = 32 * CX, TCY = 8 * CY;
-    // Number of cells needed to cover the outputs on each axis.
-    auto cells = [](int out, int pad0, int U) {
-        if (U == 1) return out;
-        const int q_min = floordiv(-pad0, U);
-        const int q_max = floordiv(out - 1 - pad0, U);
-        return q_max - q_min + 1;
-    };
-    const int tiles_x = cdiv(cells(p.out_w, p.pad_x0, UX), TCX);
-    const int tiles_y = cdiv(cells(p.out_h, p.pad_y0, UY), TCY);
-    const int64_t nblocks = (int64_t)tiles_x * tiles_y * p.n * p.c;
-    if (nblocks > 0x7fffffff) { set_error("upfirdn2d: grid too large"); return IDE3D_EINVAL; }
-    hipLaunchKernelGGL((upfirdn2d_tile_kernel<T, UX, UY, DX, DY, FW, FH, CX, CY>), dim3((unsigned)nblocks),
-                       dim3(256), 0, st, p, ep, tiles_x, tiles_y);
-    IDE3D_CHECK_LAUNCH("upfirdn2d_tile");
-    return IDE3D_OK;
-}
-
-template <class T>
-static int launch_generic(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep, hipStream_t st) {
-    const int64_t total = (int64_t)p.n * p.c * p.out_h * p.out_w;
-    const int c_fastest = (p.y_stride[1] == 1 && p.c > 1) ? 1 : 0;
-    hipLaunchKernelGGL((upfirdn2d_generic_kernel<T>), dim3(stream_grid(total, 256)), dim3(256), 0, st, p, ep, c_fastest);
-    IDE3D_CHECK_LAUNCH("upfirdn2d_generic");
-    return IDE3D_OK;
-}
-
-template <class T, int U>
-static int launch_cell(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep, hipStream_t st) {
-    const int qx_min = floordiv(-p.pad_x0, U), qy_min = floordiv(-p.pad_y0, U);
-    const int cells_x = floordiv(p.out_w - 1 - p.pad_x0, U) - qx_min + 1, cells_y = floordiv(p.out_h - 1 - p.pad_y0, U) - qy_min + 1;
-    const int ntx = cdiv(p.f_w, U), nty = cdiv(p.f_h, U);
-    const size_t lds = (size_t)cell_row_floats(ntx, U) * (nty + 1) * U * sizeof(float);
-    const int64_t total = (int64_t)p.n * p.c * cells_y * U * cells_x;
-    hipLaunchKernelGGL((upfirdn2d_cell_kernel<T, U>), dim3(stream_grid(total, 256)), dim3(256), lds, st, p, ep, cells_x, cells_y, qx_min, qy_min, ntx, nty);
-    IDE3D_CHECK_LAUNCH("upfirdn2d_cell");
-    return IDE3D_OK;
-}
 // up-sampling by 2 x 2 / 4 x 4 without decimation through a filter of >= 36 taps that no tile instance covers (and whose padded copy fits 48 KB of LDS)
 static bool cell_applies(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep) {
     if (knob_live("IDE3D_FIR_NO_CELL")) return false;
@@ -785,49 +756,174 @@ static bool cell_applies(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_
     return (int64_t)cell_row_floats(cdiv(p.f_w, U), U) * (cdiv(p.f_h, U) + 1) * U * 4 <= 48 * 1024 && p.x_stride[3] * (int64_t)p.in_w < (1ll << 31);
 }
 
-template <class T>
-static int dispatch(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep, hipStream_t st) {
+// cells of U shifted outputs that cover `out` outputs of one axis: floor(-pad0 / U) is the cell holding output 0
+static inline int cells_of(int out, int pad0, int U) {
+    if (U == 1) return out;
+    return floordiv(out - 1 - pad0, U) - floordiv(-pad0, U) + 1;
+}
+
+// how the planes of x stage in a tile instance that may stage by 16 bytes: plane (n, c) starts at x + n stride[0] + c stride[1]; the
+// alignment of the planes repeats with period 4 in n and in c
+static int tile_staging(const ide3d_upfirdn2d_params& p) {
+    int staged = 0, planes = 0;
+    for (int n = 0; n < (p.n < 4 ? p.n : 4); ++n)
+        for (int c = 0; c < (p.c < 4 ? p.c : 4); ++c, ++planes)
+            staged += tile_stage16_plane(p.x_stride[2], p.in_w, p.x_row_floats,
+                                         reinterpret_cast<uintptr_t>(p.x) + (uintptr_t)((n * p.x_stride[0] + c * p.x_stride[1]) * 4)) ? 1 : 0;
+    return staged == planes ? 1 : staged == 0 ? 0 : 2;
+}
+
+template <int UX, int UY, int DX, int DY, int FW, int FH, int CX, int CY>
+static int plan_tile(const ide3d_upfirdn2d_params& p, ide3d_upfirdn2d_plan_info* o) {
+    using G = TileGeom<UX, UY, DX, DY, FW, FH, CX, CY>;
+    o->form = IDE3D_UPFIRDN_TILE;
+    o->ux = UX; o->uy = UY; o->dx = DX; o->dy = DY; o->fw = FW; o->fh = FH; o->cx = CX; o->cy = CY;
+    o->tiles_x = cdiv(cells_of(p.out_w, p.pad_x0, UX), G::TCX);
+    o->tiles_y = cdiv(cells_of(p.out_h, p.pad_y0, UY), G::TCY);
+    o->grid = (int64_t)o->tiles_x * o->tiles_y * p.n * p.c;
+    o->staging = (p.dtype == IDE3D_F32 && tile_stage16_instance(4, G::NLD4)) ? tile_staging(p) : 0;
+    if (o->grid > 0x7fffffff) { set_error("upfirdn2d: grid too large"); return IDE3D_EINVAL; }
+    return IDE3D_OK;
+}
+
+// Which kernel form runs, with its launch geometry.  Host arithmetic only: pointers count for their alignment and are never dereferenced.
+static int upfirdn2d_plan(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep, ide3d_upfirdn2d_plan_info* o) {
+    *o = ide3d_upfirdn2d_plan_info{};
+    o->staging = -1;
     const bool w_contig = (p.x_stride[3] == 1 && p.y_stride[3] == 1);
-    if constexpr (!std::is_same<T, double>::value) {
+    const bool f32 = p.dtype == IDE3D_F32;
+    if (p.dtype != IDE3D_F64) {
         if (w_contig && p.f_w == 4 && p.f_h == 4) {
             if (p.up_x == 1 && p.up_y == 1 && p.down_x == 1 && p.down_y == 1) {
                 // 4 output rows per thread: 7 window rows serve 4 rows (halo 9 % instead of 19 %); narrow images get a
                 // 64-wide tile so that lanes are not wasted on columns that do not exist
-                if (p.out_w <= 64) return launch_tile<T, 1, 1, 1, 1, 4, 4, 2, 4>(p, ep, st);
-                if constexpr (std::is_same<T, float>::value) { if (fir44_applies(p, ep)) return launch_fir44(p, ep, st); }
-                return launch_tile<T, 1, 1, 1, 1, 4, 4, 4, 4>(p, ep, st);
+                if (p.out_w <= 64) return plan_tile<1, 1, 1, 1, 4, 4, 2, 4>(p, o);
+                if (f32 && fir44_applies(p, ep)) {
+                    o->form = IDE3D_UPFIRDN_FIR44;
+                    o->ux = 1; o->uy = 1; o->dx = 1; o->dy = 1; o->fw = 4; o->fh = 4; o->cx = 4; o->cy = 4;
+                    o->staging = 1;
+                    o->tiles_x = cdiv(p.out_w, 128); o->tiles_y = cdiv(p.out_h, 32);
+                    o->grid = (int64_t)o->tiles_x * o->tiles_y * p.n * p.c;
+                    if (o->grid > 0x7fffffff) { set_error("upfirdn2d: grid too large"); return IDE3D_EINVAL; }
+                    return IDE3D_OK;
+                }
+                return plan_tile<1, 1, 1, 1, 4, 4, 4, 4>(p, o);
             }
             if (p.up_x == 2 && p.up_y == 2 && p.down_x == 1 && p.down_y == 1) {
-                if constexpr (std::is_same<T, float>::value) { if (fir_up2_applies(p, ep)) return launch_fir_up2(p, ep, st); }
-                return launch_tile<T, 2, 2, 1, 1, 4, 4, 2, 2>(p, ep, st);
+                if (f32 && fir_up2_applies(p, ep)) {
+                    o->form = IDE3D_UPFIRDN_FIR_UP2;
+                    o->ux = 2; o->uy = 2; o->dx = 1; o->dy = 1; o->fw = 4; o->fh = 4; o->cx = 2; o->cy = 2;
+                    o->staging = 1;
+                    o->tiles_x = cdiv(cells_of(p.out_w, p.pad_x0, 2), 64); o->tiles_y = cdiv(cells_of(p.out_h, p.pad_y0, 2), 16);
+                    o->grid = (int64_t)o->tiles_x * o->tiles_y * p.n * p.c;
+                    if (o->grid > 0x7fffffff) { set_error("upfirdn2d: grid too large"); return IDE3D_EINVAL; }
+                    return IDE3D_OK;
+                }
+                return plan_tile<2, 2, 1, 1, 4, 4, 2, 2>(p, o);
             }
-            if (p.up_x == 1 && p.up_y == 1 && p.down_x == 2 && p.down_y == 2)
-                return launch_tile<T, 1, 1, 2, 2, 4, 4, 4, 2>(p, ep, st);
+            if (p.up_x == 1 && p.up_y == 1 && p.down_x == 2 && p.down_y == 2) return plan_tile<1, 1, 2, 2, 4, 4, 4, 2>(p, o);
         }
         // one pass of a separable 12-tap filter (upfirdn2d.py:192-199 runs [1, 12] then [12, 1]; training/augment.py:295,306 sym6
         // wavelets, StyleGAN3-style up / down by 2): the same LDS-tiled polyphase kernel with a 1-D tap set
-        if constexpr (std::is_same<T, float>::value) {
+        if (f32) {
             if (w_contig && p.f_w == 12 && p.f_h == 1 && p.up_y == 1 && p.down_y == 1) {
-                if (p.up_x == 2 && p.down_x == 1) return launch_tile<T, 2, 1, 1, 1, 12, 1, 2, 4>(p, ep, st);
-                if (p.up_x == 1 && p.down_x == 2) return launch_tile<T, 1, 1, 2, 1, 12, 1, 4, 4>(p, ep, st);
-                if (p.up_x == 1 && p.down_x == 1) return launch_tile<T, 1, 1, 1, 1, 12, 1, 4, 4>(p, ep, st);
+                if (p.up_x == 2 && p.down_x == 1) return plan_tile<2, 1, 1, 1, 12, 1, 2, 4>(p, o);
+                if (p.up_x == 1 && p.down_x == 2) return plan_tile<1, 1, 2, 1, 12, 1, 4, 4>(p, o);
+                if (p.up_x == 1 && p.down_x == 1) return plan_tile<1, 1, 1, 1, 12, 1, 4, 4>(p, o);
             }
             if (w_contig && p.f_w == 1 && p.f_h == 12 && p.up_x == 1 && p.down_x == 1) {
-                if (p.up_y == 2 && p.down_y == 1) return launch_tile<T, 1, 2, 1, 1, 1, 12, 4, 2>(p, ep, st);
-                if (p.up_y == 1 && p.down_y == 2) return launch_tile<T, 1, 1, 1, 2, 1, 12, 4, 2>(p, ep, st);
-                if (p.up_y == 1 && p.down_y == 1) return launch_tile<T, 1, 1, 1, 1, 1, 12, 4, 4>(p, ep, st);
+                if (p.up_y == 2 && p.down_y == 1) return plan_tile<1, 2, 1, 1, 1, 12, 4, 2>(p, o);
+                if (p.up_y == 1 && p.down_y == 2) return plan_tile<1, 1, 1, 2, 1, 12, 4, 2>(p, o);
+                if (p.up_y == 1 && p.down_y == 1) return plan_tile<1, 1, 1, 1, 1, 12, 4, 4>(p, o);
             }
         }
+        if (cell_applies(p, ep)) {
+            const int U = p.up_x;
+            o->form = IDE3D_UPFIRDN_CELL;
+            o->cell_u = U;
+            o->tiles_x = cells_of(p.out_w, p.pad_x0, U); o->tiles_y = cells_of(p.out_h, p.pad_y0, U);
+            o->lds_bytes = (int64_t)cell_row_floats(cdiv(p.f_w, U), U) * (cdiv(p.f_h, U) + 1) * U * (int64_t)sizeof(float);
+            o->grid = stream_grid((int64_t)p.n * p.c * o->tiles_y * U * o->tiles_x, 256);
+            return IDE3D_OK;
+        }
     }
-    if constexpr (!std::is_same<T, double>::value) {
-        if (cell_applies(p, ep)) return p.up_x == 2 ? launch_cell<T, 2>(p, ep, st) : launch_cell<T, 4>(p, ep, st);
+    o->form = IDE3D_UPFIRDN_GENERIC;
+    o->c_fastest = (p.y_stride[1] == 1 && p.c > 1) ? 1 : 0;
+    o->grid = stream_grid((int64_t)p.n * p.c * p.out_h * p.out_w, 256);
+    return IDE3D_OK;
+}
+
+template <class T, int UX, int UY, int DX, int DY, int FW, int FH, int CX, int CY>
+static int launch_tile(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep, const ide3d_upfirdn2d_plan_info& pl, hipStream_t st) {
+    hipLaunchKernelGGL((upfirdn2d_tile_kernel<T, UX, UY, DX, DY, FW, FH, CX, CY>), dim3((unsigned)pl.grid),
+                       dim3(256), 0, st, p, ep, pl.tiles_x, pl.tiles_y);
+    IDE3D_CHECK_LAUNCH("upfirdn2d_tile");
+    return IDE3D_OK;
+}
+
+template <class T, int U>
+static int launch_cell(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep, const ide3d_upfirdn2d_plan_info& pl, hipStream_t st) {
+    hipLaunchKernelGGL((upfirdn2d_cell_kernel<T, U>), dim3((unsigned)pl.grid), dim3(256), (size_t)pl.lds_bytes, st, p, ep, pl.tiles_x, pl.tiles_y,
+                       floordiv(-p.pad_x0, U), floordiv(-p.pad_y0, U), cdiv(p.f_w, U), cdiv(p.f_h, U));
+    IDE3D_CHECK_LAUNCH("upfirdn2d_cell");
+    return IDE3D_OK;
+}
+
+// launch what the plan says; a plan that names a form the storage type has no kernel for cannot come out of upfirdn2d_plan
+template <class T>
+static int launch_planned(const ide3d_upfirdn2d_params& p, const ide3d_upfirdn2d_epilogue& ep, const ide3d_upfirdn2d_plan_info& pl, hipStream_t st) {
+#define IDE3D_TILE_CASE(UX, UY, DX, DY, FW, FH, CX, CY)                                                                              \
+    if (pl.ux == UX && pl.uy == UY && pl.dx == DX && pl.dy == DY && pl.fw == FW && pl.fh == FH && pl.cx == CX && pl.cy == CY)         \
+        return launch_tile<T, UX, UY, DX, DY, FW, FH, CX, CY>(p, ep, pl, st)
+    switch (pl.form) {
+    case IDE3D_UPFIRDN_FIR44:
+        if constexpr (std::is_same<T, float>::value) {
+            hipLaunchKernelGGL(fir44_kernel, dim3((unsigned)pl.grid), dim3(256), 0, st, p, ep, pl.tiles_x, pl.tiles_y);
+            IDE3D_CHECK_LAUNCH("upfirdn2d (fir44)");
+            return IDE3D_OK;
+        }
+        break;
+    case IDE3D_UPFIRDN_FIR_UP2:
+        if constexpr (std::is_same<T, float>::value) {
+            hipLaunchKernelGGL(fir_up2_kernel, dim3((unsigned)pl.grid), dim3(256), 0, st, p, ep, pl.tiles_x, pl.tiles_y);
+            IDE3D_CHECK_LAUNCH("upfirdn2d (fir_up2)");
+            return IDE3D_OK;
+        }
+        break;
+    case IDE3D_UPFIRDN_TILE:
+        if constexpr (!std::is_same<T, double>::value) {
+            IDE3D_TILE_CASE(1, 1, 1, 1, 4, 4, 2, 4);
+            IDE3D_TILE_CASE(1, 1, 1, 1, 4, 4, 4, 4);
+            IDE3D_TILE_CASE(2, 2, 1, 1, 4, 4, 2, 2);
+            IDE3D_TILE_CASE(1, 1, 2, 2, 4, 4, 4, 2);
+        }
+        if constexpr (std::is_same<T, float>::value) {
+            IDE3D_TILE_CASE(2, 1, 1, 1, 12, 1, 2, 4);
+            IDE3D_TILE_CASE(1, 1, 2, 1, 12, 1, 4, 4);
+            IDE3D_TILE_CASE(1, 1, 1, 1, 12, 1, 4, 4);
+            IDE3D_TILE_CASE(1, 2, 1, 1, 1, 12, 4, 2);
+            IDE3D_TILE_CASE(1, 1, 1, 2, 1, 12, 4, 2);
+            IDE3D_TILE_CASE(1, 1, 1, 1, 1, 12, 4, 4);
+        }
+        break;
+    case IDE3D_UPFIRDN_CELL:
+        if constexpr (!std::is_same<T, double>::value) return pl.cell_u == 2 ? launch_cell<T, 2>(p, ep, pl, st) : launch_cell<T, 4>(p, ep, pl, st);
+        break;
+    case IDE3D_UPFIRDN_GENERIC:
+        hipLaunchKernelGGL((upfirdn2d_generic_kernel<T>), dim3((unsigned)pl.grid), dim3(256), 0, st, p, ep, pl.c_fastest);
+        IDE3D_CHECK_LAUNCH("upfirdn2d_generic");
+        return IDE3D_OK;
     }
-    return launch_generic<T>(p, ep, st);
+#undef IDE3D_TILE_CASE
+    set_error("upfirdn2d: no kernel for the planned form %d", pl.form);
+    return IDE3D_ENOKERNEL;
 }
 
 }  // namespace ide3d
 
-static int upfirdn2d_entry(const ide3d_upfirdn2d_params* pp, const ide3d_upfirdn2d_epilogue* epp, void* stream) {
+// what ide3d_upfirdn2d, ide3d_upfirdn2d_ex and ide3d_upfirdn2d_plan refuse, and the plan of the rest
+static int upfirdn2d_checked_plan(const ide3d_upfirdn2d_params* pp, const ide3d_upfirdn2d_epilogue* epp, ide3d_upfirdn2d_epilogue* ep_out,
+                                  ide3d_upfirdn2d_plan_info* plan) {
     using namespace ide3d;
     IDE3D_CHECK_ARG(pp != nullptr, "upfirdn2d: null params");
     const ide3d_upfirdn2d_params& p = *pp;
@@ -840,15 +936,35 @@ static int upfirdn2d_entry(const ide3d_upfirdn2d_params* pp, const ide3d_upfirdn
     IDE3D_CHECK_ARG(p.down_x >= 1 && p.down_y >= 1, "upfirdn2d: downsampling factor must be at least 1");
     IDE3D_CHECK_ARG(p.out_h >= 1 && p.out_w >= 1, "upfirdn2d: output must be at least 1x1");
     IDE3D_CHECK_ARG(!ep.fused_act || ep.act == 1 || ep.act == 3, "upfirdn2d_ex: fused activation must be linear (1) or lrelu (3)");
+    if (p.dtype != IDE3D_F32 && p.dtype != IDE3D_F16 && p.dtype != IDE3D_BF16 && p.dtype != IDE3D_F64) {
+        set_error("upfirdn2d: unsupported dtype code %d", p.dtype);
+        return IDE3D_EINVAL;
+    }
+    *ep_out = ep;
+    return upfirdn2d_plan(p, ep, plan);
+}
+
+static int upfirdn2d_entry(const ide3d_upfirdn2d_params* pp, const ide3d_upfirdn2d_epilogue* epp, void* stream) {
+    using namespace ide3d;
+    ide3d_upfirdn2d_epilogue ep;
+    ide3d_upfirdn2d_plan_info plan;
+    const int rc = upfirdn2d_checked_plan(pp, epp, &ep, &plan);
+    if (rc != IDE3D_OK) return rc;
+    const ide3d_upfirdn2d_params& p = *pp;
     hipStream_t st = (hipStream_t)stream;
     switch (p.dtype) {
-    case IDE3D_F32:  return dispatch<float>(p, ep, st);
-    case IDE3D_F16:  return dispatch<__half>(p, ep, st);
-    case IDE3D_BF16: return dispatch<__hip_bfloat16>(p, ep, st);
-    case IDE3D_F64:  return dispatch<double>(p, ep, st);
+    case IDE3D_F32:  return launch_planned<float>(p, ep, plan, st);
+    case IDE3D_F16:  return launch_planned<__half>(p, ep, plan, st);
+    case IDE3D_BF16: return launch_planned<__hip_bfloat16>(p, ep, plan, st);
+    default:         return launch_planned<double>(p, ep, plan, st);
     }
-    set_error("upfirdn2d: unsupported dtype code %d", p.dtype);
-    return IDE3D_EINVAL;
+}
+
+extern "C" int ide3d_upfirdn2d_plan(const ide3d_upfirdn2d_params* pp, const ide3d_upfirdn2d_epilogue* epp, ide3d_upfirdn2d_plan_info* out) {
+    using namespace ide3d;
+    IDE3D_CHECK_ARG(out, "upfirdn2d_plan: null pointer");
+    ide3d_upfirdn2d_epilogue ep;
+    return upfirdn2d_checked_plan(pp, epp, &ep, out);
 }
 
 extern "C" int ide3d_upfirdn2d(const ide3d_upfirdn2d_params* pp, void* stream) {

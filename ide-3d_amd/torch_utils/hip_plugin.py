@@ -203,6 +203,18 @@ class _CompositePlanInfo(ctypes.Structure):
 
 COMPOSITE_FORMS = ('fallback', 'lds8', 'lds20', 'lds40')     # IDE3D_COMPOSITE_*
 
+
+class _UpfirdnPlanInfo(ctypes.Structure):
+    """ide3d_upfirdn2d_plan_info (include/ide3d_hip.h): what ide3d_upfirdn2d / ide3d_upfirdn2d_ex would launch."""
+    _fields_ = [('form', ctypes.c_int32),
+                ('ux', ctypes.c_int32), ('uy', ctypes.c_int32), ('dx', ctypes.c_int32), ('dy', ctypes.c_int32),
+                ('fw', ctypes.c_int32), ('fh', ctypes.c_int32), ('cx', ctypes.c_int32), ('cy', ctypes.c_int32),
+                ('cell_u', ctypes.c_int32), ('staging', ctypes.c_int32), ('c_fastest', ctypes.c_int32),
+                ('tiles_x', ctypes.c_int32), ('tiles_y', ctypes.c_int32), ('grid', ctypes.c_int64), ('lds_bytes', ctypes.c_int64)]
+
+
+UPFIRDN_FORMS = ('generic', 'cell', 'tile', 'fir44', 'fir_up2')     # IDE3D_UPFIRDN_*
+
 PLAN_KINDS = ('fp32', 'split', 'split_teams', 'head_split', 'head_resident', 'head_small')     # IDE3D_PLAN_*
 
 STYLE_BATCH_MAX = 24        # IDE3D_STYLE_BATCH_MAX
@@ -359,6 +371,7 @@ def load():
             'ide3d_bias_act': [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, f32, f32, f32, i64, i64, i64, vp],
             'ide3d_upfirdn2d': [ctypes.POINTER(_UpfirdnParams), vp],
             'ide3d_upfirdn2d_ex': [ctypes.POINTER(_UpfirdnParams), ctypes.POINTER(_UpfirdnEpilogue), vp],
+            'ide3d_upfirdn2d_plan': [ctypes.POINTER(_UpfirdnParams), ctypes.POINTER(_UpfirdnEpilogue), ctypes.POINTER(_UpfirdnPlanInfo)],
             'ide3d_filtered_lrelu': [ctypes.POINTER(_FlreluParams), vp],
             'ide3d_filtered_lrelu_act': [vp, vp, ctypes.c_int, i32, i32, i32, i32, ctypes.POINTER(i64 * 4),
                                          i32, i32, i32, i32, f32, f32, f32, ctypes.c_int, vp],
@@ -477,7 +490,7 @@ def load():
 
 
 EXPORTED_SYMBOLS = (
-    'ide3d_last_error', 'ide3d_abi_version', 'ide3d_build_arch', 'ide3d_build_flags', 'ide3d_exclusive_violations', 'ide3d_exclusive_violation_text', 'ide3d_bias_act', 'ide3d_upfirdn2d', 'ide3d_upfirdn2d_ex',
+    'ide3d_last_error', 'ide3d_abi_version', 'ide3d_build_arch', 'ide3d_build_flags', 'ide3d_exclusive_violations', 'ide3d_exclusive_violation_text', 'ide3d_bias_act', 'ide3d_upfirdn2d', 'ide3d_upfirdn2d_ex', 'ide3d_upfirdn2d_plan',
     'ide3d_filtered_lrelu', 'ide3d_filtered_lrelu_act', 'ide3d_triplane_sample', 'ide3d_triplane_sample_rays', 'ide3d_triplane_taps', 'ide3d_triplane_tile_masks',
     'ide3d_triplane_sample_backward', 'ide3d_composite', 'ide3d_composite_plan', 'ide3d_sample_pdf', 'ide3d_render_rays', 'ide3d_render_rays_backward', 'ide3d_sample_voxel',
     'ide3d_lattice_points', 'ide3d_density_lattice',
@@ -731,6 +744,31 @@ class BiasActPlugin:
 # upfirdn2d_plugin
 # ------------------------------------------------------------------------------------------------
 
+def _upfirdn_params(x_shape, x_stride, dtype, x_ptr, row_floats, f_shape, f_stride, f_ptr, upx, upy, downx, downy, padx0, padx1, pady0, pady1, flip, gain):
+    """The `_UpfirdnParams` of one call, all but the output's address and strides -> (params, output shape, channels_last output?).
+    `Upfirdn2dPlugin.upfirdn2d_ex` and the host-only `upfirdn2d_plan` both build their parameters here."""
+    _require(f_shape[0] >= 1 and f_shape[1] >= 1, 'f must be at least 1x1')
+    _require(upx >= 1 and upy >= 1, 'upsampling factor must be at least 1')
+    _require(downx >= 1 and downy >= 1, 'downsampling factor must be at least 1')
+    n, c, ih, iw = x_shape
+    ow = (iw * upx + padx0 + padx1 - f_shape[1] + downx) // downx
+    oh = (ih * upy + pady0 + pady1 - f_shape[0] + downy) // downy
+    _require(ow >= 1 and oh >= 1, 'output must be at least 1x1')
+    cl = x_stride[1] == 1 and c > 1
+    p = _UpfirdnParams()
+    p.x, p.f = x_ptr, f_ptr
+    p.dtype = _DTYPE_CODE[dtype]
+    p.n, p.c, p.in_h, p.in_w, p.out_h, p.out_w = n, c, ih, iw, oh, ow
+    p.x_stride = _i64x4(x_stride)
+    p.f_h, p.f_w = f_shape
+    p.f_stride = (ctypes.c_int64 * 2)(f_stride[0], f_stride[1])
+    p.up_x, p.up_y, p.down_x, p.down_y = upx, upy, downx, downy
+    p.pad_x0, p.pad_y0 = padx0, pady0
+    p.flip, p.gain = int(bool(flip)), float(gain)
+    p.x_row_floats = row_floats
+    return p, (n, c, oh, ow), cl
+
+
 class Upfirdn2dPlugin:
     """`upfirdn2d_plugin` of the reference (upfirdn2d.cpp:16-105)."""
 
@@ -751,28 +789,11 @@ class Upfirdn2dPlugin:
         _require(f.numel() > 0, 'f has zero size')
         _require(x.ndim == 4, 'x must be rank 4')
         _require(f.ndim == 2, 'f must be rank 2')
-        _require(f.shape[0] >= 1 and f.shape[1] >= 1, 'f must be at least 1x1')
-        _require(upx >= 1 and upy >= 1, 'upsampling factor must be at least 1')
-        _require(downx >= 1 and downy >= 1, 'downsampling factor must be at least 1')
-        n, c, ih, iw = x.shape
-        ow = (iw * upx + padx0 + padx1 - f.shape[1] + downx) // downx
-        oh = (ih * upy + pady0 + pady1 - f.shape[0] + downy) // downy
-        _require(ow >= 1 and oh >= 1, 'output must be at least 1x1')
-        cl = x.ndim == 4 and x.stride(1) == 1 and c > 1
+        p, (n, c, oh, ow), cl = _upfirdn_params(tuple(x.shape), x.stride(), x.dtype, x.data_ptr(), _row_floats_readable(x), tuple(f.shape), f.stride(), f.data_ptr(),
+                                                upx, upy, downx, downy, padx0, padx1, pady0, pady1, flip, gain)
         y = torch.empty([n, c, oh, ow], dtype=x.dtype, device=x.device,
                         memory_format=torch.channels_last if cl else torch.contiguous_format)
-        p = _UpfirdnParams()
-        p.x, p.f, p.y = x.data_ptr(), f.data_ptr(), y.data_ptr()
-        p.dtype = _DTYPE_CODE[x.dtype]
-        p.n, p.c, p.in_h, p.in_w, p.out_h, p.out_w = n, c, ih, iw, oh, ow
-        p.x_stride = _i64x4(x.stride())
-        p.y_stride = _i64x4(y.stride())
-        p.f_h, p.f_w = f.shape
-        p.f_stride = (ctypes.c_int64 * 2)(f.stride(0), f.stride(1))
-        p.up_x, p.up_y, p.down_x, p.down_y = upx, upy, downx, downy
-        p.pad_x0, p.pad_y0 = padx0, pady0
-        p.flip, p.gain = int(bool(flip)), float(gain)
-        p.x_row_floats = _row_floats_readable(x)
+        p.y, p.y_stride = y.data_ptr(), _i64x4(y.stride())
         plain = add is None and noise is None and act is None and y_amax is None
         with _dev_guard(x.device):
             if plain:
@@ -2537,6 +2558,54 @@ def composite_plan(rgb_sigma, rays=None, steps=None, ch=None):
     if rc != 0:
         raise RuntimeError(f'composite_plan failed (code {rc}): ' + load().ide3d_last_error().decode('utf-8', 'replace'))
     return dict(form=COMPOSITE_FORMS[info.form], grid=info.grid, workgroup=info.workgroup, lds_bytes=info.lds_bytes)
+
+
+def upfirdn2d_plan(x, f, upx=1, upy=1, downx=1, downy=1, padx0=0, padx1=0, pady0=0, pady1=0, flip=False, gain=1.0,
+                   add=None, noise=None, bias=False, act=None, alpha=0.0, act_gain=1.0, clamp=-1.0, y_amax=False):
+    """Host-only (works without a GPU): the kernel form `Upfirdn2dPlugin.upfirdn2d_ex` would launch for these arguments -> dict of the
+    ide3d_upfirdn2d_plan_info fields: `form` as a name from UPFIRDN_FORMS, `instance` = (ux, uy, dx, dy, fw, fh, cx, cy) (None unless the
+    form is tiled), `cell_u`, `staging`, `c_fastest`, `tiles_x`, `tiles_y`, `grid`, `lds_bytes`.
+    x: a rank-4 tensor on any device (shape, strides, dtype, the 16-byte alignment of its address and the readable row length count), or a
+    dict(shape=, stride=, dtype=, align=0, row_floats=0) (`align` = address modulo 16).  f: a rank-2 tensor or its shape.  add: None, a tensor
+    or such a dict; noise: None / False, True (aligned), a tensor or an address modulo 16; bias, y_amax: present or not.  The output is laid
+    out as the call lays it out, on a 16-byte aligned address (as device allocations are)."""
+    base = 4096          # a non-null, 16-byte aligned stand-in address: the query never dereferences
+
+    def spec(v):
+        if torch.is_tensor(v):
+            return tuple(v.shape), tuple(v.stride()), v.dtype, base + v.data_ptr() % 16, _row_floats_readable(v)
+        return tuple(v['shape']), tuple(v['stride']), v['dtype'], base + int(v.get('align', 0)), int(v.get('row_floats', 0))
+
+    x_shape, x_stride, dtype, x_ptr, row_floats = spec(x)
+    _require(dtype in _DTYPE_CODE, 'x must be float16, bfloat16, float32 or float64')
+    _require(len(x_shape) == 4, 'x must be rank 4')
+    f_shape, f_stride = (tuple(f.shape), tuple(f.stride())) if torch.is_tensor(f) else (tuple(f), (f[1], 1))
+    _require(len(f_shape) == 2, 'f must be rank 2')
+    p, oshape, cl = _upfirdn_params(x_shape, x_stride, dtype, x_ptr, row_floats, f_shape, f_stride, base, upx, upy, downx, downy, padx0, padx1, pady0, pady1, flip, gain)
+    y = torch.empty(oshape, dtype=dtype, device='meta', memory_format=torch.channels_last if cl else torch.contiguous_format)
+    p.y, p.y_stride = base, _i64x4(y.stride())
+    ep = _UpfirdnEpilogue()
+    if add is not None:
+        a_shape, a_stride, a_dtype, a_ptr, _ = spec(add)
+        _require(a_shape == tuple(oshape) and a_dtype == dtype, 'add must match the output')
+        ep.add, ep.add_stride = a_ptr, _i64x4(a_stride)
+    if noise is not None and noise is not False:
+        ep.noise = base + (0 if noise is True else noise.data_ptr() % 16 if torch.is_tensor(noise) else int(noise))
+    if act is not None:
+        ep.fused_act, ep.act = 1, int(act)
+        ep.alpha, ep.act_gain, ep.clamp = float(alpha), float(act_gain), float(clamp)
+        if bias:
+            ep.bias = base
+    if y_amax:
+        ep.y_amax = base
+    info = _UpfirdnPlanInfo()
+    rc = load().ide3d_upfirdn2d_plan(ctypes.byref(p), ctypes.byref(ep), ctypes.byref(info))       # (not a launch: stays out of CALLS)
+    if rc != 0:
+        raise RuntimeError(f'upfirdn2d_plan failed (code {rc}): ' + load().ide3d_last_error().decode('utf-8', 'replace'))
+    form = UPFIRDN_FORMS[info.form]
+    return dict(form=form, instance=(info.ux, info.uy, info.dx, info.dy, info.fw, info.fh, info.cx, info.cy) if form in ('tile', 'fir44', 'fir_up2') else None,
+                cell_u=info.cell_u, staging=info.staging, c_fastest=info.c_fastest, tiles_x=info.tiles_x, tiles_y=info.tiles_y,
+                grid=info.grid, lds_bytes=info.lds_bytes)
 
 
 _ARITH_NAMES = {'fp32': 1, 'bf16x3': 3, 'bf16x6': 6, 'f16x3': 16, 'default': 0}

@@ -128,6 +128,30 @@ typedef struct ide3d_upfirdn2d_epilogue {
 
 int ide3d_upfirdn2d_ex(const ide3d_upfirdn2d_params* p, const ide3d_upfirdn2d_epilogue* ep, void* stream);
 
+/* Host-only planning query (no launch, no device access): which kernel form ide3d_upfirdn2d / ide3d_upfirdn2d_ex would launch for these
+ * parameters, with its geometry.  The pointers of `p` and `ep` (`ep` may be NULL) count for whether they are null and for their 16-byte
+ * alignment only and are never dereferenced.  The launch goes through the same decision (and the tile kernel through the same staging
+ * predicate), and the query refuses exactly what the launch refuses.  The knobs IDE3D_FIR_NO_LEAN / IDE3D_FIR_NO_CELL are read per
+ * query as they are per launch.  For tests and tooling; not part of the reference's interface. */
+enum { IDE3D_UPFIRDN_GENERIC = 0,   /* upfirdn2d_generic_kernel: one output per lane, any factors / filter / strides / dtype */
+       IDE3D_UPFIRDN_CELL = 1,      /* upfirdn2d_cell_kernel<U>: up U x U (2 or 4), no decimation, filter of >= 36 taps in LDS */
+       IDE3D_UPFIRDN_TILE = 2,      /* upfirdn2d_tile_kernel<ux, uy, dx, dy, fw, fh, cx, cy>: LDS-tiled polyphase kernel */
+       IDE3D_UPFIRDN_FIR44 = 3,     /* fir44_kernel: fp32 4x4 filter at unit rate, lean form */
+       IDE3D_UPFIRDN_FIR_UP2 = 4 }; /* fir_up2_kernel: fp32 4x4 filter with 2x zero-upsampling, lean form */
+typedef struct ide3d_upfirdn2d_plan_info {
+    int32_t form;                    /* IDE3D_UPFIRDN_* */
+    int32_t ux, uy, dx, dy, fw, fh, cx, cy;      /* TILE: the template instance (cx, cy = cells per thread; the workgroup is 32 x 8 threads).  The lean
+                                        forms report the instance whose values they reproduce bit for bit; 0 for the other forms */
+    int32_t cell_u;                  /* CELL: U; 0 otherwise */
+    int32_t staging;                 /* how the input window reaches LDS.  TILE: 1 = every plane by 16-byte loads, 0 = every plane by scalar loads,
+                                        2 = mixed (planes differ in their 16-byte alignment); the lean forms: 1; GENERIC / CELL: -1 (no staging) */
+    int32_t c_fastest;               /* GENERIC: 1 = lanes run along the channels (channels_last output with c > 1); 0 otherwise */
+    int32_t tiles_x, tiles_y;        /* tiled forms: tiles per plane; CELL: cells per plane (each U x U outputs); GENERIC: 0 */
+    int64_t grid;                    /* workgroups of 256 threads */
+    int64_t lds_bytes;               /* dynamic LDS per workgroup (CELL: the padded filter; 0 for the other forms, whose LDS is static) */
+} ide3d_upfirdn2d_plan_info;
+int ide3d_upfirdn2d_plan(const ide3d_upfirdn2d_params* p, const ide3d_upfirdn2d_epilogue* ep, ide3d_upfirdn2d_plan_info* out);
+
 /* ---- filtered_lrelu ------------------------------------------------------------------- */
 /*
  * Replaces `_plugin.filtered_lrelu(x, fu, fd, b, si, up, down, px0, px1, py0, py1, sx, sy,

@@ -32,6 +32,13 @@ def _calls(name):
     return hip_plugin.CALLS.get(name, 0)
 
 
+def _fir_plan(x, f, up=1, down=1, padding=(0, 0, 0, 0), flip_filter=False, gain=1, **epilogue):
+    """The kernel form `upfirdn2d.upfirdn2d(x, f, ...)` launches for a 2-D filter (host-only query, hip_plugin.upfirdn2d_plan)."""
+    from torch_utils import hip_plugin
+    px0, px1, py0, py1 = padding
+    return hip_plugin.upfirdn2d_plan(x, f, up, up, down, down, px0, px1, py0, py1, flip_filter, gain, **epilogue)
+
+
 # ---- bias_act ------------------------------------------------------------------------------------------------
 
 def test_bias_act_golden(golden, gpu_device):
@@ -149,6 +156,11 @@ def test_upfirdn2d_tile_kernels(gpu_device, shape, kw, dtype, tol):
     y = upfirdn2d.upfirdn2d(x.to(gpu_device), f.to(gpu_device), **kw)
     ref = fast_ops.upfirdn2d(x.float(), f, **kw)
     assert y.dtype == dtype
+    plan = _fir_plan(x.to(gpu_device), f, **kw)          # the tiled forms: a tile instance, or (fp32, aligned rows) the lean kernel with the same values
+    lean = dtype == torch.float32 and shape in ((2, 5, 32, 32), (1, 2, 300, 200), (1, 2, 40, 300))
+    assert plan['form'] == ({1: 'fir44', 2: 'fir_up2'}[kw.get('up', 1)] if lean else 'tile'), plan
+    assert plan['instance'] == {(1, 1): (1, 1, 1, 1, 4, 4, 4, 4) if shape[3] > 65 else (1, 1, 1, 1, 4, 4, 2, 4), (2, 1): (2, 2, 1, 1, 4, 4, 2, 2),
+                                (1, 2): (1, 1, 2, 2, 4, 4, 4, 2)}[(kw.get('up', 1), kw.get('down', 1))], plan
     assert_close(y.float(), ref, rtol=tol, atol=tol, what=f'{shape} {kw}')
 
 
@@ -169,7 +181,10 @@ def test_upfirdn2d_cell_kernel_equals_generic(gpu_device, monkeypatch):
             for fmt in (torch.contiguous_format, torch.channels_last):
                 x = torch.randn(*shape, generator=g).to(dtype).to(gpu_device).contiguous(memory_format=fmt)
                 y = upfirdn2d.upfirdn2d(x, f.to(gpu_device), **kw)
+                plan = _fir_plan(x, f, **kw)
+                assert (plan['form'], plan['cell_u']) == ('cell', kw['up']), plan
                 monkeypatch.setenv('IDE3D_FIR_NO_CELL', '1')
+                assert _fir_plan(x, f, **kw)['form'] == 'generic'
                 y_gen = upfirdn2d.upfirdn2d(x, f.to(gpu_device), **kw)
                 monkeypatch.delenv('IDE3D_FIR_NO_CELL')
                 assert y.dtype == dtype and torch.equal(y, y_gen), f'{shape} {fh}x{fw} {kw} {dtype} {fmt}'
@@ -180,7 +195,10 @@ def test_upfirdn2d_cell_kernel_equals_generic(gpu_device, monkeypatch):
     add = torch.randn(2, 4, 40, 40, generator=g).to(gpu_device); nz = torch.randn(40, 40, generator=g).to(gpu_device); b = torch.randn(4, generator=g).to(gpu_device)
     run = lambda: hip_plugin.Upfirdn2dPlugin.upfirdn2d_ex(x, f, 2, 2, 1, 1, 5, 4, 5, 4, False, 4.0, add=add, noise=nz, noise_strength=0.3, bias=b, act=3, alpha=0.2, act_gain=1.4, clamp=1.1)
     y = run()
+    plan = lambda: hip_plugin.upfirdn2d_plan(x, f, 2, 2, 1, 1, 5, 4, 5, 4, False, 4.0, add=add, noise=nz, bias=True, act=3, alpha=0.2, act_gain=1.4, clamp=1.1)['form']
+    assert plan() == 'cell'
     monkeypatch.setenv('IDE3D_FIR_NO_CELL', '1')
+    assert plan() == 'generic'
     assert torch.equal(y, run())
 
 
@@ -202,7 +220,12 @@ def test_upfirdn2d_views_never_read_past_their_storage(gpu_device):
         'H-strided view, odd row count': base[:, :, ::2],
         'H-strided view of a 50-wide tensor (in_w % 4 = 2)': torch.randn(1, 2, 33, 50, generator=g).to(gpu_device)[:, :, ::2],
     }
+    # 1 = 16-byte staging, 0 = scalar (the 64-wide tile instance throughout: out_w <= 64)
+    staging = dict(zip(cases, (1, 1, 0, 1, 1, 0)))
     for name, x in cases.items():
+        for pad in ([1, 1, 1, 1], [2, 1, 2, 1]):
+            plan = _fir_plan(x, f, padding=pad)
+            assert (plan['form'], plan['instance'], plan['staging']) == ('tile', (1, 1, 1, 1, 4, 4, 2, 4), staging[name]), (name, plan)
         n_readable = hip_plugin._row_floats_readable(x)
         last_row = x.storage_offset() + sum((x.shape[i] - 1) * x.stride(i) for i in range(3))
         total = x.untyped_storage().nbytes() // 4
@@ -215,6 +238,7 @@ def test_upfirdn2d_views_never_read_past_their_storage(gpu_device):
     pad = torch.randn(2, 4, 65, 68, generator=g).to(gpu_device)
     view = pad[..., :65]
     assert hip_plugin._row_floats_readable(view) >= 68
+    assert _fir_plan(view, f, padding=[1, 1, 1, 1], gain=4)['staging'] == 1
     y = upfirdn2d.upfirdn2d(view, f.to(gpu_device), up=1, padding=[1, 1, 1, 1], gain=4)
     assert_close(y, fast_ops.upfirdn2d(view.cpu().contiguous(), f, up=1, padding=[1, 1, 1, 1], gain=4), rtol=1e-5, atol=1e-5, what='padded rows')
 
@@ -796,6 +820,9 @@ def test_upfirdn2d_fused_epilogue(gpu_device):
         b = torch.randn(shape[1], generator=g).to(gpu_device)
         got = P.upfirdn2d_ex(x, f, 1, 1, 1, 1, pad, pad, pad, pad, False, 4.0, noise=noise, noise_strength=0.37, bias=b, act=3, alpha=0.2,
                              act_gain=math.sqrt(2), clamp=1.5)
+        plan = hip_plugin.upfirdn2d_plan(x, f, 1, 1, 1, 1, pad, pad, pad, pad, False, 4.0, noise=noise, bias=True, act=3, alpha=0.2, act_gain=math.sqrt(2), clamp=1.5)
+        assert (plan['form'], plan['instance']) == {(2, 5, 65, 65): ('tile', (1, 1, 1, 1, 4, 4, 2, 4)), (1, 3, 131, 131): ('tile', (1, 1, 1, 1, 4, 4, 4, 4)),
+                                                    (2, 4, 38, 43): ('tile', (1, 1, 1, 1, 4, 4, 2, 4)), (1, 2, 21, 30): ('generic', None)}[shape], plan
         ref = up._upfirdn2d_ref(x.cpu().double(), f.cpu(), padding=[pad] * 4, gain=4)
         ref = bias_act._bias_act_ref(ref + noise.cpu().double() * 0.37, b.cpu().double(), act='lrelu', gain=math.sqrt(2), clamp=1.5)
         assert_close(got, ref.float(), rtol=1e-5, atol=1e-5, what=f'fir+noise+bias_act {shape}')
@@ -805,6 +832,9 @@ def test_upfirdn2d_fused_epilogue(gpu_device):
         big = torch.randn(shape[0], shape[1], 2 * shape[2], 2 * shape[3] + 3, generator=g).to(gpu_device)
         for add in (big[..., :2 * shape[3]].contiguous(), big[..., 1:2 * shape[3] + 1]):
             got = P.upfirdn2d_ex(x, f4, 2, 2, 1, 1, 2, 1, 2, 1, False, 4.0, add=add)
+            # aligned 16-byte add rows go with the lean kernel; the view one float off the grid takes the tile kernel's scalar add branch
+            lean = add.is_contiguous() and shape[3] % 4 == 0
+            assert hip_plugin.upfirdn2d_plan(x, f4, 2, 2, 1, 1, 2, 1, 2, 1, False, 4.0, add=add)['form'] == ('fir_up2' if lean else 'tile'), shape
             ref = up._upfirdn2d_ref(x.cpu().double(), f4.cpu(), up=2, padding=[2, 1, 2, 1], gain=4) + add.cpu().double()
             assert_close(got, ref.float(), rtol=1e-5, atol=1e-5, what=f'up2+add {shape}')
 
@@ -843,6 +873,9 @@ def test_lean_fir_kernels_equal_the_tile_kernels_bit_for_bit(gpu_device):
                     def run():
                         am = torch.zeros(n, hip_plugin.AMAX_FLOATS, device=gpu_device)
                         return P.upfirdn2d_ex(x, f, 1, 1, 1, 1, 1, 1, 1, 1, flip, 4.0, y_amax=am, **kw), am.amax(dim=1)
+                    plan = lambda: hip_plugin.upfirdn2d_plan(x, f, 1, 1, 1, 1, 1, 1, 1, 1, flip, 4.0, y_amax=True, noise=kw.get('noise'), bias='bias' in kw, act=kw.get('act'),
+                                                             alpha=kw.get('alpha', 0.0), act_gain=kw.get('act_gain', 1.0), clamp=kw.get('clamp', -1.0))['form']
+                    assert both(plan) == ('fir44', 'tile')
                     (y, am), (yr, amr) = both(run)
                     assert torch.equal(y, yr) and torch.equal(am, amr), f'fir44 {(n, c, h, w)} flip {flip} {sorted(kw)}'
                     assert torch.equal(am, y.abs().amax(dim=(1, 2, 3)))
@@ -856,6 +889,8 @@ def test_lean_fir_kernels_equal_the_tile_kernels_bit_for_bit(gpu_device):
         for f in (f4, fa):
             for flip in (False, True):
                 for kw in ({}, dict(add=add), dict(add=add, bias=bb, act=3, alpha=0.2, act_gain=1.3, clamp=0.9)):
+                    assert both(lambda: hip_plugin.upfirdn2d_plan(x, f, 2, 2, 1, 1, 2, 1, 2, 1, flip, 4.0, add=kw.get('add'), bias='bias' in kw, act=kw.get('act'),
+                                                                  alpha=kw.get('alpha', 0.0), act_gain=kw.get('act_gain', 1.0), clamp=kw.get('clamp', -1.0))['form']) == ('fir_up2', 'tile')
                     (y, yr) = both(lambda: P.upfirdn2d_ex(x, f, 2, 2, 1, 1, 2, 1, 2, 1, flip, 4.0, **kw))
                     assert torch.equal(y, yr), f'fir_up2 {(n, c, h, w)} flip {flip} {sorted(kw)}'
                     checked += 1
