@@ -127,6 +127,12 @@ __device__ __forceinline__ void amax_lds_commit(float* amax, const unsigned* s_a
 __host__ __device__ __forceinline__ int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ __forceinline__ int     cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// ATen's max-pool comparison: v replaces the running maximum m (so the first maximum in scan order wins, and NaN wins).
+__device__ __forceinline__ bool pool_gt(float v, float m) { return v > m || v != v; }
+
+// p is a multiple of `bytes` (a power of two); true for a null pointer.  The host-side test in front of every 8- and 16-byte vector access.
+inline bool ptr_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
 // Grid size for a streaming kernel: enough workgroups to fill 256 CUs x 8 blocks, grid-stride beyond.
 inline int stream_grid(int64_t work_items, int per_block) {
     int64_t g = cdiv64(work_items, per_block);

@@ -52,8 +52,6 @@ static dim3 id_grid(int64_t planes, int64_t per_plane) {
     return dim3((unsigned)stream_grid(per_plane, kIdThreads), (unsigned)(planes < 65535 ? planes : 65535));
 }
 
-static bool id_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 // ---- pooling, crop, pooling ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kIdThreads)
 id_prep_kernel(const float* __restrict__ x, float* __restrict__ y, int f, int64_t planes) {
@@ -368,7 +366,7 @@ extern "C" int ide3d_prelu(const float* x, const float* slope, float* y, int32_t
     const int64_t planes = (int64_t)n * c;
     const int hw = h * w;
     hipStream_t st = (hipStream_t)stream;
-    if (hw % 4 == 0 && id_aligned(x, 16) && id_aligned(y, 16))
+    if (hw % 4 == 0 && ptr_aligned(x, 16) && ptr_aligned(y, 16))
         hipLaunchKernelGGL(id_prelu_kernel<true>, id_grid(planes, hw / 4), dim3(kIdThreads), 0, st, x, slope, y, c, hw, planes);
     else
         hipLaunchKernelGGL(id_prelu_kernel<false>, id_grid(planes, hw), dim3(kIdThreads), 0, st, x, slope, y, c, hw, planes);
@@ -387,7 +385,7 @@ extern "C" int ide3d_prelu_backward(const float* dy, int64_t dy_batch_stride, in
     const int hw = h * w;
     const bool dense = dy_row_pitch == w && dy_plane_stride == hw && dy_batch_stride == (int64_t)c * hw;
     hipStream_t st = (hipStream_t)stream;
-    if (dense && hw % 4 == 0 && id_aligned(dy, 16) && id_aligned(x, 16) && id_aligned(dx, 16))
+    if (dense && hw % 4 == 0 && ptr_aligned(dy, 16) && ptr_aligned(x, 16) && ptr_aligned(dx, 16))
         hipLaunchKernelGGL(id_prelu_bwd_kernel<true>, id_grid(planes, hw / 4), dim3(kIdThreads), 0, st, dy, dy_batch_stride, dy_plane_stride,
                            dy_row_pitch, x, slope, dx, c, h, w, planes);
     else
@@ -429,7 +427,7 @@ extern "C" int ide3d_linear(const float* x, const float* weight, const float* bi
                             int64_t workspace_bytes, void* stream) {
     IDE3D_CHECK_ARG(x && weight && y, "linear: null pointer");
     IDE3D_CHECK_ARG(id_linear_ok(n, K, M), "linear: x [n <= %d, K], weight [M, K] with K a multiple of 4", kLinMaxN);
-    IDE3D_CHECK_ARG(id_aligned(x, 16) && id_aligned(weight, 16), "linear: x and weight must be 16-byte aligned");
+    IDE3D_CHECK_ARG(ptr_aligned(x, 16) && ptr_aligned(weight, 16), "linear: x and weight must be 16-byte aligned");
     const int slices = cdiv(K, kLinChunk);
     IDE3D_CHECK_ARG(workspace && workspace_bytes >= (int64_t)slices * n * M * (int64_t)sizeof(float), "linear: workspace too small");
     hipStream_t st = (hipStream_t)stream;
@@ -445,9 +443,9 @@ extern "C" int ide3d_linear_backward_input(const float* dy, const float* weight,
                                            int64_t workspace_bytes, void* stream) {
     IDE3D_CHECK_ARG(dy && weight && dx, "linear_backward_input: null pointer");
     IDE3D_CHECK_ARG(id_linear_ok(n, K, M), "linear_backward_input: dy [n <= %d, M], weight [M, K] with K a multiple of 4", kLinMaxN);
-    IDE3D_CHECK_ARG(id_aligned(weight, 16), "linear_backward_input: weight must be 16-byte aligned");
+    IDE3D_CHECK_ARG(ptr_aligned(weight, 16), "linear_backward_input: weight must be 16-byte aligned");
     const int slices = cdiv(M, kLinBwdRows);
-    IDE3D_CHECK_ARG(workspace && id_aligned(workspace, 16) && workspace_bytes >= (int64_t)slices * n * K * (int64_t)sizeof(float),
+    IDE3D_CHECK_ARG(workspace && ptr_aligned(workspace, 16) && workspace_bytes >= (int64_t)slices * n * K * (int64_t)sizeof(float),
                     "linear_backward_input: workspace too small or misaligned");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(id_linear_bwd_partial_kernel, dim3(cdiv(K / 4, kLinBwdThreads), slices), dim3(kLinBwdThreads), 0, st, dy, weight, workspace,

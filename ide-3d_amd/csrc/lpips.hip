@@ -5,6 +5,7 @@
 //   ide3d_lpips_prep / _backward     f x f area mean + affine (0..255 -> -1..1) + z-score in one pass; the adjoint broadcast;
 //   ide3d_maxpool2                   2x2 stride-2 max, floor on odd sides, bit-equal to ATen's;
 //   ide3d_lpips_stage_backward       max-pool backward + add of the tap's gradient + ReLU backward in one pass over the tap;
+//   ide3d_maxpool2_relu_backward     the same pass without a tap (in front of a VGG19 pool);
 //   ide3d_lpips_head                 channel norm, difference to the cached normalised target, lin-weighted sum, pixel mean: one launch per
 //                                    tap (per-workgroup partial sums -> workspace) and ONE finishing launch for all taps; or normalise only;
 //   ide3d_lpips_head_backward        the closed-form gradient of the same, one launch per tap.
@@ -25,8 +26,6 @@ constexpr int kLpThreads = 256;
 constexpr int kLpSlices = kLpThreads / 64;      // channel slices of a head workgroup, one wave each
 constexpr int kLpPixels = 64;                    // pixels of a head workgroup
 constexpr double kLpEps = 1e-10;                 // reference inversion/criteria/lpips/utils.py:6
-
-__device__ __forceinline__ bool lp_gt(float v, float m) { return v > m || v != v; }          // ATen's max-pool comparison (NaN wins)
 
 // ---- prep ---------------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kLpThreads)
@@ -82,18 +81,18 @@ lp_pool_kernel(const float* __restrict__ x, float* __restrict__ y, int h, int w,
             const float4 a = *reinterpret_cast<const float4*>(r0 + 4 * cx);
             const float4 b = *reinterpret_cast<const float4*>(r0 + w + 4 * cx);
             float m0 = a.x, m1 = a.z;
-            if (lp_gt(a.y, m0)) m0 = a.y;
-            if (lp_gt(b.x, m0)) m0 = b.x;
-            if (lp_gt(b.y, m0)) m0 = b.y;
-            if (lp_gt(a.w, m1)) m1 = a.w;
-            if (lp_gt(b.z, m1)) m1 = b.z;
-            if (lp_gt(b.w, m1)) m1 = b.w;
+            if (pool_gt(a.y, m0)) m0 = a.y;
+            if (pool_gt(b.x, m0)) m0 = b.x;
+            if (pool_gt(b.y, m0)) m0 = b.y;
+            if (pool_gt(a.w, m1)) m1 = a.w;
+            if (pool_gt(b.z, m1)) m1 = b.z;
+            if (pool_gt(b.w, m1)) m1 = b.w;
             *reinterpret_cast<float2*>(o + 2 * cx) = make_float2(m0, m1);
         } else {
             float m = r0[2 * cx];
-            if (lp_gt(r0[2 * cx + 1], m)) m = r0[2 * cx + 1];
-            if (lp_gt(r0[w + 2 * cx], m)) m = r0[w + 2 * cx];
-            if (lp_gt(r0[w + 2 * cx + 1], m)) m = r0[w + 2 * cx + 1];
+            if (pool_gt(r0[2 * cx + 1], m)) m = r0[2 * cx + 1];
+            if (pool_gt(r0[w + 2 * cx], m)) m = r0[w + 2 * cx];
+            if (pool_gt(r0[w + 2 * cx + 1], m)) m = r0[w + 2 * cx + 1];
             o[cx] = m;
         }
     }
@@ -103,24 +102,34 @@ lp_pool_kernel(const float* __restrict__ x, float* __restrict__ y, int h, int w,
 // One 2x2 cell of the tap: dz = (route(gp) + dtap) where y > 0, else 0.  `pooled`: the cell is a window of the pool (all four pixels exist and
 // the stage has a pool behind it); the pooled gradient goes to the window's first maximum in row-major order.  Which of several equal maxima
 // receives it cannot matter: y >= 0 after the ReLU, so a tie at the maximum with a positive value is a measure-zero coincidence of two
-// different convolution outputs, and a tie at 0 is masked.
+// different convolution outputs, and a tie at 0 is masked.  Without HAS_TAP the t's are not read and the routed value is stored as it is (no
+// `+ 0.f`, so a -0.f stays -0.f); a cell that is no window is written as 0.
+template <bool HAS_TAP>
 __device__ __forceinline__ void lp_cell(float v00, float v01, float v10, float v11, float t00, float t01, float t10, float t11, bool pooled,
                                         float gp, float& d00, float& d01, float& d10, float& d11) {
     int idx = 0;
     float m = v00;
-    if (lp_gt(v01, m)) { m = v01; idx = 1; }
-    if (lp_gt(v10, m)) { m = v10; idx = 2; }
-    if (lp_gt(v11, m)) { m = v11; idx = 3; }
+    if (pool_gt(v01, m)) { m = v01; idx = 1; }
+    if (pool_gt(v10, m)) { m = v10; idx = 2; }
+    if (pool_gt(v11, m)) { m = v11; idx = 3; }
     if (!pooled) idx = -1;
-    d00 = v00 > 0.f ? t00 + (idx == 0 ? gp : 0.f) : 0.f;
-    d01 = v01 > 0.f ? t01 + (idx == 1 ? gp : 0.f) : 0.f;
-    d10 = v10 > 0.f ? t10 + (idx == 2 ? gp : 0.f) : 0.f;
-    d11 = v11 > 0.f ? t11 + (idx == 3 ? gp : 0.f) : 0.f;
+    if (HAS_TAP) {
+        d00 = v00 > 0.f ? t00 + (idx == 0 ? gp : 0.f) : 0.f;
+        d01 = v01 > 0.f ? t01 + (idx == 1 ? gp : 0.f) : 0.f;
+        d10 = v10 > 0.f ? t10 + (idx == 2 ? gp : 0.f) : 0.f;
+        d11 = v11 > 0.f ? t11 + (idx == 3 ? gp : 0.f) : 0.f;
+    } else {
+        d00 = (idx == 0 && v00 > 0.f) ? gp : 0.f;
+        d01 = (idx == 1 && v01 > 0.f) ? gp : 0.f;
+        d10 = (idx == 2 && v10 > 0.f) ? gp : 0.f;
+        d11 = (idx == 3 && v11 > 0.f) ? gp : 0.f;
+    }
 }
 
 // Cells cover ceil(h / 2) x ceil(w / 2): the last row / column of an odd side is a cell without a window and receives dtap only.
 // V4 (w % 4 == 0, 16-byte aligned y, dtap and dz, 8-byte aligned dpool): one thread = two neighbouring cells.
-template <bool V4>
+// HAS_TAP false (ide3d_maxpool2_relu_backward): dtap is NULL and never read.
+template <bool V4, bool HAS_TAP>
 __global__ void __launch_bounds__(kLpThreads)
 lp_stage_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dpool, const float* __restrict__ dtap, float* __restrict__ dz,
                     int h, int w, int64_t total) {
@@ -137,27 +146,27 @@ lp_stage_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dpool
         if (V4) {
             const int64_t e = e0 + 4 * cx;
             const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 a = *reinterpret_cast<const float4*>(y + e), ta = *reinterpret_cast<const float4*>(dtap + e);
+            const float4 a = *reinterpret_cast<const float4*>(y + e), ta = HAS_TAP ? *reinterpret_cast<const float4*>(dtap + e) : z4;
             const float4 b = row1 ? *reinterpret_cast<const float4*>(y + e + w) : z4;
-            const float4 tb = row1 ? *reinterpret_cast<const float4*>(dtap + e + w) : z4;
+            const float4 tb = (HAS_TAP && row1) ? *reinterpret_cast<const float4*>(dtap + e + w) : z4;
             const bool pooled = gp != nullptr && row1;
             const float2 g = pooled ? *reinterpret_cast<const float2*>(gp + 2 * cx) : make_float2(0.f, 0.f);
             float4 da, db;
-            lp_cell(a.x, a.y, b.x, b.y, ta.x, ta.y, tb.x, tb.y, pooled, g.x, da.x, da.y, db.x, db.y);
-            lp_cell(a.z, a.w, b.z, b.w, ta.z, ta.w, tb.z, tb.w, pooled, g.y, da.z, da.w, db.z, db.w);
+            lp_cell<HAS_TAP>(a.x, a.y, b.x, b.y, ta.x, ta.y, tb.x, tb.y, pooled, g.x, da.x, da.y, db.x, db.y);
+            lp_cell<HAS_TAP>(a.z, a.w, b.z, b.w, ta.z, ta.w, tb.z, tb.w, pooled, g.y, da.z, da.w, db.z, db.w);
             *reinterpret_cast<float4*>(dz + e) = da;
             if (row1) *reinterpret_cast<float4*>(dz + e + w) = db;
         } else {
             const int64_t e = e0 + 2 * cx;
             const bool col1 = 2 * cx + 1 < w;
-            const float v00 = y[e], t00 = dtap[e];
-            const float v01 = col1 ? y[e + 1] : 0.f, t01 = col1 ? dtap[e + 1] : 0.f;
-            const float v10 = row1 ? y[e + w] : 0.f, t10 = row1 ? dtap[e + w] : 0.f;
-            const float v11 = (row1 && col1) ? y[e + w + 1] : 0.f, t11 = (row1 && col1) ? dtap[e + w + 1] : 0.f;
+            const float v00 = y[e], t00 = HAS_TAP ? dtap[e] : 0.f;
+            const float v01 = col1 ? y[e + 1] : 0.f, t01 = (HAS_TAP && col1) ? dtap[e + 1] : 0.f;
+            const float v10 = row1 ? y[e + w] : 0.f, t10 = (HAS_TAP && row1) ? dtap[e + w] : 0.f;
+            const float v11 = (row1 && col1) ? y[e + w + 1] : 0.f, t11 = (HAS_TAP && row1 && col1) ? dtap[e + w + 1] : 0.f;
             const bool pooled = gp != nullptr && row1 && col1;
             const float g = pooled ? gp[cx] : 0.f;
             float d00, d01, d10, d11;
-            lp_cell(v00, v01, v10, v11, t00, t01, t10, t11, pooled, g, d00, d01, d10, d11);
+            lp_cell<HAS_TAP>(v00, v01, v10, v11, t00, t01, t10, t11, pooled, g, d00, d01, d10, d11);
             dz[e] = d00;
             if (col1) dz[e + 1] = d01;
             if (row1) dz[e + w] = d10;
@@ -279,8 +288,6 @@ lp_head_bwd_kernel(const float* __restrict__ a, const float* __restrict__ t, con
         }
 }
 
-static bool lp_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 static bool lp_taps_ok(const ide3d_lpips_tap* taps, int32_t k, int32_t n, int64_t* blocks_total) {
     if (!taps || k < 1 || k > IDE3D_LPIPS_MAX_TAPS || n < 1) return false;
     int64_t total = 0;
@@ -294,6 +301,22 @@ static bool lp_taps_ok(const ide3d_lpips_tap* taps, int32_t k, int32_t n, int64_
     if (total > 0x7fffffffLL) return false;
     if (blocks_total) *blocks_total = total;
     return true;
+}
+
+// The 16-byte form where the width is a multiple of 4 and every pointer it moves vectors through is aligned (a NULL dpool or dtap counts as
+// aligned); the scalar form otherwise.
+template <bool HAS_TAP>
+static void lp_stage_launch(const float* y, const float* dpool, const float* dtap, float* dz, int64_t planes, int h, int w, hipStream_t st) {
+    const int ch = (h + 1) / 2, cw = (w + 1) / 2;
+    if (w % 4 == 0 && ptr_aligned(y, 16) && ptr_aligned(dtap, 16) && ptr_aligned(dz, 16) && ptr_aligned(dpool, 8)) {
+        const int64_t total = planes * ch * (cw / 2);
+        hipLaunchKernelGGL((lp_stage_bwd_kernel<true, HAS_TAP>), dim3(stream_grid(total, kLpThreads)), dim3(kLpThreads), 0, st, y, dpool, dtap, dz, h,
+                           w, total);
+    } else {
+        const int64_t total = planes * ch * cw;
+        hipLaunchKernelGGL((lp_stage_bwd_kernel<false, HAS_TAP>), dim3(stream_grid(total, kLpThreads)), dim3(kLpThreads), 0, st, y, dpool, dtap, dz, h,
+                           w, total);
+    }
 }
 
 }  // namespace ide3d
@@ -330,7 +353,7 @@ extern "C" int ide3d_maxpool2(const float* x, float* y, int64_t planes, int32_t 
     IDE3D_CHECK_ARG(x && y, "maxpool2: null pointer");
     IDE3D_CHECK_ARG(planes >= 1 && h >= 2 && w >= 2 && planes * h * w < (1LL << 40), "maxpool2: [planes, h, w] with h, w >= 2");
     hipStream_t st = (hipStream_t)stream;
-    if (w % 4 == 0 && lp_aligned(x, 16) && lp_aligned(y, 8)) {
+    if (w % 4 == 0 && ptr_aligned(x, 16) && ptr_aligned(y, 8)) {
         const int64_t total = planes * (h / 2) * (w / 4);
         hipLaunchKernelGGL(lp_pool_kernel<true>, dim3(stream_grid(total, kLpThreads)), dim3(kLpThreads), 0, st, x, y, h, w, total);
     } else {
@@ -346,16 +369,16 @@ extern "C" int ide3d_lpips_stage_backward(const float* y, const float* dpool, co
     IDE3D_CHECK_ARG(y && dtap && dz, "lpips_stage_backward: null pointer");
     IDE3D_CHECK_ARG(planes >= 1 && h >= 1 && w >= 1 && planes * h * w < (1LL << 40), "lpips_stage_backward: [planes, h, w]");
     IDE3D_CHECK_ARG(dpool == nullptr || (h >= 2 && w >= 2), "lpips_stage_backward: a pooled gradient needs h, w >= 2");
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = (h + 1) / 2, cw = (w + 1) / 2;
-    if (w % 4 == 0 && lp_aligned(y, 16) && lp_aligned(dtap, 16) && lp_aligned(dz, 16) && lp_aligned(dpool, 8)) {
-        const int64_t total = planes * ch * (cw / 2);
-        hipLaunchKernelGGL(lp_stage_bwd_kernel<true>, dim3(stream_grid(total, kLpThreads)), dim3(kLpThreads), 0, st, y, dpool, dtap, dz, h, w, total);
-    } else {
-        const int64_t total = planes * ch * cw;
-        hipLaunchKernelGGL(lp_stage_bwd_kernel<false>, dim3(stream_grid(total, kLpThreads)), dim3(kLpThreads), 0, st, y, dpool, dtap, dz, h, w, total);
-    }
+    lp_stage_launch<true>(y, dpool, dtap, dz, planes, h, w, (hipStream_t)stream);
     IDE3D_CHECK_LAUNCH("lpips_stage_backward");
+    return IDE3D_OK;
+}
+
+extern "C" int ide3d_maxpool2_relu_backward(const float* y, const float* dpool, float* dz, int64_t planes, int32_t h, int32_t w, void* stream) {
+    IDE3D_CHECK_ARG(y && dpool && dz, "maxpool2_relu_backward: null pointer");
+    IDE3D_CHECK_ARG(planes >= 1 && h >= 2 && w >= 2 && planes * h * w < (1LL << 40), "maxpool2_relu_backward: [planes, h, w] with h, w >= 2");
+    lp_stage_launch<false>(y, dpool, nullptr, dz, planes, h, w, (hipStream_t)stream);
+    IDE3D_CHECK_LAUNCH("maxpool2_relu_backward");
     return IDE3D_OK;
 }
 
@@ -382,7 +405,7 @@ extern "C" int ide3d_lpips_head(const ide3d_lpips_tap* taps, int32_t k, int32_t 
         return IDE3D_OK;
     }
     for (int i = 0; i < k; ++i) IDE3D_CHECK_ARG(taps[i].a && taps[i].t && taps[i].lin, "lpips_head: a, t and lin of every tap");
-    IDE3D_CHECK_ARG(workspace && lp_aligned(workspace, 8) && workspace_bytes >= blocks * (int64_t)sizeof(double), "lpips_head: workspace too small");
+    IDE3D_CHECK_ARG(workspace && ptr_aligned(workspace, 8) && workspace_bytes >= blocks * (int64_t)sizeof(double), "lpips_head: workspace too small");
     double* partial = reinterpret_cast<double*>(workspace);
     LpFinish f;
     f.k = k;

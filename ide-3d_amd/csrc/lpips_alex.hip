@@ -91,7 +91,7 @@ la_pool_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned char
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
                 const float v = p[(int64_t)ky * w + kx];
-                if (v > m || v != v) { m = v; win = ky * 3 + kx; }
+                if (pool_gt(v, m)) { m = v; win = ky * 3 + kx; }
             }
         y[i] = m;
         if (idx) idx[i] = (unsigned char)win;

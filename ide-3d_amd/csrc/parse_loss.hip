@@ -210,7 +210,7 @@ pl_pool3_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned cha
         for (int ky = ky0; ky < 3 && y0 + ky < h; ++ky)
             for (int kx = kx0; kx < 3 && x0 + kx < w; ++kx) {
                 const float v = p[(int64_t)(y0 + ky) * w + x0 + kx];
-                if (v > m || v != v) { m = v; win = ky * 3 + kx; }
+                if (pool_gt(v, m)) { m = v; win = ky * 3 + kx; }
             }
         const int64_t o = plane * oh * (int64_t)ow + i;
         y[o] = m;
@@ -345,8 +345,6 @@ pl_stem_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ wt, f
     dx[o + 2 * plane] = (float)acc2;
 }
 
-static bool pl_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 static bool pl_sides_ok(int64_t planes, int32_t h, int32_t w, int32_t H, int32_t W) {
     return planes >= 1 && h >= 1 && w >= 1 && H >= 2 && W >= 2 && h <= kPlMaxSide && w <= kPlMaxSide && H <= kPlMaxSide && W <= kPlMaxSide
            && planes * h * w < (1LL << 40) && planes * H * W < (1LL << 40);
@@ -386,7 +384,7 @@ extern "C" int ide3d_parse_ce(const float* logits, const int64_t* labels, int32_
     IDE3D_CHECK_ARG(logits && labels && lse && loss, "parse_ce: null pointer");
     IDE3D_CHECK_ARG(pl_ce_ok(n, C, h, w, H, W), "parse_ce: logits [n, C, h, w], labels [n, H, W] with H, W >= 2 and sides <= %d", kPlMaxSide);
     const int64_t pixels = (int64_t)n * H * W, blocks = cdiv64(pixels, kPlThreads);
-    IDE3D_CHECK_ARG(workspace && pl_aligned(workspace, 8) && pl_aligned(lse, 8) && workspace_bytes >= blocks * (int64_t)sizeof(double),
+    IDE3D_CHECK_ARG(workspace && ptr_aligned(workspace, 8) && ptr_aligned(lse, 8) && workspace_bytes >= blocks * (int64_t)sizeof(double),
                     "parse_ce: workspace too small or misaligned");
     double* partial = reinterpret_cast<double*>(workspace);
     hipStream_t st = (hipStream_t)stream;
@@ -434,14 +432,14 @@ extern "C" int ide3d_parse_join(const ide3d_parse_join_params* p, void* stream) 
     IDE3D_CHECK_ARG(p->n >= 1 && p->c >= 1 && p->h >= 1 && p->w >= 1 && p->h <= kPlMaxSide && p->w <= kPlMaxSide
                     && (int64_t)p->n * p->c * p->h * p->w < (1LL << 40), "parse_join: out [n, c, h, w] with sides <= %d", kPlMaxSide);
     IDE3D_CHECK_ARG(p->post >= 0 && p->post <= 2 && (p->post != 2 || p->y != nullptr), "parse_join: post 0 (none), 1 (relu) or 2 (mask by y > 0, y given)");
-    bool v4 = p->w % 4 == 0 && pl_aligned(p->out, 16) && (p->post != 2 || pl_aligned(p->y, 16));
+    bool v4 = p->w % 4 == 0 && ptr_aligned(p->out, 16) && (p->post != 2 || ptr_aligned(p->y, 16));
     for (int i = 0; i < IDE3D_PARSE_JOIN_TERMS; ++i) {
         const ide3d_parse_term& t = p->term[i];
         if (t.p == nullptr) continue;
         const int th = t.half ? (p->h + 1) / 2 : p->h, tw = t.half ? (p->w + 1) / 2 : p->w;
         IDE3D_CHECK_ARG(t.row_pitch >= tw && t.plane_stride >= (int64_t)(th - 1) * t.row_pitch + tw && t.batch_stride >= (p->c - 1) * t.plane_stride + 1,
                         "parse_join: term %d: row pitch, plane stride and batch stride must cover its [n, c, h, w]", i);
-        v4 = v4 && !t.half && pl_aligned(t.p, 16) && t.row_pitch % 4 == 0 && t.plane_stride % 4 == 0 && t.batch_stride % 4 == 0;
+        v4 = v4 && !t.half && ptr_aligned(t.p, 16) && t.row_pitch % 4 == 0 && t.plane_stride % 4 == 0 && t.batch_stride % 4 == 0;
     }
     const int64_t planes = (int64_t)p->n * p->c, per_plane = (int64_t)p->h * (v4 ? p->w / 4 : p->w);
     hipStream_t st = (hipStream_t)stream;

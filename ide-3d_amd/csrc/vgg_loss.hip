@@ -2,15 +2,15 @@
 //
 // The 13 convolutions (+ bias + ReLU) of the feature net and the 13 of its input gradient are launches of ide3d_modconv2d, the interior ReLU
 // gradients are ide3d_modconv_act_backward, the (x + 1) / 2 in front, its adjoint and the four pools are ide3d_lpips_prep, _prep_backward and
-// ide3d_maxpool2 (lpips.hip).  This file holds the three passes the L1 distance adds, all over dense NCHW fp32:
+// ide3d_maxpool2 (lpips.hip), and the pass in front of a pool (max-pool backward + ReLU backward, never at a tap in VGG19) is
+// ide3d_maxpool2_relu_backward, the tap-less form of ide3d_lpips_stage_backward's kernel (lpips.hip).  This file holds the two passes the L1
+// distance adds, both over dense NCHW fp32:
 //   ide3d_feat_l1                  sum_k weight_k mean |a_k - t_k|: one launch per tap (per-workgroup partial sums -> workspace) and ONE
 //                                  finishing launch for all taps;
 //   ide3d_feat_l1_tap_backward     at a tap: L1 backward (a sign times a per-tap constant) + add of the next convolution's input gradient +
-//                                  ReLU backward in one pass, so that no tap gradient is ever written out and read back;
-//   ide3d_maxpool2_relu_backward   in front of a pool (never a tap in VGG19): max-pool backward + ReLU backward in one pass.
+//                                  ReLU backward in one pass, so that no tap gradient is ever written out and read back.
 // The L1 sum and the tap backward are flat streams: 16 bytes per lane where the element count is a multiple of 4 (any width that is one)
-// and the pointers are 16-byte aligned, one float per lane otherwise.  The pool backward works on 2x2 cells like ide3d_lpips_stage_backward:
-// 16 bytes per lane and row where the width is a multiple of 4, a scalar form otherwise.  At most 256 CUs x 8 workgroups, grid-stride beyond.
+// and the pointers are 16-byte aligned, one float per lane otherwise.  At most 256 CUs x 8 workgroups, grid-stride beyond.
 // Deterministic: fixed-order sums inside a thread, across a wave (butterfly), across the 4 waves of a workgroup (LDS, wave order) and across
 // workgroups and taps (the finishing launch); no atomics; bit-reproducible.  |a - t| and the sums are carried in float64 (an fp32 difference
 // is exact there), so the loss agrees with a float64 evaluation of the same fp32 taps to the final rounding.
@@ -23,8 +23,6 @@ namespace ide3d {
 constexpr int kVlThreads = 256;
 constexpr int kVlWaves = kVlThreads / 64;
 constexpr int kVlPerBlock = kVlThreads * 4;      // elements of one workgroup pass in either form of the flat kernels
-
-__device__ __forceinline__ bool vl_gt(float v, float m) { return v > m || v != v; }          // ATen's max-pool comparison (NaN wins)
 
 // ---- L1 head ----------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double vl_abs_diff(float a, float t) { return fabs((double)a - (double)t); }
@@ -104,63 +102,6 @@ vl_tap_bwd_kernel(const float* __restrict__ a, const float* __restrict__ t, cons
     }
 }
 
-// ---- pool + ReLU backward ---------------------------------------------------------------------------------------------------------------------
-// One 2x2 window of y: the pooled gradient goes to the window's first maximum in row-major order where that maximum is positive, the other
-// three pixels get 0.  Which of several equal maxima receives it cannot matter (the argument of ide3d_lpips_stage_backward): y >= 0 after the
-// ReLU, a tie at a positive maximum needs two equal convolution outputs, and a tie at 0 is masked.
-__device__ __forceinline__ void vl_window(float v00, float v01, float v10, float v11, float gp, float& d00, float& d01, float& d10, float& d11) {
-    int idx = 0;
-    float m = v00;
-    if (vl_gt(v01, m)) { m = v01; idx = 1; }
-    if (vl_gt(v10, m)) { m = v10; idx = 2; }
-    if (vl_gt(v11, m)) { m = v11; idx = 3; }
-    d00 = (idx == 0 && v00 > 0.f) ? gp : 0.f;
-    d01 = (idx == 1 && v01 > 0.f) ? gp : 0.f;
-    d10 = (idx == 2 && v10 > 0.f) ? gp : 0.f;
-    d11 = (idx == 3 && v11 > 0.f) ? gp : 0.f;
-}
-
-// Cells cover ceil(h / 2) x ceil(w / 2): the last row / column of an odd side is a cell without a window and is written as 0.
-// V4 (w % 4 == 0, 16-byte aligned y and dz, 8-byte aligned dpool): one thread = two neighbouring cells.
-template <bool V4>
-__global__ void __launch_bounds__(kVlThreads)
-vl_pool_relu_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dpool, float* __restrict__ dz, int h, int w, int64_t total) {
-    const int ph = h / 2, pw = w / 2, ch = (h + 1) / 2, cw = (w + 1) / 2;
-    const int cols = V4 ? cw / 2 : cw;
-    for (int64_t i = (int64_t)blockIdx.x * kVlThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kVlThreads) {
-        const int cx = (int)(i % cols);
-        const int64_t r = i / cols;
-        const int cy = (int)(r % ch);
-        const int64_t plane = r / ch;
-        const bool row1 = 2 * cy + 1 < h;                                                            // (row1 => cy < ph)
-        const int64_t e0 = (plane * h + 2 * cy) * (int64_t)w;
-        const float* __restrict__ gp = dpool + (plane * ph + (row1 ? cy : 0)) * (int64_t)pw;        // (read only where row1)
-        if (V4) {
-            const int64_t e = e0 + 4 * cx;
-            float4 da = make_float4(0.f, 0.f, 0.f, 0.f), db = da;
-            if (row1) {
-                const float4 a = *reinterpret_cast<const float4*>(y + e), b = *reinterpret_cast<const float4*>(y + e + w);
-                const float2 g = *reinterpret_cast<const float2*>(gp + 2 * cx);
-                vl_window(a.x, a.y, b.x, b.y, g.x, da.x, da.y, db.x, db.y);
-                vl_window(a.z, a.w, b.z, b.w, g.y, da.z, da.w, db.z, db.w);
-                *reinterpret_cast<float4*>(dz + e + w) = db;
-            }
-            *reinterpret_cast<float4*>(dz + e) = da;
-        } else {
-            const int64_t e = e0 + 2 * cx;
-            const bool col1 = 2 * cx + 1 < w;                                                        // (col1 => cx < pw)
-            float d00 = 0.f, d01 = 0.f, d10 = 0.f, d11 = 0.f;
-            if (row1 && col1) vl_window(y[e], y[e + 1], y[e + w], y[e + w + 1], gp[cx], d00, d01, d10, d11);
-            dz[e] = d00;
-            if (col1) dz[e + 1] = d01;
-            if (row1) dz[e + w] = d10;
-            if (row1 && col1) dz[e + w + 1] = d11;
-        }
-    }
-}
-
-static bool vl_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 // Workgroups of a flat pass over `elements` floats: one per kVlPerBlock elements up to the cap of stream_grid, the same in both forms (so
 // that the workspace size does not depend on the pointers' alignment).
 static int vl_flat_grid(int64_t elements) { return stream_grid(elements, kVlPerBlock); }
@@ -195,7 +136,7 @@ extern "C" int ide3d_feat_l1(const ide3d_feat_l1_tap* taps, int32_t k, int32_t n
     IDE3D_CHECK_ARG(vl_taps_ok(taps, k, n, &blocks), "feat_l1: 1..%d taps [n, c, h, w] with positive sizes", IDE3D_LPIPS_MAX_TAPS);
     IDE3D_CHECK_ARG(loss != nullptr, "feat_l1: null loss");
     for (int i = 0; i < k; ++i) IDE3D_CHECK_ARG(taps[i].a && taps[i].t, "feat_l1: a and t of every tap");
-    IDE3D_CHECK_ARG(workspace && vl_aligned(workspace, 8) && workspace_bytes >= blocks * (int64_t)sizeof(double), "feat_l1: workspace too small");
+    IDE3D_CHECK_ARG(workspace && ptr_aligned(workspace, 8) && workspace_bytes >= blocks * (int64_t)sizeof(double), "feat_l1: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     double* partial = reinterpret_cast<double*>(workspace);
     VlFinish f;
@@ -206,7 +147,7 @@ extern "C" int ide3d_feat_l1(const ide3d_feat_l1_tap* taps, int32_t k, int32_t n
         const int64_t elements = (int64_t)n * t.c * t.h * t.w;
         const int nb = vl_flat_grid(elements);
         f.count[i] = nb; f.offset[i] = (int)off; f.scale[i] = (double)t.weight / (double)elements;
-        if (elements % 4 == 0 && vl_aligned(t.a, 16) && vl_aligned(t.t, 16))
+        if (elements % 4 == 0 && ptr_aligned(t.a, 16) && ptr_aligned(t.t, 16))
             hipLaunchKernelGGL(vl_l1_kernel<true>, dim3(nb), dim3(kVlThreads), 0, st, t.a, t.t, partial + off, elements / 4);
         else
             hipLaunchKernelGGL(vl_l1_kernel<false>, dim3(nb), dim3(kVlThreads), 0, st, t.a, t.t, partial + off, elements);
@@ -225,27 +166,11 @@ extern "C" int ide3d_feat_l1_tap_backward(const float* a, const float* t, const 
     const int64_t elements = planes * h * w;
     const dim3 grid(vl_flat_grid(elements)), threads(kVlThreads);
     const double wt = (double)weight, cnt = (double)count;
-    const bool v4 = elements % 4 == 0 && vl_aligned(a, 16) && vl_aligned(t, 16) && vl_aligned(g, 16) && vl_aligned(dz, 16);
+    const bool v4 = elements % 4 == 0 && ptr_aligned(a, 16) && ptr_aligned(t, 16) && ptr_aligned(g, 16) && ptr_aligned(dz, 16);
     if (v4 && g)       hipLaunchKernelGGL((vl_tap_bwd_kernel<true, true>), grid, threads, 0, st, a, t, g, dz, dloss, wt, cnt, elements / 4);
     else if (v4)       hipLaunchKernelGGL((vl_tap_bwd_kernel<true, false>), grid, threads, 0, st, a, t, g, dz, dloss, wt, cnt, elements / 4);
     else if (g)        hipLaunchKernelGGL((vl_tap_bwd_kernel<false, true>), grid, threads, 0, st, a, t, g, dz, dloss, wt, cnt, elements);
     else               hipLaunchKernelGGL((vl_tap_bwd_kernel<false, false>), grid, threads, 0, st, a, t, g, dz, dloss, wt, cnt, elements);
     IDE3D_CHECK_LAUNCH("feat_l1_tap_backward");
-    return IDE3D_OK;
-}
-
-extern "C" int ide3d_maxpool2_relu_backward(const float* y, const float* dpool, float* dz, int64_t planes, int32_t h, int32_t w, void* stream) {
-    IDE3D_CHECK_ARG(y && dpool && dz, "maxpool2_relu_backward: null pointer");
-    IDE3D_CHECK_ARG(planes >= 1 && h >= 2 && w >= 2 && planes * h * w < (1LL << 40), "maxpool2_relu_backward: [planes, h, w] with h, w >= 2");
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = (h + 1) / 2, cw = (w + 1) / 2;
-    if (w % 4 == 0 && vl_aligned(y, 16) && vl_aligned(dz, 16) && vl_aligned(dpool, 8)) {
-        const int64_t total = planes * ch * (cw / 2);
-        hipLaunchKernelGGL(vl_pool_relu_bwd_kernel<true>, dim3(stream_grid(total, kVlThreads)), dim3(kVlThreads), 0, st, y, dpool, dz, h, w, total);
-    } else {
-        const int64_t total = planes * ch * cw;
-        hipLaunchKernelGGL(vl_pool_relu_bwd_kernel<false>, dim3(stream_grid(total, kVlThreads)), dim3(kVlThreads), 0, st, y, dpool, dz, h, w, total);
-    }
-    IDE3D_CHECK_LAUNCH("maxpool2_relu_backward");
     return IDE3D_OK;
 }

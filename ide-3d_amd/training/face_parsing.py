@@ -55,7 +55,6 @@ def conv_bn_act(x, conv, bn=None, relu=False):
             y = bn(y)
         return F.relu(y) if relu else y
     w, b = _folded(conv, bn)
-    act, alpha = (3, 0.0) if relu else (1, 0.0)           # bias_act ids: 3 = lrelu (slope 0 = relu), 1 = linear
     mode = 0
     x = x.float()
     if (k, s) == (3, 2):
@@ -67,7 +66,7 @@ def conv_bn_act(x, conv, bn=None, relu=False):
         ho, wo = (h + 2 * p - k) // s + 1, (wd + 2 * p - k) // s + 1
         x = F.unfold(x, k, padding=p, stride=s).reshape(n, c * k * k, ho, wo)          # channel order (c, ky, kx) = weight.reshape(cout, -1)
         w = w.reshape(w.shape[0], -1, 1, 1)
-    return networks._modconv_plugin.modconv2d(x.contiguous(), w, None, None, None, 0.0, b, act, alpha, 1.0, -1.0, mode=mode)
+    return networks.plain_conv(x.contiguous(), w, b, relu, mode)
 
 
 class ConvBNReLU(nn.Module):

@@ -144,7 +144,7 @@ class _HipOps:
 
     @staticmethod
     def conv(x, w, bias, relu, mode=0):
-        return networks._modconv_plugin.modconv2d(x, w, None, None, None, 0.0, bias, 3 if relu else 1, 0.0, 1.0, -1.0, mode=mode, arith=arith)
+        return networks.plain_conv(x, w, bias, relu, mode, arith)          # (this module's own `arith`, hence not parse_loss's method)
 
 
 def _bn_affine(bn):

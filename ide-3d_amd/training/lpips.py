@@ -27,20 +27,22 @@ never autograd through sqrt.
 ReLU fused), 4 x ide3d_maxpool2, ide3d_lpips_head forward, and ide3d_lpips_head_backward, 5 x ide3d_lpips_stage_backward, 13 x
 ide3d_modconv2d on the transposed-flipped weights, 8 x ide3d_modconv_act_backward, ide3d_lpips_prep_backward backward; it returns the
 image gradient only (the weights are frozen).  Everything else — CPU, other dtypes, `fused = False`, parameters that require grad — takes the
-torch definition in this file, differentiable by autograd except for the closed-form normalisation.
+torch definition in this file, differentiable by autograd except for the closed-form normalisation.  The chain of launches is run by the
+walkers of training/feature_loss.py over `VGG16Features.plan()`; this module adds the prep, the head and `LPIPS._relu_grad`.
 """
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from training import networks
+from training import feature_loss, networks
 
 # True: what the HIP path takes (see above) runs on it.  False: always the torch definition.
 fused = True
 
 STAGES = (2, 2, 3, 3, 3)                                             # convolutions per stage
 CONV_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)        # their positions in torchvision's vgg16().features
+TAP_INDEX = (3, 8, 15, 22, 29)                                       # the last ReLU of every stage (relu1_2 .. relu5_3)
 VGG16_WIDTHS = (64, 128, 256, 512, 512)
 MEAN, STD = (-.030, -.088, -.188), (.458, .448, .450)
 EPS = 1e-10
@@ -85,24 +87,13 @@ class VGG16Features(nn.Module):
         self.register_buffer('std', torch.tensor(STD)[None, :, None, None])
         self.requires_grad_(False)
 
-    def stages(self):
-        """[[conv, ...] per stage]."""
-        convs = [m for m in self.layers if isinstance(m, nn.Conv2d)]
-        out, i = [], 0
-        for count in STAGES:
-            out.append(convs[i:i + count]); i += count
-        return out
+    def plan(self):
+        """[(kind, module)] in launch order (training/feature_loss.py): a tap behind the last ReLU of every stage."""
+        return feature_loss.sequential_plan(self.layers, TAP_INDEX)
 
     def taps(self, z):
         """The five stage outputs of an already z-scored image (torch definition)."""
-        out, h = [], z
-        for s, convs in enumerate(self.stages()):
-            if s > 0:
-                h = F.max_pool2d(h, 2)
-            for conv in convs:
-                h = F.relu(conv(h))
-            out.append(h)
-        return out
+        return feature_loss.torch_taps(self.plan(), z)
 
     def forward(self, x):
         """x in [-1, 1] -> the five normalised taps (torch definition)."""
@@ -117,88 +108,79 @@ def _prep_torch(x, net, f, in_scale, in_shift):
     return (x - net.mean) / net.std
 
 
+# ---- the fused pass over the walkers of training/feature_loss.py, written against an `ops` object (tests/feature_loss_ref.py) -------------
+def _fused_features(ops, lp, y, f, in_scale, in_shift):
+    net = lp.net
+    saved = feature_loss.forward_walk(ops, feature_loss.plan_of(net), lambda: ops.prep(y, net.mean, net.std, f, in_scale, in_shift), False)
+    return ops.normalize(feature_loss.tapped(saved))
+
+
+def _fused_forward(ops, lp, x, feats, lins, f, in_scale, in_shift):
+    """-> (loss, saved): prep -> the net's chain -> head; `saved` is what `forward_walk` returns."""
+    net = lp.net
+    saved = feature_loss.forward_walk(ops, feature_loss.plan_of(net), lambda: ops.prep(x, net.mean, net.std, f, in_scale, in_shift), True)
+    return ops.head(feature_loss.tapped(saved), feats, lins), saved
+
+
+def _fused_backward(ops, lp, saved, feats, lins, f, in_scale, dloss):
+    """-> the image gradient: head backward -> the chain backwards with the net's ReLU-gradient passes -> prep backward."""
+    dtaps = ops.head_backward(feature_loss.tapped(saved), feats, lins, dloss)
+    g = feature_loss.backward_walk(ops, feature_loss.plan_of(lp.net), saved, lp._relu_grad(ops, saved, dtaps))
+    return ops.prep_backward(g, lp.net.std, f, in_scale)
+
+
 class _FusedLpips(torch.autograd.Function):
-    """prep -> 13 convolutions, 4 pools -> head, and the image gradient back through all of it, on the HIP entry points.  The only
-    differentiable input is the image."""
+    """prep -> the convolutions and pools of `lp.net` -> head, and the image gradient back through all of it, on the HIP entry points.  The
+    only differentiable input is the image."""
 
     @staticmethod
     def forward(ctx, x, lp, feats, f, in_scale, in_shift):
-        from torch_utils import hip_plugin
-        P, conv = hip_plugin.LpipsPlugin, networks._modconv_plugin.modconv2d
-        net = lp.net
-        h = P.prep(x, net.mean, net.std, f, in_scale, in_shift)
-        acts = []
-        for s, convs in enumerate(net.stages()):
-            if s > 0:
-                h = P.maxpool2(h)
-            for c in convs:
-                h = conv(h, c.weight, None, None, None, 0.0, c.bias, 3, 0.0, 1.0, -1.0)
-                acts.append(h)
         lins = lp._lin_vectors()
-        taps = _stage_ends(acts)
-        loss = P.head(taps, feats, lins)
-        ctx.save_for_backward(*acts)
-        ctx.lp, ctx.feats, ctx.lins, ctx.prep = lp, feats, lins, (f, in_scale)
+        loss, (acts, tap_at, idxs, sizes) = _fused_forward(feature_loss.HipOps.get(), lp, x, feats, lins, f, in_scale, in_shift)
+        ctx.save_for_backward(*acts, *idxs)
+        ctx.lp, ctx.feats, ctx.lins, ctx.prep, ctx.walk = lp, feats, lins, (f, in_scale), (tap_at, sizes)
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
-        from torch_utils import hip_plugin
-        P, conv = hip_plugin.LpipsPlugin, networks._modconv_plugin.modconv2d
-        acts = ctx.saved_tensors
-        net = ctx.lp.net
-        dtaps = P.head_backward(_stage_ends(acts), ctx.feats, ctx.lins, dloss.to(torch.float32))
-        g, last = None, len(acts)
-        for s in reversed(range(len(STAGES))):
-            convs = net.stages()[s]
-            first = last - len(convs)
-            dz = P.stage_backward(acts[last - 1], g, dtaps[s])
-            for j in reversed(range(first, last)):
-                g = conv(dz, networks._grad_weight(convs[j - first].weight, True), None, None, None, 0.0, None, 1, 0.0, 1.0, -1.0)
-                if j > first:
-                    dz, _ = networks._modconv_grad_plugin.act_backward(g, acts[j - 1], 3, 0.0, 1.0, -1.0)
-            last = first
-        f, in_scale = ctx.prep
-        return P.prep_backward(g, net.std, f, in_scale), None, None, None, None, None
-
-
-def _stage_ends(acts):
-    out, i = [], 0
-    for count in STAGES:
-        i += count
-        out.append(acts[i - 1])
-    return out
+        (tap_at, sizes), (f, in_scale) = ctx.walk, ctx.prep
+        acts, idxs = ctx.saved_tensors[:len(sizes)], ctx.saved_tensors[len(sizes):]
+        dx = _fused_backward(feature_loss.HipOps.get(), ctx.lp, (acts, tap_at, idxs, sizes), ctx.feats, ctx.lins, f, in_scale,
+                             dloss.to(torch.float32))
+        return dx, None, None, None, None, None
 
 
 class LPIPS(nn.Module):
     """`LPIPS('vgg')(x, y)` -> scalar, x and y [N, 3, H, W] in [-1, 1] (reference lpips.py:8-35).  `.net`: VGG16Features, `.lin`: five
     [1, C, 1, 1] non-negative weights without bias, in the reference's `Sequential(Identity, Conv2d)` layout.  No download: the weights are
-    random until a state dict is loaded (`load_state_dict` of one saved from the reference class, or `load_torchvision_state_dict`)."""
+    random until a state dict is loaded (`load_state_dict` of one saved from the reference class, or `load_torchvision_state_dict`).
+    `training.lpips_alex.LPIPS` derives from this class: what a net sets is `_make_net`, `_on_hip`, `_sides_ok`, `_check_sides` and
+    `_relu_grad`."""
 
     def __init__(self, net_type='vgg', version='0.1', widths=VGG16_WIDTHS):
         super().__init__()
         assert version in ['0.1'], 'v0.1 is only supported now'
-        if net_type in ('alex', 'squeeze'):
-            raise NotImplementedError(f"net_type '{net_type}' is not supported: AlexNet and SqueezeNet need 11x11, 5x5 and strided "
-                                      "convolutions, which the HIP convolution kernel does not have; use 'vgg'")
-        if net_type != 'vgg':
-            raise NotImplementedError('choose net_type from [vgg].')
-        self.net = VGG16Features(widths)
+        self.net = self._make_net(net_type, widths)
         self.lin = nn.ModuleList([nn.Sequential(nn.Identity(), nn.Conv2d(c, 1, 1, 1, 0, bias=False)) for c in self.net.widths])
         with torch.no_grad():
             for l in self.lin:
                 l[1].weight.uniform_(0, 1)          # (the trained weights are non-negative)
         self.requires_grad_(False)
 
+    @staticmethod
+    def _make_net(net_type, widths):
+        if net_type in ('alex', 'squeeze'):
+            raise NotImplementedError(f"net_type '{net_type}' is not supported: AlexNet and SqueezeNet need 11x11, 5x5 and strided "
+                                      "convolutions, which the HIP convolution kernel does not have; use 'vgg'")
+        if net_type != 'vgg':
+            raise NotImplementedError('choose net_type from [vgg].')
+        return VGG16Features(widths)
+
     def load_torchvision_state_dict(self, features, lin):
         """`features`: a state dict with torchvision's keys (`features.N.weight`, `features.N.bias`, or without the prefix; other keys, such
         as the classifier's, are ignored); `lin`: the five lin tensors ([1, C, 1, 1] or [C]) in tap order."""
-        sd = {}
-        for i in CONV_INDEX:
-            for name in ('weight', 'bias'):
-                key = f'features.{i}.{name}' if f'features.{i}.{name}' in features else f'{i}.{name}'
-                sd[f'net.layers.{i}.{name}'] = features[key]
-        assert len(lin) == len(STAGES)
+        sd = feature_loss.torchvision_convs(features, {i: f'net.layers.{i}' for i, m in enumerate(self.net.layers) if isinstance(m, nn.Conv2d)})
+        assert len(lin) == len(self.lin)
         for k, w in enumerate(lin):
             sd[f'lin.{k}.1.weight'] = torch.as_tensor(w).reshape(1, -1, 1, 1)
         sd['net.mean'], sd['net.std'] = self.net.mean, self.net.std
@@ -209,39 +191,37 @@ class LPIPS(nn.Module):
         return [networks._wgrad_cache.get((l[1].weight,), lambda w=l[1].weight: w.detach().reshape(-1).float().contiguous(), key='lpips_lin')
                 for l in self.lin]
 
-    def _frozen(self):
-        return not any(p.requires_grad for p in self.parameters())
-
     def _on_hip(self, x, feats=None):
-        if not (fused and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim == 4 and x.shape[1] == 3
-                and x.is_contiguous() and self._frozen() and next(self.parameters()).dtype == torch.float32
-                and next(self.parameters()).device == x.device):
-            return False
-        if feats is not None and not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and not t.requires_grad for t in feats):
-            return False
-        return networks._modconv_init() and networks._modconv_grad_init()
+        return feature_loss.on_hip(fused, x, feats, self.parameters(), False, (), True)
 
     @staticmethod
     def _sides_ok(h, w):
         return (h >> 4) >= 1 and (w >> 4) >= 1
+
+    def _check_sides(self, x, f):
+        """A net with a minimum side raises ValueError here, on every path; this one leaves a small image to the torch definition."""
+
+    def _relu_grad(self, ops, saved, dtaps):
+        """The ReLU gradients of `backward_walk`: a stage's last ReLU is a tap with (but for the last stage) a pool behind it."""
+        acts = saved[0]
+
+        def relu_grad(j, behind, k, g):
+            return ops.stage_backward(acts[j], g, dtaps[k]) if behind == 'tap' else ops.relu_backward(g, acts[j])
+        return relu_grad
+
+    def _takes_hip(self, x, feats, f):
+        H, W = x.shape[2:]
+        return self._on_hip(x, feats) and H % f == 0 and W % f == 0 and self._sides_ok(H // f, W // f)
 
     def features(self, y):
         """The five normalised taps of y (in [-1, 1]), detached: what a projector caches for its target."""
         return self._features(y, 1, 1.0, 0.0)
 
     def _features(self, y, f, in_scale, in_shift):
+        self._check_sides(y, f)
         with torch.no_grad():
-            if self._on_hip(y) and y.shape[2] % f == 0 and y.shape[3] % f == 0 and self._sides_ok(y.shape[2] // f, y.shape[3] // f):
-                from torch_utils import hip_plugin
-                P, conv = hip_plugin.LpipsPlugin, networks._modconv_plugin.modconv2d
-                h, taps = P.prep(y, self.net.mean, self.net.std, f, in_scale, in_shift), []
-                for s, convs in enumerate(self.net.stages()):
-                    if s > 0:
-                        h = P.maxpool2(h)
-                    for c in convs:
-                        h = conv(h, c.weight, None, None, None, 0.0, c.bias, 3, 0.0, 1.0, -1.0)
-                    taps.append(h)
-                return P.normalize(taps)
+            if self._takes_hip(y, None, f):
+                return _fused_features(feature_loss.HipOps.get(), self, y, f, in_scale, in_shift)
             z = _prep_torch(y, self.net, f, in_scale, in_shift)
             return [_Normalize.apply(a).detach() for a in self.net.taps(z)]
 
@@ -250,15 +230,15 @@ class LPIPS(nn.Module):
         return self._distance(x, feats, 1, 1.0, 0.0)
 
     def _distance(self, x, feats, f, in_scale, in_shift):
-        n, _, H, W = x.shape
-        if self._on_hip(x, feats) and H % f == 0 and W % f == 0 and self._sides_ok(H // f, W // f):
+        self._check_sides(x, f)
+        if self._takes_hip(x, feats, f):
             return _FusedLpips.apply(x, self, list(feats), f, in_scale, in_shift)
         z = _prep_torch(x, self.net, f, in_scale, in_shift)
         total = None
         for a, t, l in zip(self.net.taps(z), feats, self.lin):
             d = ((_Normalize.apply(a) - t).square() * l[1].weight).sum(dim=1).mean(dim=(1, 2)).sum()
             total = d if total is None else total + d
-        return total / n
+        return total / x.shape[0]
 
     def forward(self, x, y):
         return self.distance_to(x, self.features(y))

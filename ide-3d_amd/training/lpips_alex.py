@@ -38,15 +38,15 @@ gradients as a 1x1 launch on the transposed weight followed by the unfolding's a
                lpips_prep_backward
 
 Every ReLU gradient sits at a tap, so ide3d_modconv_act_backward is not called.  Everything else — CPU, other dtypes, `fused = False`,
-parameters that require grad — takes the torch definition in this file.
+parameters that require grad — takes the torch definition of training/lpips.py, whose fused pass this is too: the walkers of
+training/feature_loss.py over `AlexNetFeatures.plan()` make the launches above (the unfold / 1x1 / fold bracketing is theirs).
 """
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
-from training import lpips, networks
-from training.lpips import MEAN, STD, _Normalize, _prep_torch
+from training import feature_loss, lpips
+from training.lpips import MEAN, STD, _Normalize
 
 # True: what the HIP path takes (see above) runs on it.  False: always the torch definition.
 fused = True
@@ -79,96 +79,32 @@ class AlexNetFeatures(nn.Module):
         self.register_buffer('std', torch.tensor(STD)[None, :, None, None])
         self.requires_grad_(False)
 
-    def convs(self):
-        return [self.layers[i] for i in CONV_INDEX]
+    def plan(self):
+        """[(kind, module)] in launch order (training/feature_loss.py): a tap behind every convolution."""
+        return feature_loss.sequential_plan(self.layers, [i + 1 for i in CONV_INDEX])
 
     def taps(self, z):
         """The five ReLU outputs of an already z-scored image (torch definition)."""
-        out, h = [], z
-        for conv, pool in zip(self.convs(), POOL_BEHIND):
-            h = F.relu(conv(h))
-            out.append(h)
-            if pool:
-                h = F.max_pool2d(h, 3, 2)
-        return out
+        return feature_loss.torch_taps(self.plan(), z)
 
     def forward(self, x):
         """x in [-1, 1] -> the five normalised taps (torch definition)."""
         return [_Normalize.apply(a) for a in self.taps((x - self.mean) / self.std)]
 
 
-def _weight_1x1(conv, transposed):
-    """A k x k convolution's weight as the 1x1 weight over its unfolded patches, [cout, cin k k, 1, 1], or that of its input gradient,
-    [cin k k, cout, 1, 1]; a 3x3 convolution's own weight, or its transposed-flipped one.  Cached per weight tensor, so that the packed
-    copies in the convolution's workspace are reused across steps."""
-    w = conv.weight
-    if conv.kernel_size[0] == 3:
-        return networks._grad_weight(w, True) if transposed else w
-    if transposed:
-        return networks._wgrad_cache.get((w,), lambda: w.detach().reshape(w.shape[0], -1).t().contiguous()[:, :, None, None], key='alex_1x1_t')
-    return networks._wgrad_cache.get((w,), lambda: w.detach().reshape(w.shape[0], -1, 1, 1), key='alex_1x1')
-
-
-def _hip_taps(net, z, want_idx):
-    """-> (the five ReLU outputs, the two pools' winner bytes or Nones, the input size of every convolution) on the HIP entry points."""
-    from torch_utils import hip_plugin
-    A, conv2d = hip_plugin.LpipsAlexPlugin, networks._modconv_plugin.modconv2d
-    acts, idxs, sizes, h = [], [], [], z
-    for conv, (k, s, p), pool in zip(net.convs(), GEOMETRY, POOL_BEHIND):
-        sizes.append(tuple(h.shape[2:]))
-        if k != 3:
-            h = A.unfold2d(h, k, s, p)
-        h = conv2d(h, _weight_1x1(conv, False), None, None, None, 0.0, conv.bias, 3, 0.0, 1.0, -1.0)
-        acts.append(h)
-        if pool:
-            h, idx = A.maxpool3s2p0(h, want_idx)
-            idxs.append(idx)
-    return acts, idxs, sizes
-
-
-class _FusedLpipsAlex(torch.autograd.Function):
-    """prep -> 5 convolutions (2 of them over unfolded patches), 2 pools -> head, and the image gradient back through all of it, on the HIP
-    entry points.  The only differentiable input is the image."""
-
-    @staticmethod
-    def forward(ctx, x, lp, feats, f, in_scale, in_shift):
-        from torch_utils import hip_plugin
-        P, net = hip_plugin.LpipsPlugin, lp.net
-        acts, idxs, sizes = _hip_taps(net, P.prep(x, net.mean, net.std, f, in_scale, in_shift), True)
-        lins = lp._lin_vectors()
-        loss = P.head(acts, feats, lins)
-        ctx.save_for_backward(*acts, *idxs)
-        ctx.lp, ctx.feats, ctx.lins, ctx.prep, ctx.sizes = lp, feats, lins, (f, in_scale), sizes
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        from torch_utils import hip_plugin
-        P, A, conv2d = hip_plugin.LpipsPlugin, hip_plugin.LpipsAlexPlugin, networks._modconv_plugin.modconv2d
-        acts, idxs = ctx.saved_tensors[:len(GEOMETRY)], list(ctx.saved_tensors[len(GEOMETRY):])
-        net = ctx.lp.net
-        dtaps = P.head_backward(list(acts), ctx.feats, ctx.lins, dloss.to(torch.float32))
-        g = None
-        for j in reversed(range(len(GEOMETRY))):
-            k, s, p = GEOMETRY[j]
-            dz = A.tap_backward(acts[j], g, idxs.pop() if POOL_BEHIND[j] else None, dtaps[j])
-            g = conv2d(dz, _weight_1x1(net.convs()[j], True), None, None, None, 0.0, None, 1, 0.0, 1.0, -1.0)
-            if k != 3:
-                g = A.fold2d(g, ctx.sizes[j], k, s, p)
-        f, in_scale = ctx.prep
-        return P.prep_backward(g, net.std, f, in_scale), None, None, None, None, None
-
-
 class LPIPS(lpips.LPIPS):
     """`LPIPS()(x, y)` -> scalar, x and y [N, 3, H, W] in [-1, 1] with H, W >= 31: the reference class at its default `net_type='alex'`
     (lpips.py:8-35).  `.net`: AlexNetFeatures, `.lin`: five [1, C, 1, 1] non-negative weights without bias, in the reference's
     `Sequential(Identity, Conv2d)` layout.  The public and closure surface is that of `training.lpips.LPIPS` (`features`, `distance_to`,
-    `forward` are inherited), so `training.lpips.lpips_distance(target, m)` and `projection.project(distance=...)` take it as they take the
-    VGG16 form.  No download: the weights are random until a state dict is loaded."""
+    `forward` are inherited, and so are the fused pass and the torch definition behind them), so `training.lpips.lpips_distance(target, m)`
+    and `projection.project(distance=...)` take it as they take the VGG16 form.  No download: the weights are random until a state dict is
+    loaded."""
 
     def __init__(self, net_type='alex', version='0.1', widths=ALEX_WIDTHS):
-        nn.Module.__init__(self)
-        assert version in ['0.1'], 'v0.1 is only supported now'
+        super().__init__(net_type, version, widths)
+
+    @staticmethod
+    def _make_net(net_type, widths):
         if net_type == 'vgg':
             raise NotImplementedError("net_type 'vgg' is training.lpips.LPIPS('vgg'); this module holds the AlexNet form")
         if net_type == 'squeeze':
@@ -176,39 +112,17 @@ class LPIPS(lpips.LPIPS):
                                       "training.lpips.LPIPS('vgg')")
         if net_type != 'alex':
             raise NotImplementedError('choose net_type from [alex].')
-        self.net = AlexNetFeatures(widths)
-        self.lin = nn.ModuleList([nn.Sequential(nn.Identity(), nn.Conv2d(c, 1, 1, 1, 0, bias=False)) for c in self.net.widths])
-        with torch.no_grad():
-            for l in self.lin:
-                l[1].weight.uniform_(0, 1)          # (the trained weights are non-negative)
-        self.requires_grad_(False)
+        return AlexNetFeatures(widths)
 
     def load_torchvision_state_dict(self, features, lin):
-        """`features`: a state dict with torchvision's keys (`features.N.weight`, `features.N.bias`, or without the prefix; other keys, such
-        as the classifier's, are ignored); `lin`: the five lin tensors ([1, C, 1, 1] or [C]) in tap order, or the state dict of the
+        """`features`, `lin`: as `training.lpips.LPIPS.load_torchvision_state_dict` takes them; `lin` may also be the state dict of the
         reference's `alex.pth` (`lin{k}.model.1.weight`)."""
-        sd = {}
-        for i in CONV_INDEX:
-            for name in ('weight', 'bias'):
-                key = f'features.{i}.{name}' if f'features.{i}.{name}' in features else f'{i}.{name}'
-                sd[f'net.layers.{i}.{name}'] = features[key]
         if isinstance(lin, dict):
-            lin = [lin[f'lin{k}.model.1.weight'] for k in range(len(GEOMETRY))]
-        assert len(lin) == len(GEOMETRY)
-        for k, w in enumerate(lin):
-            sd[f'lin.{k}.1.weight'] = torch.as_tensor(w).reshape(1, -1, 1, 1)
-        sd['net.mean'], sd['net.std'] = self.net.mean, self.net.std
-        self.load_state_dict(sd)
-        return self
+            lin = [lin[f'lin{k}.model.1.weight'] for k in range(len(self.lin))]
+        return super().load_torchvision_state_dict(features, lin)
 
     def _on_hip(self, x, feats=None):
-        if not (fused and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim == 4 and x.shape[1] == 3
-                and x.is_contiguous() and self._frozen() and next(self.parameters()).dtype == torch.float32
-                and next(self.parameters()).device == x.device):
-            return False
-        if feats is not None and not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and not t.requires_grad for t in feats):
-            return False
-        return networks._modconv_init()
+        return feature_loss.on_hip(fused, x, feats, self.parameters(), False, (), False)
 
     @staticmethod
     def _sides_ok(h, w):
@@ -220,23 +134,11 @@ class LPIPS(lpips.LPIPS):
             raise ValueError(f'AlexNet LPIPS needs image sides of at least {MIN_SIDE} (after the area factor), got {h} x {w}: '
                              'the second MaxPool2d(3, 2) would have no window')
 
-    def _features(self, y, f, in_scale, in_shift):
-        self._check_sides(y, f)
-        with torch.no_grad():
-            if self._on_hip(y) and y.shape[2] % f == 0 and y.shape[3] % f == 0:
-                from torch_utils import hip_plugin
-                P = hip_plugin.LpipsPlugin
-                return P.normalize(_hip_taps(self.net, P.prep(y, self.net.mean, self.net.std, f, in_scale, in_shift), False)[0])
-            z = _prep_torch(y, self.net, f, in_scale, in_shift)
-            return [_Normalize.apply(a).detach() for a in self.net.taps(z)]
+    def _relu_grad(self, ops, saved, dtaps):
+        """The ReLU gradients of `backward_walk`: every ReLU output is a tap; the first two have a 3x3 pool behind them, whose gradient is
+        routed through the winner bytes."""
+        acts, _, idxs, _ = saved
 
-    def _distance(self, x, feats, f, in_scale, in_shift):
-        self._check_sides(x, f)
-        if self._on_hip(x, feats) and x.shape[2] % f == 0 and x.shape[3] % f == 0:
-            return _FusedLpipsAlex.apply(x, self, list(feats), f, in_scale, in_shift)
-        z = _prep_torch(x, self.net, f, in_scale, in_shift)
-        total = None
-        for a, t, l in zip(self.net.taps(z), feats, self.lin):
-            d = ((_Normalize.apply(a) - t).square() * l[1].weight).sum(dim=1).mean(dim=(1, 2)).sum()
-            total = d if total is None else total + d
-        return total / x.shape[0]
+        def relu_grad(j, behind, k, g):
+            return ops.tap_backward(acts[j], g, idxs[sum(POOL_BEHIND[:j])] if POOL_BEHIND[j] else None, dtaps[k])
+        return relu_grad

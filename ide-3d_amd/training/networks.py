@@ -457,6 +457,17 @@ def _grad_weight(weight, flip):
     return _wgrad_cache.get((weight,), lambda: (weight.detach().transpose(0, 1).flip(2, 3) if flip else weight.detach().transpose(0, 1)).contiguous(), key=bool(flip))
 
 
+def plain_conv(x, w, bias=None, relu=False, mode=0, arith=0):
+    """relu?(conv(x, w) + bias) on ide3d_modconv2d without styles, demodulation or noise: what the frozen loss networks launch, forward (bias
+    and ReLU fused) and backward (on a `_grad_weight`).  The caller has run `_modconv_init()`."""
+    return _modconv_plugin.modconv2d(x, w, None, None, None, 0.0, bias, 3 if relu else 1, 0.0, 1.0, -1.0, mode=mode, arith=arith)
+
+
+def relu_backward(dy, y):
+    """dy where the ReLU output y > 0, else 0 (ide3d_modconv_act_backward).  The caller has run `_modconv_grad_init()`."""
+    return _modconv_grad_plugin.act_backward(dy, y, 3, 0.0, 1.0, -1.0)[0]
+
+
 def _bias_noise_grads(ctx, dz, i_noise, i_bias):
     """(d bias, d noise) of a layer from dz (ide3d_bias_noise_grad), each None unless autograd asks for it (a trainable bias; a const noise
     map that carries a trainable noise strength)."""

@@ -51,14 +51,11 @@ class _HipOps:
         self.ce, self.ce_backward = self.P.ce, self.P.ce_backward
         self.maxpool, self.maxpool_backward = self.P.maxpool, self.P.maxpool_backward
         self.join, self.plane_sums, self.stem_backward = self.P.join, self.P.plane_sums, self.P.stem_backward
+        self.relu_backward = networks.relu_backward
 
     @staticmethod
     def conv(x, w, bias, relu, mode=0):
-        return networks._modconv_plugin.modconv2d(x, w, None, None, None, 0.0, bias, 3 if relu else 1, 0.0, 1.0, -1.0, mode=mode, arith=arith)
-
-    @staticmethod
-    def relu_backward(dy, y):
-        return networks._modconv_grad_plugin.act_backward(dy, y, 3, 0.0, 1.0, -1.0)[0]
+        return networks.plain_conv(x, w, bias, relu, mode, arith)
 
 
 def _conv(ops, x, conv, bn=None, relu=False):

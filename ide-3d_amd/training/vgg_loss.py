@@ -25,6 +25,8 @@ fp32 cached features without grad run on the HIP path, one autograd Function tha
                taps 4..1: feat_l1_tap_backward(g) -> modconv2d likewise
                lpips_prep_backward
 
+The chain of launches is run by the walkers of training/feature_loss.py over `VGG19Features.plan()`; `_fused_backward` here holds the tap /
+pool / interior choice as the walker's `relu_grad`.
 Everything else — CPU, other dtypes, `fused = False`, parameters that require grad — takes the torch definition in this file.  `fused` ships
 True: on an MI355X the HIP path is faster than the ATen path of this module at 256 x 256 and 512 x 512, batch 1 and 4 (DESIGN.md section
 5.22, scripts/bench_vgg_loss.py).
@@ -34,7 +36,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from training import networks
+from training import feature_loss
 
 # True: what the HIP path takes (see above) runs on it.  False: always the torch definition.
 fused = True
@@ -88,42 +90,42 @@ class VGG19Features(nn.Module):
         """[(kind, module)] in launch order, kind in 'conv' (a convolution + its ReLU), 'pool', 'tap' (the end of a slice)."""
         out = []
         for piece in self.layers:
-            for m in piece:
-                if isinstance(m, nn.Conv2d):
-                    out.append(('conv', m))
-                elif isinstance(m, nn.MaxPool2d):
-                    out.append(('pool', m))
-            out.append(('tap', None))
+            out += feature_loss.sequential_plan(piece, ()) + [('tap', None)]
         return out
 
     def taps(self, z):
         """The slice outputs of an image already mapped to [0, 1] (torch definition)."""
-        out, h = [], z
-        for piece in self.layers:
-            h = piece(h)
-            out.append(h)
-        return out
+        return feature_loss.torch_taps(self.plan(), z)
 
     def forward(self, x):
         """x in [-1, 1] -> the raw taps (torch definition)."""
         return self.taps((x + 1) / 2)
 
 
-def _hip_taps(net, x):
-    """-> (the output of every convolution + ReLU in order, the indices of the taps among them) on the HIP entry points."""
-    from torch_utils import hip_plugin
-    P, conv2d = hip_plugin.LpipsPlugin, networks._modconv_plugin.modconv2d
-    h = P.prep(x, net._prep_mean, net._prep_std, 1, 0.5, 0.5)
-    acts, tap_at = [], []
-    for kind, m in net.plan():
-        if kind == 'conv':
-            h = conv2d(h, m.weight, None, None, None, 0.0, m.bias, 3, 0.0, 1.0, -1.0)
-            acts.append(h)
-        elif kind == 'pool':
-            h = P.maxpool2(h)
-        else:
-            tap_at.append(len(acts) - 1)
-    return acts, tap_at
+# ---- the fused pass over the walkers of training/feature_loss.py, written against an `ops` object (tests/feature_loss_ref.py) -------------
+def _fused_taps(ops, net, x):
+    """-> what `forward_walk` returns for x in [-1, 1]: (the output of every convolution + ReLU, the positions of the taps among them, ...)."""
+    return feature_loss.forward_walk(ops, feature_loss.plan_of(net), lambda: ops.prep(x, net._prep_mean, net._prep_std, 1, 0.5, 0.5), False)
+
+
+def _fused_forward(ops, net, x, feats):
+    """-> (loss, saved)."""
+    saved = _fused_taps(ops, net, x)
+    return ops.feat_l1(feature_loss.tapped(saved), feats, net.weights[:len(saved[1])]), saved
+
+
+def _fused_backward(ops, net, saved, feats, dloss):
+    """-> the image gradient.  What follows a ReLU picks its gradient pass: a tap (the L1 term joins the next convolution's input gradient,
+    None behind the last tap), a pool (routed to the window's first maximum) or the next convolution."""
+    acts = saved[0]
+
+    def relu_grad(j, behind, k, g):
+        if behind == 'tap':
+            return ops.feat_l1_tap_backward(acts[j], feats[k], g, dloss, net.weights[k])
+        if behind == 'pool':
+            return ops.maxpool2_relu_backward(acts[j], g)
+        return ops.relu_backward(g, acts[j])
+    return ops.prep_backward(feature_loss.backward_walk(ops, feature_loss.plan_of(net), saved, relu_grad), net._prep_std, 1, 0.5)
 
 
 class _FusedVggLoss(torch.autograd.Function):
@@ -132,37 +134,16 @@ class _FusedVggLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, net, feats):
-        from torch_utils import hip_plugin
-        acts, tap_at = _hip_taps(net, x)
-        loss = hip_plugin.VggLossPlugin.feat_l1([acts[i] for i in tap_at], feats, net.weights[:len(tap_at)])
+        loss, (acts, tap_at, _, sizes) = _fused_forward(feature_loss.HipOps.get(), net, x, feats)
         ctx.save_for_backward(*acts)
-        ctx.net, ctx.feats = net, feats
+        ctx.net, ctx.feats, ctx.walk = net, feats, (tap_at, sizes)
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
-        from torch_utils import hip_plugin
-        P, V, conv2d = hip_plugin.LpipsPlugin, hip_plugin.VggLossPlugin, networks._modconv_plugin.modconv2d
-        acts, net = ctx.saved_tensors, ctx.net
-        dloss = dloss.to(torch.float32)
-        # walk the plan backwards; `behind` is what follows the convolution whose ReLU gradient is due: a tap, a pool or the next convolution
-        j, k, g, behind = len(acts), len(ctx.feats), None, None
-        for kind, m in reversed(net.plan()):
-            if kind != 'conv':
-                behind = kind
-                if kind == 'tap':
-                    k -= 1
-                continue
-            j -= 1
-            if behind == 'tap':
-                dz = V.feat_l1_tap_backward(acts[j], ctx.feats[k], g, dloss, net.weights[k])
-            elif behind == 'pool':
-                dz = V.maxpool2_relu_backward(acts[j], g)
-            else:
-                dz, _ = networks._modconv_grad_plugin.act_backward(g, acts[j], 3, 0.0, 1.0, -1.0)
-            g = conv2d(dz, networks._grad_weight(m.weight, True), None, None, None, 0.0, None, 1, 0.0, 1.0, -1.0)
-            behind = 'conv'
-        return P.prep_backward(g, net._prep_std, 1, 0.5), None, None
+        tap_at, sizes = ctx.walk
+        saved = (ctx.saved_tensors, tap_at, (), sizes)
+        return _fused_backward(feature_loss.HipOps.get(), ctx.net, saved, ctx.feats, dloss.to(torch.float32)), None, None
 
 
 class VGGLoss(VGG19Features):
@@ -180,27 +161,12 @@ class VGGLoss(VGG19Features):
     def load_torchvision_state_dict(self, features):
         """`features`: a state dict with torchvision's keys (`features.N.weight`, `features.N.bias`, or without the prefix; other keys, such
         as the classifier's or the layers behind position 29, are ignored)."""
-        sd, prev = {}, 0
-        for s, end in enumerate(SLICE_ENDS[:self.n_layers]):
-            for i in (i for i in CONV_INDEX if prev <= i < end):
-                for name in ('weight', 'bias'):
-                    key = f'features.{i}.{name}' if f'features.{i}.{name}' in features else f'{i}.{name}'
-                    sd[f'layers.{s}.{i}.{name}'] = features[key]
-            prev = end
-        self.load_state_dict(sd)
+        names = {int(pos): f'layers.{s}.{pos}' for s, piece in enumerate(self.layers) for pos, m in piece.named_children() if isinstance(m, nn.Conv2d)}
+        self.load_state_dict(feature_loss.torchvision_convs(features, names))
         return self
 
-    def _frozen(self):
-        return not any(p.requires_grad for p in self.parameters())
-
     def _on_hip(self, x, feats=None):
-        if not (fused and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim == 4 and x.shape[1] == 3
-                and x.is_contiguous() and self._frozen() and all(p.dtype == torch.float32 and p.device == x.device for p in self.parameters())
-                and self._prep_std.device == x.device):
-            return False
-        if feats is not None and not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and not t.requires_grad for t in feats):
-            return False
-        return networks._modconv_init() and networks._modconv_grad_init()
+        return feature_loss.on_hip(fused, x, feats, self.parameters(), True, (self._prep_std,), True)
 
     @staticmethod
     def _check_sides(x):
@@ -214,8 +180,7 @@ class VGGLoss(VGG19Features):
         self._check_sides(target)
         with torch.no_grad():
             if self._on_hip(target):
-                acts, tap_at = _hip_taps(self, target)
-                return [acts[i] for i in tap_at]
+                return feature_loss.tapped(_fused_taps(feature_loss.HipOps.get(), self, target))
             return [t.detach() for t in self.taps((target + 1) / 2)]
 
     def distance_to(self, source, feats):

@@ -11,56 +11,12 @@ weights (the timing does not depend on them)."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'ide-3d_amd')); sys.path.insert(0, ROOT)
 
-PATHS = {'hip': True, 'aten': False}
-
-
-def measure(cases, blocks, iters, warmup):
-    """cases: {name: callable()}; every callable is run under both paths -> {name: {path: figures}}."""
-    import torch
-    from training import id_loss
-    from torch_utils import hip_plugin
-    for name, fn in cases.items():
-        for fused in PATHS.values():
-            id_loss.fused = fused
-            before = hip_plugin.CALLS.get('id_head', 0)
-            for _ in range(warmup):
-                fn()
-            took_hip = hip_plugin.CALLS.get('id_head', 0) > before
-            assert took_hip == fused, f'{name}: fused = {fused} but the HIP loss head ' + ('ran' if took_hip else 'did not run')
-    torch.cuda.synchronize()
-    times = {(c, p): [] for c in cases for p in PATHS}
-    for _ in range(blocks):
-        for c, fn in cases.items():
-            for p, fused in PATHS.items():
-                id_loss.fused = fused
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(iters):
-                    fn()
-                e1.record()
-                torch.cuda.synchronize()
-                times[(c, p)].append(e0.elapsed_time(e1) / iters)
-    out = {}
-    for c, fn in cases.items():
-        out[c] = {}
-        for p, fused in PATHS.items():
-            id_loss.fused = fused
-            torch.cuda.synchronize()
-            base = torch.cuda.memory_allocated()
-            torch.cuda.reset_peak_memory_stats()
-            fn()
-            torch.cuda.synchronize()
-            t = times[(c, p)]
-            out[c][p] = dict(ms=round(statistics.median(t), 3), spread_ms=round(max(t) - min(t), 3), blocks_ms=[round(v, 3) for v in t],
-                             peak_mib=round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1))
-        out[c]['hip_over_aten'] = round(out[c]['hip']['ms'] / out[c]['aten']['ms'], 3)
-    return out
+import loss_bench
 
 
 def main():
@@ -69,7 +25,7 @@ def main():
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--only', default=None, help='run one case (for a kernel trace)')
-    ap.add_argument('--path', default=None, choices=list(PATHS), help='with --only: run that path alone, untimed')
+    ap.add_argument('--path', default=None, choices=list(loss_bench.PATHS), help='with --only: run that path alone, untimed')
     args = ap.parse_args()
 
     import torch
@@ -94,13 +50,13 @@ def main():
     result = dict(bench='id_loss', blocks=args.blocks, iters=args.iters)
     try:
         if args.only and args.path:
-            id_loss.fused = PATHS[args.path]
+            id_loss.fused = loss_bench.PATHS[args.path]
             for _ in range(args.warmup + args.iters):
                 cases[args.only]()
             torch.cuda.synchronize()
             result.update(only=args.only, path=args.path, untimed=True)
         else:
-            result.update(measure(cases, args.blocks, args.iters, args.warmup))
+            result.update(loss_bench.measure(id_loss, cases, args.blocks, args.iters, args.warmup, hip_call='id_head'))
     finally:
         id_loss.fused = default
     print(json.dumps(result))

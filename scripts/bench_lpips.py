@@ -12,52 +12,12 @@ random weights (the timing does not depend on them)."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'ide-3d_amd')); sys.path.insert(0, ROOT)
 
-PATHS = {'hip': True, 'aten': False}
-
-
-def measure(cases, blocks, iters, warmup):
-    """cases: {name: callable()}; every callable is run under both paths -> {name: {path: figures}}."""
-    import torch
-    from training import lpips
-    for fn in cases.values():
-        for fused in PATHS.values():
-            lpips.fused = fused
-            for _ in range(warmup):
-                fn()
-    torch.cuda.synchronize()
-    times = {(c, p): [] for c in cases for p in PATHS}
-    for _ in range(blocks):
-        for c, fn in cases.items():
-            for p, fused in PATHS.items():
-                lpips.fused = fused
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(iters):
-                    fn()
-                e1.record()
-                torch.cuda.synchronize()
-                times[(c, p)].append(e0.elapsed_time(e1) / iters)
-    out = {}
-    for c, fn in cases.items():
-        out[c] = {}
-        for p, fused in PATHS.items():
-            lpips.fused = fused
-            torch.cuda.synchronize()
-            base = torch.cuda.memory_allocated()
-            torch.cuda.reset_peak_memory_stats()
-            fn()
-            torch.cuda.synchronize()
-            t = times[(c, p)]
-            out[c][p] = dict(ms=round(statistics.median(t), 3), spread_ms=round(max(t) - min(t), 3), blocks_ms=[round(v, 3) for v in t],
-                             peak_mib=round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1))
-        out[c]['hip_over_aten'] = round(out[c]['hip']['ms'] / out[c]['aten']['ms'], 3)
-    return out
+import loss_bench
 
 
 def main():
@@ -90,7 +50,7 @@ def main():
         cases[f'lpips_b{n}'] = call
     result = dict(bench='lpips', size=args.size, blocks=args.blocks, iters=args.iters)
     try:
-        result.update(measure(cases, args.blocks, args.iters, args.warmup))
+        result.update(loss_bench.measure(lpips, cases, args.blocks, args.iters, args.warmup))
         if not args.no_projector:
             sp = triplane.GeneratorSpec()
             G = triplane.TriPlaneGenerator(sp).eval().requires_grad_(False)
@@ -110,7 +70,7 @@ def main():
             def step():
                 counter[0] += 1
                 P.step(counter[0])
-            result.update(measure({'projector_step': step}, args.blocks, max(args.iters // 5, 1), max(args.warmup - 1, 1)))
+            result.update(loss_bench.measure(lpips, {'projector_step': step}, args.blocks, max(args.iters // 5, 1), max(args.warmup - 1, 1)))
             result['projector_resolution'] = sp.img_resolution
     finally:
         lpips.fused = default

@@ -12,56 +12,12 @@ random weights (the timing does not depend on them)."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'ide-3d_amd')); sys.path.insert(0, ROOT)
 
-PATHS = {'hip': True, 'aten': False}
-
-
-def measure(cases, blocks, iters, warmup):
-    """cases: {name: callable()}; every callable is run under both paths -> {name: {path: figures}}."""
-    import torch
-    from training import parse_loss
-    from torch_utils import hip_plugin
-    for name, fn in cases.items():
-        for fused in PATHS.values():
-            parse_loss.fused = fused
-            before = hip_plugin.CALLS.get('parse_ce', 0)
-            for _ in range(warmup):
-                fn()
-            took_hip = hip_plugin.CALLS.get('parse_ce', 0) > before
-            assert took_hip == fused, f'{name}: fused = {fused} but the HIP loss head ' + ('ran' if took_hip else 'did not run')
-    torch.cuda.synchronize()
-    times = {(c, p): [] for c in cases for p in PATHS}
-    for _ in range(blocks):
-        for c, fn in cases.items():
-            for p, fused in PATHS.items():
-                parse_loss.fused = fused
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(iters):
-                    fn()
-                e1.record()
-                torch.cuda.synchronize()
-                times[(c, p)].append(e0.elapsed_time(e1) / iters)
-    out = {}
-    for c, fn in cases.items():
-        out[c] = {}
-        for p, fused in PATHS.items():
-            parse_loss.fused = fused
-            torch.cuda.synchronize()
-            base = torch.cuda.memory_allocated()
-            torch.cuda.reset_peak_memory_stats()
-            fn()
-            torch.cuda.synchronize()
-            t = times[(c, p)]
-            out[c][p] = dict(ms=round(statistics.median(t), 3), spread_ms=round(max(t) - min(t), 3), blocks_ms=[round(v, 3) for v in t],
-                             peak_mib=round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1))
-        out[c]['hip_over_aten'] = round(out[c]['hip']['ms'] / out[c]['aten']['ms'], 3)
-    return out
+import loss_bench
 
 
 def main():
@@ -92,7 +48,7 @@ def main():
         cases[f'parse_b{n}'] = call
     result = dict(bench='parse_loss', size=args.size, blocks=args.blocks, iters=args.iters)
     try:
-        result.update(measure(cases, args.blocks, args.iters, args.warmup))
+        result.update(loss_bench.measure(parse_loss, cases, args.blocks, args.iters, args.warmup, hip_call='parse_ce'))
         if not args.no_projector:
             sp = triplane.GeneratorSpec()
             G = triplane.TriPlaneGenerator(sp).eval().requires_grad_(False)
@@ -112,7 +68,7 @@ def main():
             def step():
                 counter[0] += 1
                 P.step(counter[0])
-            result.update(measure({'projector_step': step}, args.blocks, max(args.iters // 5, 1), max(args.warmup - 1, 1)))
+            result.update(loss_bench.measure(parse_loss, {'projector_step': step}, args.blocks, max(args.iters // 5, 1), max(args.warmup - 1, 1), hip_call='parse_ce'))
             result['projector_resolution'] = sp.img_resolution
     finally:
         parse_loss.fused = default
