@@ -46,6 +46,15 @@
 //   ray's image in the wave's own slice [n][12] of a second workspace, plain vector loads and stores again; a second launch adds the slices in
 //   a fixed order and writes [n, 4, 4] with a zero last row.  No atomics: the camera gradient IS bit-reproducible, and equal whether the
 //   call also scatters to the planes or sums the decoder gradients.
+//
+// Merged march of the hierarchical pass (ide3d_render_rays_merged_backward, the body's fourth compile-time switch MERGED; the instantiations
+// above are compiled from the body with every statement below removed):
+//   The ray has T = 2 * steps samples; the per-ray arrays, the chunk loops and the launch plan are sized by T.  Sample s is entry
+//   src[ray, s] (clamped into [0, T) like render_rays_merged_kernel does) of [fine | coarse]: a coarse entry is placed by ray_world_point
+//   from z_lin and the jitter draw, a fine entry at origin + dir_world * z_fine with the forward's fmul / fadd sequence, so both sweeps
+//   gather the taps the forward gathered.  Depth and delta come from z_all; there is no density noise.  z_all, src and z_fine are constants
+//   (the step-wise definition draws the fine depths and forms the fine points without gradient), so sweep 1, the reverse scan, sweep 2 and
+//   the scatter are the plain kernel's over T samples.  Composes with PARAMS, not with CAM.
 #include <algorithm>
 
 #include "common.h"
@@ -276,12 +285,22 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// What places the samples of the merged march: sample s of a ray is entry src[ray, s] of the concatenation [fine | coarse], at depth
+// z_all[ray, s].  All three arrays are constants of the backward.
+struct MergedSamples {
+    const float* z_all;      // [n * rays, T] ascending depths
+    const int* src;          // [n * rays, T] index into [fine | coarse]
+    const float* z_fine;     // [n * rays, steps]
+};
+
 // The body of all kernels.  PARAMS = false: gradients of the tri-planes only (sl unused).  PARAMS = true: also the decoder-parameter sums,
 // into the wave's slice of `slices`; a NULL grad_tex_planes / grad_geo_planes then skips that plane's scatter.  CAM = true: also the 12
 // camera sums per image, into the wave's slice of `cam_slices`; a NULL plane gradient skips that plane's scatter without PARAMS too.
-template <int C, int HID, bool PARAMS, bool CAM = false>
+// MERGED = true: the T = 2 * steps samples of the hierarchical pass's merged march, placed by `ms`; sp is T rounded up to 64.
+template <int C, int HID, bool PARAMS, bool CAM = false, bool MERGED = false>
 __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_params& p, const ide3d_render_grads& gr, int sp, float* slices,
-                                                          float* cam_slices = nullptr) {
+                                                          float* cam_slices = nullptr, const MergedSamples& ms = MergedSamples{}) {
+    static_assert(!(MERGED && CAM), "the merged march has no camera gradient");
     using L = BwdLds<C, HID>;
     using PS = ParamSlice<C, HID>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -313,10 +332,11 @@ __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_par
     float* const sl = PARAMS ? slices + ((int64_t)blockIdx.x * nw + wid) * PS::stride(p.seg_ch, p.feat_ch) : nullptr;
     float* const csl = CAM ? cam_slices + ((int64_t)blockIdx.x * nw + wid) * ((int64_t)p.n * 12) : nullptr;
 
-    const int S = p.steps, R = p.rays_per_img, nch = p.feat_ch + p.seg_ch;
+    // S: samples per ray (MERGED: T = 2 * steps, of which SC = steps are the coarse ones)
+    const int SC = p.steps, S = MERGED ? 2 * SC : SC, R = p.rays_per_img, nch = p.feat_ch + p.seg_ch;
     const int64_t total_rays = (int64_t)p.n * R;
     const int sH = (int)p.tex_stride[2], sW = (int)p.tex_stride[3];
-    const float zstep = (S > 1) ? (p.z_lin[1] - p.z_lin[0]) : 0.f;
+    const float zstep = (SC > 1) ? (p.z_lin[1] - p.z_lin[0]) : 0.f;
 
     for (int64_t ray = (int64_t)blockIdx.x * nw + wid; ray < total_rays; ray += (int64_t)gridDim.x * nw) {
         const int n = __builtin_amdgcn_readfirstlane((int)(ray / R));
@@ -358,16 +378,43 @@ __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_par
         // what both sweeps rebuild of sample s: its taps, its depth and its delta
         auto sample_setup = [&](int s, Tap2 (&t)[3], TapAddr (&a)[3], float& z, float& delta) {
             const int sc = s < S ? s : S - 1;
-            const float zl = p.z_lin[sc];
-            const float jl = p.jitter ? p.jitter[ray * S + sc] : 0.5f;
             float wx, wy, wz;
-            ray_world_point(p, n, r, zl, jl, zstep, wx, wy, wz);
+            if constexpr (MERGED) {
+                // the entry is clamped into [0, T) before it indexes anything, as the forward does
+                const int sv = min(max(ms.src[ray * S + sc], 0), S - 1);
+                if (sv < SC) {
+                    // origin + dir_world * z_fine, the multiply and the add rounded separately: render_rays_merged_kernel's sequence,
+                    // operation for operation (the taps must be the ones the forward gathered)
+                    const float zf = ms.z_fine[ray * SC + sv];
+                    const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];
+                    const float* M = p.cam2world + n * 16;
+                    const float ux = fmaf(M[0], dx, fmaf(M[1], dy, __fmul_rn(M[2], dz)));
+                    const float uy = fmaf(M[4], dx, fmaf(M[5], dy, __fmul_rn(M[6], dz)));
+                    const float uz = fmaf(M[8], dx, fmaf(M[9], dy, __fmul_rn(M[10], dz)));
+                    wx = __fadd_rn(M[3], __fmul_rn(ux, zf));
+                    wy = __fadd_rn(M[7], __fmul_rn(uy, zf));
+                    wz = __fadd_rn(M[11], __fmul_rn(uz, zf));
+                } else {
+                    const int i = sv - SC;
+                    ray_world_point(p, n, r, p.z_lin[i], p.jitter ? p.jitter[ray * SC + i] : 0.5f, zstep, wx, wy, wz);
+                }
+            } else {
+                const float zl = p.z_lin[sc];
+                const float jl = p.jitter ? p.jitter[ray * S + sc] : 0.5f;
+                ray_world_point(p, n, r, zl, jl, zstep, wx, wy, wz);
+            }
             triplane_taps(wx, wy, wz, p.W, p.H, t);
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) a[pl] = tap_addr(t[pl], p.W, p.H, sH, sW);
-            z = ray_sample_depth(p, ray, sc, zstep);
-            const float znext = (sc + 1 < S) ? ray_sample_depth(p, ray, sc + 1, zstep) : 0.f;
-            delta = (sc + 1 < S) ? (znext - z) * dnorm : 1e10f;
+            if constexpr (MERGED) {
+                z = ms.z_all[ray * S + sc];
+                const float znext = (sc + 1 < S) ? ms.z_all[ray * S + sc + 1] : 0.f;
+                delta = (sc + 1 < S) ? (znext - z) * dnorm : 1e10f;
+            } else {
+                z = ray_sample_depth(p, ray, sc, zstep);
+                const float znext = (sc + 1 < S) ? ray_sample_depth(p, ray, sc + 1, zstep) : 0.f;
+                delta = (sc + 1 < S) ? (znext - z) * dnorm : 1e10f;
+            }
         };
 
         // ---- sweep 1: alpha_i, T_i, h_i, sigma_i + noise_i ----
@@ -391,7 +438,7 @@ __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_par
             float ht = 0.f;
 #pragma unroll 2
             for (int k = 0; k < HID; ++k) ht = fmaf(s_u[64 + k], softplus_fast(hidden_pre<C>(s_tw0, s_tb0, k, f)), ht);
-            const float x = sigma + (p.sigma_noise ? p.sigma_noise[ray * S + (live ? s : S - 1)] : 0.f);
+            const float x = sigma + ((!MERGED && p.sigma_noise) ? p.sigma_noise[ray * S + (live ? s : S - 1)] : 0.f);
             const float dens = p.clamp_mode == 0 ? softplus_fast(x) : fmaxf(x, 0.f);
             const float alpha = live ? 1.0f - __expf(-delta * dens) : 0.f;
             const float fac = live ? (1.0f - alpha + 1e-10f) : 1.0f;
@@ -589,11 +636,19 @@ __device__ __forceinline__ void render_rays_backward_body(const ide3d_render_par
     }
 }
 
-// The kernel of every form: the pointers a form does not use are passed as null.
+// The kernel of every plain form: the pointers a form does not use are passed as null.
 template <int C, int HID, bool PARAMS, bool CAM>
 __global__ void __launch_bounds__(512)
 render_rays_backward_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp, float* slices, float* cam_slices) {
     render_rays_backward_body<C, HID, PARAMS, CAM>(p, gr, sp, slices, cam_slices);
+}
+
+// The kernel of the merged forms (MERGED on, CAM off): the same body with the three arrays that place its samples.  A kernel of its own,
+// so that the plain forms keep their arguments and with them their instruction streams.
+template <int C, int HID, bool PARAMS>
+__global__ void __launch_bounds__(512)
+render_rays_merged_backward_kernel(ide3d_render_params p, ide3d_render_grads gr, int sp, float* slices, MergedSamples ms) {
+    render_rays_backward_body<C, HID, PARAMS, false, true>(p, gr, sp, slices, nullptr, ms);
 }
 
 // Adds the slices in a fixed order: thread (element e, group g) sums slices g, g + 8, ..., then group 0 adds the 8 partial sums.
@@ -655,11 +710,11 @@ struct BwdPlan {
     int64_t nblk;
 };
 
-template <int C, int HID, bool PARAMS>
+template <int C, int HID, bool PARAMS, bool MERGED = false>
 static BwdPlan plan_render_backward(const ide3d_render_params& p) {
     using L = BwdLds<C, HID>;
     BwdPlan pl;
-    pl.sp = (int)cdiv64(p.steps, 64) * 64;
+    pl.sp = (int)cdiv64((MERGED ? 2 : 1) * (int64_t)p.steps, 64) * 64;
     const size_t wave_bytes = (L::FIXED + (PARAMS ? L::PSUMS : 0) + (size_t)L::ARRAYS * pl.sp) * sizeof(float), shared_bytes = L::SHARED * sizeof(float);
     pl.nw = 8;
     while (pl.nw > 1 && shared_bytes + pl.nw * wave_bytes > 160 * 1024) pl.nw /= 2;
@@ -672,9 +727,9 @@ static BwdPlan plan_render_backward(const ide3d_render_params& p) {
     return pl;
 }
 
-template <int C, int HID>
+template <int C, int HID, bool MERGED = false>
 static int64_t param_workspace_bytes(const ide3d_render_params& p) {
-    const BwdPlan pl = plan_render_backward<C, HID, true>(p);
+    const BwdPlan pl = plan_render_backward<C, HID, true, MERGED>(p);
     return pl.nw ? pl.nblk * pl.nw * (int64_t)ParamSlice<C, HID>::stride(p.seg_ch, p.feat_ch) * (int64_t)sizeof(float) : 0;
 }
 
@@ -695,20 +750,20 @@ static const char* stage_name(const char* what, const char* stage) {
 }
 
 // The launch of every form (q is read when PARAMS, c when CAM): the kernel, then one launch per kind of slices that adds them up.
-// `what` is the entry point that was called, for the error texts.
-template <int C, int HID, bool PARAMS, bool CAM>
+// `what` is the entry point that was called, for the error texts.  MERGED: the merged march's kernel, its samples placed by `ms`.
+template <int C, int HID, bool PARAMS, bool CAM, bool MERGED = false>
 static int launch_render_backward(const ide3d_render_params& p, const ide3d_render_grads& g, const ide3d_render_param_grads* q,
-                                  const ide3d_render_camera_grads* c, hipStream_t st, const char* what) {
+                                  const ide3d_render_camera_grads* c, hipStream_t st, const char* what, const MergedSamples& ms = MergedSamples{}) {
     using PS = ParamSlice<C, HID>;
-    const BwdPlan pl = plan_render_backward<C, HID, PARAMS>(p);
+    const BwdPlan pl = plan_render_backward<C, HID, PARAMS, MERGED>(p);
     if (!pl.nw) {
-        set_error("%s: %d steps per ray need %zu bytes of LDS per workgroup (at most 160 KiB)", what, p.steps, pl.lds_bytes);
+        set_error("%s: %d steps per ray need %zu bytes of LDS per workgroup (at most 160 KiB)", what, (MERGED ? 2 : 1) * p.steps, pl.lds_bytes);
         return IDE3D_ENOKERNEL;
     }
     const int64_t nslices = pl.nblk * pl.nw, cam_floats = (int64_t)p.n * 12;
     float *slices = nullptr, *cam_slices = nullptr;
     if constexpr (PARAMS) {
-        const int64_t need = param_workspace_bytes<C, HID>(p);
+        const int64_t need = param_workspace_bytes<C, HID, MERGED>(p);
         IDE3D_CHECK_ARG(q->workspace != nullptr && q->workspace_bytes >= need && (reinterpret_cast<uintptr_t>(q->workspace) & 15) == 0,
                         "%s: workspace of %lld bytes (16-byte aligned) required, got %lld", what, (long long)need, (long long)q->workspace_bytes);
         slices = static_cast<float*>(q->workspace);
@@ -726,9 +781,15 @@ static int launch_render_backward(const ide3d_render_params& p, const ide3d_rend
             return IDE3D_ELAUNCH;
         }
     }
-    auto kern = render_rays_backward_kernel<C, HID, PARAMS, CAM>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
-    hipLaunchKernelGGL(kern, dim3((unsigned)pl.nblk), dim3(64 * pl.nw), pl.lds_bytes, st, p, g, pl.sp, slices, cam_slices);
+    if constexpr (MERGED) {
+        auto kern = render_rays_merged_backward_kernel<C, HID, PARAMS>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+        hipLaunchKernelGGL(kern, dim3((unsigned)pl.nblk), dim3(64 * pl.nw), pl.lds_bytes, st, p, g, pl.sp, slices, ms);
+    } else {
+        auto kern = render_rays_backward_kernel<C, HID, PARAMS, CAM>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+        hipLaunchKernelGGL(kern, dim3((unsigned)pl.nblk), dim3(64 * pl.nw), pl.lds_bytes, st, p, g, pl.sp, slices, cam_slices);
+    }
     IDE3D_CHECK_LAUNCH(what);
     if constexpr (PARAMS) {
         const ParamOut out = {{q->grad_geo_w0, q->grad_tex_w0, q->grad_geo_b0, q->grad_tex_b0, q->grad_geo_w1, q->grad_tex_w1, q->grad_geo_b1, q->grad_tex_b1},
@@ -746,10 +807,12 @@ static int launch_render_backward(const ide3d_render_params& p, const ide3d_rend
     return IDE3D_OK;
 }
 
-// The instantiation for what was asked for.
+// The instantiation for what was asked for.  ms: the merged march (never with c).
 template <int C, int HID>
 static int launch_render_backward_form(const ide3d_render_params& p, const ide3d_render_grads& g, const ide3d_render_param_grads* q,
-                                       const ide3d_render_camera_grads* c, hipStream_t st, const char* what) {
+                                       const ide3d_render_camera_grads* c, hipStream_t st, const char* what, const MergedSamples* ms) {
+    if (ms) return q ? launch_render_backward<C, HID, true, false, true>(p, g, q, nullptr, st, what, *ms)
+                     : launch_render_backward<C, HID, false, false, true>(p, g, q, nullptr, st, what, *ms);
     if (q) return c ? launch_render_backward<C, HID, true, true>(p, g, q, c, st, what) : launch_render_backward<C, HID, true, false>(p, g, q, c, st, what);
     return c ? launch_render_backward<C, HID, false, true>(p, g, q, c, st, what) : launch_render_backward<C, HID, false, false>(p, g, q, c, st, what);
 }
@@ -761,14 +824,20 @@ static bool grads_fit(const ide3d_render_params& p, const ide3d_render_grads& g)
     return (!g.grad_tex_planes || ok(g.grad_tex_stride)) && (!g.grad_geo_planes || ok(g.grad_geo_stride));
 }
 
-// The checks and the (C, hidden) dispatch of all three entry points.  q = NULL: no decoder gradients; c = NULL: no camera gradient.
+// The checks and the (C, hidden) dispatch of all four entry points.  q = NULL: no decoder gradients; c = NULL: no camera gradient;
+// ms = NULL: the plain march, else the merged one (its pointers and total_steps checked by the caller) under the hierarchical pass's step
+// limits (ide3d_render_rays_merged: an inner pdf needs 3 samples, ide3d_merge_depths orders at most 2048 per ray).
 static int render_backward(const ide3d_render_params& p, const ide3d_render_grads& g, const ide3d_render_param_grads* q,
-                           const ide3d_render_camera_grads* c, void* stream, const char* what) {
+                           const ide3d_render_camera_grads* c, void* stream, const char* what, const MergedSamples* ms = nullptr) {
     int rc = check_render_params(p, what, false);
     if (rc) return rc;
     IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world, "%s: null ray pointer", what);
     IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "%s: bad ray shape", what);
     IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "%s: Need to choose clamp mode", what);
+    if (ms && (p.steps < kMergedMinSteps || p.steps > kMergedMaxSteps)) {
+        set_error("%s: the hierarchical pass takes %d .. %d steps, got %d", what, kMergedMinSteps, kMergedMaxSteps, p.steps);
+        return IDE3D_ENOKERNEL;
+    }
     // the tri-plane-only kernel scatters to both planes unconditionally
     IDE3D_CHECK_ARG(q || c || (g.grad_tex_planes && g.grad_geo_planes), "%s: null gradient output", what);
     IDE3D_CHECK_ARG(!c || c->grad_cam2world != nullptr, "%s: null camera-gradient output", what);
@@ -778,8 +847,8 @@ static int render_backward(const ide3d_render_params& p, const ide3d_render_grad
     if (!planes_fast(p)) { set_error("%s: tri-planes must be channels_last, 16-byte aligned", what); return IDE3D_ENOKERNEL; }
     if (!grads_fit(p, g)) { set_error("%s: gradient buffers must be channels_last (channel stride 1)", what); return IDE3D_ENOKERNEL; }
     hipStream_t st = (hipStream_t)stream;
-    if (p.C == 32 && p.hidden == 64) return launch_render_backward_form<32, 64>(p, g, q, c, st, what);
-    if (p.C == 16 && p.hidden == 32) return launch_render_backward_form<16, 32>(p, g, q, c, st, what);
+    if (p.C == 32 && p.hidden == 64) return launch_render_backward_form<32, 64>(p, g, q, c, st, what, ms);
+    if (p.C == 16 && p.hidden == 32) return launch_render_backward_form<16, 32>(p, g, q, c, st, what, ms);
     set_error("%s: no fused kernel for C=%d hidden=%d", what, p.C, p.hidden);
     return IDE3D_ENOKERNEL;
 }
@@ -818,4 +887,25 @@ extern "C" int ide3d_render_rays_backward_camera(const ide3d_render_params* pp, 
     IDE3D_CHECK_ARG(pp != nullptr && gg != nullptr, "render_rays_backward_camera: null params");
     IDE3D_CHECK_ARG(qq != nullptr || cc != nullptr || gg->grad_tex_planes || gg->grad_geo_planes, "render_rays_backward_camera: no gradient requested");
     return ide3d::render_backward(*pp, *gg, qq, cc, stream, "render_rays_backward_camera");
+}
+
+extern "C" int64_t ide3d_render_merged_param_grad_workspace_bytes(const ide3d_render_params* pp) {
+    using namespace ide3d;
+    if (pp == nullptr || pp->n <= 0 || pp->rays_per_img <= 0 || pp->steps < kMergedMinSteps || pp->steps > kMergedMaxSteps || pp->feat_ch < 0 ||
+        pp->seg_ch < 0)
+        return 0;
+    if (pp->C == 32 && pp->hidden == 64) return param_workspace_bytes<32, 64, true>(*pp);
+    if (pp->C == 16 && pp->hidden == 32) return param_workspace_bytes<16, 32, true>(*pp);
+    return 0;
+}
+
+extern "C" int ide3d_render_rays_merged_backward(const ide3d_render_params* pp, const float* z_all, const int32_t* src, const float* z_fine,
+                                                 int32_t total_steps, const ide3d_render_grads* gg, const ide3d_render_param_grads* qq,
+                                                 void* stream) {
+    IDE3D_CHECK_ARG(pp != nullptr && gg != nullptr && z_all != nullptr && src != nullptr && z_fine != nullptr,
+                    "render_rays_merged_backward: null pointer");
+    IDE3D_CHECK_ARG((int64_t)total_steps == 2 * (int64_t)pp->steps, "render_rays_merged_backward: total_steps must be 2 * steps = %d, got %d",
+                    2 * pp->steps, total_steps);
+    const ide3d::MergedSamples ms = {z_all, src, z_fine};
+    return ide3d::render_backward(*pp, *gg, qq, nullptr, stream, "render_rays_merged_backward", &ms);
 }

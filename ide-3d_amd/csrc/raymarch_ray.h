@@ -79,6 +79,10 @@ static inline int check_render_params(const ide3d_render_params& p, const char* 
     return IDE3D_OK;
 }
 
+// Steps per ray of the hierarchical pass: an inner pdf needs 3 samples, and ide3d_merge_depths orders at most 2048 merged samples per ray
+// (kMergeMaxT, raymarch.hip).  The merged march's backward declines what its forward declines.
+constexpr int kMergedMinSteps = 3, kMergedMaxSteps = 1024;
+
 static inline bool planes_fast(const ide3d_render_params& p) {
     auto ok = [&](const float* base, const int64_t* s) {
         return s[1] == 1 && (s[0] % 4 == 0) && (s[2] % 4 == 0) && (s[3] % 4 == 0) &&

@@ -395,6 +395,9 @@ def load():
             'ide3d_render_camera_grad_workspace_bytes': [ctypes.POINTER(_RenderParams)],
             'ide3d_render_rays_backward_camera': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_RenderGrads), ctypes.POINTER(_RenderParamGrads),
                                                   ctypes.POINTER(_RenderCameraGrads), vp],
+            'ide3d_render_merged_param_grad_workspace_bytes': [ctypes.POINTER(_RenderParams)],
+            'ide3d_render_rays_merged_backward': [ctypes.POINTER(_RenderParams), vp, vp, vp, i32, ctypes.POINTER(_RenderGrads),
+                                                  ctypes.POINTER(_RenderParamGrads), vp],
             'ide3d_sample_voxel': [ctypes.POINTER(_RenderParams), vp, i64, vp, vp, ctypes.c_int, vp],
             'ide3d_lattice_points': [ctypes.POINTER(_Lattice), i64, i64, vp, vp],
             'ide3d_density_lattice': [ctypes.POINTER(_RenderParams), ctypes.POINTER(_Lattice), i64, i64, vp, vp],
@@ -515,6 +518,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_linear_weight_grad', 'ide3d_residual_join', 'ide3d_id_head', 'ide3d_id_head_backward',
     'ide3d_mesh_workspace_bytes', 'ide3d_mesh_count', 'ide3d_mesh_emit',
     'ide3d_render_ray_weights', 'ide3d_merge_depths', 'ide3d_render_rays_merged',
+    'ide3d_render_merged_param_grad_workspace_bytes', 'ide3d_render_rays_merged_backward',
     'ide3d_raster_workspace_bytes', 'ide3d_raster_project', 'ide3d_raster_depth', 'ide3d_raster_shade',
 )
 
@@ -1206,14 +1210,22 @@ class VolumeRenderPlugin:
         return feat, depth, wsum
 
     @staticmethod
-    def _render_backward(what, ray_args, upstream, plane_grads, param_grads, camera_grad):
-        """The one backward call behind the three public methods: `what` names the entry point (C symbol `ide3d_<what>`, error texts,
+    def _render_backward(what, ray_args, upstream, plane_grads, param_grads, camera_grad, merged=None):
+        """The one backward call behind the four public methods: `what` names the entry point (C symbol `ide3d_<what>`, error texts,
         `CALLS`), `ray_args` are the forward's twelve arguments, `upstream` is (grad_feat, grad_depth, grad_wsum) -> (dtex, dgeo, grads,
-        dcam) with None for what was not asked; None when the library has no kernel for the configuration (IDE3D_ENOKERNEL)."""
+        dcam) with None for what was not asked; None when the library has no kernel for the configuration (IDE3D_ENOKERNEL).  `merged`:
+        (z_all, src, z_fine) of the merged march (`render_rays_merged_backward` only)."""
         tex_planes, geo_planes, mlp = ray_args[5:8]
         dev = tex_planes.device
         p, keep = VolumeRenderPlugin._ray_params(*ray_args)
         n, R, nch = p.n, p.rays_per_img, p.feat_ch + p.seg_ch
+        if merged is not None:
+            S = p.steps
+            shapes = (('z_all', (n * R, 2 * S), torch.float32), ('src', (n * R, 2 * S), torch.int32), ('z_fine', (n * R, S), torch.float32))
+            for t_, (name, shape, dt) in zip(merged, shapes):
+                _require(t_.dtype == dt and t_.device == dev and tuple(t_.shape) == shape,
+                         f'{what}: {name} must be {list(shape)} {dt} next to the tri-planes, got {list(t_.shape)} {t_.dtype}')
+            merged = tuple(t_.contiguous() for t_ in merged)
         g = _RenderGrads()
         for name, t, shape in zip(('grad_feat', 'grad_depth', 'grad_wsum'), upstream, ((n, nch, R), (n, R), (n, R))):
             if t is not None:
@@ -1243,7 +1255,8 @@ class VolumeRenderPlugin:
             c.grad_cam2world, c.workspace, c.workspace_bytes = dcam.data_ptr(), workspace('render_camera_grad', cbytes), cbytes
             c_ref = ctypes.byref(c)
         if param_grads:
-            nbytes = lib.ide3d_render_param_grad_workspace_bytes(ctypes.byref(p))
+            query = lib.ide3d_render_param_grad_workspace_bytes if merged is None else lib.ide3d_render_merged_param_grad_workspace_bytes
+            nbytes = query(ctypes.byref(p))
             if nbytes <= 0:        # as above
                 return None
             q = _RenderParamGrads()
@@ -1252,9 +1265,13 @@ class VolumeRenderPlugin:
                 setattr(q, 'grad_' + k, t.data_ptr())
             q.workspace, q.workspace_bytes = workspace('render_param_grad', nbytes), nbytes
             q_ref = ctypes.byref(q)
-        extra = {'render_rays_backward': (), 'render_rays_backward_params': (q_ref,), 'render_rays_backward_camera': (q_ref, c_ref)}[what]
         with _dev_guard(dev):
-            rc = getattr(lib, 'ide3d_' + what)(ctypes.byref(p), ctypes.byref(g), *extra, _stream(tex_planes))
+            if merged is not None:
+                rc = lib.ide3d_render_rays_merged_backward(ctypes.byref(p), *(_ptr(t_) for t_ in merged), 2 * p.steps, ctypes.byref(g), q_ref,
+                                                           _stream(tex_planes))
+            else:
+                extra = {'render_rays_backward': (), 'render_rays_backward_params': (q_ref,), 'render_rays_backward_camera': (q_ref, c_ref)}[what]
+                rc = getattr(lib, 'ide3d_' + what)(ctypes.byref(p), ctypes.byref(g), *extra, _stream(tex_planes))
         if rc == -2:        # IDE3D_ENOKERNEL
             return None
         _check(rc, what)
@@ -1295,6 +1312,22 @@ class VolumeRenderPlugin:
         return VolumeRenderPlugin._render_backward('render_rays_backward_camera', (rays_d_cam, z_lin, cam2world, jitter, sigma_noise,
                                                    tex_planes, geo_planes, mlp, clamp_mode, last_back, white_back, max_depth),
                                                    (grad_feat, grad_depth, grad_wsum), plane_grads, param_grads, True)
+
+    @staticmethod
+    def render_rays_merged_backward(rays_d_cam, z_lin, cam2world, jitter, tex_planes, geo_planes, mlp, clamp_mode, white_back, max_depth,
+                                    z_all, src, z_fine, grad_feat, grad_depth, grad_wsum, plane_grads=True, param_grads=False,
+                                    last_back=False):
+        """Gradients of `render_rays_merged` (ide3d_render_rays_merged_backward): its arguments, then dL/dfeat, dL/ddepth, dL/dwsum (each may
+        be None = zero) -> (dL/dtex_planes | None, dL/dgeo_planes | None, {key of mlp: gradient} | None); None when the library has no
+        kernel for the configuration (IDE3D_ENOKERNEL: what `render_rays_merged` and `render_rays_backward` decline).  z_all, src and
+        z_fine are constants of the backward, like jitter and the camera.  `plane_grads=False` (with `param_grads=True`): the tap scatter is
+        skipped; `param_grads=True`: the eight decoder gradients, bit-reproducible, their partial sums in a workspace of this plugin's
+        cache."""
+        _require(plane_grads or param_grads, 'render_rays_merged_backward: no gradient requested')
+        res = VolumeRenderPlugin._render_backward('render_rays_merged_backward', (rays_d_cam, z_lin, cam2world, jitter, None, tex_planes,
+                                                  geo_planes, mlp, clamp_mode, last_back, white_back, max_depth),
+                                                  (grad_feat, grad_depth, grad_wsum), plane_grads, param_grads, False, (z_all, src, z_fine))
+        return None if res is None else res[:3]
 
     @staticmethod
     def sample_voxel(tex_planes, geo_planes, mlp, pts, sigma_only=False):

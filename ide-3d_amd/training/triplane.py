@@ -60,6 +60,12 @@ fused_render_camera_grad = False
 # Opt-in: set by a driver that renders with `render_params=dict(hierarchical=True)`; False = the step-wise definition.
 fused_hierarchical = False
 
+# Take those four launches with a backward as well (`hierarchical=True` calls without `sigma_noise_fine` whose tri-planes need a gradient,
+# or whose decoder does under `fused_render_param_grad`): the merged march is then differentiated by ide3d_render_rays_merged_backward
+# (DESIGN.md section 5.29), with the fine depths as constants like the step-wise definition below.  A camera, jitter, density noise or pdf
+# draw that requires grad keeps the step-wise path.  Opt-in and independent of `fused_hierarchical`; False = the step-wise definition.
+fused_hierarchical_grad = False
+
 
 @dataclasses.dataclass
 class GeneratorSpec:
@@ -235,6 +241,20 @@ class TriplaneRenderer(torch.nn.Module):
             return False
         return not any(t is not None and t.requires_grad for t in (jitter, sigma_noise))
 
+    def _fused_hier_grad_ok(self, img_v, seg_v, cam2world, jitter, sigma_noise, importance_u):
+        """The fused importance pass with its backward kernel (`fused_hierarchical_grad`): `_fused_grad_ok`'s rules for the planes and,
+        under `fused_render_param_grad`, the decoder, except that the camera may never need a gradient (the merged march has none for it,
+        whatever `fused_render_camera_grad` says), nor may the draws of the pdf."""
+        params = list(self.decoder.parameters())
+        param_grad = any(p.requires_grad for p in params)
+        if not torch.is_grad_enabled() or not (img_v.requires_grad or seg_v.requires_grad or (fused_render_param_grad and param_grad)):
+            return False
+        if not _all_fp32_cuda(img_v, seg_v, cam2world, *(params if fused_render_param_grad else ())):
+            return False
+        if param_grad and not fused_render_param_grad:
+            return False
+        return not any(t is not None and t.requires_grad for t in (cam2world, jitter, sigma_noise, importance_u))
+
     # -- full rendering -----------------------------------------------------------------------------------
     def forward(self, img_v, seg_v, cam2world, fov=None, num_steps=None, ray_start=None, ray_end=None, img_size=None,
                 nerf_noise=0.0, jitter=None, sigma_noise=None, white_back=False, clamp_mode=None,
@@ -287,6 +307,14 @@ class TriplaneRenderer(torch.nn.Module):
                                                   white_back=white_back)
             if res is not None:
                 return res
+        elif hierarchical and fused_hierarchical_grad and sigma_noise_fine is None \
+                and self._fused_hier_grad_ok(img_v, seg_v, cam2world, jitter, sigma_noise, importance_u):
+            res = vr.render_triplane_hierarchical(_as_channels_last(img_v), _as_channels_last(seg_v), self.decoder.kernel_weights(),
+                                                  cam2world.float(), fov, (size, size), steps, t0, t1, jitter=jitter,
+                                                  sigma_noise=sigma_noise, importance_u=importance_u, clamp_mode=clamp_mode,
+                                                  white_back=white_back)
+            if res is not None:
+                return res
 
         # step-wise definition (CPU / autograd / configurations outside the fused kernel)
         points, z_vals, rays_d_cam = vr.get_initial_rays_trig(n, steps, device, fov, (size, size), t0, t1)
@@ -319,6 +347,11 @@ class TriplaneRenderer(torch.nn.Module):
 
 def _as_channels_last(t):
     return t if t.stride(1) == 1 else t.contiguous(memory_format=torch.channels_last)
+
+
+def _all_fp32_cuda(*tensors):
+    """What a launch can take by raw pointer."""
+    return all(t.device.type == 'cuda' and t.dtype == torch.float32 for t in tensors)
 
 
 @persistence.persistent_class

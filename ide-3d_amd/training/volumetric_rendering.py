@@ -387,6 +387,42 @@ class _RenderRaysFused(torch.autograd.Function):
             + (None,) * 5 + tuple(dmlp[k] if need[10 + i] else None for i, k in enumerate(_MLP_KEYS))
 
 
+class _RenderRaysMerged(torch.autograd.Function):
+    """`ide3d_render_rays_merged`, the last of the hierarchical pass's four launches, with a gradient for the two tri-planes and the eight
+    decoder tensors (`ide3d_render_rays_merged_backward`, csrc/raymarch_bwd.hip).  The three launches before it ran without autograd:
+    z_all, src and z_fine arrive as constants, as the step-wise definition takes them (fine depths and points under no_grad).  Saved are
+    the planes, the decoder tensors and those three arrays ([rays, 2S] / [rays, S]), nothing per sample.  The backward is one call,
+    without the tap scatter when no plane needs a gradient.  No gradient for the camera, the jitter or the fine depths."""
+
+    @staticmethod
+    def forward(ctx, tex_planes, geo_planes, rays_d_cam, z_lin, cam2world, jitter, z_all, src, z_fine, clamp_code, white_back, max_depth,
+                *mlp_tensors):
+        mlp = dict(zip(_MLP_KEYS, mlp_tensors))
+        res = _plugin.render_rays_merged(rays_d_cam, z_lin, cam2world, jitter, tex_planes, geo_planes, mlp, clamp_code, white_back, max_depth,
+                                         z_all, src, z_fine)
+        if res is None:
+            raise _NoFusedKernel()
+        ctx.save_for_backward(tex_planes, geo_planes, z_all, src, z_fine, *mlp_tensors)
+        ctx.args = (rays_d_cam, z_lin, cam2world, jitter, clamp_code, white_back, max_depth)
+        return res
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_feat, grad_depth, grad_wsum):
+        tex_planes, geo_planes, z_all, src, z_fine, *mlp_tensors = ctx.saved_tensors
+        mlp = dict(zip(_MLP_KEYS, mlp_tensors))
+        a = ctx.args
+        need = ctx.needs_input_grad
+        res = _plugin.render_rays_merged_backward(*a[:4], tex_planes, geo_planes, mlp, *a[4:], z_all, src, z_fine, grad_feat, grad_depth,
+                                                  grad_wsum, plane_grads=need[0] or need[1], param_grads=any(need[12:]))
+        if res is None:
+            raise RuntimeError('render_rays_merged_backward: no backward kernel for this configuration: '
+                               + hip_plugin.load().ide3d_last_error().decode('utf-8', 'replace'))
+        dtex, dgeo, dmlp = res
+        return (dtex if need[0] else None, dgeo if need[1] else None) + (None,) * 10 \
+            + tuple(dmlp[k] if need[12 + i] else None for i, k in enumerate(_MLP_KEYS))
+
+
 def render_triplane_fused(tex_planes, geo_planes, mlp, cam2world, fov, resolution, num_steps, ray_start, ray_end,
                           jitter=None, sigma_noise=None, clamp_mode='softplus', white_back=False, max_depth=None):
     """One HIP launch for: get_initial_rays_trig -> perturb_points -> cam2world transform -> two
@@ -449,8 +485,14 @@ def render_triplane_hierarchical(tex_planes, geo_planes, mlp, cam2world, fov, re
       `ide3d_render_rays_merged`  the fused march over the 2 * num_steps samples, no density noise
 
     Arguments as `render_triplane_fused`; importance_u: the draws of `sample_pdf`, [num_steps] (one row for every ray) or
-    [N * R, num_steps]; None -> torch.rand.  Inference only: no gradients.  Returns the same triple, or None when the library
-    has no kernel for the configuration (what `render_triplane_fused` declines, and num_steps < 3 or > 1024).
+    [N * R, num_steps]; None -> torch.rand.  Returns the same triple, or None when the library has no kernel for the
+    configuration (what `render_triplane_fused` declines, and num_steps < 3 or > 1024).
+
+    Gradients: when grad mode is on and a tri-plane or a tensor of `mlp` requires grad, the outputs are
+    differentiable with respect to tex_planes, geo_planes and the eight tensors of `mlp` through the merged march (one backward call,
+    `ide3d_render_rays_merged_backward`; first order only).  As in the step-wise definition the fine depths are constants: nothing
+    flows into the first pass, the pdf draw or the merge, and no gradient is returned for `cam2world`, `jitter`, `sigma_noise` or
+    `importance_u`, whether or not they require grad.  The forward values are those of the no-grad call, bit for bit.
     """
     assert clamp_mode in ('softplus', 'relu')
     _init()
@@ -471,8 +513,15 @@ def render_triplane_hierarchical(tex_planes, geo_planes, mlp, cam2world, fov, re
     u = torch.rand(n * W * H, num_steps, device=device) if importance_u is None else importance_u
     z_fine = _plugin.sample_pdf(bins, pdf_w, u.float())
     z_all, src = _plugin.merge_depths(z_fine, z_vals)
-    res = _plugin.render_rays_merged(rays_d_cam, z_lin, cam2world, jitter, tex_planes, geo_planes, mlp, clamp_code, white_back,
-                                     max_depth, z_all, src, z_fine)
+    if torch.is_grad_enabled() and (tex_planes.requires_grad or geo_planes.requires_grad or any(mlp[k].requires_grad for k in _MLP_KEYS)):
+        try:
+            res = _RenderRaysMerged.apply(tex_planes, geo_planes, rays_d_cam, z_lin, cam2world, jitter, z_all, src, z_fine, clamp_code,
+                                          white_back, max_depth, *(mlp[k] for k in _MLP_KEYS))
+        except _NoFusedKernel:
+            return None
+    else:
+        res = _plugin.render_rays_merged(rays_d_cam, z_lin, cam2world, jitter, tex_planes, geo_planes, mlp, clamp_code, white_back,
+                                         max_depth, z_all, src, z_fine)
     if res is None:
         return None
     feat, depth, wsum = res

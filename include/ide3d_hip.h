@@ -453,6 +453,25 @@ int ide3d_render_rays_merged(const ide3d_render_params* p, const float* z_all, c
                              int32_t total_steps, void* stream);
 
 /*
+ * Backward of ide3d_render_rays_merged with respect to the two tri-planes and, with q, the decoder's eight tensors (DESIGN.md section
+ * 5.29).  The definition is the step-wise importance pass (TriplaneRenderer.forward, training/triplane.py:300-313), which draws the fine
+ * depths and forms the fine points under torch.no_grad(): differentiated are the gathers of the 2 * steps merged samples, both decoders
+ * and the compositing (white_back / max_depth included); constants are z_all, src, z_fine, the jitter and the camera, so no gradient flows
+ * into the first pass, the pdf draw or the merge.  It is ide3d_render_rays_backward(_params) over total_steps samples placed and spaced as
+ * ide3d_render_rays_merged places and spaces them (src clamped into [0, total_steps) before use; p->sigma_noise ignored), nothing per
+ * sample saved.  p, z_all, src, z_fine, total_steps: what the forward received (out_* ignored).  g as for ide3d_render_rays_backward: plane
+ * gradients are ADDED to caller-zeroed channels_last buffers (float atomics: not bit-reproducible); with q either plane pointer may be NULL
+ * (scatter skipped).  q: NULL (planes only, both plane pointers required) or as for ide3d_render_rays_backward_params: the eight
+ * gradients are WRITTEN, bit-reproducible, workspace of ide3d_render_merged_param_grad_workspace_bytes(p) bytes (sized by 2 * p->steps;
+ * 0 = no kernel), 16-byte aligned.  IDE3D_EINVAL: null pointers, total_steps != 2 * steps.  IDE3D_ENOKERNEL with an error text: steps < 3
+ * or steps > 1024, last_back, planes or gradient buffers not channels_last, (C, hidden) other than (32, 64) / (16, 32), total_steps whose
+ * per-ray state does not fit in LDS.  There is no camera gradient through the merged march.
+ */
+int64_t ide3d_render_merged_param_grad_workspace_bytes(const ide3d_render_params* p);
+int ide3d_render_rays_merged_backward(const ide3d_render_params* p, const float* z_all, const int32_t* src, const float* z_fine,
+                                      int32_t total_steps, const ide3d_render_grads* g, const ide3d_render_param_grads* q, void* stream);
+
+/*
  * `renderer.sample_voxel(img_v, seg_v, pts)` (call site extract_shapes.py:146): the same two
  * gathers + MLPs for arbitrary points, no compositing.  out: [n*m, feat_ch + seg_ch + 1]
  * (sigma last).  If sigma_only != 0 only out_sigma [n*m] is written (the 256^3 density-cube
