@@ -142,6 +142,27 @@ inline int stream_grid(int64_t work_items, int per_block) {
     return (int)g;
 }
 
+// ---- plane gate (include/ide3d_hip.h `ide3d_plane_gate`) ------------------------------------------------------
+// Is any cell of planes [pl0, pl0 + npl) of image n set under the texel rectangle [y0, y0 + th) x [x0, x0 + tw)?  Wave-uniform: every
+// wave of a workgroup asks for itself (the same few bytes, an L2 hit after the first) and gets the same answer, so the workgroup can leave
+// before its first barrier without LDS traffic.  The rectangle is clipped to the map.
+__device__ __forceinline__ bool plane_gate_live(const ide3d_plane_gate& g, int n, int pl0, int npl, int y0, int x0, int th, int tw) {
+    const int cy0 = max(y0 >> 2, 0), cx0 = max(x0 >> 2, 0);
+    const int cy1 = min((y0 + th - 1) >> 2, g.cells_h - 1), cx1 = min((x0 + tw - 1) >> 2, g.cells_w - 1);
+    const int nx = cx1 - cx0 + 1, ny = cy1 - cy0 + 1;
+    bool any = false;
+    if (nx > 0 && ny > 0) {
+        const int per = nx * ny, count = per * npl;
+        for (int i = (int)(threadIdx.x & 63u); i < count; i += 64) {
+            const int pl = pl0 + i / per, r = i % per;
+            any |= g.cells[(((int64_t)n * 3 + pl) * g.cells_h + cy0 + r / nx) * g.cells_w + cx0 + r % nx] != 0;
+        }
+    }
+    return __builtin_amdgcn_ballot_w64(any) != 0ull;
+}
+// Host side: the gate a launch really uses (none when the caller passed none, or under IDE3D_NO_PLANE_GATE: csrc/knobs.h).
+ide3d_plane_gate resolve_plane_gate(const ide3d_plane_gate* gate);
+
 // XCD-aware remap of a linear workgroup id: hardware places block b on XCD b % 8, so consecutive
 // *logical* tiles (which share halo / plane lines) are sent to the same XCD's L2.  Bijective for any n.
 __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {

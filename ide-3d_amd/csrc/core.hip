@@ -1,5 +1,6 @@
 // core.hip — error reporting and library identity for libide3d_hip.so.
 #include "common.h"
+#include "knobs.h"
 #include <string.h>
 #include <stdio.h>
 #include <map>
@@ -54,6 +55,11 @@ bool exclusive_checked(const void* kernel, int threads, size_t dyn_lds, const ch
     }
     if (occ > 1) refuse_launch(name);
     return occ <= 1;
+}
+
+ide3d_plane_gate resolve_plane_gate(const ide3d_plane_gate* gate) {
+    if (!gate || !gate->cells || knob_live("IDE3D_NO_PLANE_GATE")) return ide3d_plane_gate{};
+    return *gate;
 }
 
 }  // namespace ide3d

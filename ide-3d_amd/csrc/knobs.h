@@ -6,9 +6,10 @@
 //   read ONCE per process (`knobs()`, first use):
 //     IDE3D_CONV_ARITH = fp32 | bf16x6 | bf16x3 | f16x3        process default of ide3d_set_conv_arithmetic (include/ide3d_hip.h)
 //     IDE3D_MAPPING_PER_LAYER                                  mapping network as one launch per layer (the form of devices where the one-launch kernel is not co-resident)
-//   read PER CALL (`knob_live`): the six fallbacks that tests/ flip inside one process to compare a lean kernel with the form it replaced
+//   read PER CALL (`knob_live`): the seven fallbacks that tests/ flip inside one process to compare a lean kernel with the form it replaced
 //     IDE3D_FIR_NO_LEAN  IDE3D_FIR_NO_CELL  IDE3D_BIAS_ACT_NO_PLANES  IDE3D_MODCONV_NO_STRIP  IDE3D_MODCONV_PAIR=0|2
 //     IDE3D_MODCONV_NO_HEAD_FUSION (ide3d_modconv2d_heads returns IDE3D_ENOKERNEL: the 3x3 layer and its dual heads as two launches)
+//     IDE3D_NO_PLANE_GATE (the gated entry points ignore their map: every workgroup of the last backbone block runs, core.hip resolve_plane_gate)
 #pragma once
 #include <stdlib.h>
 #include <string.h>

@@ -738,6 +738,7 @@ struct HeadEpi {
     float clamp;             // < 0: none
     int store_x;             // 0: the layer's own output is not written
     int bias_first;          // 1: accumulators start from the bias (head_resident_kernel), 0: bias added to the sum (head_split_kernel)
+    ide3d_plane_gate gate;   // cells != nullptr: a workgroup with no set cell of any plane under its tile writes nothing (ide3d_modconv2d_heads_gated)
 };
 template <int PH, int PW, int NWV, int MTW, int NTW, int BM, int MT, int PARTS, int SCRATCH>
 __device__ __forceinline__ void split_heads_finish(const ide3d_modconv_params& p, const HeadEpi& he, f32x16 (&acc)[1][MTW][NTW], float* smem,
@@ -1694,7 +1695,19 @@ modconv_split_heads_kernel(ide3d_modconv_params p, const u32x4* __restrict__ wp,
     using K = SpCfg<MODE_CONV3, BIG, PH, 3, 2, 8>;
     if constexpr (kSpExclusive) asm volatile("" ::: "v255");
     __shared__ __attribute__((aligned(16))) unsigned char sp_smem[K::LDS_BYTES];
-    const BlockId b = decode_block(g);
+    BlockId b;
+    if (he.gate.tile_list) {
+        // plane gate with the live tiles listed (ide3d_plane_tile_list): workgroup i takes the i-th of them, in the order and XCD grouping the
+        // dense launch gives its tiles, and the workgroups past the count leave.  Wave-uniform, before any barrier or LDS access.
+        const int live = __builtin_amdgcn_readfirstlane(he.gate.tile_list[0]);
+        if ((int)blockIdx.x >= live) return;
+        const int id = __builtin_amdgcn_readfirstlane(he.gate.tile_list[1 + xcd_remap(blockIdx.x, live)]);
+        b.mb = 0; b.split = 0; b.tile = id % g.tile_base[4]; b.grp = id / g.tile_base[4];      // (one M block, no split-K, one image per tile: the fused form's plan)
+    } else {
+        b = decode_block(g);
+        // plane gate without a list: every wave decides for itself before the first barrier, LDS access or global load of the tile
+        if (he.gate.cells && !plane_gate_live(he.gate, b.grp, 0, 3, (b.tile / g.tiles_x[0]) * PH, (b.tile % g.tiles_x[0]) * K::PW, PH, K::PW)) return;
+    }
     modconv_split_tile<MODE_CONV3, BIG, PH, 3, 2, 8, 0, 1, -1, HEAD_MT>(p, wp, nullptr, g, sp_smem, b.mb, b.tile, b.grp, b.split, g.tiles_x[0], nullptr, nullptr, &he);
 }
 
@@ -2322,6 +2335,10 @@ extern "C" int ide3d_modconv2d(const ide3d_modconv_params* pp, void* stream) {
 // The layer + heads in one launch where the layer's plan keeps every output channel of a tile in one workgroup (see HeadEpi).  The routing
 // of both halves is the one ide3d_modconv2d would take, so that the fused launch reproduces exactly those two launches.
 extern "C" int ide3d_modconv2d_heads(const ide3d_modconv_params* pp, const ide3d_modconv_head_epilogue* hp, void* stream) {
+    return ide3d_modconv2d_heads_gated(pp, hp, nullptr, stream);
+}
+
+extern "C" int ide3d_modconv2d_heads_gated(const ide3d_modconv_params* pp, const ide3d_modconv_head_epilogue* hp, const ide3d_plane_gate* gate, void* stream) {
     using namespace ide3d;
     IDE3D_CHECK_ARG(pp != nullptr && hp != nullptr, "modconv2d_heads: null params");
     const ide3d_modconv_params& p = *pp;
@@ -2364,6 +2381,10 @@ extern "C" int ide3d_modconv2d_heads(const ide3d_modconv_params* pp, const ide3d
     HeadEpi e;
     e.w = hw_packed; e.bias = h.bias; e.y = h.y; e.rows = h.rows; e.clamp = h.clamp; e.store_x = !h.no_activation_output;
     e.bias_first = head_resident_applies(q) ? 1 : 0;
+    e.gate = resolve_plane_gate(gate);
+    if (e.gate.cells)
+        IDE3D_CHECK_ARG(4 * (int64_t)e.gate.cells_h >= p.h && 4 * (int64_t)e.gate.cells_w >= p.w_, "modconv2d_heads: the plane gate's cell map does not cover the output");
+    if (!e.gate.cells || e.gate.tile_h != ph || e.gate.tile_w != 16) e.gate.tile_list = nullptr;      // (a list of other tiles than this launch's)
     const ConvGeom& g = pl.g;
     const unsigned nblocks = (unsigned)((int64_t)g.mblocks * g.tile_base[4] * g.img_groups * g.split_k);
     const u32x4* wu = reinterpret_cast<const u32x4*>(p.workspace);

@@ -28,6 +28,7 @@ struct SkipArgs {
     int64_t lo_s[4], add_s[4];           // element strides [n, c, y, x]
     int n, c, h, w;                      // low-resolution size; output 2h x 2w
     int tiles_x, tiles_y, cgroups;
+    ide3d_plane_gate gate;               // cells == nullptr: every workgroup runs
 };
 
 __global__ void __launch_bounds__(256)
@@ -42,6 +43,9 @@ skip_upsample_add_cl_kernel(const SkipArgs p) {
     const int n = b;
     const int c0 = cg * SK_CH, Y0 = ty * SK_ROWS, X0 = tx * SK_COLS;
     const int H = 2 * p.h, W = 2 * p.w;
+    // plane gate: a 32-channel group is one plane of a tri-plane tensor (96 channels: planes 0, 1, 2); nothing this tile would write is
+    // read when no cell of that plane lies under it
+    if (p.gate.cells && !plane_gate_live(p.gate, n, cg % 3, 1, Y0, X0, SK_ROWS, SK_COLS)) return;
     // ---- low-resolution patch (zero outside the image) and this thread's 32 `add` values: every global load of the tile is
     // issued before the first one is used (one HBM round trip per workgroup instead of one per channel) ----
     const int m0 = Y0 / 2 - 1, q0 = X0 / 2 - 1;
@@ -157,6 +161,11 @@ bilinear_up2_split_kernel(const BilinArgs p) {
 
 extern "C" int ide3d_skip_upsample_add_cl(const float* lo, const int64_t lo_stride[4], const float* add, const int64_t add_stride[4],
                                           int32_t n, int32_t c, int32_t h, int32_t w, float* out, void* stream) {
+    return ide3d_skip_upsample_add_cl_gated(lo, lo_stride, add, add_stride, n, c, h, w, out, nullptr, stream);
+}
+
+extern "C" int ide3d_skip_upsample_add_cl_gated(const float* lo, const int64_t lo_stride[4], const float* add, const int64_t add_stride[4],
+                                                int32_t n, int32_t c, int32_t h, int32_t w, float* out, const ide3d_plane_gate* gate, void* stream) {
     using namespace ide3d;
     IDE3D_CHECK_ARG(lo && add && out && lo_stride && add_stride, "skip_upsample_add_cl: null pointer");
     IDE3D_CHECK_ARG(n > 0 && c > 0 && h > 0 && w > 0, "skip_upsample_add_cl: bad shape");
@@ -165,6 +174,10 @@ extern "C" int ide3d_skip_upsample_add_cl(const float* lo, const int64_t lo_stri
     a.lo = lo; a.add = add; a.out = out;
     for (int i = 0; i < 4; ++i) { a.lo_s[i] = lo_stride[i]; a.add_s[i] = add_stride[i]; }
     a.n = n; a.c = c; a.h = h; a.w = w;
+    a.gate = resolve_plane_gate(gate);
+    if (a.gate.cells)
+        IDE3D_CHECK_ARG(c % (3 * SK_CH) == 0 && 4 * (int64_t)a.gate.cells_h >= 2 * (int64_t)h && 4 * (int64_t)a.gate.cells_w >= 2 * (int64_t)w,
+                        "skip_upsample_add_cl: a plane gate needs 96-channel tri-planes and a cell map that covers the output");
     a.tiles_x = cdiv(2 * w, SK_COLS); a.tiles_y = cdiv(2 * h, SK_ROWS); a.cgroups = cdiv(c, SK_CH);
     const int64_t blocks = (int64_t)n * a.tiles_x * a.tiles_y * a.cgroups;
     IDE3D_CHECK_ARG(blocks < 0x7fffffffLL, "skip_upsample_add_cl: too many tiles");

@@ -410,6 +410,10 @@ def load():
             'ide3d_raster_shade': [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, i32, f32, f32, ctypes.POINTER(ctypes.c_float * 3), f32, vp, i64, vp, vp, vp, vp, vp],
             'ide3d_modconv2d': [ctypes.POINTER(_ModconvParams), vp],
             'ide3d_modconv2d_heads': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), vp],
+            'ide3d_modconv2d_heads_gated': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), ctypes.POINTER(_PlaneGate), vp],
+            'ide3d_plane_cells': [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
+            'ide3d_plane_tile_list': [ctypes.POINTER(_PlaneGate), i32, i32, i32, i32, i32, vp, vp],
+            'ide3d_skip_upsample_add_cl_gated': [vp, ctypes.POINTER(i64 * 4), vp, ctypes.POINTER(i64 * 4), i32, i32, i32, i32, vp, ctypes.POINTER(_PlaneGate), vp],
             'ide3d_modconv_plan': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvPlanInfo)],
             'ide3d_modconv_workspace_bytes': [i32, i32, i32, i32, i32, i32, i32, i32],
             'ide3d_act_bwd_workspace_bytes': [i32, i32, i32, i32],
@@ -520,6 +524,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_render_ray_weights', 'ide3d_merge_depths', 'ide3d_render_rays_merged',
     'ide3d_render_merged_param_grad_workspace_bytes', 'ide3d_render_rays_merged_backward',
     'ide3d_raster_workspace_bytes', 'ide3d_raster_project', 'ide3d_raster_depth', 'ide3d_raster_shade',
+    'ide3d_plane_cells', 'ide3d_plane_tile_list', 'ide3d_modconv2d_heads_gated', 'ide3d_skip_upsample_add_cl_gated',
 )
 
 
@@ -1472,11 +1477,14 @@ class ModconvPlugin:
 
     @staticmethod
     def modconv2d_heads(x, w, styles, dcoefs, noise, noise_strength, bias, act, alpha, gain, clamp, head_w, head_bias, head_clamp,
-                        want_x=True, arith=0):
+                        want_x=True, arith=0, gate=None, heads_out=None):
         """A stride-1 3x3 `modconv2d` and the dual heads that read its output (`modconv2d(y, head_w, None, None, None, 0.0, head_bias, 1,
         0.0, 1.0, head_clamp)`, head_w [n, rows, cin, 1, 1] per-image) in one launch (ide3d_modconv2d_heads) -> (y or None, heads
         [n, rows, h, w]), bit-equal to the two calls; None when the fused form does not apply (the caller then makes the two calls).
-        want_x=False: y is not written."""
+        want_x=False: y is not written.  `gate` (plane_cells' map [n, 3, ceil(h / 4), ceil(w / 4)]): a workgroup with no set cell under its
+        tile writes nothing, so the outputs hold defined values only under set cells (ide3d_modconv2d_heads_gated); or (map, plane_tile_list(map, h, w,
+        th, tw), (th, tw)) with the launch's tile size (16 x 16 for 128 output channels, 32 x 16 for 64): the live tiles packed to the front of the grid.  `heads_out`: the contiguous
+        [n, rows, h, w] tensor the heads are written into instead of a fresh one."""
         for t in (x, w, head_w):
             _require(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), 'modconv2d_heads: contiguous float32 CUDA tensors required')
         n, cin, h, wd = x.shape
@@ -1496,7 +1504,9 @@ class ModconvPlugin:
         if knob_off or shape_key in ModconvPlugin._heads_declined:
             return None
         y = torch.empty([n, cout, h, wd], dtype=torch.float32, device=x.device) if want_x else None
-        heads = torch.empty([n, rows, h, wd], dtype=torch.float32, device=x.device)
+        heads = torch.empty([n, rows, h, wd], dtype=torch.float32, device=x.device) if heads_out is None else heads_out
+        _require(heads.dtype == torch.float32 and heads.device == x.device and tuple(heads.shape) == (n, rows, h, wd) and heads.is_contiguous(),
+                 'modconv2d_heads: heads_out must be a contiguous float32 [n, rows, h, w] tensor on the device of x')
         p, ent, keep = ModconvPlugin._params(lib, x, w, y, styles, dcoefs, noise, noise_strength, bias, act, alpha, gain, clamp, 0, arith, None, None)
         hent = ModconvPlugin._workspace(lib, heads, head_w, n, cout, rows, h, wd, 1, 0, True, arith)
         e = _ModconvHeadEpilogue()
@@ -1507,7 +1517,10 @@ class ModconvPlugin:
             e.bias = head_bias.data_ptr()
         e.workspace, e.workspace_bytes = hent[0].data_ptr(), hent[0].numel() * 4
         with _dev_guard(x.device):
-            rc = lib.ide3d_modconv2d_heads(ctypes.byref(p), ctypes.byref(e), _stream(x))
+            if gate is not None:
+                rc = lib.ide3d_modconv2d_heads_gated(ctypes.byref(p), ctypes.byref(e), ctypes.byref(_plane_gate(gate, n, h, wd)), _stream(x))
+            else:
+                rc = lib.ide3d_modconv2d_heads(ctypes.byref(p), ctypes.byref(e), _stream(x))
         if rc == -2:        # IDE3D_ENOKERNEL
             ModconvPlugin._heads_declined.add(shape_key)
             return None
@@ -2920,19 +2933,79 @@ class MappingPlugin:
         return out
 
 
+class _PlaneGate(ctypes.Structure):
+    """ide3d_plane_gate"""
+    _fields_ = [('cells', ctypes.c_void_p), ('cells_h', ctypes.c_int32), ('cells_w', ctypes.c_int32),
+                ('tile_list', ctypes.c_void_p), ('tile_h', ctypes.c_int32), ('tile_w', ctypes.c_int32)]
+
+
+def _plane_gate(gate, n, h, w):
+    """The C struct of a needed-cell map [n, 3, ceil(h / 4), ceil(w / 4)] (uint8, contiguous) for an h x w output.  `gate`: the map, or
+    (map, plane_tile_list's output, (tile_h, tile_w))."""
+    cells, tiles, tile_hw = gate if isinstance(gate, tuple) else (gate, None, None)
+    _require(cells.is_cuda and cells.dtype == torch.uint8 and cells.is_contiguous() and tuple(cells.shape) == (n, 3, (h + 3) // 4, (w + 3) // 4),
+             f'plane gate: cells must be a contiguous uint8 CUDA tensor [{n}, 3, {(h + 3) // 4}, {(w + 3) // 4}], got {list(cells.shape)} {cells.dtype}')
+    g = _PlaneGate()
+    g.cells, g.cells_h, g.cells_w = cells.data_ptr(), cells.shape[2], cells.shape[3]
+    if tiles is not None:
+        th, tw = tile_hw
+        _require(tiles.is_cuda and tiles.dtype == torch.int32 and tiles.is_contiguous() and tiles.device == cells.device
+                 and tiles.numel() == 1 + n * (-(-h // th)) * (-(-w // tw)), 'plane gate: the tile list must be plane_tile_list(cells, h, w, tile_h, tile_w)')
+        g.tile_list, g.tile_h, g.tile_w = tiles.data_ptr(), th, tw
+    return g
+
+
+def plane_tile_list(cells, h, w, tile_h, tile_w):
+    """int32 [1 + n * tiles]: the number of tile_h x tile_w tiles of an h x w output with a set cell of `cells` under them, then their indices
+    (ide3d_plane_tile_list).  Handed to a gated launch with that tile size beside the map, it spreads the live tiles evenly over the device."""
+    n = cells.shape[0]
+    g = _plane_gate(cells, n, h, w)
+    out = torch.empty([1 + n * (-(-h // tile_h)) * (-(-w // tile_w))], dtype=torch.int32, device=cells.device)
+    with _dev_guard(cells.device):
+        rc = load().ide3d_plane_tile_list(ctypes.byref(g), n, int(h), int(w), int(tile_h), int(tile_w), _ptr(out), _stream(cells))
+    _check(rc, 'plane_tile_list')
+    return out
+
+
+def plane_cells(rays_d_cam, z_lin, cam2world, H, W):
+    """The needed-cell map of an H x W tri-plane for the cameras `cam2world` [n, 4, 4] of a render with the camera-space ray directions
+    `rays_d_cam` [R, 3] and the depth ramp `z_lin` [S] (the fused renderer's own arguments) -> uint8 [n, 3, ceil(H / 4), ceil(W / 4)]: 1 where a
+    sample can address a texel of the 4 x 4 cell, whatever the jitter draw (ide3d_plane_cells, csrc/camera.hip)."""
+    for t in (rays_d_cam, z_lin, cam2world):
+        _require(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), 'plane_cells: contiguous float32 CUDA tensors required')
+    _require(rays_d_cam.ndim == 2 and rays_d_cam.shape[1] == 3 and z_lin.ndim == 1 and cam2world.ndim == 3 and tuple(cam2world.shape[1:]) == (4, 4),
+             'plane_cells: rays_d_cam [R, 3], z_lin [S], cam2world [n, 4, 4]')
+    n = cam2world.shape[0]
+    cells = torch.empty([n, 3, (H + 3) // 4, (W + 3) // 4], dtype=torch.uint8, device=cam2world.device)
+    with _dev_guard(cells.device):
+        rc = load().ide3d_plane_cells(_ptr(rays_d_cam), _ptr(z_lin), _ptr(cam2world), n, rays_d_cam.shape[0], z_lin.shape[0], int(H), int(W),
+                                      _ptr(cells), _stream(cells))
+    _check(rc, 'plane_cells')
+    return cells
+
+
 class ResamplePlugin:
     @staticmethod
-    def skip_upsample_add_cl(lo, add):
-        """upsample2d(lo, [1,3,3,1]) + add -> [n, c, 2h, 2w] in channels_last memory format (lo / add: any strides)."""
+    def skip_upsample_add_cl(lo, add, gate=None, out=None):
+        """upsample2d(lo, [1,3,3,1]) + add -> [n, c, 2h, 2w] in channels_last memory format (lo / add: any strides).  `gate` (plane_cells' map
+        [n, 3, ceil(2h / 4), ceil(2w / 4)], c a multiple of 96): only the 8 x 32 tiles with a set cell of their own plane under them are
+        written (ide3d_skip_upsample_add_cl_gated).  `out`: the channels_last tensor to write into instead of a fresh one."""
         _require(lo.is_cuda and lo.dtype == torch.float32 and add.dtype == torch.float32 and add.device == lo.device,
                  'skip_upsample_add_cl: float32 CUDA tensors on one device required')
         n, c, h, w = lo.shape
         _require(tuple(add.shape) == (n, c, 2 * h, 2 * w), 'skip_upsample_add_cl: add must be [n, c, 2h, 2w]')
         _require(c % 4 == 0, 'skip_upsample_add_cl: channel count must be a multiple of 4')
-        out = torch.empty([n, c, 2 * h, 2 * w], dtype=torch.float32, device=lo.device, memory_format=torch.channels_last)
+        if out is None:
+            out = torch.empty([n, c, 2 * h, 2 * w], dtype=torch.float32, device=lo.device, memory_format=torch.channels_last)
+        _require(out.dtype == torch.float32 and out.device == lo.device and tuple(out.shape) == (n, c, 2 * h, 2 * w)
+                 and out.is_contiguous(memory_format=torch.channels_last), 'skip_upsample_add_cl: out must be a channels_last float32 [n, c, 2h, 2w] tensor')
         with _dev_guard(lo.device):
-            rc = load().ide3d_skip_upsample_add_cl(_ptr(lo), ctypes.byref(_i64x4(lo.stride())), _ptr(add), ctypes.byref(_i64x4(add.stride())),
-                                                   n, c, h, w, _ptr(out), _stream(lo))
+            if gate is not None:
+                rc = load().ide3d_skip_upsample_add_cl_gated(_ptr(lo), ctypes.byref(_i64x4(lo.stride())), _ptr(add), ctypes.byref(_i64x4(add.stride())),
+                                                             n, c, h, w, _ptr(out), ctypes.byref(_plane_gate(gate, n, 2 * h, 2 * w)), _stream(lo))
+            else:
+                rc = load().ide3d_skip_upsample_add_cl(_ptr(lo), ctypes.byref(_i64x4(lo.stride())), _ptr(add), ctypes.byref(_i64x4(add.stride())),
+                                                       n, c, h, w, _ptr(out), _stream(lo))
         _check(rc, 'skip_upsample_add_cl')
         return out
 

@@ -44,7 +44,7 @@ _pools = {}                                  # (device index, stream handle) -> 
 STATS = collections.Counter()                # 'eager', 'capture', 'replay', 'ineligible:<why>' — read by tests and bench.py
 
 
-_PASS_ENV = ('IDE3D_NO_SKIP_MERGE', 'IDE3D_NO_STYLE_PREFETCH', 'IDE3D_NO_STYLE_BATCH', 'IDE3D_NO_LOWRES_GROUP')
+_PASS_ENV = ('IDE3D_NO_SKIP_MERGE', 'IDE3D_NO_STYLE_PREFETCH', 'IDE3D_NO_STYLE_BATCH', 'IDE3D_NO_LOWRES_GROUP', 'IDE3D_NO_PLANE_GATE')
 
 
 def _env_int(name, default):

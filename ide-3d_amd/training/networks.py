@@ -668,7 +668,25 @@ def _dual_head(x, torgb, toseg, w, wcat=None):
     return y[:, :co], y[:, co:]
 
 
-def _conv1_dual_head(block, x, w1, w_shared, want_x, noise_mode='random', gain=1, input_noise=None, **unused):
+class PlaneGate:
+    """The needed-cell map of a call's tri-planes (hip_plugin.plane_cells) on its way to the last backbone block, which then writes only the
+    texels under set cells.  `taken`: the fused conv1 + heads launch ran under the map, so the skip accumulations
+    behind it may be gated too (their `add` input is defined under set cells only from then on, which is all they then read for them)."""
+
+    def __init__(self, cells):
+        self.cells, self.taken = cells, False
+        self._lists = {}
+
+    def with_tiles(self, h, w, tile_h, tile_w):
+        """(map, list of its live tile_h x tile_w tiles, tile size): the form a convolution launch with that tile size balances itself by."""
+        from torch_utils import hip_plugin
+        key = (h, w, tile_h, tile_w)
+        if key not in self._lists:
+            self._lists[key] = hip_plugin.plane_tile_list(self.cells, h, w, tile_h, tile_w)
+        return self.cells, self._lists[key], (tile_h, tile_w)
+
+
+def _conv1_dual_head(block, x, w1, w_shared, want_x, noise_mode='random', gain=1, input_noise=None, _plane_gate=None, **unused):
     """`block.conv1(x, w1)` followed by `_dual_head(., block.torgb, block.toseg, w_shared)`, with the heads in the epilogue of the
     convolution's launch where csrc/modconv.hip has that form (ide3d_modconv2d_heads: bit-equal to the two launches) -> (x, (y, y_seg));
     x is None when not `want_x` and the fused launch ran.  None, before anything was launched, when the path does not apply: training,
@@ -702,9 +720,15 @@ def _conv1_dual_head(block, x, w1, w_shared, want_x, noise_mode='random', gain=1
     hbias = _cat_cached(tr.bias, ts.bias)
     hclamp = -1.0 if tr.conv_clamp is None else tr.conv_clamp
     xc = x.contiguous()
+    gate = None
+    if _plane_gate is not None and not want_x:
+        # the fused form's tiles (csrc/modconv.hip ide3d_modconv2d_heads): 16 x 16 for its 128-channel instance, 32 x 16 for the 64-channel one
+        gate = _plane_gate.with_tiles(x.shape[2], x.shape[3], 16 if c1.weight.shape[0] == 128 else 32, 16)
     out = _modconv_plugin.modconv2d_heads(xc, c1.weight.contiguous(), styles.contiguous(), dcoefs, noise, 1.0, bias,
                                           spec.cuda_idx, spec.def_alpha, act_gain, -1.0 if act_clamp is None else act_clamp,
-                                          wcat, hbias, hclamp, want_x=want_x)
+                                          wcat, hbias, hclamp, want_x=want_x, gate=gate)
+    if gate is not None and out is not None:
+        _plane_gate.taken = True
     if out is None:
         x = _modconv_bias_act(x, c1.weight, styles, True, noise, 1.0, bias, c1.activation, act_gain, act_clamp, dcoefs=dcoefs)
         return x, _dual_head(x, tr, ts, w_shared, wcat=wcat)
@@ -1311,14 +1335,14 @@ class SegSynthesisBlock(torch.nn.Module):
             return skip
         raise NotImplementedError
 
-    def _accumulate(self, lo, cur, y):
+    def _accumulate(self, lo, cur, y, gate=None):
         """skip = upsample2d(lo) + y  (one HIP launch when `lo` is the deferred low-resolution skip image).  A block flagged
         `skip_channels_last` (the last tri-plane block: its skip images ARE the tri-planes the ray-marcher gathers from) gets
         the result in channels_last memory format straight from the kernel (csrc/resample.hip) instead of NCHW + a transpose."""
         if lo is not None:
             if (getattr(self, 'skip_channels_last', False) and lo.shape[1] % 4 == 0 and self.resample_filter.shape == (4, 4)
                     and _inference_on_gpu(lo, y) and self._filter_is_1331() and _resample_init()):
-                return _resample_plugin.skip_upsample_add_cl(lo, y)
+                return _resample_plugin.skip_upsample_add_cl(lo, y, gate=(gate.cells if gate is not None and lo.shape[1] % 96 == 0 else None))
             f = self.resample_filter
             return _upfirdn_plugin().upfirdn2d_ex(lo, f, 2, 2, 1, 1, 2, 1, 2, 1, False, 4.0, add=y)
         return cur.add_(y) if cur is not None else y
@@ -1335,6 +1359,7 @@ class SegSynthesisBlock(torch.nn.Module):
         misc.assert_shape(ws, [None, self.num_conv + self.num_torgb, self.w_dim])
         resume_after_conv0 = bool(layer_kwargs.pop('_resume_after_conv0', False))
         x_unused = bool(layer_kwargs.pop('_x_unused', False))       # the caller drops this block's x (the last block of backbone / superres)
+        plane_gate = layer_kwargs.pop('_plane_gate', None)          # PlaneGate: the caller reads img / seg under its set cells only
         ws_list = ws.unbind(dim=1)
         w_iter = iter(ws_list)
         dtype = torch.float16 if self.use_fp16 and not force_fp32 else torch.float32
@@ -1368,7 +1393,7 @@ class SegSynthesisBlock(torch.nn.Module):
                 layer_kwargs['input_noise'] = block_noise[:, 1:2] if block_noise is not None else None
                 w1 = next(w_iter)
                 if (self.is_last or self.architecture == 'skip') and not disable_rgb and dtype == torch.float32:
-                    fused = _conv1_dual_head(self, x, w1, ws_list[self.num_conv], not x_unused, **layer_kwargs)
+                    fused = _conv1_dual_head(self, x, w1, ws_list[self.num_conv], not x_unused, _plane_gate=plane_gate, **layer_kwargs)
                 if fused is not None:
                     x, fused_heads = fused
                 else:
@@ -1402,8 +1427,11 @@ class SegSynthesisBlock(torch.nn.Module):
                     both = self._accumulate(lo_both, None, y_both)
                     img, seg = both[:, :y.shape[1]], both[:, y.shape[1]:]
                 else:
-                    img = self._accumulate(img_lo, img, y)
-                    seg = self._accumulate(seg_lo, seg, y_seg)
+                    # (a gate that the fused launch took leaves y / y_seg undefined outside its cells; the accumulation is element-wise in
+                    # them, so a dense one stays right under the cells, and the channels-last launch skips the tiles outside them as well)
+                    skip_gate = plane_gate if (plane_gate is not None and plane_gate.taken) else None
+                    img = self._accumulate(img_lo, img, y, gate=skip_gate)
+                    seg = self._accumulate(seg_lo, seg, y_seg, gate=skip_gate)
         assert x is None or x.dtype == dtype
         if x is not None and out_dtype != dtype:
             x = x.to(out_dtype)

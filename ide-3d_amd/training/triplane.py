@@ -255,6 +255,27 @@ class TriplaneRenderer(torch.nn.Module):
             return False
         return not any(t is not None and t.requires_grad for t in (cam2world, jitter, sigma_noise, importance_u))
 
+    def resolve_camera_model(self, fov=None, num_steps=None, ray_start=None, ray_end=None, img_size=None):
+        """(fov, steps, ray_start, ray_end, render size) of a call: its own values where given, the spec's otherwise.  The one place where
+        they are resolved, for `forward` and for whoever must know them before it runs (`needed_cells`)."""
+        sp = self.spec
+        return (sp.fov if fov is None else fov, sp.num_steps if num_steps is None else num_steps,
+                sp.ray_start if ray_start is None else ray_start, sp.ray_end if ray_end is None else ray_end,
+                sp.render_size if img_size is None else img_size)
+
+    def needed_cells(self, cam2world, plane_hw, fov=None, num_steps=None, ray_start=None, ray_end=None, img_size=None):
+        """uint8 [N, 3, ceil(H / 4), ceil(W / 4)]: the 4 x 4-texel cells of H x W tri-planes that `forward` with these cameras and this
+        camera model can address, whatever its jitter draws (one launch on the device: hip_plugin.plane_cells)."""
+        fov, steps, t0, t1, size = self.resolve_camera_model(fov, num_steps, ray_start, ray_end, img_size)
+        vr._init()
+        rays_d_cam, z_lin = vr._fused_ray_setup(cam2world.device, float(fov), (size, size), int(steps), float(t0), float(t1))
+        from torch_utils import hip_plugin
+        return hip_plugin.plane_cells(rays_d_cam, z_lin, cam2world.float().contiguous(), plane_hw[0], plane_hw[1])
+
+    def fused_kernel_exists(self):
+        """The decoder widths ide3d_render_rays is compiled for (csrc/raymarch.hip): any other renders through the step-wise ops."""
+        return (self.spec.plane_channels, self.spec.decoder_hidden) in ((32, 64), (16, 32))
+
     # -- full rendering -----------------------------------------------------------------------------------
     def forward(self, img_v, seg_v, cam2world, fov=None, num_steps=None, ray_start=None, ray_end=None, img_size=None,
                 nerf_noise=0.0, jitter=None, sigma_noise=None, white_back=False, clamp_mode=None,
@@ -268,11 +289,7 @@ class TriplaneRenderer(torch.nn.Module):
                 the draws (None -> torch.rand); `sigma_noise_fine` [N, R*R, 2S] the density noise of the merged integration.
         """
         sp = self.spec
-        fov = sp.fov if fov is None else fov
-        steps = sp.num_steps if num_steps is None else num_steps
-        t0 = sp.ray_start if ray_start is None else ray_start
-        t1 = sp.ray_end if ray_end is None else ray_end
-        size = sp.render_size if img_size is None else img_size
+        fov, steps, t0, t1, size = self.resolve_camera_model(fov, num_steps, ray_start, ray_end, img_size)
         clamp_mode = sp.clamp_mode if clamp_mode is None else clamp_mode
         n, device = img_v.shape[0], img_v.device
         rays = size * size
@@ -420,8 +437,9 @@ class TriplaneSynthesisNetwork(torch.nn.Module):
                 w_idx += block.num_conv
         return voxel_ws, block_ws
 
-    def backbone(self, voxel_ws, **block_kwargs):
-        """ws -> (texture tri-plane, semantic tri-plane); pose independent."""
+    def backbone(self, voxel_ws, _plane_gate=None, **block_kwargs):
+        """ws -> (texture tri-plane, semantic tri-plane); pose independent — unless the caller hands in the `networks.PlaneGate` of the one
+        render the planes are for: the last block then leaves the texels that render cannot address unwritten."""
         x_v = img_v = seg_v = None
         blocks = [getattr(self, f'vb{res}') for res in self.voxel_block_resolutions]
         start, resume = 0, False
@@ -435,6 +453,8 @@ class TriplaneSynthesisNetwork(torch.nn.Module):
             extra = dict(_resume_after_conv0=True) if (resume and i == start) else {}
             if i == len(blocks) - 1:
                 extra['_x_unused'] = True            # only the tri-planes leave the backbone
+                if _plane_gate is not None:
+                    extra['_plane_gate'] = _plane_gate
             x_v, img_v, seg_v = block(x_v, img_v, cur_ws, condition_img=seg_v, **block_kwargs, **extra)
         return img_v, seg_v
 
@@ -514,6 +534,25 @@ class TriplaneSynthesisNetwork(torch.nn.Module):
             return graph_cache.run(self, impl, ws, c, render_params, noise_mode, flags, force_fp32, ray_jitter, cached_planes, unused)
         return impl(ws, c, ray_jitter, cached_planes)
 
+    def _plane_gate_ok(self, ws, cam2world, render_params):
+        """May the last backbone block of this call leave out what its renderer cannot read?  Only when the planes go
+        nowhere but the fused, non-hierarchical renderer of the same call (the caller has checked that they are not returned): inference on
+        the GPU, nobody hooked to see the planes, an arithmetic without side reductions over them, and the fallback switch not set."""
+        if os.environ.get('IDE3D_NO_PLANE_GATE') is not None or not ws.is_cuda or torch.is_grad_enabled() or not networks.use_hip_modconv:
+            return False
+        hierarchical = render_params.get('hierarchical')
+        if (self.spec.hierarchical if hierarchical is None else hierarchical) or not self.renderer.fused_kernel_exists():
+            return False
+        if cam2world.device != ws.device or any(p.device != ws.device for p in self.renderer.decoder.parameters()):
+            return False
+        last = getattr(self, f'vb{self.voxel_block_resolutions[-1]}')
+        if not getattr(last, 'skip_channels_last', False) or networks._hooked(self, last, self.renderer):
+            return False
+        # the gate hangs on the fused conv1 + heads launch (networks._conv1_dual_head): 128- or 64-channel blocks in bf16x6.  (f16x3 must
+        # decline anyway, its amax side outputs are reductions over the gated tensors; fp32 and bf16x3 have no fused launch to gate.)
+        from torch_utils import hip_plugin
+        return last.out_channels in (64, 128) and hip_plugin.conv_arithmetic() == 'bf16x6'
+
     def _forward_impl(self, ws, c, render_params, noise_mode, flags, force_fp32, ray_jitter, cached_planes):
         """The pass itself, launch by launch (what `forward` runs eagerly, and what a capture records)."""
         return_seg, return_raw, return_dict = flags
@@ -521,11 +560,19 @@ class TriplaneSynthesisNetwork(torch.nn.Module):
         # `force_fp32` (viz/renderer.py:439 passes it) reaches the blocks; without fp16 blocks in the spec it changes nothing
         block_kwargs = dict(noise_mode=noise_mode, force_fp32=force_fp32)
         with self._pass_scope(ws, ([] if cached_planes is not None else list(zip(self.voxel_block_resolutions, voxel_ws)), list(zip(self.block_resolutions, block_ws)))):
+            cam2world = c[:, :16].reshape(-1, 4, 4).to(torch.float32)
             if cached_planes is not None:
                 img_v, seg_v = cached_planes
             else:
-                img_v, seg_v = self.backbone(voxel_ws, **block_kwargs)
-            cam2world = c[:, :16].reshape(-1, 4, 4).to(torch.float32)
+                gate = None
+                if not return_dict and self._plane_gate_ok(ws, cam2world, render_params):
+                    res = self.voxel_block_resolutions[-1]
+                    gate = networks.PlaneGate(self.renderer.needed_cells(
+                        cam2world, (res, res), fov=render_params.get('fov'), num_steps=render_params.get('num_steps'),
+                        ray_start=render_params.get('ray_start'), ray_end=render_params.get('ray_end')))
+                    last = getattr(self, f'vb{res}')
+                    gate.with_tiles(res, res, 16 if last.out_channels == 128 else 32, 16)      # (listed here: ahead of the backbone, beside the style launches)
+                img_v, seg_v = self.backbone(voxel_ws, _plane_gate=gate, **block_kwargs)
             feat, depth, wsum = self.renderer(
                 img_v, seg_v, cam2world, fov=render_params.get('fov'), num_steps=render_params.get('num_steps'),
                 ray_start=render_params.get('ray_start'), ray_end=render_params.get('ray_end'),

@@ -663,6 +663,40 @@ typedef struct ide3d_modconv_head_epilogue {
 int ide3d_modconv2d_heads(const ide3d_modconv_params* p, const ide3d_modconv_head_epilogue* heads, void* stream);
 
 /*
+ * ABI 8 (entry points added).  The plane gate: the last backbone block writes only the tri-plane texels the renderer of the same call can
+ * read.
+ *
+ * ide3d_plane_cells fills cells [n, 3, cells_h, cells_w] bytes, cells_h = ceil(H / 4), cells_w = ceil(W / 4): a cell is a 4 x 4 block of
+ * texels of one plane (0: xy, 1: yz, 2: xz, the order of sample_from_triplane) of an H x W tri-plane, and is 1 when a sample that
+ * ide3d_render_rays can take for this camera (rays_d_cam [rays_per_img, 3], z_lin [steps], cam2world [n, 16]: its own arguments) addresses
+ * a texel in it, whatever the jitter draw: for every ray and step, the texel rectangle spanned by the taps of the jitter draws 0 and 1,
+ * widened by one texel on every side and clamped into the plane like the marcher's own addresses (csrc/triplane_tap.h `tap_addr`: the
+ * zero-weight loads of a tap outside the plane land on the border texels).  The map is zeroed first, in the same stream.
+ *
+ * A launch that is given a gate leaves every workgroup whose output tile has no set cell under it (see each entry point) before it reads
+ * or writes anything else: those output elements keep what the buffer held.  gate == NULL, gate->cells == NULL, or IDE3D_NO_PLANE_GATE
+ * in the environment (read per call): the dense launch.  The texels under set cells are bit-equal to the dense launch's.
+ */
+typedef struct ide3d_plane_gate {
+    const uint8_t* cells;     /* [n, 3, cells_h, cells_w] */
+    int32_t        cells_h, cells_w;
+    const int32_t* tile_list; /* NULL, or ide3d_plane_tile_list's output for tile_h x tile_w tiles: see there */
+    int32_t        tile_h, tile_w;
+} ide3d_plane_gate;
+int ide3d_plane_cells(const float* rays_d_cam, const float* z_lin, const float* cam2world, int32_t n, int32_t rays_per_img, int32_t steps,
+                      int32_t H, int32_t W, uint8_t* cells, void* stream);
+/* The live tiles of a map, compacted on the device: list[0] = their number, list[1 ...] = their indices (image * tiles_y + ty) * tiles_x + tx
+ * in ascending order, for the tile_h x tile_w-texel tiles (multiples of 4) of an h x w output; a tile is live iff a cell of any plane lies
+ * under it.  list holds 1 + n * tiles_y * tiles_x entries.  One small launch.  A gated launch that is handed the list of ITS tile size
+ * (ide3d_plane_gate.tile_list / tile_h / tile_w) gives workgroup i the i-th live tile and sends the workgroups past the count home: the
+ * live tiles then spread evenly over the XCDs whatever their position (without the list a workgroup keeps its tile, and the XCD that
+ * owns the most live tiles sets the launch's length).  A list of another tile size is ignored. */
+int ide3d_plane_tile_list(const ide3d_plane_gate* gate, int32_t n, int32_t h, int32_t w, int32_t tile_h, int32_t tile_w, int32_t* list, void* stream);
+/* ide3d_modconv2d_heads whose workgroups are live iff a cell of ANY of the three planes lies under their output tile (4 * cells_h >= h,
+ * 4 * cells_w >= w required). */
+int ide3d_modconv2d_heads_gated(const ide3d_modconv_params* p, const ide3d_modconv_head_epilogue* heads, const ide3d_plane_gate* gate, void* stream);
+
+/*
  * Frozen-generator backward of the synthesis convolutions (gradients for the layer inputs and the styles; weights, biases and affines
  * frozen).  Replaces the autograd of `modulated_conv2d` + `bias_act` (inversion/networks.py:55-130, SynthesisLayer :457-512), of the
  * transposed up-sampling convolution (conv2d_resample.py:112-129) and of ToRGBLayer (:670-713).  The matrix work is ide3d_modconv2d
@@ -950,6 +984,11 @@ int ide3d_mapping(const ide3d_mapping_params* p, void* stream);
  */
 int ide3d_skip_upsample_add_cl(const float* lo, const int64_t lo_stride[4], const float* add, const int64_t add_stride[4],
                                int32_t n, int32_t c, int32_t h, int32_t w, float* out, void* stream);
+/* ABI 8 (entry point added).  The same launch under a plane gate (ide3d_plane_gate above; 4 * cells_h >= 2h, 4 * cells_w >= 2w): the
+ * workgroup of an 8 x 32 output tile of the 32-channel group cg is live iff a cell of plane cg % 3 lies under it — c must be a multiple of
+ * 96: every 96 channels are one tri-plane tensor, three planes of 32. */
+int ide3d_skip_upsample_add_cl_gated(const float* lo, const int64_t lo_stride[4], const float* add, const int64_t add_stride[4],
+                                     int32_t n, int32_t c, int32_t h, int32_t w, float* out, const ide3d_plane_gate* gate, void* stream);
 
 /*
  * torch.nn.functional.interpolate(x, scale 2, mode='bilinear', align_corners=False) of x [n, c, h, w] (dense NCHW float32),
