@@ -2882,6 +2882,8 @@ class MappingPlugin:
     @staticmethod
     def mapping(z, c, embed_w, embed_b, embed_wgain, embed_bgain, fc_ws, fc_bs, lr_multiplier, alpha, act_gain, num_ws, w_avg, psi, cutoff, trusted=False):
         """z [n, z_dim], c [n, c_dim] | None, raw parameters of the embed / fc layers -> ws [n, num_ws, w_dim] (one launch).
+        `cutoff` has the meaning it has in `MappingNetwork._truncate`'s `ws[:, :cutoff]`, a Python slice: None truncates every row, a value
+        k >= 0 the first min(k, num_ws) rows, a negative value the first max(num_ws + k, 0) rows (truncation applies where psi != 1 only).
         `trusted`: the caller has passed these very parameter objects (and this batch size) through the checks before; only z / c are checked."""
         dev = z.device
         if trusted:
@@ -2926,7 +2928,8 @@ class MappingPlugin:
         p.n, p.z_dim, p.c_dim, p.embed, p.layers, p.num_ws = n, z_dim, (c.shape[1] if c is not None else 0), embed, len(fc_ws), num_ws
         p.embed_weight_gain, p.embed_bias_gain, p.lr_multiplier = float(embed_wgain), float(embed_bgain), float(lr_multiplier)
         p.alpha, p.act_gain, p.truncation_psi = float(alpha), float(act_gain), float(psi)
-        p.truncation_cutoff = -1 if cutoff is None else int(cutoff)
+        # `ws[:, :cutoff]` is a Python slice: a negative cut-off counts from the end.  The ABI reads every negative value as "all rows".
+        p.truncation_cutoff = -1 if cutoff is None else (int(cutoff) if cutoff >= 0 else max(num_ws + int(cutoff), 0))
         with _dev_guard(dev):
             rc = lib.ide3d_mapping(ctypes.byref(p), _stream(z))
         _check(rc, 'mapping')
