@@ -538,12 +538,128 @@ __device__ __forceinline__ void heads_per_ray(const unsigned char* sm, const flo
 template <bool SPLIT> struct RmWaves { static constexpr int value = SPLIT ? 8 : 4; };
 template <bool SPLIT> __device__ __forceinline__ void rm_claim_half_simd() { if constexpr (SPLIT) asm volatile("" ::: "v255"); }
 
+// ---- the parts the three ray marchers (render_rays_kernel and the two of the hierarchical pass) are built from ----------------------------
+
+// the tile after (ray, n, r, s0) of a wave that takes every NW-th ray and walks `steps` samples per ray in tiles of 16
+template <int NW>
+__device__ __forceinline__ void next_tile(int steps, int rays_per_img, int64_t& ray, int& n, int& r, int& s0) {
+    s0 += 16;
+    if (s0 >= steps) {
+        s0 = 0; ray += NW; r += NW;
+        while (r >= rays_per_img) { r -= rays_per_img; ++n; }
+    }
+}
+
+// Dynamic LDS of a marcher: the geometry branch's image, the texture branch's when it runs one (TEX), then `s_row`.
+template <int C, int HID, bool SPLIT, bool TEX>
+constexpr int kMarchLdsBytes = (TEX ? 2 : 1) * RmRender<C, HID, SPLIT>::BYTES + RmRender<C, HID, SPLIT>::ROW * (int)sizeof(float);
+
+// What a marcher's wave knows once its workgroup has staged the decoder: the LDS images, its lane in both layouts (matrix: lane 16 g + j;
+// gather: 16-byte channel block gl), the end of the workgroup's contiguous ray range (XCD-remapped, see the head of the file) and the wave's
+// first ray with its image n and index r in the image (wave-uniform, scalar registers).
+struct MarchWave {
+    unsigned char *s_geo, *s_tex;
+    float* s_row;                                          // row 0 of geo_w1 + its bias
+    int lane, wid, g, j, gl;
+    int64_t ray_end, ray;
+    int n, r;
+};
+template <int C, int HID, bool SPLIT, bool TEX>
+__device__ __forceinline__ MarchWave march_prologue(const ide3d_render_params& p, int64_t rays_per_block) {
+    using R = RmRender<C, HID, SPLIT>;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    MarchWave m;
+    m.s_geo = reinterpret_cast<unsigned char*>(lds);
+    m.s_tex = m.s_geo + R::BYTES;
+    m.s_row = reinterpret_cast<float*>(m.s_geo + (TEX ? 2 : 1) * R::BYTES);
+    stage_render_branch<C, HID, SPLIT>(m.s_geo, p.geo_w0, p.geo_b0, p.geo_w1, p.geo_b1, 1 + p.seg_ch);
+    if constexpr (TEX) stage_render_branch<C, HID, SPLIT>(m.s_tex, p.tex_w0, p.tex_b0, p.tex_w1, p.tex_b1, p.feat_ch);
+    for (int i = threadIdx.x; i <= HID; i += blockDim.x) m.s_row[i] = (i < HID) ? p.geo_w1[i] : p.geo_b1[0];
+    __syncthreads();
+
+    m.lane = lane_id(); m.wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    m.g = m.lane >> 4; m.j = m.lane & 15; m.gl = gather_block(m.lane);
+    const int64_t total_rays = (int64_t)p.n * p.rays_per_img;
+    const int blk = xcd_remap(blockIdx.x, gridDim.x);
+    const int64_t ray_begin = (int64_t)blk * rays_per_block;
+    m.ray_end = ray_begin + rays_per_block;
+    if (m.ray_end > total_rays) m.ray_end = total_rays;
+    // (the image index advances by comparison from here on, not by a 64-bit division per tile)
+    m.ray = ray_begin + m.wid;
+    m.n = __builtin_amdgcn_readfirstlane((int)(m.ray / p.rays_per_img));
+    m.r = __builtin_amdgcn_readfirstlane((int)(m.ray - (int64_t)m.n * p.rays_per_img));
+    return m;
+}
+
+// Compositing weight of sample j of a tile of ray r, in every lane of the sample, from its geometry hidden vector: sigma (+ noise) -> density
+// -> alpha over the distance to the next sample (`inner`; 1e10 behind the ray's last) -> the transmittance in front of it = `carry` (the
+// ray's before this tile) times the 16-lane exclusive scan.  `tot`: the transmittance of the whole tile, for the caller's carry.  Lanes past
+// the ray's end (`!live`) weigh nothing and leave the scan alone.
+template <int HID, bool NOISE>
+__device__ __forceinline__ float composite_step(const ide3d_render_params& p, const float* s_row, const f32x4 (&hg)[HID / 16], int r, float noise,
+                                                float z, float znext, bool live, bool inner, float carry, float& tot) {
+    float sigma = sigma_row0<HID>(s_row, hg);
+    if constexpr (NOISE) sigma += noise;
+    const float dens = p.clamp_mode == 0 ? softplus_fast(sigma) : fmaxf(sigma, 0.f);
+    const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];
+    const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
+    const float delta = inner ? (znext - z) * dnorm : 1e10f;
+    const float alpha = live ? 1.0f - __expf(-delta * dens) : 0.f;
+    const float fac = live ? (1.0f - alpha + 1e-10f) : 1.0f;
+    const float excl = seg16_excl_prod(fac, tot);
+    return alpha * (carry * excl);
+}
+
+// acc[4 mt + r] += w * h[mt][r]: sum_i w_i h_i of the units 16 mt + 4 g + r, over this lane's samples
+template <int MT1>
+__device__ __forceinline__ void accumulate_hidden(float (&acc)[4 * MT1], float w, const f32x4 (&h)[MT1]) {
+#pragma unroll
+    for (int mt = 0; mt < MT1; ++mt)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) acc[mt * 4 + rr] += w * h[mt][rr];
+}
+
+// Closing ray `ray` (r of image n): reduce over the 16 samples held by lanes with equal g, then the output layers on the sums; the feature
+// image, depth and weight sum are written with white_back / max_depth applied, and the ray's running sums start over.
+template <int C, int HID, bool SPLIT>
+__device__ __forceinline__ void close_ray(const ide3d_render_params& p, const MarchWave& m, int64_t ray, int n, int r, float (&acc_t)[HID / 4],
+                                          float (&acc_g)[HID / 4], float& carry, float& wsum, float& dsum) {
+    constexpr int NA = HID / 4;
+    const int g = m.g, j = m.j, nch = p.feat_ch + p.seg_ch;
+    wsum = row16_sum(wsum); dsum = row16_sum(dsum);
+#pragma unroll
+    for (int i = 0; i < NA; ++i) { acc_g[i] = row16_sum(acc_g[i]); acc_t[i] = row16_sum(acc_t[i]); }
+    float o_t[2], o_g[2];
+    heads_per_ray<C, HID, SPLIT>(m.s_tex, acc_t, wsum, o_t);
+    heads_per_ray<C, HID, SPLIT>(m.s_geo, acc_g, wsum, o_g);
+    // every lane holds rows j and j + 16 of both branches: the g = 0 .. 3 lanes write texture row j, j + 16, geometry row j, j + 16.
+    // last_back needs the un-weighted features of the final sample; not supported in the fused kernel (host guards), white_back / max_depth are.
+    const float bg = p.white_back ? (1.0f - wsum) : 0.f;
+    float* of = p.out_feat + (int64_t)n * nch * p.rays_per_img + r;
+    const int idx = j + 16 * (g & 1);
+    const float v = (g & 2) ? ((g & 1) ? o_g[1] : o_g[0]) : ((g & 1) ? o_t[1] : o_t[0]);
+    if (g < 2) {
+        if (idx < p.feat_ch) of[(int64_t)idx * p.rays_per_img] = v + bg;
+    } else {
+        if (idx >= 1 && idx <= p.seg_ch) of[(int64_t)(p.feat_ch + idx - 1) * p.rays_per_img] = v + bg;      // row 0 is sigma
+    }
+    if (m.lane == 0) {
+        if (p.out_depth) p.out_depth[ray] = dsum + ((p.max_depth != 0.f) ? (1.0f - wsum) * p.max_depth : 0.f);
+        if (p.out_wsum) p.out_wsum[ray] = wsum;
+    }
+#pragma unroll
+    for (int i = 0; i < NA; ++i) { acc_t[i] = 0.f; acc_g[i] = 0.f; }
+    carry = 1.0f; wsum = 0.f; dsum = 0.f;
+}
+
+
 template <int C, int HID, bool SPLIT>
 __global__ void __launch_bounds__(64 * RmWaves<SPLIT>::value, 2)
 render_rays_kernel(ide3d_render_params p, int64_t rays_per_block) {
     using K = RmCfg<C, HID>;
     constexpr int NW = RmWaves<SPLIT>::value;
     rm_claim_half_simd<SPLIT>();
+    // march_prologue<C, HID, SPLIT, true>, written out: this kernel's instruction stream is pinned
     extern __shared__ __attribute__((aligned(16))) float lds[];
     using R = RmRender<C, HID, SPLIT>;
     constexpr int NA = HID / 4;                            // hidden units per lane and branch
@@ -578,9 +694,7 @@ render_rays_kernel(ide3d_render_params p, int64_t rays_per_block) {
     auto tile_taps = [&](int n, int r, float zl, float jl, TapAddr (&t)[3]) {
         float wx, wy, wz;
         ray_world_point(p, n, r, zl, jl, zstep, wx, wy, wz);
-        t[0] = make_tap_addr(wx, wy, p.W, p.H, sH, sW);
-        t[1] = make_tap_addr(wy, wz, p.W, p.H, sH, sW);
-        t[2] = make_tap_addr(wx, wz, p.W, p.H, sH, sW);
+        triplane_tap_addrs(wx, wy, wz, p.W, p.H, sH, sW, t);
     };
 
     // Software pipeline over the tiles (ray, s0) of this wave, flattened across rays.  The loads of a tile's texture taps fly during
@@ -610,7 +724,7 @@ render_rays_kernel(ide3d_render_params p, int64_t rays_per_block) {
     float carry = 1.0f, wsum = 0.f, dsum = 0.f;
 
     while (have) {
-        // successor tile
+        // successor tile (next_tile, written out: pinned)
         int s0n = s0 + 16, nn = n, rn = r;
         int64_t rayn = ray;
         if (s0n >= S) {
@@ -645,23 +759,11 @@ render_rays_kernel(ide3d_render_params p, int64_t rays_per_block) {
         hidden_branch<C, HID, SPLIT>(s_geo, fg, hg);
 
         // --- compositing weights (before the texture MLP: the geometry hidden vector dies here) ---
-        float sigma = sigma_row0<HID>(s_row, hg);             // in every lane of sample j
-        sigma += noise;
-        const float dens = p.clamp_mode == 0 ? softplus_fast(sigma) : fmaxf(sigma, 0.f);
-        float dnorm;
-        {
-            const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];
-            dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-        }
-        const float delta = (sc + 1 < S) ? (znext - z) * dnorm : 1e10f;
-        const float alpha = live ? 1.0f - __expf(-delta * dens) : 0.f;
-        const float fac = live ? (1.0f - alpha + 1e-10f) : 1.0f;
         float tot;
-        const float excl = seg16_excl_prod(fac, tot);
-        const float w = alpha * (carry * excl);
+        const float w = composite_step<HID, true>(p, s_row, hg, r, noise, z, znext, live, sc + 1 < S, carry, tot);
         carry *= tot;
         wsum += w; dsum += w * z;
-#pragma unroll
+#pragma unroll        // accumulate_hidden, written out here and below: pinned
         for (int mt = 0; mt < K::MT1; ++mt)
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) acc_g[mt * 4 + rr] += w * hg[mt][rr];
@@ -677,7 +779,7 @@ render_rays_kernel(ide3d_render_params p, int64_t rays_per_block) {
             for (int rr = 0; rr < 4; ++rr) acc_t[mt * 4 + rr] += w * ht[mt][rr];
 
         if (s0n == 0) {
-            // --- close the ray: reduce over the 16 samples held by lanes with equal g, then the output layers on the sums ---
+            // --- close the ray (close_ray, written out: pinned) ---
             wsum = row16_sum(wsum); dsum = row16_sum(dsum);
 #pragma unroll
             for (int i = 0; i < NA; ++i) { acc_g[i] = row16_sum(acc_g[i]); acc_t[i] = row16_sum(acc_t[i]); }
@@ -685,9 +787,6 @@ render_rays_kernel(ide3d_render_params p, int64_t rays_per_block) {
             heads_per_ray<C, HID, SPLIT>(s_tex, acc_t, wsum, o_t);
             heads_per_ray<C, HID, SPLIT>(s_geo, acc_g, wsum, o_g);
             {
-                // every lane holds rows j and j + 16 of both branches: the g = 0 .. 3 lanes write texture row j, j + 16, geometry row j, j + 16.
-                // last_back needs the un-weighted features of the final sample; not supported in the fused
-                // kernel (host guards), white_back / max_depth are.
                 const float bg = p.white_back ? (1.0f - wsum) : 0.f;
                 float* of = p.out_feat + (int64_t)n * nch * p.rays_per_img + r;
                 const int idx = j + 16 * (g & 1);
@@ -791,11 +890,7 @@ sample_voxel_kernel(ide3d_render_params p, const Src src, int64_t m, float* __re
         while (rc >= e) { ++dn; e += m; }
         src.get(rc, rc - (e - m), wx, wy, wz);
     };
-    auto tile_taps = [&](float wx, float wy, float wz, TapAddr (&t)[3]) {
-        t[0] = make_tap_addr(wx, wy, p.W, p.H, sH, sW);
-        t[1] = make_tap_addr(wy, wz, p.W, p.H, sH, sW);
-        t[2] = make_tap_addr(wx, wz, p.W, p.H, sH, sW);
-    };
+    auto tile_taps = [&](float wx, float wy, float wz, TapAddr (&t)[3]) { triplane_tap_addrs(wx, wy, wz, p.W, p.H, sH, sW, t); };
     const unsigned geo_img_b = (unsigned)p.geo_stride[0] * 4u, tex_img_b = (unsigned)p.tex_stride[0] * 4u;
 
     bool have = tile < tile_end;
@@ -897,9 +992,7 @@ density_kernel(ide3d_render_params p, const Src src, int64_t m, float* __restric
         while (rc >= e) { ++dnl; e += m; }
         float wx, wy, wz;
         src.get(rc, rc - (e - m), wx, wy, wz);
-        tl[0] = make_tap_addr(wx, wy, p.W, p.H, sH, sW);
-        tl[1] = make_tap_addr(wy, wz, p.W, p.H, sH, sW);
-        tl[2] = make_tap_addr(wx, wz, p.W, p.H, sH, sW);
+        triplane_tap_addrs(wx, wy, wz, p.W, p.H, sH, sW, tl);
     };
     // tile k of the super tile, gather layout: lane 4 j + g takes the taps of row 16 k + j from lane 16 k + j
     auto tile_taps = [&](const TapAddr (&tl)[3], int dnl, int k, TapAddr (&t)[3], int& dn) {
@@ -947,70 +1040,39 @@ density_kernel(ide3d_render_params p, const Src src, int64_t m, float* __restric
     if constexpr (SPLIT) __syncthreads();          // exclusive residency (see render_rays_kernel)
 }
 
-// grid of the ray marchers (render_rays_kernel and the two of the hierarchical pass): 8 waves per CU either way, contiguous ray ranges
-template <bool SPLIT>
-static void ray_grid(int64_t total_rays, int64_t& nblk, int64_t& rpb) {
+// The launch of every persistent kernel of this file: 8 waves per CU either way (RmWaves), each workgroup a contiguous range of `units` (rays,
+// 16-row tiles, 64-row super tiles) whose length goes to the kernel as its last argument, after `args`; exclusive residency for the SPLIT forms.
+template <bool SPLIT, class Kern, class... Args>
+static int launch_persistent(Kern kern, const char* what, int64_t units, size_t lds_bytes, hipStream_t st, const Args&... args) {
     constexpr int NW = RmWaves<SPLIT>::value;
-    nblk = kNumCU * 8 / NW;
-    rpb = cdiv64(cdiv64(total_rays, nblk), NW) * NW;
-    if (rpb < NW) rpb = NW;
-    nblk = cdiv64(total_rays, rpb);
-}
-
-template <int C, int HID, bool SPLIT = false>
-static int launch_render(const ide3d_render_params& p, hipStream_t st) {
-    using R = RmRender<C, HID, SPLIT>;
-    const size_t lds_bytes = (size_t)2 * R::BYTES + (size_t)R::ROW * sizeof(float);
-    constexpr int NW = RmWaves<SPLIT>::value;
-    int64_t nblk, rpb;
-    ray_grid<SPLIT>((int64_t)p.n * p.rays_per_img, nblk, rpb);
-    auto kern = render_rays_kernel<C, HID, SPLIT>;
+    int64_t nblk = kNumCU * 8 / NW;
+    int64_t per_block = cdiv64(cdiv64(units, nblk), NW) * NW;
+    if (per_block < NW) per_block = NW;
+    nblk = cdiv64(units, per_block);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if constexpr (SPLIT) IDE3D_EXCL_LAUNCH(kern, dim3((unsigned)nblk), 64 * NW, lds_bytes, st, p, rpb);
-    else hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * NW), lds_bytes, st, p, rpb);
-    IDE3D_CHECK_LAUNCH("render_rays");
+    if constexpr (SPLIT) IDE3D_EXCL_LAUNCH(kern, dim3((unsigned)nblk), 64 * NW, lds_bytes, st, args..., per_block);
+    else hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * NW), lds_bytes, st, args..., per_block);
+    IDE3D_CHECK_LAUNCH(what);
     return IDE3D_OK;
 }
 
-template <int C, int HID, class Src, bool SPLIT = false>
+template <int C, int HID, bool SPLIT, class Src>
 static int launch_voxel(const ide3d_render_params& p, const Src& src, int64_t m, float* out, float* out_sigma,
                         int sigma_only, hipStream_t st) {
-    constexpr int NW = RmWaves<SPLIT>::value;
     // a lane whose row lies in a later image than the first row of its (super) tile adds whole image strides to its 32-bit byte
     // offsets: at most rows_per_tile - 1 images when m = 1
+    const int64_t rows = (int64_t)p.n * m, rows_per_tile = sigma_only ? 64 : 16;
     {
-        const int64_t rows_per_tile = sigma_only ? 64 : 16;
         const int64_t max_dn = (p.n > 1) ? ((rows_per_tile - 1) / (m > 0 ? m : 1) + 1 < p.n - 1 ? (rows_per_tile - 1) / (m > 0 ? m : 1) + 1 : p.n - 1) : 0;
         const int64_t img = p.geo_stride[0] > p.tex_stride[0] ? p.geo_stride[0] : p.tex_stride[0];
         if ((max_dn * img + img) * 4 >= 0xffffffffLL) { set_error("sample_voxel: too few points per image for planes this large"); return IDE3D_ENOKERNEL; }
     }
-    if (sigma_only) {
-        const size_t lds_bytes = (size_t)MlpBytes<C, HID, SPLIT>::value + (size_t)(HID + 4) * sizeof(float);
-        const int64_t nsuper = cdiv64((int64_t)p.n * m, 64);
-        int64_t nblk = kNumCU * 8 / NW;
-        int64_t spb = cdiv64(cdiv64(nsuper, nblk), NW) * NW;
-        if (spb < NW) spb = NW;
-        nblk = cdiv64(nsuper, spb);
-        auto kern = density_kernel<C, HID, Src, SPLIT>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if constexpr (SPLIT) IDE3D_EXCL_LAUNCH(kern, dim3((unsigned)nblk), 64 * NW, lds_bytes, st, p, src, m, out_sigma, spb);
-        else hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * NW), lds_bytes, st, p, src, m, out_sigma, spb);
-        IDE3D_CHECK_LAUNCH("sample_voxel (densities)");
-        return IDE3D_OK;
-    }
-    const int width = p.feat_ch + p.seg_ch + 1;
-    const size_t lds_bytes = (size_t)2 * MlpBytes<C, HID, SPLIT>::value + (size_t)NW * 16 * width * sizeof(float);
-    const int64_t ntiles = cdiv64((int64_t)p.n * m, 16);
-    int64_t nblk = kNumCU * 8 / NW;
-    int64_t tpb = cdiv64(cdiv64(ntiles, nblk), NW) * NW;
-    if (tpb < NW) tpb = NW;
-    nblk = cdiv64(ntiles, tpb);
-    auto kern = sample_voxel_kernel<C, HID, Src, SPLIT>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if constexpr (SPLIT) IDE3D_EXCL_LAUNCH(kern, dim3((unsigned)nblk), 64 * NW, lds_bytes, st, p, src, m, out, tpb);
-    else hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * NW), lds_bytes, st, p, src, m, out, tpb);
-    IDE3D_CHECK_LAUNCH("sample_voxel");
-    return IDE3D_OK;
+    if (sigma_only)
+        return launch_persistent<SPLIT>(density_kernel<C, HID, Src, SPLIT>, "sample_voxel (densities)", cdiv64(rows, 64),
+                                        (size_t)MlpBytes<C, HID, SPLIT>::value + (size_t)(HID + 4) * sizeof(float), st, p, src, m, out_sigma);
+    const size_t stage_bytes = (size_t)RmWaves<SPLIT>::value * 16 * (p.feat_ch + p.seg_ch + 1) * sizeof(float);
+    return launch_persistent<SPLIT>(sample_voxel_kernel<C, HID, Src, SPLIT>, "sample_voxel", cdiv64(rows, 16),
+                                    (size_t)2 * MlpBytes<C, HID, SPLIT>::value + stage_bytes, st, p, src, m, out);
 }
 
 // ---- the hierarchical (importance) pass: first-pass weights, depth merge, merged march ---------------------------
@@ -1022,15 +1084,6 @@ static int launch_voxel(const ide3d_render_params& p, const Src& src, int64_t m,
 // Both marchers prefetch two tiles deep: a tile's taps hang on its depths (first pass) or on what its `src` entries select (merged march:
 // a load that depends on a load), so those small loads are issued one tile before the taps they feed, and a tile's `src` one tile before that.
 
-// the tile after (ray, n, r, s0) of a wave that takes every NW-th ray and walks `steps` samples per ray in tiles of 16
-template <int NW>
-__device__ __forceinline__ void next_tile(int steps, int rays_per_img, int64_t& ray, int& n, int& r, int& s0) {
-    s0 += 16;
-    if (s0 >= steps) {
-        s0 = 0; ray += NW; r += NW;
-        while (r >= rays_per_img) { r -= rays_per_img; ++n; }
-    }
-}
 
 // First pass: the compositing weights of the S linear (jittered) samples of every ray, their depths, and the pdf that ide3d_sample_pdf draws
 // the fine depths from (bins = depth mid-points, weights = inner samples' weights + 1e-5), any of them optional.
@@ -1039,23 +1092,11 @@ __global__ void __launch_bounds__(64 * RmWaves<SPLIT>::value, 2)
 render_ray_weights_kernel(ide3d_render_params p, float* __restrict__ out_w, float* __restrict__ out_z, float* __restrict__ out_bins,
                           float* __restrict__ out_pw, int64_t rays_per_block) {
     using K = RmCfg<C, HID>;
-    using R = RmRender<C, HID, SPLIT>;
     constexpr int NW = RmWaves<SPLIT>::value;
     rm_claim_half_simd<SPLIT>();
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    unsigned char* s_geo = reinterpret_cast<unsigned char*>(lds);
-    float* const s_row = reinterpret_cast<float*>(s_geo + R::BYTES);           // row 0 of geo_w1 + its bias
-    stage_render_branch<C, HID, SPLIT>(s_geo, p.geo_w0, p.geo_b0, p.geo_w1, p.geo_b1, 1 + p.seg_ch);
-    for (int i = threadIdx.x; i <= HID; i += blockDim.x) s_row[i] = (i < HID) ? p.geo_w1[i] : p.geo_b1[0];
-    __syncthreads();
-
-    const int lane = lane_id(), wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int g = lane >> 4, j = lane & 15, gl = gather_block(lane);
-    const int64_t total_rays = (int64_t)p.n * p.rays_per_img;
-    const int blk = xcd_remap(blockIdx.x, gridDim.x);
-    const int64_t ray_begin = (int64_t)blk * rays_per_block;
-    int64_t ray_end = ray_begin + rays_per_block;
-    if (ray_end > total_rays) ray_end = total_rays;
+    const MarchWave m = march_prologue<C, HID, SPLIT, false>(p, rays_per_block);
+    const int lane = m.lane, g = m.g, j = m.j, gl = m.gl;
+    const int64_t ray_end = m.ray_end;
     const int S = p.steps;
     const int sH = (int)p.geo_stride[2], sW = (int)p.geo_stride[3];
     const float zstep = p.z_lin[1] - p.z_lin[0];              // S >= 3 (host)
@@ -1068,15 +1109,11 @@ render_ray_weights_kernel(ide3d_render_params p, float* __restrict__ out_w, floa
     auto tile_taps = [&](int n, int r, float zl, float jl, TapAddr (&t)[3]) {
         float wx, wy, wz;
         ray_world_point(p, n, r, zl, jl, zstep, wx, wy, wz);
-        t[0] = make_tap_addr(wx, wy, p.W, p.H, sH, sW);
-        t[1] = make_tap_addr(wy, wz, p.W, p.H, sH, sW);
-        t[2] = make_tap_addr(wx, wz, p.W, p.H, sH, sW);
+        triplane_tap_addrs(wx, wy, wz, p.W, p.H, sH, sW, t);
     };
 
-    int64_t ray = ray_begin + wid;
-    int n = __builtin_amdgcn_readfirstlane((int)(ray / p.rays_per_img));
-    int r = __builtin_amdgcn_readfirstlane((int)(ray - (int64_t)n * p.rays_per_img));
-    int s0 = 0;
+    int64_t ray = m.ray;
+    int n = m.n, r = m.r, s0 = 0;
     bool have = ray < ray_end;
     TapAddr t[3];
     TapBuf<C> buf;
@@ -1120,22 +1157,10 @@ render_ray_weights_kernel(ide3d_render_params p, float* __restrict__ out_w, floa
         tile_taps(np, rp, zl1, jl1, t);                                          // next tile's taps: in flight during this tile's MLP
         issue_taps<C>(uniform_ptr(p.geo_planes + np * p.geo_stride[0]), t, gl, buf);
         tile_depth(rayq, s0q, zl1, jl1);
-        hidden_branch<C, HID, SPLIT>(s_geo, fg, hg);
+        hidden_branch<C, HID, SPLIT>(m.s_geo, fg, hg);
 
-        float sigma = sigma_row0<HID>(s_row, hg);             // in every lane of sample j
-        sigma += noise;
-        const float dens = p.clamp_mode == 0 ? softplus_fast(sigma) : fmaxf(sigma, 0.f);
-        float dnorm;
-        {
-            const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];
-            dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-        }
-        const float delta = (sc + 1 < S) ? (znext - z) * dnorm : 1e10f;
-        const float alpha = live ? 1.0f - __expf(-delta * dens) : 0.f;
-        const float fac = live ? (1.0f - alpha + 1e-10f) : 1.0f;
         float tot;
-        const float excl = seg16_excl_prod(fac, tot);
-        const float w = alpha * (carry * excl);
+        const float w = composite_step<HID, true>(p, m.s_row, hg, r, noise, z, znext, live, sc + 1 < S, carry, tot);
         carry = (s0n == 0) ? 1.0f : carry * tot;
 
         // the four lanes of a sample hold the same values: one output each
@@ -1160,7 +1185,7 @@ __device__ __forceinline__ unsigned depth_key(float v) {
 }
 
 constexpr int kMergeWaves = 4;             // rays per workgroup and step
-constexpr int kMergeMaxT = 2048;           // merged samples per ray: 4 * 2048 keys = 32 KB of LDS
+constexpr int kMergeMaxT = 2 * kMergedMaxSteps;           // merged samples per ray: 4 * 2048 keys = 32 KB of LDS
 
 // Stable ascending order of [z_fine | z_coarse] per ray (torch.sort(torch.cat([z_fine, z_coarse]), stable=True)): one wave per ray, the T
 // keys in LDS, the rank of an element = how many precede it in (key, index) order, counted by every lane for its elements from broadcast
@@ -1205,27 +1230,12 @@ render_rays_merged_kernel(ide3d_render_params p, const float* __restrict__ z_all
                           const float* __restrict__ z_fine, int64_t rays_per_block) {
     using K = RmCfg<C, HID>;
     constexpr int NW = RmWaves<SPLIT>::value;
-    rm_claim_half_simd<SPLIT>();
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    using R = RmRender<C, HID, SPLIT>;
     constexpr int NA = HID / 4;                            // hidden units per lane and branch
-    unsigned char* s_geo = reinterpret_cast<unsigned char*>(lds);
-    unsigned char* s_tex = s_geo + R::BYTES;
-    float* const s_row = reinterpret_cast<float*>(s_tex + R::BYTES);           // row 0 of geo_w1 + its bias
-    stage_render_branch<C, HID, SPLIT>(s_geo, p.geo_w0, p.geo_b0, p.geo_w1, p.geo_b1, 1 + p.seg_ch);
-    stage_render_branch<C, HID, SPLIT>(s_tex, p.tex_w0, p.tex_b0, p.tex_w1, p.tex_b1, p.feat_ch);
-    for (int i = threadIdx.x; i <= HID; i += blockDim.x) s_row[i] = (i < HID) ? p.geo_w1[i] : p.geo_b1[0];
-    __syncthreads();
-
-    const int lane = lane_id(), wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int g = lane >> 4, j = lane & 15, gl = gather_block(lane);
-    const int64_t total_rays = (int64_t)p.n * p.rays_per_img;
-    const int blk = xcd_remap(blockIdx.x, gridDim.x);
-    const int64_t ray_begin = (int64_t)blk * rays_per_block;
-    int64_t ray_end = ray_begin + rays_per_block;
-    if (ray_end > total_rays) ray_end = total_rays;
+    rm_claim_half_simd<SPLIT>();
+    const MarchWave m = march_prologue<C, HID, SPLIT, true>(p, rays_per_block);
+    const int lane = m.lane, j = m.j, gl = m.gl;
+    const int64_t ray_end = m.ray_end;
     const int S = p.steps, T = 2 * S;
-    const int nch = p.feat_ch + p.seg_ch;
     const int sH = (int)p.tex_stride[2], sW = (int)p.tex_stride[3];   // host guarantees tex / geo share the layout
     const float zstep = p.z_lin[1] - p.z_lin[0];             // S >= 3 (host)
 
@@ -1255,15 +1265,11 @@ render_rays_merged_kernel(ide3d_render_params p, const float* __restrict__ z_all
             wy = __fadd_rn(M[7], __fmul_rn(uy, a));
             wz = __fadd_rn(M[11], __fmul_rn(uz, a));
         }
-        t[0] = make_tap_addr(wx, wy, p.W, p.H, sH, sW);
-        t[1] = make_tap_addr(wy, wz, p.W, p.H, sH, sW);
-        t[2] = make_tap_addr(wx, wz, p.W, p.H, sH, sW);
+        triplane_tap_addrs(wx, wy, wz, p.W, p.H, sH, sW, t);
     };
 
-    int64_t ray = ray_begin + wid;
-    int n = __builtin_amdgcn_readfirstlane((int)(ray / p.rays_per_img));
-    int r = __builtin_amdgcn_readfirstlane((int)(ray - (int64_t)n * p.rays_per_img));
-    int s0 = 0;
+    int64_t ray = m.ray;
+    int n = m.n, r = m.r, s0 = 0;
     bool have = ray < ray_end;
     TapAddr t[3];
     TapBuf<C> buf;
@@ -1309,99 +1315,26 @@ render_rays_merged_kernel(ide3d_render_params p, const float* __restrict__ z_all
         blend_taps<C>(buf, t, fg);
         to_matrix_lanes(fg);
         issue_taps<C>(uniform_ptr(p.tex_planes + n * p.tex_stride[0]), t, gl, buf);          // in flight during the geometry MLP
-        hidden_branch<C, HID, SPLIT>(s_geo, fg, hg);
+        hidden_branch<C, HID, SPLIT>(m.s_geo, fg, hg);
 
         // --- compositing weights (before the texture MLP: the geometry hidden vector dies here) ---
-        const float sigma = sigma_row0<HID>(s_row, hg);       // in every lane of sample j
-        const float dens = p.clamp_mode == 0 ? softplus_fast(sigma) : fmaxf(sigma, 0.f);
-        float dnorm;
-        {
-            const float dx = p.rays_d_cam[r * 3 + 0], dy = p.rays_d_cam[r * 3 + 1], dz = p.rays_d_cam[r * 3 + 2];
-            dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-        }
-        const float delta = (sc + 1 < T) ? (znext - z) * dnorm : 1e10f;
-        const float alpha = live ? 1.0f - __expf(-delta * dens) : 0.f;
-        const float fac = live ? (1.0f - alpha + 1e-10f) : 1.0f;
         float tot;
-        const float excl = seg16_excl_prod(fac, tot);
-        const float w = alpha * (carry * excl);
+        const float w = composite_step<HID, false>(p, m.s_row, hg, r, 0.f, z, znext, live, sc + 1 < T, carry, tot);
         carry *= tot;
         wsum += w; dsum += w * z;
-#pragma unroll
-        for (int mt = 0; mt < K::MT1; ++mt)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) acc_g[mt * 4 + rr] += w * hg[mt][rr];
+        accumulate_hidden(acc_g, w, hg);
 
         blend_taps<C>(buf, t, ft);
         to_matrix_lanes(ft);
         tile_taps(np, rp, svn, zln, an, t);                                     // next tile's geometry taps: during the texture MLP
         issue_taps<C>(uniform_ptr(p.geo_planes + np * p.geo_stride[0]), t, gl, buf);
-        hidden_branch<C, HID, SPLIT>(s_tex, ft, ht);
-#pragma unroll
-        for (int mt = 0; mt < K::MT1; ++mt)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) acc_t[mt * 4 + rr] += w * ht[mt][rr];
+        hidden_branch<C, HID, SPLIT>(m.s_tex, ft, ht);
+        accumulate_hidden(acc_t, w, ht);
 
-        if (s0n == 0) {
-            // --- close the ray (as render_rays_kernel does) ---
-            wsum = row16_sum(wsum); dsum = row16_sum(dsum);
-#pragma unroll
-            for (int i = 0; i < NA; ++i) { acc_g[i] = row16_sum(acc_g[i]); acc_t[i] = row16_sum(acc_t[i]); }
-            float o_t[2], o_g[2];
-            heads_per_ray<C, HID, SPLIT>(s_tex, acc_t, wsum, o_t);
-            heads_per_ray<C, HID, SPLIT>(s_geo, acc_g, wsum, o_g);
-            {
-                const float bg = p.white_back ? (1.0f - wsum) : 0.f;
-                float* of = p.out_feat + (int64_t)n * nch * p.rays_per_img + r;
-                const int idx = j + 16 * (g & 1);
-                const float v = (g & 2) ? ((g & 1) ? o_g[1] : o_g[0]) : ((g & 1) ? o_t[1] : o_t[0]);
-                if (g < 2) {
-                    if (idx < p.feat_ch) of[(int64_t)idx * p.rays_per_img] = v + bg;
-                } else {
-                    if (idx >= 1 && idx <= p.seg_ch) of[(int64_t)(p.feat_ch + idx - 1) * p.rays_per_img] = v + bg;      // row 0 is sigma
-                }
-                if (lane == 0) {
-                    if (p.out_depth) p.out_depth[ray] = dsum + ((p.max_depth != 0.f) ? (1.0f - wsum) * p.max_depth : 0.f);
-                    if (p.out_wsum) p.out_wsum[ray] = wsum;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < NA; ++i) { acc_t[i] = 0.f; acc_g[i] = 0.f; }
-            carry = 1.0f; wsum = 0.f; dsum = 0.f;
-        }
+        if (s0n == 0) close_ray<C, HID, SPLIT>(p, m, ray, n, r, acc_t, acc_g, carry, wsum, dsum);
         ray = rayn; n = nn; r = rn; s0 = s0n; have = haven;
     }
     if constexpr (SPLIT) __syncthreads();          // exclusive residency (see render_rays_kernel)
-}
-
-template <int C, int HID, bool SPLIT = false>
-static int launch_ray_weights(const ide3d_render_params& p, float* w, float* z, float* bins, float* pw, hipStream_t st) {
-    using R = RmRender<C, HID, SPLIT>;
-    const size_t lds_bytes = (size_t)R::BYTES + (size_t)R::ROW * sizeof(float);
-    constexpr int NW = RmWaves<SPLIT>::value;
-    int64_t nblk, rpb;
-    ray_grid<SPLIT>((int64_t)p.n * p.rays_per_img, nblk, rpb);
-    auto kern = render_ray_weights_kernel<C, HID, SPLIT>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if constexpr (SPLIT) IDE3D_EXCL_LAUNCH(kern, dim3((unsigned)nblk), 64 * NW, lds_bytes, st, p, w, z, bins, pw, rpb);
-    else hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * NW), lds_bytes, st, p, w, z, bins, pw, rpb);
-    IDE3D_CHECK_LAUNCH("render_ray_weights");
-    return IDE3D_OK;
-}
-
-template <int C, int HID, bool SPLIT = false>
-static int launch_render_merged(const ide3d_render_params& p, const float* z_all, const int* src, const float* z_fine, hipStream_t st) {
-    using R = RmRender<C, HID, SPLIT>;
-    const size_t lds_bytes = (size_t)2 * R::BYTES + (size_t)R::ROW * sizeof(float);
-    constexpr int NW = RmWaves<SPLIT>::value;
-    int64_t nblk, rpb;
-    ray_grid<SPLIT>((int64_t)p.n * p.rays_per_img, nblk, rpb);
-    auto kern = render_rays_merged_kernel<C, HID, SPLIT>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if constexpr (SPLIT) IDE3D_EXCL_LAUNCH(kern, dim3((unsigned)nblk), 64 * NW, lds_bytes, st, p, z_all, src, z_fine, rpb);
-    else hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * NW), lds_bytes, st, p, z_all, src, z_fine, rpb);
-    IDE3D_CHECK_LAUNCH("render_rays_merged");
-    return IDE3D_OK;
 }
 
 }  // namespace ide3d
@@ -1414,15 +1347,13 @@ extern "C" int ide3d_render_rays(const ide3d_render_params* pp, void* stream) {
     using namespace ide3d;
     IDE3D_CHECK_ARG(pp != nullptr, "render_rays: null params");
     const ide3d_render_params& p = *pp;
-    int rc = check_render_params(p, "render_rays", true);
+    int rc = check_render_params(p, "render_rays", kRaysAndOutput);
+    if (!rc) rc = check_march_declines(p, "render_rays");
     if (rc) return rc;
-    if (p.last_back) { set_error("render_rays: last_back is not fused; use the step-wise ops"); return IDE3D_ENOKERNEL; }
-    if (!planes_fast(p)) { set_error("render_rays: tri-planes must be channels_last, 16-byte aligned"); return IDE3D_ENOKERNEL; }
-    hipStream_t st = (hipStream_t)stream;
-    if (p.C == 32 && p.hidden == 64) return mlp_split_selected() ? launch_render<32, 64, true>(p, st) : launch_render<32, 64>(p, st);
-    if (p.C == 16 && p.hidden == 32) return launch_render<16, 32>(p, st);
-    set_error("render_rays: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
-    return IDE3D_ENOKERNEL;
+    return with_form(p, mlp_split_selected(), "render_rays", [&](auto f) {
+        return launch_persistent<f.SPLIT>(render_rays_kernel<f.C, f.HID, f.SPLIT>, "render_rays", (int64_t)p.n * p.rays_per_img,
+                                          kMarchLdsBytes<f.C, f.HID, f.SPLIT, true>, (hipStream_t)stream, p);
+    });
 }
 
 extern "C" int ide3d_sample_voxel(const ide3d_render_params* pp, const float* pts, int64_t m,
@@ -1430,19 +1361,16 @@ extern "C" int ide3d_sample_voxel(const ide3d_render_params* pp, const float* pt
     using namespace ide3d;
     IDE3D_CHECK_ARG(pp != nullptr && pts != nullptr, "sample_voxel: null params");
     const ide3d_render_params& p = *pp;
-    int rc = check_render_params(p, "sample_voxel", false);
+    int rc = check_render_params(p, "sample_voxel", kNoRays);
     if (rc) return rc;
     IDE3D_CHECK_ARG(m >= 0, "sample_voxel: bad point count");
     IDE3D_CHECK_ARG(sigma_only ? out_sigma != nullptr : out != nullptr, "sample_voxel: null output");
     if (m == 0) return IDE3D_OK;
     if (!planes_fast(p)) { set_error("sample_voxel: tri-planes must be channels_last, 16-byte aligned"); return IDE3D_ENOKERNEL; }
-    hipStream_t st = (hipStream_t)stream;
     const PointsFromMemory src{pts};
-    if (p.C == 32 && p.hidden == 64) return mlp_split_selected() ? launch_voxel<32, 64, PointsFromMemory, true>(p, src, m, out, out_sigma, sigma_only, st)
-                                                                  : launch_voxel<32, 64>(p, src, m, out, out_sigma, sigma_only, st);
-    if (p.C == 16 && p.hidden == 32) return launch_voxel<16, 32>(p, src, m, out, out_sigma, sigma_only, st);
-    set_error("sample_voxel: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
-    return IDE3D_ENOKERNEL;
+    return with_form(p, mlp_split_selected(), "sample_voxel", [&](auto f) {
+        return launch_voxel<f.C, f.HID, f.SPLIT>(p, src, m, out, out_sigma, sigma_only, (hipStream_t)stream);
+    });
 }
 
 static int check_lattice(const ide3d_lattice* lat, int64_t first, int64_t count, const char* what) {
@@ -1471,35 +1399,26 @@ extern "C" int ide3d_density_lattice(const ide3d_render_params* pp, const ide3d_
     using namespace ide3d;
     IDE3D_CHECK_ARG(pp != nullptr, "density_lattice: null params");
     const ide3d_render_params& p = *pp;
-    int rc = check_render_params(p, "density_lattice", false);
+    int rc = check_render_params(p, "density_lattice", kNoRays);
     if (rc) return rc;
     rc = check_lattice(lat, first, count, "density_lattice");
     if (rc) return rc;
     IDE3D_CHECK_ARG(out_sigma != nullptr || count == 0, "density_lattice: null output");
     if (count == 0) return IDE3D_OK;
     if (!planes_fast(p)) { set_error("density_lattice: tri-planes must be channels_last, 16-byte aligned"); return IDE3D_ENOKERNEL; }
-    hipStream_t st = (hipStream_t)stream;
     const PointsFromLattice src{*lat, first};
-    if (p.C == 32 && p.hidden == 64) return mlp_split_selected() ? launch_voxel<32, 64, PointsFromLattice, true>(p, src, count, nullptr, out_sigma, 1, st)
-                                                                  : launch_voxel<32, 64>(p, src, count, nullptr, out_sigma, 1, st);
-    if (p.C == 16 && p.hidden == 32) return launch_voxel<16, 32>(p, src, count, nullptr, out_sigma, 1, st);
-    set_error("density_lattice: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
-    return IDE3D_ENOKERNEL;
+    return with_form(p, mlp_split_selected(), "density_lattice", [&](auto f) {
+        return launch_voxel<f.C, f.HID, f.SPLIT>(p, src, count, nullptr, out_sigma, 1, (hipStream_t)stream);
+    });
 }
 
 // What the two marchers of the hierarchical pass check alike: ide3d_render_rays' rules without its outputs, then its declines plus the step
 // counts the pass cannot take (an inner pdf needs 3 samples; ide3d_merge_depths holds 2 * steps keys per ray in LDS).
 static int check_hierarchical(const ide3d_render_params& p, const char* who) {
     using namespace ide3d;
-    int rc = check_render_params(p, who, false);
-    if (rc) return rc;
-    IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world, "%s: null ray pointer", who);
-    IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "%s: bad ray shape", who);
-    IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "%s: Need to choose clamp mode", who);
-    if (p.steps < 3 || 2 * (int64_t)p.steps > kMergeMaxT) { set_error("%s: the hierarchical pass takes 3 .. %d steps, got %d", who, kMergeMaxT / 2, p.steps); return IDE3D_ENOKERNEL; }
-    if (p.last_back) { set_error("%s: last_back is not fused; use the step-wise ops", who); return IDE3D_ENOKERNEL; }
-    if (!planes_fast(p)) { set_error("%s: tri-planes must be channels_last, 16-byte aligned", who); return IDE3D_ENOKERNEL; }
-    return IDE3D_OK;
+    int rc = check_render_params(p, who, kRays);
+    if (!rc) rc = check_hierarchical_steps(p, who);
+    return rc ? rc : check_march_declines(p, who);
 }
 
 extern "C" int ide3d_render_ray_weights(const ide3d_render_params* pp, float* weights, float* z_vals, float* pdf_bins, float* pdf_weights,
@@ -1509,12 +1428,10 @@ extern "C" int ide3d_render_ray_weights(const ide3d_render_params* pp, float* we
     const ide3d_render_params& p = *pp;
     int rc = check_hierarchical(p, "render_ray_weights");
     if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (p.C == 32 && p.hidden == 64) return mlp_split_selected() ? launch_ray_weights<32, 64, true>(p, weights, z_vals, pdf_bins, pdf_weights, st)
-                                                                  : launch_ray_weights<32, 64>(p, weights, z_vals, pdf_bins, pdf_weights, st);
-    if (p.C == 16 && p.hidden == 32) return launch_ray_weights<16, 32>(p, weights, z_vals, pdf_bins, pdf_weights, st);
-    set_error("render_ray_weights: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
-    return IDE3D_ENOKERNEL;
+    return with_form(p, mlp_split_selected(), "render_ray_weights", [&](auto f) {
+        return launch_persistent<f.SPLIT>(render_ray_weights_kernel<f.C, f.HID, f.SPLIT>, "render_ray_weights", (int64_t)p.n * p.rays_per_img,
+                                          kMarchLdsBytes<f.C, f.HID, f.SPLIT, false>, (hipStream_t)stream, p, weights, z_vals, pdf_bins, pdf_weights);
+    });
 }
 
 extern "C" int ide3d_merge_depths(const float* z_fine, const float* z_coarse, int64_t rays, int32_t steps_fine, int32_t steps_coarse,
@@ -1540,12 +1457,10 @@ extern "C" int ide3d_render_rays_merged(const ide3d_render_params* pp, const flo
     if (rc) return rc;
     IDE3D_CHECK_ARG(p.out_feat != nullptr, "render_rays_merged: null output pointer");
     IDE3D_CHECK_ARG((int64_t)total_steps == 2 * (int64_t)p.steps, "render_rays_merged: total_steps must be 2 * steps = %d, got %d", 2 * p.steps, total_steps);
-    hipStream_t st = (hipStream_t)stream;
-    if (p.C == 32 && p.hidden == 64) return mlp_split_selected() ? launch_render_merged<32, 64, true>(p, z_all, src, z_fine, st)
-                                                                  : launch_render_merged<32, 64>(p, z_all, src, z_fine, st);
-    if (p.C == 16 && p.hidden == 32) return launch_render_merged<16, 32>(p, z_all, src, z_fine, st);
-    set_error("render_rays_merged: no fused kernel for C=%d hidden=%d", p.C, p.hidden);
-    return IDE3D_ENOKERNEL;
+    return with_form(p, mlp_split_selected(), "render_rays_merged", [&](auto f) {
+        return launch_persistent<f.SPLIT>(render_rays_merged_kernel<f.C, f.HID, f.SPLIT>, "render_rays_merged", (int64_t)p.n * p.rays_per_img,
+                                          kMarchLdsBytes<f.C, f.HID, f.SPLIT, true>, (hipStream_t)stream, p, z_all, src, z_fine);
+    });
 }
 
 namespace ide3d {

@@ -829,28 +829,18 @@ static bool grads_fit(const ide3d_render_params& p, const ide3d_render_grads& g)
 // limits (ide3d_render_rays_merged: an inner pdf needs 3 samples, ide3d_merge_depths orders at most 2048 per ray).
 static int render_backward(const ide3d_render_params& p, const ide3d_render_grads& g, const ide3d_render_param_grads* q,
                            const ide3d_render_camera_grads* c, void* stream, const char* what, const MergedSamples* ms = nullptr) {
-    int rc = check_render_params(p, what, false);
+    int rc = check_render_params(p, what, kRays);
+    if (!rc && ms) rc = check_hierarchical_steps(p, what);
     if (rc) return rc;
-    IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world, "%s: null ray pointer", what);
-    IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "%s: bad ray shape", what);
-    IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "%s: Need to choose clamp mode", what);
-    if (ms && (p.steps < kMergedMinSteps || p.steps > kMergedMaxSteps)) {
-        set_error("%s: the hierarchical pass takes %d .. %d steps, got %d", what, kMergedMinSteps, kMergedMaxSteps, p.steps);
-        return IDE3D_ENOKERNEL;
-    }
     // the tri-plane-only kernel scatters to both planes unconditionally
     IDE3D_CHECK_ARG(q || c || (g.grad_tex_planes && g.grad_geo_planes), "%s: null gradient output", what);
     IDE3D_CHECK_ARG(!c || c->grad_cam2world != nullptr, "%s: null camera-gradient output", what);
     IDE3D_CHECK_ARG(!q || (q->grad_geo_w0 && q->grad_geo_b0 && q->grad_geo_w1 && q->grad_geo_b1 && q->grad_tex_w0 && q->grad_tex_b0 &&
                            q->grad_tex_w1 && q->grad_tex_b1), "%s: null parameter-gradient output", what);
-    if (p.last_back) { set_error("%s: last_back is not fused; use the step-wise ops", what); return IDE3D_ENOKERNEL; }
-    if (!planes_fast(p)) { set_error("%s: tri-planes must be channels_last, 16-byte aligned", what); return IDE3D_ENOKERNEL; }
+    rc = check_march_declines(p, what);
+    if (rc) return rc;
     if (!grads_fit(p, g)) { set_error("%s: gradient buffers must be channels_last (channel stride 1)", what); return IDE3D_ENOKERNEL; }
-    hipStream_t st = (hipStream_t)stream;
-    if (p.C == 32 && p.hidden == 64) return launch_render_backward_form<32, 64>(p, g, q, c, st, what, ms);
-    if (p.C == 16 && p.hidden == 32) return launch_render_backward_form<16, 32>(p, g, q, c, st, what, ms);
-    set_error("%s: no fused kernel for C=%d hidden=%d", what, p.C, p.hidden);
-    return IDE3D_ENOKERNEL;
+    return with_form(p, false, what, [&](auto f) { return launch_render_backward_form<f.C, f.HID>(p, g, q, c, (hipStream_t)stream, what, ms); });
 }
 
 }  // namespace ide3d
@@ -863,9 +853,7 @@ extern "C" int ide3d_render_rays_backward(const ide3d_render_params* pp, const i
 extern "C" int64_t ide3d_render_param_grad_workspace_bytes(const ide3d_render_params* pp) {
     using namespace ide3d;
     if (pp == nullptr || pp->n <= 0 || pp->rays_per_img <= 0 || pp->steps <= 0 || pp->feat_ch < 0 || pp->seg_ch < 0) return 0;
-    if (pp->C == 32 && pp->hidden == 64) return param_workspace_bytes<32, 64>(*pp);
-    if (pp->C == 16 && pp->hidden == 32) return param_workspace_bytes<16, 32>(*pp);
-    return 0;
+    return with_form(*pp, false, nullptr, [&](auto f) { return param_workspace_bytes<f.C, f.HID>(*pp); });
 }
 
 extern "C" int ide3d_render_rays_backward_params(const ide3d_render_params* pp, const ide3d_render_grads* gg, const ide3d_render_param_grads* qq,
@@ -877,9 +865,7 @@ extern "C" int ide3d_render_rays_backward_params(const ide3d_render_params* pp, 
 extern "C" int64_t ide3d_render_camera_grad_workspace_bytes(const ide3d_render_params* pp) {
     using namespace ide3d;
     if (pp == nullptr || pp->n <= 0 || pp->rays_per_img <= 0 || pp->steps <= 0) return 0;
-    if (pp->C == 32 && pp->hidden == 64) return camera_workspace_bytes<32, 64>(*pp);
-    if (pp->C == 16 && pp->hidden == 32) return camera_workspace_bytes<16, 32>(*pp);
-    return 0;
+    return with_form(*pp, false, nullptr, [&](auto f) { return camera_workspace_bytes<f.C, f.HID>(*pp); });
 }
 
 extern "C" int ide3d_render_rays_backward_camera(const ide3d_render_params* pp, const ide3d_render_grads* gg, const ide3d_render_param_grads* qq,
@@ -891,12 +877,8 @@ extern "C" int ide3d_render_rays_backward_camera(const ide3d_render_params* pp, 
 
 extern "C" int64_t ide3d_render_merged_param_grad_workspace_bytes(const ide3d_render_params* pp) {
     using namespace ide3d;
-    if (pp == nullptr || pp->n <= 0 || pp->rays_per_img <= 0 || pp->steps < kMergedMinSteps || pp->steps > kMergedMaxSteps || pp->feat_ch < 0 ||
-        pp->seg_ch < 0)
-        return 0;
-    if (pp->C == 32 && pp->hidden == 64) return param_workspace_bytes<32, 64, true>(*pp);
-    if (pp->C == 16 && pp->hidden == 32) return param_workspace_bytes<16, 32, true>(*pp);
-    return 0;
+    if (pp == nullptr || pp->n <= 0 || pp->rays_per_img <= 0 || !hierarchical_steps_ok(pp->steps) || pp->feat_ch < 0 || pp->seg_ch < 0) return 0;
+    return with_form(*pp, false, nullptr, [&](auto f) { return param_workspace_bytes<f.C, f.HID, true>(*pp); });
 }
 
 extern "C" int ide3d_render_rays_merged_backward(const ide3d_render_params* pp, const float* z_all, const int32_t* src, const float* z_fine,

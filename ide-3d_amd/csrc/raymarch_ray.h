@@ -61,18 +61,28 @@ __device__ __forceinline__ void triplane_taps(float wx, float wy, float wz, int 
     t[1] = make_tap(wy, wz, W, H);
     t[2] = make_tap(wx, wz, W, H);
 }
+// The same with the taps' element offsets in a plane of row stride sH, texel stride sW: what the forward's scalar-base loads take.
+__device__ __forceinline__ void triplane_tap_addrs(float wx, float wy, float wz, int W, int H, int sH, int sW, TapAddr (&t)[3]) {
+    t[0] = make_tap_addr(wx, wy, W, H, sH, sW);
+    t[1] = make_tap_addr(wy, wz, W, H, sH, sW);
+    t[2] = make_tap_addr(wx, wz, W, H, sH, sW);
+}
 
 // ---- host-side rules shared by the forward and the backward launch ----------------------------------------------------------------
 
-static inline int check_render_params(const ide3d_render_params& p, const char* who, bool need_rays) {
+// What a call must bring of its rays: nothing (sample_voxel), the rays (hierarchical pass, backward), or the feature image as well.
+enum RayCheck { kNoRays, kRays, kRaysAndOutput };
+
+static inline int check_render_params(const ide3d_render_params& p, const char* who, RayCheck rays) {
     IDE3D_CHECK_ARG(p.tex_planes && p.geo_planes, "%s: null tri-plane pointer", who);
     IDE3D_CHECK_ARG(p.geo_w0 && p.geo_b0 && p.geo_w1 && p.geo_b1 && p.tex_w0 && p.tex_b0 && p.tex_w1 && p.tex_b1,
                     "%s: null MLP weight pointer", who);
     IDE3D_CHECK_ARG(p.n > 0 && p.C > 0 && p.H > 0 && p.W > 0, "%s: bad tri-plane shape", who);
     IDE3D_CHECK_ARG(p.feat_ch >= 1 && p.feat_ch <= 32 && p.seg_ch >= 0 && p.seg_ch <= 31,
                     "%s: feat_ch <= 32 and seg_ch <= 31 required", who);
-    if (need_rays) {
-        IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world && p.out_feat, "%s: null ray / output pointer", who);
+    if (rays != kNoRays) {
+        IDE3D_CHECK_ARG(p.rays_d_cam && p.z_lin && p.cam2world && (p.out_feat || rays == kRays),
+                        rays == kRays ? "%s: null ray pointer" : "%s: null ray / output pointer", who);
         IDE3D_CHECK_ARG(p.rays_per_img > 0 && p.steps > 0, "%s: bad ray shape", who);
         IDE3D_CHECK_ARG(p.clamp_mode == 0 || p.clamp_mode == 1, "%s: Need to choose clamp mode", who);
     }
@@ -80,8 +90,26 @@ static inline int check_render_params(const ide3d_render_params& p, const char* 
 }
 
 // Steps per ray of the hierarchical pass: an inner pdf needs 3 samples, and ide3d_merge_depths orders at most 2048 merged samples per ray
-// (kMergeMaxT, raymarch.hip).  The merged march's backward declines what its forward declines.
+// (kMergeMaxT = 2 * kMergedMaxSteps, raymarch.hip).  The merged march's backward declines what its forward declines.
 constexpr int kMergedMinSteps = 3, kMergedMaxSteps = 1024;
+constexpr bool hierarchical_steps_ok(int steps) { return steps >= kMergedMinSteps && steps <= kMergedMaxSteps; }
+static inline int check_hierarchical_steps(const ide3d_render_params& p, const char* who) {
+    if (hierarchical_steps_ok(p.steps)) return IDE3D_OK;
+    set_error("%s: the hierarchical pass takes %d .. %d steps, got %d", who, kMergedMinSteps, kMergedMaxSteps, p.steps);
+    return IDE3D_ENOKERNEL;
+}
+
+// The compiled forms of the renderer.  with_form calls f(RmForm<C, HID, SPLIT>{}) for the form that p (and, where the kernel has one, the
+// split arithmetic) selects; without one the error is set under `who` (who = NULL: a size query, which answers 0).
+template <int C_, int HID_, bool SPLIT_> struct RmForm { static constexpr int C = C_, HID = HID_; static constexpr bool SPLIT = SPLIT_; };
+template <class F>
+static inline auto with_form(const ide3d_render_params& p, bool split, const char* who, F&& f) -> decltype(f(RmForm<16, 32, false>{})) {
+    if (p.C == 32 && p.hidden == 64) return split ? f(RmForm<32, 64, true>{}) : f(RmForm<32, 64, false>{});
+    if (p.C == 16 && p.hidden == 32) return f(RmForm<16, 32, false>{});
+    if (!who) return 0;
+    set_error("%s: no fused kernel for C=%d hidden=%d", who, p.C, p.hidden);
+    return IDE3D_ENOKERNEL;
+}
 
 static inline bool planes_fast(const ide3d_render_params& p) {
     auto ok = [&](const float* base, const int64_t* s) {
@@ -91,6 +119,13 @@ static inline bool planes_fast(const ide3d_render_params& p) {
     return ok(p.tex_planes, p.tex_stride) && ok(p.geo_planes, p.geo_stride) &&
            p.tex_stride[2] == p.geo_stride[2] && p.tex_stride[3] == p.geo_stride[3] &&
            (p.tex_stride[2] * p.H + p.tex_stride[3] * p.W + 3 * p.C) * 4 < 0x7fffffffLL;       // byte offsets inside an image: 31 bits (launch_voxel bounds the image strides a straddling tile adds)
+}
+
+// What no fused march takes, forward or backward (IDE3D_ENOKERNEL: the step-wise ops do).
+static inline int check_march_declines(const ide3d_render_params& p, const char* who) {
+    if (p.last_back) { set_error("%s: last_back is not fused; use the step-wise ops", who); return IDE3D_ENOKERNEL; }
+    if (!planes_fast(p)) { set_error("%s: tri-planes must be channels_last, 16-byte aligned", who); return IDE3D_ENOKERNEL; }
+    return IDE3D_OK;
 }
 
 }  // namespace ide3d

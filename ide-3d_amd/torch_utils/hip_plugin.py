@@ -1136,16 +1136,32 @@ class VolumeRenderPlugin:
         return p, keep
 
     @staticmethod
-    def render_rays(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
-                    clamp_mode, last_back, white_back, max_depth):
-        dev = tex_planes.device
-        p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
-                                                 clamp_mode, last_back, white_back, max_depth)
+    def _ray_outputs(p, dev):
+        """Allocates (feat [n, feat+seg, rays], depth [n, rays], wsum [n, rays]) of a march and points `p`'s outputs at them."""
         n, R = p.n, p.rays_per_img
         feat = torch.empty([n, p.feat_ch + p.seg_ch, R], dtype=torch.float32, device=dev)
         depth = torch.empty([n, R], dtype=torch.float32, device=dev)
         wsum = torch.empty([n, R], dtype=torch.float32, device=dev)
         p.out_feat, p.out_depth, p.out_wsum = feat.data_ptr(), depth.data_ptr(), wsum.data_ptr()
+        return feat, depth, wsum
+
+    @staticmethod
+    def _merged_samples(what, p, dev, merged):
+        """(z_all, src, z_fine) of the merged march, checked against `p`'s shape -> the three, contiguous."""
+        rays, S = p.n * p.rays_per_img, p.steps
+        shapes = (('z_all', (rays, 2 * S), torch.float32), ('src', (rays, 2 * S), torch.int32), ('z_fine', (rays, S), torch.float32))
+        for t_, (name, shape, dt) in zip(merged, shapes):
+            _require(t_.dtype == dt and t_.device == dev and tuple(t_.shape) == shape,
+                     f'{what}: {name} must be {list(shape)} {dt} next to the tri-planes, got {list(t_.shape)} {t_.dtype}')
+        return tuple(t_.contiguous() for t_ in merged)
+
+    @staticmethod
+    def render_rays(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
+                    clamp_mode, last_back, white_back, max_depth):
+        dev = tex_planes.device
+        p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, sigma_noise, tex_planes, geo_planes, mlp,
+                                                 clamp_mode, last_back, white_back, max_depth)
+        feat, depth, wsum = VolumeRenderPlugin._ray_outputs(p, dev)
         with _dev_guard(dev):
             rc = load().ide3d_render_rays(ctypes.byref(p), _stream(tex_planes))
         if rc == -2:        # IDE3D_ENOKERNEL: configuration not covered by the fused kernel
@@ -1197,18 +1213,10 @@ class VolumeRenderPlugin:
         dev = tex_planes.device
         p, keep = VolumeRenderPlugin._ray_params(rays_d_cam, z_lin, cam2world, jitter, None, tex_planes, geo_planes, mlp,
                                                  clamp_mode, last_back, white_back, max_depth)
-        n, R, S = p.n, p.rays_per_img, p.steps
-        for name, t_, shape, dt in (('z_all', z_all, (n * R, 2 * S), torch.float32), ('src', src, (n * R, 2 * S), torch.int32),
-                                    ('z_fine', z_fine, (n * R, S), torch.float32)):
-            _require(t_.dtype == dt and t_.device == dev and tuple(t_.shape) == shape,
-                     f'render_rays_merged: {name} must be {list(shape)} {dt} next to the tri-planes, got {list(t_.shape)} {t_.dtype}')
-        z_all, src, z_fine = z_all.contiguous(), src.contiguous(), z_fine.contiguous()
-        feat = torch.empty([n, p.feat_ch + p.seg_ch, R], dtype=torch.float32, device=dev)
-        depth = torch.empty([n, R], dtype=torch.float32, device=dev)
-        wsum = torch.empty([n, R], dtype=torch.float32, device=dev)
-        p.out_feat, p.out_depth, p.out_wsum = feat.data_ptr(), depth.data_ptr(), wsum.data_ptr()
+        z_all, src, z_fine = VolumeRenderPlugin._merged_samples('render_rays_merged', p, dev, (z_all, src, z_fine))
+        feat, depth, wsum = VolumeRenderPlugin._ray_outputs(p, dev)
         with _dev_guard(dev):
-            rc = load().ide3d_render_rays_merged(ctypes.byref(p), _ptr(z_all), _ptr(src), _ptr(z_fine), 2 * S, _stream(tex_planes))
+            rc = load().ide3d_render_rays_merged(ctypes.byref(p), _ptr(z_all), _ptr(src), _ptr(z_fine), 2 * p.steps, _stream(tex_planes))
         if rc == -2:        # IDE3D_ENOKERNEL
             return None
         _check(rc, 'render_rays_merged')
@@ -1225,12 +1233,7 @@ class VolumeRenderPlugin:
         p, keep = VolumeRenderPlugin._ray_params(*ray_args)
         n, R, nch = p.n, p.rays_per_img, p.feat_ch + p.seg_ch
         if merged is not None:
-            S = p.steps
-            shapes = (('z_all', (n * R, 2 * S), torch.float32), ('src', (n * R, 2 * S), torch.int32), ('z_fine', (n * R, S), torch.float32))
-            for t_, (name, shape, dt) in zip(merged, shapes):
-                _require(t_.dtype == dt and t_.device == dev and tuple(t_.shape) == shape,
-                         f'{what}: {name} must be {list(shape)} {dt} next to the tri-planes, got {list(t_.shape)} {t_.dtype}')
-            merged = tuple(t_.contiguous() for t_ in merged)
+            merged = VolumeRenderPlugin._merged_samples(what, p, dev, merged)
         g = _RenderGrads()
         for name, t, shape in zip(('grad_feat', 'grad_depth', 'grad_wsum'), upstream, ((n, nch, R), (n, R), (n, R))):
             if t is not None:

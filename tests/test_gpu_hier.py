@@ -382,3 +382,71 @@ def test_declines_fall_back_to_the_stepwise_path(gpu_device):
         assert P.render_rays_merged(rays_d, z_lin, cam, jit, tex, geo, mlp, 0, False, None, sc['z_all'].to(dev), sc['src'].to(dev),
                                     sc['z_fine'].to(dev), last_back=True) is None
     assert not _calls()
+
+
+def test_declines_and_argument_errors_keep_code_and_text(gpu_device):
+    """Every decline (IDE3D_ENOKERNEL = -2) and argument error (IDE3D_EINVAL = -1) of the three marchers and the two backward entry points,
+    once per entry point, straight at the library: the return code and the exact ide3d_last_error() text.  Nothing is launched: each call
+    carries one fault and is turned away by the host-side checks."""
+    import ctypes
+    from torch_utils import hip_plugin
+    dev, P, lib = gpu_device, hip_plugin.VolumeRenderPlugin, hip_plugin.load()
+    C, hidden, feat, seg, S, rays = 16, 32, 8, 5, 12, 25
+    z = lambda *shape: torch.zeros(*shape, device=dev)
+    tex, geo = (z(1, 3 * C, 8, 8).contiguous(memory_format=torch.channels_last) for _ in range(2))
+    mlp = dict(geo_w0=z(hidden, C), geo_b0=z(hidden), geo_w1=z(1 + seg, hidden), geo_b1=z(1 + seg),
+               tex_w0=z(hidden, C), tex_b0=z(hidden), tex_w1=z(feat, hidden), tex_b1=z(feat))
+    p0, keep = P._ray_params(z(rays, 3), z(S), z(1, 4, 4), None, None, tex, geo, mlp, 0, False, False, None)
+    outs = P._ray_outputs(p0, dev)
+    z_all, src, z_fine = z(rays, 2 * S), torch.zeros(rays, 2 * S, dtype=torch.int32, device=dev), z(rays, S)
+    dtex, dgeo = torch.zeros_like(tex), torch.zeros_like(geo)
+    g = hip_plugin._RenderGrads()
+    g.grad_tex_planes, g.grad_geo_planes = dtex.data_ptr(), dgeo.data_ptr()
+    g.grad_tex_stride, g.grad_geo_stride = hip_plugin._i64x4(dtex.stride()), hip_plugin._i64x4(dgeo.stride())
+    ptr, stream = hip_plugin._ptr, hip_plugin._stream(tex)
+    merged = (ptr(z_all), ptr(src), ptr(z_fine))
+    entries = {        # name -> (hierarchical, call(p, total_steps))
+        'render_rays': (False, lambda p, T: lib.ide3d_render_rays(ctypes.byref(p), stream)),
+        'render_ray_weights': (True, lambda p, T: lib.ide3d_render_ray_weights(ctypes.byref(p), None, None, None, None, stream)),
+        'render_rays_merged': (True, lambda p, T: lib.ide3d_render_rays_merged(ctypes.byref(p), *merged, T, stream)),
+        'render_rays_backward': (False, lambda p, T: lib.ide3d_render_rays_backward(ctypes.byref(p), ctypes.byref(g), stream)),
+        'render_rays_merged_backward': (True, lambda p, T: lib.ide3d_render_rays_merged_backward(ctypes.byref(p), *merged, T, ctypes.byref(g), None,
+                                                                                                 stream)),
+    }
+
+    def fault(**fields):
+        p = type(p0).from_buffer_copy(p0)
+        for k, v in fields.items():
+            setattr(p, k, v)
+        return p
+
+    nchw = hip_plugin._i64x4((3 * C * 64, 64, 8, 1))
+    small = hip_plugin._i64x4((24 * 64, 1, 24 * 8, 24))
+    cases = [        # (fault, code, text after "<entry>: ", hierarchical entries only)
+        (fault(last_back=1), -2, 'last_back is not fused; use the step-wise ops', False),
+        (fault(tex_stride=nchw, geo_stride=nchw), -2, 'tri-planes must be channels_last, 16-byte aligned', False),
+        (fault(C=8, hidden=16, tex_stride=small, geo_stride=small), -2, 'no fused kernel for C=8 hidden=16', False),
+        (fault(steps=2), -2, 'the hierarchical pass takes 3 .. 1024 steps, got 2', True),
+        (fault(steps=1025), -2, 'the hierarchical pass takes 3 .. 1024 steps, got 1025', True),
+        (fault(clamp_mode=2), -1, 'Need to choose clamp mode', False),
+    ]
+    hip_plugin.CALLS.clear()
+    seen = 0
+    for name, (hier, call) in entries.items():
+        for p, code, text, hier_only in cases:
+            if hier_only and not hier:
+                continue
+            rc = call(p, 2 * p.steps)
+            got = lib.ide3d_last_error().decode()
+            print(name, rc, got)
+            assert rc == code and got == f'{name}: {text}', (name, rc, got)
+            seen += 1
+    for name in ('render_rays_merged', 'render_rays_merged_backward'):
+        rc = entries[name][1](p0, 2 * S + 1)
+        got = lib.ide3d_last_error().decode()
+        print(name, rc, got)
+        assert rc == -1 and got == f'{name}: total_steps must be 2 * steps = {2 * S}, got {2 * S + 1}', (name, rc, got)
+        seen += 1
+    assert seen == 5 * 4 + 3 * 2 + 2 and not _calls()
+    assert all(float(o.abs().max()) == 0 for o in (dtex, dgeo)), 'nothing ran'
+    del keep, outs
