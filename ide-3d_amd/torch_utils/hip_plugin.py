@@ -408,6 +408,9 @@ def load():
             'ide3d_raster_project': [vp, i64, vp, i32, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp, i64, vp],
             'ide3d_raster_depth': [vp, i64, i64, i32, i32, i32, i32, i32, vp, i64, vp],
             'ide3d_raster_shade': [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, i32, f32, f32, ctypes.POINTER(ctypes.c_float * 3), f32, vp, i64, vp, vp, vp, vp, vp],
+            'ide3d_png_workspace_bytes': [i32, i32, i32, i32, i32],
+            'ide3d_png_out_bytes': [i32, i32, i32, i32, i32],
+            'ide3d_png_encode': [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, vp],
             'ide3d_modconv2d': [ctypes.POINTER(_ModconvParams), vp],
             'ide3d_modconv2d_heads': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), vp],
             'ide3d_modconv2d_heads_gated': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), ctypes.POINTER(_PlaneGate), vp],
@@ -525,6 +528,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_render_merged_param_grad_workspace_bytes', 'ide3d_render_rays_merged_backward',
     'ide3d_raster_workspace_bytes', 'ide3d_raster_project', 'ide3d_raster_depth', 'ide3d_raster_shade',
     'ide3d_plane_cells', 'ide3d_plane_tile_list', 'ide3d_modconv2d_heads_gated', 'ide3d_skip_upsample_add_cl_gated',
+    'ide3d_png_workspace_bytes', 'ide3d_png_out_bytes', 'ide3d_png_encode',
 )
 
 
@@ -2099,6 +2103,47 @@ class MeshPlugin:
         return MeshPlugin.emit(volume, threshold, table, ws, nv, nt, normals=normals, flip=flip, lattice=lattice)
 
 
+class PngPlugin:
+    """Row filters + deflate of uint8 CUDA frames (csrc/png.hip): the compression inside `save_image` of
+    gen_images.py:115-116.  `training.png` holds the host definition of the same bytes, the container and the copies to the host."""
+
+    _ws = _Workspaces()          # (bytes, device index, launch domain) -> filtered streams + segment slots + segment records
+
+    @staticmethod
+    def _shape(frames, segment_bytes):
+        _require(frames.is_cuda and frames.dtype == torch.uint8 and frames.ndim == 4 and frames.is_contiguous(),
+                 'png_encode: frames must be a contiguous [N, H, W, C] uint8 CUDA tensor')
+        N, H, W, C = (int(v) for v in frames.shape)
+        lib = load()
+        ws_bytes, out_bytes = lib.ide3d_png_workspace_bytes(N, H, W, C, segment_bytes), lib.ide3d_png_out_bytes(N, H, W, C, segment_bytes)
+        _require(ws_bytes > 0 and 0 < out_bytes < 2 ** 31, f'png_encode: unsupported call: {N} frames of {H} x {W} x {C}, segments of {segment_bytes} bytes '
+                 '(1 or 3 channels, a power of two in [1024, 32768], below 2 GiB per call)')
+        return (N, H, W, C), ws_bytes, out_bytes
+
+    @staticmethod
+    def launch(frames, filter_mode, segment_bytes, workspace, out, offsets):
+        """ide3d_png_encode into the caller's buffers (uint8 workspace and out, int64 offsets [N + 1], all on the frames' device)."""
+        (N, H, W, C), _, _ = PngPlugin._shape(frames, segment_bytes)
+        for t, dt in ((workspace, torch.uint8), (out, torch.uint8), (offsets, torch.int64)):
+            _require(t.is_cuda and t.device == frames.device and t.dtype == dt and t.is_contiguous(), 'png_encode: workspace / out are uint8, offsets int64, on the frames\' device')
+        _require(offsets.numel() == N + 1, 'png_encode: offsets holds N + 1 values')
+        with _dev_guard(frames.device):
+            rc = load().ide3d_png_encode(_ptr(frames), N, H, W, C, int(filter_mode), int(segment_bytes), _ptr(workspace), workspace.numel(),
+                                         _ptr(out), out.numel(), _ptr(offsets), _stream(frames))
+        _check(rc, 'png_encode')
+
+    @staticmethod
+    def encode(frames, filter_mode, segment_bytes):
+        """-> (out uint8 [worst case], offsets int64 [N + 1]) on the device: stream k is out[offsets[k]:offsets[k + 1]]."""
+        (N, H, W, C), ws_bytes, out_bytes = PngPlugin._shape(frames, segment_bytes)
+        dev = frames.device if frames.device.index is not None else torch.device('cuda', torch.cuda.current_device())
+        ws = PngPlugin._ws.entry((ws_bytes, dev.index, _ws_domain(dev)), lambda: torch.empty([ws_bytes], dtype=torch.uint8, device=dev))[0]
+        out = torch.empty([out_bytes], dtype=torch.uint8, device=dev)
+        offsets = torch.empty([N + 1], dtype=torch.int64, device=dev)
+        PngPlugin.launch(frames, filter_mode, segment_bytes, ws, out, offsets)
+        return out, offsets
+
+
 class RasterPlugin:
     """Triangle rasterizer on float32 CUDA meshes (csrc/raster.hip): the pyrender step of render_mesh.py:36-61.
     `training.mesh_render` prepares the arguments (camera inversion in float64, the pixel grid) and holds the host definition."""
@@ -3132,6 +3177,7 @@ class LowresPlugin:
 PLUGINS = {
     'mesh_plugin': MeshPlugin,
     'raster_plugin': RasterPlugin,
+    'png_plugin': PngPlugin,
     'lowres_plugin': LowresPlugin,
     'bias_act_plugin': BiasActPlugin,
     'upfirdn2d_plugin': Upfirdn2dPlugin,

@@ -168,6 +168,29 @@ def write_y4m(frames: Iterable[torch.Tensor], path: str, fps: int = 60) -> int:
     return count
 
 
+def write_png_sequence(frames: Iterable[torch.Tensor], pattern: str, batch: int = 8) -> int:
+    """Write uint8 [H, W, 3] RGB frames (any device) as numbered PNG files `pattern % index` (e.g. 'out/frame%05d.png'), compressed where
+    the frames live (`training.png.encode_png`: HIP kernels for CUDA frames), `batch` frames per call.  Returns the number of files written."""
+    from training import png
+    count, pending = 0, []
+
+    def flush():
+        nonlocal count
+        if pending:
+            png.save_png(torch.stack(pending), [pattern % (count + k) for k in range(len(pending))])
+            count += len(pending)
+            pending.clear()
+
+    for frame in frames:
+        if pending and (frame.shape != pending[0].shape or frame.device != pending[0].device):
+            flush()
+        pending.append(frame)
+        if len(pending) >= batch:
+            flush()
+    flush()
+    return count
+
+
 def read_y4m(path: str):
     """(header dict, uint8 array [frames, 3, H, W]) of a 4:4:4 stream written by `write_y4m` (tests, round trips)."""
     with open(path, 'rb') as f:

@@ -596,6 +596,34 @@ int ide3d_raster_shade(const float* vertices, const int32_t* triangles, int64_t 
                        float ambient, float diffuse, const float* base_color, float bg, const void* workspace, int64_t workspace_bytes,
                        float* depth, int32_t* triangle, float* image, int32_t* label, void* stream);
 
+/* ---- PNG: row filters and deflate -------------------------------------------------------------- */
+/*
+ * The compression half of `save_image(imgs, 'seed0000.png', normalize=True, range=(-1, 1))`
+ * (gen_images.py:115-116; torchvision + PIL on the host there): frames uint8 [n, h, w, c]
+ * contiguous, c = 1 (grey) or 3 (RGB), to the n zlib streams of their PNG files (78 01, deflate
+ * blocks, Adler-32 big endian), back to back in `out`; stream k is out[offsets[k], offsets[k + 1]),
+ * offsets int64 [n + 1] in device memory.  The caller adds signature, IHDR, IDAT framing and CRCs.
+ * training/png.py states every integer of the stream and holds the host definition that gives the
+ * same bytes: PNG filter types 0-4 per row (filter_mode 0-4 forces one; 5: per row the type with
+ * the smallest sum of min(v, 256 - v) over the filtered bytes, lowest type on a tie); the filtered
+ * stream cut into segments of segment_bytes (a power of two, 1024..32768); per segment one deflate
+ * block with dynamic Huffman codes (lengths <= 15, code-length alphabet <= 7) whose only matches are
+ * runs at distance 1, ended on a byte boundary by an empty stored block (the last one by BFINAL),
+ * or one stored block where that is not smaller: a segment of m bytes takes at most m + 5.
+ * Four launches (filter, deflate, scan, compact); integer arithmetic, integer LDS atomics only:
+ * two runs are bit-equal.
+ * workspace: ide3d_png_workspace_bytes() bytes (-1: unsupported shape), 16-byte aligned: the
+ * filtered streams, one slot of segment_bytes + 32 per segment, sizes and Adler sums per segment.
+ * out_capacity >= ide3d_png_out_bytes() = n * (F + 5 * segments + 6), F = h * (w * c + 1): every
+ * segment stored.  Refused with IDE3D_EINVAL before any launch: c not in {1, 3}, a bad
+ * segment_bytes or filter_mode, an empty axis, a workspace or out below those sizes, and any of
+ * the workspace, out or row count at or above 2^31.
+ */
+int64_t ide3d_png_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t segment_bytes);
+int64_t ide3d_png_out_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t segment_bytes);
+int ide3d_png_encode(const uint8_t* frames, int32_t n, int32_t h, int32_t w, int32_t c, int32_t filter_mode, int32_t segment_bytes,
+                     void* workspace, int64_t workspace_bytes, uint8_t* out, int64_t out_capacity, int64_t* offsets, void* stream);
+
 /* ---- modulated 3x3 / 1x1 convolution (MFMA implicit GEMM) --------------------------------- */
 /*
  * Replaces the ATen conv behind `conv2d_gradfix.conv2d` for the StyleGAN2 modulated
