@@ -411,6 +411,9 @@ def load():
             'ide3d_png_workspace_bytes': [i32, i32, i32, i32, i32],
             'ide3d_png_out_bytes': [i32, i32, i32, i32, i32],
             'ide3d_png_encode': [vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, vp],
+            'ide3d_jpeg_workspace_bytes': [i32, i32, i32, i32, i32, i32],
+            'ide3d_jpeg_out_bytes': [i32, i32, i32, i32, i32, i32],
+            'ide3d_jpeg_encode': [vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, vp],
             'ide3d_modconv2d': [ctypes.POINTER(_ModconvParams), vp],
             'ide3d_modconv2d_heads': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), vp],
             'ide3d_modconv2d_heads_gated': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), ctypes.POINTER(_PlaneGate), vp],
@@ -529,6 +532,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_raster_workspace_bytes', 'ide3d_raster_project', 'ide3d_raster_depth', 'ide3d_raster_shade',
     'ide3d_plane_cells', 'ide3d_plane_tile_list', 'ide3d_modconv2d_heads_gated', 'ide3d_skip_upsample_add_cl_gated',
     'ide3d_png_workspace_bytes', 'ide3d_png_out_bytes', 'ide3d_png_encode',
+    'ide3d_jpeg_workspace_bytes', 'ide3d_jpeg_out_bytes', 'ide3d_jpeg_encode',
 )
 
 
@@ -2144,6 +2148,48 @@ class PngPlugin:
         return out, offsets
 
 
+class JpegPlugin:
+    """Colour conversion, DCT, quantiser and Huffman coding of uint8 CUDA frames (csrc/jpeg.hip): the compression
+    of the Motion-JPEG video sink.  `training.jpeg` holds the host definition of the same bytes, the markers and the copies to the host."""
+
+    _ws = _Workspaces()          # (bytes, device index, launch domain) -> interval slots + their sizes and positions
+
+    @staticmethod
+    def _shape(frames, subsampling, restart_interval):
+        _require(frames.is_cuda and frames.dtype == torch.uint8 and frames.ndim == 4 and frames.is_contiguous(),
+                 'jpeg_encode: frames must be a contiguous [N, H, W, C] uint8 CUDA tensor')
+        N, H, W, C = (int(v) for v in frames.shape)
+        lib = load()
+        args = (N, H, W, C, int(subsampling), int(restart_interval))
+        ws_bytes, out_bytes = lib.ide3d_jpeg_workspace_bytes(*args), lib.ide3d_jpeg_out_bytes(*args)
+        _require(ws_bytes > 0 and 0 < out_bytes < 2 ** 31, f'jpeg_encode: unsupported call: {N} frames of {H} x {W} x {C}, subsampling {subsampling}, '
+                 f'restart interval {restart_interval} (1 or 3 channels, sides 1..65535, 444 or 420 (RGB only), 1..65535 MCUs, below 2 GiB per call)')
+        return (N, H, W, C), ws_bytes, out_bytes
+
+    @staticmethod
+    def launch(frames, quality, subsampling, restart_interval, workspace, out, offsets):
+        """ide3d_jpeg_encode into the caller's buffers (uint8 workspace and out, int64 offsets [N + 1], all on the frames' device)."""
+        (N, H, W, C), _, _ = JpegPlugin._shape(frames, subsampling, restart_interval)
+        for t, dt in ((workspace, torch.uint8), (out, torch.uint8), (offsets, torch.int64)):
+            _require(t.is_cuda and t.device == frames.device and t.dtype == dt and t.is_contiguous(), 'jpeg_encode: workspace / out are uint8, offsets int64, on the frames\' device')
+        _require(offsets.numel() == N + 1, 'jpeg_encode: offsets holds N + 1 values')
+        with _dev_guard(frames.device):
+            rc = load().ide3d_jpeg_encode(_ptr(frames), N, H, W, C, int(quality), int(subsampling), int(restart_interval), _ptr(workspace), workspace.numel(),
+                                          _ptr(out), out.numel(), _ptr(offsets), _stream(frames))
+        _check(rc, 'jpeg_encode')
+
+    @staticmethod
+    def encode(frames, quality, subsampling, restart_interval):
+        """-> (out uint8 [worst case], offsets int64 [N + 1]) on the device: scan k is out[offsets[k]:offsets[k + 1]]."""
+        (N, H, W, C), ws_bytes, out_bytes = JpegPlugin._shape(frames, subsampling, restart_interval)
+        dev = frames.device if frames.device.index is not None else torch.device('cuda', torch.cuda.current_device())
+        ws = JpegPlugin._ws.entry((ws_bytes, dev.index, _ws_domain(dev)), lambda: torch.empty([ws_bytes], dtype=torch.uint8, device=dev))[0]
+        out = torch.empty([out_bytes], dtype=torch.uint8, device=dev)
+        offsets = torch.empty([N + 1], dtype=torch.int64, device=dev)
+        JpegPlugin.launch(frames, quality, subsampling, restart_interval, ws, out, offsets)
+        return out, offsets
+
+
 class RasterPlugin:
     """Triangle rasterizer on float32 CUDA meshes (csrc/raster.hip): the pyrender step of render_mesh.py:36-61.
     `training.mesh_render` prepares the arguments (camera inversion in float64, the pixel grid) and holds the host definition."""
@@ -3178,6 +3224,7 @@ PLUGINS = {
     'mesh_plugin': MeshPlugin,
     'raster_plugin': RasterPlugin,
     'png_plugin': PngPlugin,
+    'jpeg_plugin': JpegPlugin,
     'lowres_plugin': LowresPlugin,
     'bias_act_plugin': BiasActPlugin,
     'upfirdn2d_plugin': Upfirdn2dPlugin,

@@ -11,6 +11,7 @@ time (`kind='cubic'`, `wraps` periodic copies), one look-at camera per frame swe
 """
 
 import math
+import struct
 import threading
 import weakref
 from typing import Iterable, Iterator, Sequence, Tuple
@@ -189,6 +190,147 @@ def write_png_sequence(frames: Iterable[torch.Tensor], pattern: str, batch: int 
             flush()
     flush()
     return count
+
+
+# ---- Motion-JPEG in AVI -----------------------------------------------------------------------------------------------------------
+# The compressed video sink: every frame a baseline JPEG file (`training.jpeg`: HIP kernels for CUDA frames, so a frame reaches the
+# host 15-40 times smaller than raw) in an AVI 1.0 container written here.  Intra-only, no rate control, below 2 GiB (no OpenDML
+# extensions).  The container is checked structurally and every frame through an independent decoder and Pillow
+# (tests/test_jpeg_cpu.py); no player was available to open a file.
+
+AVI_MAX_BYTES = 2 ** 31 - 1          # the file stays below 2 GiB: 32-bit RIFF sizes, signed in many readers
+
+
+class AviWriter:
+    """`get_writer`'s object: `append_data(frame)` per uint8 [H, W, 3] (or [H, W, 1] / [H, W]) frame, numpy or tensor on any device, then
+    `close()`; a context manager.  Frames are encoded `batch` at a time; chunks are streamed to the file, sizes, counts and the index are
+    written at `close()`.  The layout: RIFF 'AVI ' { LIST hdrl { avih, LIST strl { strh vids/MJPG (dwScale 1, dwRate fps), strf
+    BITMAPINFOHEADER MJPG 24 bit } }, LIST movi { 00dc chunks padded to even length }, idx1 { 16-byte keyframe entries, offsets relative
+    to the 'movi' fourcc } }."""
+
+    _HEADER_BYTES = 12 + (12 + (8 + 56) + (12 + (8 + 56) + (8 + 40))) + 12          # up to and including 'movi'
+
+    def __init__(self, path, fps=60, quality=90, subsampling='4:2:0', batch=8):
+        self.path, self.fps, self.quality, self.subsampling, self.batch = path, int(fps), int(quality), subsampling, max(1, int(batch))
+        if self.fps < 1:
+            raise ValueError('write_avi: fps must be a positive integer')
+        self._file = open(path, 'wb')
+        self._file.write(b'\x00' * self._HEADER_BYTES)
+        self._pending, self._index, self._size = [], [], None
+        self._movi = 4                      # bytes of LIST movi's payload so far ('movi' itself)
+        self._largest = 0
+        self.count = 0
+
+    def append_data(self, frame):
+        if self._file is None:
+            raise ValueError('append_data: the writer is closed')
+        frame = torch.as_tensor(frame)
+        if frame.ndim == 2:
+            frame = frame[..., None]
+        if not (frame.dtype == torch.uint8 and frame.ndim == 3 and frame.shape[2] in (1, 3)):
+            raise ValueError(f'append_data: a uint8 [H, W, 3] or [H, W, 1] frame is expected, got {frame.dtype} {tuple(frame.shape)}')
+        size = (int(frame.shape[0]), int(frame.shape[1]))
+        if self._size is None:
+            self._size = size
+        if size != self._size:
+            raise ValueError(f'append_data: all frames of a stream have one size ({self._size}, got {size})')
+        if self._pending and (frame.shape != self._pending[0].shape or frame.device != self._pending[0].device):
+            self._flush()
+        self._pending.append(frame)
+        if len(self._pending) >= self.batch:
+            self._flush()
+
+    def _flush(self):
+        from training import jpeg
+        if not self._pending:
+            return
+        files = jpeg.encode_jpeg(torch.stack(self._pending), self.quality, self.subsampling)
+        self._pending = []
+        for data in files:
+            padded = len(data) + (len(data) & 1)
+            # what the file would hold after this chunk, its index entry and the idx1 header
+            if self._HEADER_BYTES + (self._movi - 4) + 8 + padded + 8 + 16 * (len(self._index) + 1) > AVI_MAX_BYTES:
+                raise ValueError(f'write_avi: {self.path} would pass 2 GiB with frame {self.count} (AVI 1.0, no OpenDML extensions): split the video')
+            self._index.append((self._movi, len(data)))
+            self._file.write(b'00dc' + len(data).to_bytes(4, 'little') + data + b'\x00' * (padded - len(data)))
+            self._movi += 8 + padded
+            self._largest = max(self._largest, len(data))
+            self.count += 1
+
+    def close(self):
+        if self._file is None:
+            return
+        f = self._file
+        try:
+            self._flush()
+        finally:                            # a file that holds the frames written so far, whatever happened
+            self._file = None
+            h, w = self._size if self._size is not None else (0, 0)
+            n = self.count
+            f.write(b'idx1' + struct.pack('<I', 16 * n) + b''.join(b'00dc' + struct.pack('<III', 0x10, at, size) for at, size in self._index))
+            total = f.tell()
+            avih = struct.pack('<14I', 1000000 // self.fps, min(self._largest * self.fps, 0xFFFFFFFF), 0, 0x10, n, 0, 1, self._largest, w, h, 0, 0, 0, 0)      # AVIF_HASINDEX
+            strh = b'vids' + b'MJPG' + struct.pack('<IHHIIIIIIII4H', 0, 0, 0, 0, 1, self.fps, 0, n, self._largest, 0xFFFFFFFF, 0, 0, 0, w, h)
+            strf = struct.pack('<IiiHH4sIiiII', 40, w, h, 1, 24, b'MJPG', w * h * 3, 0, 0, 0, 0)
+            strl = b'LIST' + struct.pack('<I', 4 + 8 + len(strh) + 8 + len(strf)) + b'strl' + b'strh' + struct.pack('<I', len(strh)) + strh \
+                + b'strf' + struct.pack('<I', len(strf)) + strf
+            hdrl = b'LIST' + struct.pack('<I', 4 + 8 + len(avih) + len(strl)) + b'hdrl' + b'avih' + struct.pack('<I', len(avih)) + avih + strl
+            head = b'RIFF' + struct.pack('<I', total - 8) + b'AVI ' + hdrl + b'LIST' + struct.pack('<I', self._movi) + b'movi'
+            assert len(head) == self._HEADER_BYTES
+            f.seek(0)
+            f.write(head)
+            f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def get_writer(path, fps=60, quality=90, subsampling='4:2:0', batch=8, **ignored) -> AviWriter:
+    """The surface of `imageio.get_writer(mp4, mode='I', fps=60, codec='libx264', bitrate='10M')` that the reference's drivers use
+    (gen_videos.py:108): `append_data(frame)`, `close()`, a context manager.  `quality` is the JPEG quality 1..100.  `mode`, `codec`,
+    `bitrate` and any other keyword are accepted and ignored: the stream is Motion-JPEG at a fixed quality, there is no rate control."""
+    return AviWriter(path, fps=fps, quality=quality, subsampling=subsampling, batch=batch)
+
+
+def write_avi(frames: Iterable[torch.Tensor], path: str, fps: int = 60, quality: int = 90, subsampling: str = '4:2:0', batch: int = 8) -> int:
+    """Write uint8 [H, W, 3] RGB frames (any device, e.g. what `gen_interp_frames` yields) as a Motion-JPEG AVI file, compressed where the
+    frames live, `batch` frames per encode call (each call synchronises its stream).  Returns the number of frames written."""
+    with get_writer(path, fps=fps, quality=quality, subsampling=subsampling, batch=batch) as w:
+        for frame in frames:
+            w.append_data(frame)
+    return w.count
+
+
+def mimwrite(path, frames, fps=30, quality=8, **ignored) -> int:
+    """`imageio.mimwrite(path, frames, fps=..., quality=...)`: `quality` is imageio's 0..10 scale, mapped HERE (our choice, imageio maps
+    it to an x264 rate factor) to the JPEG quality 10 * quality clamped to 1..100.  Other keywords are accepted and ignored."""
+    return write_avi(frames, path, fps=fps, quality=min(100, max(1, int(round(10 * quality)))))
+
+
+def read_avi(path: str):
+    """(info dict: width, height, fps, frames; list of the frames' JPEG files as bytes) of a file written by `write_avi` (tests, round
+    trips).  Frames are found through idx1."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    assert data[:4] == b'RIFF' and data[8:12] == b'AVI ' and data[12:16] == b'LIST' and data[20:24] == b'hdrl' and data[24:28] == b'avih'
+    avih = struct.unpack('<14I', data[32:88])
+    assert data[88:92] == b'LIST' and data[96:100] == b'strl' and data[100:104] == b'strh' and data[108:116] == b'vidsMJPG'
+    scale, rate = struct.unpack('<II', data[128:136])
+    movi = AviWriter._HEADER_BYTES - 4
+    assert data[movi:movi + 4] == b'movi'
+    idx = movi + struct.unpack('<I', data[movi - 4:movi])[0]
+    assert data[idx:idx + 4] == b'idx1'
+    n = struct.unpack('<I', data[idx + 4:idx + 8])[0] // 16
+    frames = []
+    for k in range(n):
+        cid, _, at, size = struct.unpack('<4sIII', data[idx + 8 + 16 * k:idx + 24 + 16 * k])
+        assert cid == b'00dc' and data[movi + at:movi + at + 4] == b'00dc'
+        frames.append(data[movi + at + 8:movi + at + 8 + size])
+    return dict(width=avih[8], height=avih[9], fps=rate / scale, frames=avih[4]), frames
 
 
 def read_y4m(path: str):

@@ -624,6 +624,38 @@ int64_t ide3d_png_out_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t 
 int ide3d_png_encode(const uint8_t* frames, int32_t n, int32_t h, int32_t w, int32_t c, int32_t filter_mode, int32_t segment_bytes,
                      void* workspace, int64_t workspace_bytes, uint8_t* out, int64_t out_capacity, int64_t* offsets, void* stream);
 
+/* ---- JPEG: colour, DCT, quantiser and Huffman coding --------------------------------------------- */
+/*
+ * The compression behind the Motion-JPEG video sink that stands in for
+ * `imageio.get_writer(mp4, mode='I', fps=60, codec='libx264', bitrate='10M')` (gen_videos.py:108,131),
+ * and `.jpg` stills: frames uint8 [n, h, w, c] contiguous, c = 1 (grey) or 3 (RGB), sides
+ * 1..65535, to the n entropy-coded scans of their baseline JPEG files (everything between the SOS
+ * header and EOI: the restart intervals with their RSTm markers), back to back in `out`; scan k is
+ * out[offsets[k], offsets[k + 1]), offsets int64 [n + 1] in device memory.  The caller adds SOI,
+ * APP0, DQT, SOF0, DHT, DRI, SOS and EOI.  training/jpeg.py states every integer of the stream and
+ * holds the host definition that gives the same bytes: full-range JFIF Y'CbCr in 16-bit fixed
+ * point; subsampling 444 (8 x 8 MCU) or 420 (16 x 16 MCU, chroma (a + b + c + d + 2) >> 2, RGB
+ * only) after edge replication to whole MCUs; an integer matrix DCT (13-bit table, 3 fractional
+ * bits after each pass, error at most 0.49 of a coefficient unit); T.81 Annex K tables scaled by
+ * `quality` 1..100 with the IJG rule, division rounding half away from zero; Annex K's Huffman
+ * tables; restart intervals of `restart_interval` MCUs (1..65535), each starting with DC
+ * predictors 0, padded with 1-bits to a byte, FF stuffed with 00, followed by RSTm (m = index
+ * mod 8) except the frame's last.  Three launches (interval, scan, compact); integer arithmetic,
+ * integer LDS atomics only: two runs are bit-equal.
+ * workspace: ide3d_jpeg_workspace_bytes() bytes (-1: unsupported call), 16-byte aligned: one
+ * worst-case slot per interval, their sizes and positions.  out_capacity >= ide3d_jpeg_out_bytes()
+ * = n * sum over the frame's intervals of 2 * ceil(1658 * blocks / 8) + 2 (a block is at most
+ * 20 + 63 * 26 bits, every byte stuffed).  Refused with IDE3D_EINVAL before any launch: c not in
+ * {1, 3}, quality outside 1..100, an unknown subsampling, 420 with c = 1, restart_interval
+ * outside 1..65535, an empty axis, a side above 65535, a workspace or out below those sizes, and
+ * any of the frames, the workspace or out at or above 2^31 bytes.
+ */
+int64_t ide3d_jpeg_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t subsampling, int32_t restart_interval);
+int64_t ide3d_jpeg_out_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t subsampling, int32_t restart_interval);
+int ide3d_jpeg_encode(const uint8_t* frames, int32_t n, int32_t h, int32_t w, int32_t c, int32_t quality, int32_t subsampling,
+                      int32_t restart_interval, void* workspace, int64_t workspace_bytes, uint8_t* out, int64_t out_capacity,
+                      int64_t* offsets, void* stream);
+
 /* ---- modulated 3x3 / 1x1 convolution (MFMA implicit GEMM) --------------------------------- */
 /*
  * Replaces the ATen conv behind `conv2d_gradfix.conv2d` for the StyleGAN2 modulated

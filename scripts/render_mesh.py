@@ -3,7 +3,8 @@ with the rasterizer of csrc/raster.hip in place of pyrender / trimesh (DESIGN.md
 
     python scripts/render_mesh.py --fname out/1.npy --size 256 --sigma-threshold 10 --w-frames 240 --outdir out
 
-writes <outdir>/render.y4m (`ffmpeg -i render.y4m render.mp4` makes the reference's file).  `--size` is the reference's cube side: the
+writes <outdir>/render.y4m (`ffmpeg -i render.y4m render.mp4` makes the reference's file), or with `--format avi` <outdir>/render.avi:
+Motion-JPEG compressed on the device (`video_render.write_avi`).  `--size` is the reference's cube side: the
 vertices are divided by it (render_mesh.py:32).  With `--colors` or `--labels` and a generator pickle in `--fname` the mesh comes from
 `extract_mesh(vertex_attributes=True)` at `--size`^3 instead of a cube file, and the frames show the vertex colours or the semantic
 labels' palette.  The shading is ambient + diffuse Lambert, not pyrender's metallic-roughness model."""
@@ -31,6 +32,7 @@ def main():
     ap.add_argument('--labels', action='store_true', help='generator pickle: shade with the semantic labels\' palette')
     ap.add_argument('--seed', type=int, default=0, help='generator pickle: the latent\'s seed')
     ap.add_argument('--image-size', type=int, default=512)
+    ap.add_argument('--format', choices=['y4m', 'avi'], default='y4m', help='y4m: raw 4:4:4 frames; avi: Motion-JPEG (quality 90, 4:2:0), 60 fps both')
     ap.add_argument('--device', default='cuda:0' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args()
     dev = torch.device(args.device)
@@ -46,9 +48,9 @@ def main():
     else:
         mesh = mesh_render.mesh_from_cube_file(args.fname, threshold=args.sigma_threshold, device=dev, normals=True, side=args.size)
     os.makedirs(args.outdir, exist_ok=True)
-    path = os.path.join(args.outdir, 'render.y4m')
+    path = os.path.join(args.outdir, 'render.' + args.format)
     frames = mesh_render.render_turntable(mesh, num_frames=args.w_frames, size=args.image_size)
-    count = video_render.write_y4m(frames, path)
+    count = (video_render.write_avi if args.format == 'avi' else video_render.write_y4m)(frames, path)
     print(f'{count} frames of {mesh["triangles"].shape[0]} triangles -> {path}')
 
 
