@@ -414,6 +414,11 @@ def load():
             'ide3d_jpeg_workspace_bytes': [i32, i32, i32, i32, i32, i32],
             'ide3d_jpeg_out_bytes': [i32, i32, i32, i32, i32, i32],
             'ide3d_jpeg_encode': [vp, i32, i32, i32, i32, i32, i32, i32, vp, i64, vp, i64, vp, vp],
+            'ide3d_metrics_workspace_bytes': [i32, i64, i64, i32, i32],
+            'ide3d_feature_moments': [vp, i64, i32, i64, vp, vp, vp],
+            'ide3d_poly_kernel_sums': [vp, i64, i64, vp, i64, i64, i32, vp, vp, i32, i32, vp, i64, vp, vp],
+            'ide3d_knn_radii': [vp, i64, i32, i64, i32, vp, i64, vp, vp],
+            'ide3d_manifold_inside': [vp, i64, i64, vp, i64, i64, i32, vp, vp, i64, vp, vp],
             'ide3d_modconv2d': [ctypes.POINTER(_ModconvParams), vp],
             'ide3d_modconv2d_heads': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), vp],
             'ide3d_modconv2d_heads_gated': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), ctypes.POINTER(_PlaneGate), vp],
@@ -533,6 +538,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_plane_cells', 'ide3d_plane_tile_list', 'ide3d_modconv2d_heads_gated', 'ide3d_skip_upsample_add_cl_gated',
     'ide3d_png_workspace_bytes', 'ide3d_png_out_bytes', 'ide3d_png_encode',
     'ide3d_jpeg_workspace_bytes', 'ide3d_jpeg_out_bytes', 'ide3d_jpeg_encode',
+    'ide3d_metrics_workspace_bytes', 'ide3d_feature_moments', 'ide3d_poly_kernel_sums', 'ide3d_knn_radii', 'ide3d_manifold_inside',
 )
 
 
@@ -2190,6 +2196,85 @@ class JpegPlugin:
         return out, offsets
 
 
+class MetricsPlugin:
+    """Float64 moments and the fp32 pair engine's three epilogues on float32 CUDA features (csrc/metrics.hip): what
+    calc_metrics.py does with a detector's features.  `training.metrics` holds the host definitions, the formulas on top and the routing.
+    Every function works in the caller's buffers, on the current stream."""
+
+    POLY, RADII, INSIDE = 0, 1, 2
+
+    @staticmethod
+    def _features(x, what):
+        _require(isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim == 2 and x.shape[0] > 0 and x.shape[1] > 0
+                 and x.stride(1) == 1 and x.stride(0) >= x.shape[1], f'{what}: features must be a [n, d] float32 CUDA tensor with contiguous rows')
+        return int(x.shape[0]), int(x.shape[1]), int(x.stride(0))
+
+    @staticmethod
+    def _buffer(t, dtype, numel, dev, what):
+        _require(t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous() and t.numel() >= numel, f'{what}: needs a contiguous {dtype} buffer of {numel} elements on {dev}')
+
+    @staticmethod
+    def workspace_bytes(op, rows, cols, d, k_or_subsets):
+        nbytes = load().ide3d_metrics_workspace_bytes(int(op), int(rows), int(cols), int(d), int(k_or_subsets))
+        _require(nbytes >= 0, f'metrics: unsupported call (op {op}, {rows} x {cols} pairs, d = {d}, k or subsets = {k_or_subsets}): '
+                 '1 <= d <= 8192, 1 <= n <= 2^22, 1 <= k <= 7 < n, 2 <= m <= 4096, 1 <= subsets <= 4096')
+        return nbytes
+
+    @staticmethod
+    def workspace(op, rows, cols, d, k_or_subsets, device):
+        return torch.empty([max(16, MetricsPlugin.workspace_bytes(op, rows, cols, d, k_or_subsets))], dtype=torch.uint8, device=device)
+
+    @staticmethod
+    def feature_moments(x, raw_mean, raw_cov):
+        """raw_mean [d] += column sums of x, raw_cov [d, d] += x^T x, in float64, in place."""
+        n, d, stride = MetricsPlugin._features(x, 'feature_moments')
+        MetricsPlugin._buffer(raw_mean, torch.float64, d, x.device, 'feature_moments: raw_mean')
+        MetricsPlugin._buffer(raw_cov, torch.float64, d * d, x.device, 'feature_moments: raw_cov')
+        with _dev_guard(x.device):
+            rc = load().ide3d_feature_moments(_ptr(x), n, d, stride, _ptr(raw_mean), _ptr(raw_cov), _stream(x))
+        _check(rc, 'feature_moments')
+
+    @staticmethod
+    def poly_kernel_sums(x, y, xi, yi, workspace, sums):
+        """sums float64 [subsets, 3] <- the three polynomial-kernel sums of every subset; xi, yi int32 [subsets, m]."""
+        nx, d, sx = MetricsPlugin._features(x, 'poly_kernel_sums')
+        ny, dy, sy = MetricsPlugin._features(y, 'poly_kernel_sums')
+        _require(d == dy and y.device == x.device, 'poly_kernel_sums: x and y must share the feature width and the device')
+        _require(xi.ndim == 2 and xi.shape == yi.shape, 'poly_kernel_sums: xi and yi must be [subsets, m]')
+        subsets, m = int(xi.shape[0]), int(xi.shape[1])
+        MetricsPlugin._buffer(xi, torch.int32, subsets * m, x.device, 'poly_kernel_sums: xi')
+        MetricsPlugin._buffer(yi, torch.int32, subsets * m, x.device, 'poly_kernel_sums: yi')
+        MetricsPlugin._buffer(sums, torch.float64, subsets * 3, x.device, 'poly_kernel_sums: sums')
+        MetricsPlugin._buffer(workspace, torch.uint8, 0, x.device, 'poly_kernel_sums: workspace')
+        with _dev_guard(x.device):
+            rc = load().ide3d_poly_kernel_sums(_ptr(x), nx, sx, _ptr(y), ny, sy, d, _ptr(xi), _ptr(yi), subsets, m, _ptr(workspace), workspace.numel(), _ptr(sums), _stream(x))
+        _check(rc, 'poly_kernel_sums')
+
+    @staticmethod
+    def knn_radii(f, k, workspace, radii_sq):
+        """radii_sq float32 [n] <- the squared distance of every row to its k-th nearest other row."""
+        n, d, stride = MetricsPlugin._features(f, 'knn_radii')
+        MetricsPlugin._buffer(radii_sq, torch.float32, n, f.device, 'knn_radii: radii_sq')
+        MetricsPlugin._buffer(workspace, torch.uint8, 0, f.device, 'knn_radii: workspace')
+        with _dev_guard(f.device):
+            rc = load().ide3d_knn_radii(_ptr(f), n, d, stride, int(k), _ptr(workspace), workspace.numel(), _ptr(radii_sq), _stream(f))
+        _check(rc, 'knn_radii')
+
+    @staticmethod
+    def manifold_inside(probes, manifold, radii_sq, workspace, inside):
+        """inside uint8 [np] <- 1 where the probe lies within the radius of some manifold row."""
+        n_p, d, sp = MetricsPlugin._features(probes, 'manifold_inside')
+        n_m, dm, sm = MetricsPlugin._features(manifold, 'manifold_inside')
+        _require(d == dm and manifold.device == probes.device, 'manifold_inside: probes and manifold must share the feature width and the device')
+        MetricsPlugin._buffer(radii_sq, torch.float32, n_m, probes.device, 'manifold_inside: radii_sq')
+        MetricsPlugin._buffer(inside, torch.uint8, n_p, probes.device, 'manifold_inside: inside')
+        MetricsPlugin._buffer(workspace, torch.uint8, 0, probes.device, 'manifold_inside: workspace')
+        with _dev_guard(probes.device):
+            rc = load().ide3d_manifold_inside(_ptr(probes), n_p, sp, _ptr(manifold), n_m, sm, d, _ptr(radii_sq), _ptr(workspace), workspace.numel(), _ptr(inside),
+                                              _stream(probes))
+        _check(rc, 'manifold_inside')
+
+
 class RasterPlugin:
     """Triangle rasterizer on float32 CUDA meshes (csrc/raster.hip): the pyrender step of render_mesh.py:36-61.
     `training.mesh_render` prepares the arguments (camera inversion in float64, the pixel grid) and holds the host definition."""
@@ -3225,6 +3310,7 @@ PLUGINS = {
     'raster_plugin': RasterPlugin,
     'png_plugin': PngPlugin,
     'jpeg_plugin': JpegPlugin,
+    'metrics_plugin': MetricsPlugin,
     'lowres_plugin': LowresPlugin,
     'bias_act_plugin': BiasActPlugin,
     'upfirdn2d_plugin': Upfirdn2dPlugin,

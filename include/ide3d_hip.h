@@ -656,6 +656,57 @@ int ide3d_jpeg_encode(const uint8_t* frames, int32_t n, int32_t h, int32_t w, in
                       int32_t restart_interval, void* workspace, int64_t workspace_bytes, uint8_t* out, int64_t out_capacity,
                       int64_t* offsets, void* stream);
 
+/* ---- generator metrics on detector features: FID moments, KID sums, precision / recall ---- */
+/*
+ * What calc_metrics.py does with a detector's features once they exist.  Features are fp32,
+ * row-major, K-contiguous, with a row stride >= d in elements.  Limits, refused beyond with
+ * IDE3D_EINVAL before the first launch: 1 <= d <= 8192, 1 <= n <= 2^22 rows, 1 <= k <= 7,
+ * 2 <= m <= 4096, 1 <= subsets <= 4096; also null pointers, a row stride below d and a workspace
+ * below ide3d_metrics_workspace_bytes() or not 16-byte aligned.  No float atomics: every output
+ * has one owner or is reduced from per-workgroup partials by a second launch in a fixed order,
+ * so two runs are bit-equal.
+ *
+ * ide3d_feature_moments replaces `FeatureStats.append` (metrics/metric_utils.py:107-122):
+ *   raw_mean[j] += sum_i x[i,j], raw_cov[j,k] += sum_i x[i,j] * x[i,k], float64 sums (one FMA per
+ *   row in row order, products exact) into the caller's running [d] and [d, d] buffers.  Both
+ *   triangles of raw_cov are written from one computed value (read from the upper one).
+ *
+ * The other three run on one pair engine: A[rows, d] . B[cols, d]^T in 128 x 128 tiles on
+ * v_mfma_f32_32x32x2f32, each dot product one chain over k in order with fp32 rounding, the same
+ * bits for (a, b) and (b, a).  The pair matrix is never written out.
+ *
+ * ide3d_poly_kernel_sums replaces the subset loop of metrics/kernel_inception_distance.py:34-43:
+ *   xi, yi int32 [subsets, m] row indices into x [nx, d] and y [ny, d] (clamped into range);
+ *   sums float64 [subsets, 3] = (sum_{i != j} p(x_i, x_j), sum_{i != j} p(y_i, y_j),
+ *   sum_{i, j} p(x_i, y_j)) over the positions i, j of the subset, p(a, b) = (dot(a, b) / d + 1)^3
+ *   with the division, the cube and the sums in float64.
+ *
+ * ide3d_knn_radii and ide3d_manifold_inside replace metrics/precision_recall.py:19-59:
+ *   d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 dot(a, b)) in fp32, the squared norms summed in float64
+ *   and rounded once to fp32 (a launch of their own, into the workspace).
+ *   radii_sq[i] = the (k + 1)-th smallest over all j of d2(f_i, f_j), the pair j == i counting as
+ *   exactly 0 (`kthvalue(nhood_size + 1)` over a row that holds the point itself); n <= k refused.
+ *   inside[p] (uint8) = 1 when d2(probe_p, manifold_j) <= radii_sq[j] for some j, else 0.
+ *
+ * ide3d_metrics_workspace_bytes(op, rows, cols, d, k_or_subsets): rows x cols are the sides of the
+ * pair matrix (m, m for POLY; n, n for RADII; np, nm for INSIDE); -1 for arguments the entry
+ * points refuse.  POLY: 8 bytes per (subset, sum, tile).  RADII: n norms, then 8 candidates per
+ * row and column split.  INSIDE: np + nm norms, then one byte per probe and column split.  Row
+ * tiles = ceil(rows / 128), column splits = min(column tiles, max(1, 1024 / row tiles)).
+ */
+#define IDE3D_METRICS_POLY   0
+#define IDE3D_METRICS_RADII  1
+#define IDE3D_METRICS_INSIDE 2
+int64_t ide3d_metrics_workspace_bytes(int32_t op, int64_t rows, int64_t cols, int32_t d, int32_t k_or_subsets);
+int ide3d_feature_moments(const float* x, int64_t n, int32_t d, int64_t row_stride, double* raw_mean, double* raw_cov, void* stream);
+int ide3d_poly_kernel_sums(const float* x, int64_t nx, int64_t x_stride, const float* y, int64_t ny, int64_t y_stride, int32_t d,
+                           const int32_t* xi, const int32_t* yi, int32_t subsets, int32_t m, void* workspace, int64_t workspace_bytes,
+                           double* sums, void* stream);
+int ide3d_knn_radii(const float* f, int64_t n, int32_t d, int64_t row_stride, int32_t k, void* workspace, int64_t workspace_bytes, float* radii_sq,
+                    void* stream);
+int ide3d_manifold_inside(const float* probes, int64_t np, int64_t probe_stride, const float* manifold, int64_t nm, int64_t manifold_stride,
+                          int32_t d, const float* radii_sq, void* workspace, int64_t workspace_bytes, uint8_t* inside, void* stream);
+
 /* ---- modulated 3x3 / 1x1 convolution (MFMA implicit GEMM) --------------------------------- */
 /*
  * Replaces the ATen conv behind `conv2d_gradfix.conv2d` for the StyleGAN2 modulated
