@@ -419,6 +419,9 @@ def load():
             'ide3d_poly_kernel_sums': [vp, i64, i64, vp, i64, i64, i32, vp, vp, i32, i32, vp, i64, vp, vp],
             'ide3d_knn_radii': [vp, i64, i32, i64, i32, vp, i64, vp, vp],
             'ide3d_manifold_inside': [vp, i64, i64, vp, i64, i64, i32, vp, vp, i64, vp, vp],
+            'ide3d_augment_geometric': [vp, vp, i32, i32, i32, i32, i64, i64, vp, vp, vp, vp, vp, vp],
+            'ide3d_augment_geometric_backward': [vp, vp, i32, i32, i32, i32, i64, i64, vp, vp, vp, vp, vp],
+            'ide3d_augment_color': [vp, vp, i32, i32, i64, i64, i64, vp, i32, vp],
             'ide3d_modconv2d': [ctypes.POINTER(_ModconvParams), vp],
             'ide3d_modconv2d_heads': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), vp],
             'ide3d_modconv2d_heads_gated': [ctypes.POINTER(_ModconvParams), ctypes.POINTER(_ModconvHeadEpilogue), ctypes.POINTER(_PlaneGate), vp],
@@ -539,6 +542,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_png_workspace_bytes', 'ide3d_png_out_bytes', 'ide3d_png_encode',
     'ide3d_jpeg_workspace_bytes', 'ide3d_jpeg_out_bytes', 'ide3d_jpeg_encode',
     'ide3d_metrics_workspace_bytes', 'ide3d_feature_moments', 'ide3d_poly_kernel_sums', 'ide3d_knn_radii', 'ide3d_manifold_inside',
+    'ide3d_augment_geometric', 'ide3d_augment_geometric_backward', 'ide3d_augment_color',
 )
 
 
@@ -2275,6 +2279,83 @@ class MetricsPlugin:
         _check(rc, 'manifold_inside')
 
 
+class AugmentPlugin:
+    """The geometric and colour stages of the ADA pipeline on float32 CUDA images (csrc/augment.hip): what
+    training/augment.py:290-306 and 363-368 do, as one launch each way.  `training.augment` draws the parameters, folds the matrices and
+    holds the PyTorch definition.  Every function works in the caller's buffers, on the current stream, and reads nothing back."""
+
+    _band_loops = {}         # device index -> int32 [1]: workgroups whose window of U exceeded the LDS budget (they looped over pieces)
+
+    @staticmethod
+    def _images(x, what):
+        _require(isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim == 4 and x.is_contiguous(),
+                 f'{what}: images must be a contiguous [n, c, h, w] float32 CUDA tensor')
+        return [int(v) for v in x.shape]
+
+    @staticmethod
+    def _buffer(t, dtype, numel, dev, what):
+        _require(isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous() and t.numel() >= numel,
+                 f'{what}: needs a contiguous {dtype} buffer of {numel} elements on {dev}')
+
+    @staticmethod
+    def _counter(dev):
+        key = dev.index if dev.index is not None else torch.cuda.current_device()
+        t = AugmentPlugin._band_loops.get(key)
+        if t is None:
+            t = AugmentPlugin._band_loops[key] = torch.zeros([1], dtype=torch.int32, device=dev)
+        return t
+
+    @staticmethod
+    def band_loops(device):
+        """Workgroups of `geometric` on `device` so far that split their tile because its window exceeded the LDS budget (reads the device)."""
+        return int(AugmentPlugin._counter(torch.device(device)).item())
+
+    @staticmethod
+    def _common(x, out, coords, margins, taps, color, what):
+        n, c, h, w = AugmentPlugin._images(x, what)
+        _require(isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.device == x.device,
+                 f'{what}: the output must be a contiguous float32 buffer on {x.device}')
+        AugmentPlugin._buffer(coords, torch.float32, n * 6, x.device, f'{what}: coords')
+        AugmentPlugin._buffer(margins, torch.int32, 4, x.device, f'{what}: margins')
+        AugmentPlugin._buffer(taps, torch.float32, 12, x.device, f'{what}: taps')
+        _require(taps.numel() == 12, f'{what}: the geometric filter must have 12 taps (got {taps.numel()})')
+        if color is not None:
+            AugmentPlugin._buffer(color, torch.float32, n * 12, x.device, f'{what}: color')
+        return n, c, h, w
+
+    @staticmethod
+    def geometric(x, out, coords, margins, taps, color=None):
+        """out [n, c, h, w] <- the geometric stage of x under coords [n, 6] and the device margins [4]; then the colour matrix [n, 12] if given."""
+        n, c, h, w = AugmentPlugin._common(x, out, coords, margins, taps, color, 'augment_geometric')
+        with _dev_guard(x.device):
+            rc = load().ide3d_augment_geometric(_ptr(x), _ptr(out), n, c, h, w, x.numel(), out.numel(), _ptr(coords), _ptr(margins), _ptr(taps), _ptr(color),
+                                                _ptr(AugmentPlugin._counter(x.device)), _stream(x))
+        _check(rc, 'augment_geometric')
+        return out
+
+    @staticmethod
+    def geometric_backward(grad_out, grad_images, coords, margins, taps, color=None):
+        """grad_images (zero-filled by the caller) += the transpose of `geometric` applied to grad_out."""
+        n, c, h, w = AugmentPlugin._common(grad_out, grad_images, coords, margins, taps, color, 'augment_geometric_backward')
+        with _dev_guard(grad_out.device):
+            rc = load().ide3d_augment_geometric_backward(_ptr(grad_out), _ptr(grad_images), n, c, h, w, grad_out.numel(), grad_images.numel(), _ptr(coords),
+                                                         _ptr(margins), _ptr(taps), _ptr(color), _stream(grad_out))
+        _check(rc, 'augment_geometric_backward')
+        return grad_images
+
+    @staticmethod
+    def color(x, out, color, transpose=False):
+        """out <- color[:, :3, :3] @ x + color[:, :3, 3] per pixel (3 channels; row 0 as scale and offset for 1); transpose: the backward."""
+        n, c, h, w = AugmentPlugin._images(x, 'augment_color')
+        _require(isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.device == x.device,
+                 f'augment_color: the output must be a contiguous float32 buffer on {x.device}')
+        AugmentPlugin._buffer(color, torch.float32, n * 12, x.device, 'augment_color: color')
+        with _dev_guard(x.device):
+            rc = load().ide3d_augment_color(_ptr(x), _ptr(out), n, c, h * w, x.numel(), out.numel(), _ptr(color), int(bool(transpose)), _stream(x))
+        _check(rc, 'augment_color')
+        return out
+
+
 class RasterPlugin:
     """Triangle rasterizer on float32 CUDA meshes (csrc/raster.hip): the pyrender step of render_mesh.py:36-61.
     `training.mesh_render` prepares the arguments (camera inversion in float64, the pixel grid) and holds the host definition."""
@@ -3311,6 +3392,7 @@ PLUGINS = {
     'png_plugin': PngPlugin,
     'jpeg_plugin': JpegPlugin,
     'metrics_plugin': MetricsPlugin,
+    'augment_plugin': AugmentPlugin,
     'lowres_plugin': LowresPlugin,
     'bias_act_plugin': BiasActPlugin,
     'upfirdn2d_plugin': Upfirdn2dPlugin,

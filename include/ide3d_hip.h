@@ -707,6 +707,40 @@ int ide3d_knn_radii(const float* f, int64_t n, int32_t d, int64_t row_stride, in
 int ide3d_manifold_inside(const float* probes, int64_t np, int64_t probe_stride, const float* manifold, int64_t nm, int64_t manifold_stride,
                           int32_t d, const float* radii_sq, void* workspace, int64_t workspace_bytes, uint8_t* inside, void* stream);
 
+/* ---- adaptive discriminator augmentation: the geometric and colour stages ---- */
+/*
+ * ide3d_augment_geometric replaces training/augment.py:290-306 (reflect F.pad, upsample2d,
+ * affine_grid + grid_sample, downsample2d) with one launch and no intermediate in device memory:
+ *   P[i, j] = x[r(i - my0), r(j - mx0)], r = one reflection; zero outside the padded extent;
+ *   U[j]    = 2 * sum_k taps[k] * P[(j + 5 - k) / 2] over the k with j + 5 - k even, per axis;
+ *   S[i, j] = bilinear sample (zero outside U) of U at (coords[0] j + coords[1] i + coords[2],
+ *             coords[3] j + coords[4] i + coords[5]), for 0 <= i < 2 (h + 6), 0 <= j < 2 (w + 6);
+ *   y[o]    = sum_k taps[k] * S[2 o + 1 + k], per axis: exactly [h, w].
+ * x, y [n, c, h, w] contiguous float32.  margins = (mx0, my0, mx1, my1): four int32 ON THE DEVICE
+ * (augment.py:278-288, batch-wide), clamped to [0, side - 1] again by the kernel.  coords [n, 6]
+ * on the device: lines 292-301 and the two unnormalisations of affine_grid / grid_sample folded
+ * into one map from S pixel indices to U pixel coordinates.  taps: the 12 floats of Hz_geom on
+ * the device.  color: NULL, or [n, 12] = rows of the 3 x 4 matrix of augment.py:365 applied to
+ * the result (c == 3), row 0 as (scale, -, -, offset) for c == 1 (augment.py:367-368).
+ * band_loops: NULL, or one int32 on the device that every workgroup raises by one when the
+ * window of U under its S tile exceeded its LDS budget and it looped over pieces of the tile.
+ * ide3d_augment_geometric_backward is the transpose with respect to x (colour transpose without
+ * the offset first): grad_images must be zero-filled, float atomic adds, so two runs agree to
+ * rounding and not bit for bit.  ide3d_augment_color is the colour stage alone (lines 363-368),
+ * plane = h * w, transpose != 0 for its backward.
+ * Refused with IDE3D_EINVAL before any launch: an empty axis, h < 2 or w < 2, a side above
+ * 16384, n or c above 65535, a buffer shorter than n c h w floats, null or misaligned pointers,
+ * a colour matrix with c other than 3 or 1.
+ */
+int ide3d_augment_geometric(const float* x, float* y, int32_t n, int32_t c, int32_t h, int32_t w, int64_t x_numel, int64_t y_numel,
+                            const float* coords, const int32_t* margins, const float* taps, const float* color, int32_t* band_loops,
+                            void* stream);
+int ide3d_augment_geometric_backward(const float* grad_out, float* grad_images, int32_t n, int32_t c, int32_t h, int32_t w, int64_t grad_out_numel,
+                                     int64_t grad_images_numel, const float* coords, const int32_t* margins, const float* taps,
+                                     const float* color, void* stream);
+int ide3d_augment_color(const float* x, float* y, int32_t n, int32_t c, int64_t plane, int64_t x_numel, int64_t y_numel, const float* color,
+                        int32_t transpose, void* stream);
+
 /* ---- modulated 3x3 / 1x1 convolution (MFMA implicit GEMM) --------------------------------- */
 /*
  * Replaces the ATen conv behind `conv2d_gradfix.conv2d` for the StyleGAN2 modulated
