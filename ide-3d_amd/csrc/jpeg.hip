@@ -11,7 +11,7 @@
 //             totals summed over the chunk; bits ORed MSB-first into LDS words; whole bytes stuffed (FF -> FF 00, counted and scanned
 //             over the workgroup) into the interval's slot of the workspace, the 0..7 bits left over carried to the next chunk.
 //             Coefficients never reach HBM.  The default restart interval is one chunk, so the loop runs once.
-//   scan      one workgroup: exclusive scan of the interval sizes (+ 2 per RSTm) -> the position of every interval in `out`, `offsets`
+//   scan      segment_positions_kernel (block_scan.h): the position of every interval in `out` (2 bytes per RSTm), `offsets`
 //   compact   one workgroup per interval: slot -> out, RSTm after every interval but a frame's last
 //
 // Worst case: a block is at most 20 bits of DC (9-bit code + 11-bit amplitude) and 63 x 26 bits of AC (16-bit code + 10-bit amplitude; a
@@ -19,7 +19,7 @@
 // 1-bit padding, twice that when every byte is FF and stuffed, plus 2 for RSTm: the slot size and ide3d_jpeg_out_bytes follow from it.
 //
 // LDS atomics (integer or) only where the result does not depend on order: two runs are bit-equal.
-#include "common.h"
+#include "block_scan.h"
 
 namespace ide3d {
 
@@ -29,7 +29,6 @@ constexpr int kJpegChunk = 32;                           // blocks per pass: 8 r
 constexpr int kJpegPerWave = kJpegChunk / kJpegWaves;    // blocks a wave codes per pass
 constexpr int kJpegBlockBits = 20 + 63 * 26;
 constexpr int kJpegBitWords = (kJpegChunk * kJpegBlockBits + 7 + 31) / 32 + 3;          // 7 carried bits; a put touches 3 words
-constexpr int kJpegScanThreads = 1024;
 
 struct JpegShape {
     int N, H, W, C;
@@ -269,12 +268,7 @@ jpeg_interval_kernel(const uint8_t* __restrict__ frames, const JpegShape s, int 
                 const unsigned e = s_huff[2 + tab][0];
                 tok[i] = e >> 5; tn[i] = (int)(e & 31);
             }
-            int inc = tn[i];
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) {
-                const int up = __shfl_up(inc, d);
-                if (lane >= d) inc += up;
-            }
+            const int inc = wave_inclusive_scan(tn[i]);
             tat[i] = inc - tn[i];
             if (lane == kWave - 1) s_blockbits[blk] = inc;
         }
@@ -299,17 +293,8 @@ jpeg_interval_kernel(const uint8_t* __restrict__ frames, const JpegShape s, int 
         const int lo = min(tid * per, nbytes), hi = min(lo + per, nbytes);
         int ff = 0;
         for (int i = lo; i < hi; ++i) ff += jpeg_byte(s_bits, i) == 255u;
-        int inc = ff;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int up = __shfl_up(inc, d);
-            if (lane >= d) inc += up;
-        }
-        if (lane == kWave - 1) s_wave[wave] = inc;
-        __syncthreads();
-        int before = inc - ff, total = 0;
-#pragma unroll
-        for (int w = 0; w < kJpegWaves; ++w) { if (w < wave) before += s_wave[w]; total += s_wave[w]; }
+        int total;
+        const int before = block_exclusive_scan<kJpegThreads, true>(ff, s_wave, total);          // fresh: two barriers end every pass of this loop
         if ((int64_t)written + nbytes + total <= s.slot) {   // always: the slot is the worst case
             uint8_t* dst = slot + written + lo + before;
             for (int i = lo; i < hi; ++i) {
@@ -333,36 +318,6 @@ jpeg_interval_kernel(const uint8_t* __restrict__ frames, const JpegShape s, int 
 
 // ---- stage b: scan and compact ----------------------------------------------------------------------------------------------------
 
-// One workgroup.  pos[g] = where interval g starts in `out`: the sizes before it plus 2 bytes for every RSTm before it (g - frame index).
-__global__ void __launch_bounds__(kJpegScanThreads)
-jpeg_scan_kernel(const unsigned* __restrict__ sizes, const JpegShape s, long long* __restrict__ pos, long long* __restrict__ offsets) {
-    __shared__ long long s_w[kJpegScanThreads / kWave];
-    const int64_t per = cdiv64(s.T, kJpegScanThreads);
-    const int64_t lo = min((int64_t)threadIdx.x * per, s.T), hi = min(lo + per, s.T);
-    long long sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += sizes[i];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long inc = sum;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const long long upv = __shfl_up(inc, d);
-        if (lane >= d) inc += upv;
-    }
-    if (lane == kWave - 1) s_w[wave] = inc;
-    __syncthreads();
-    long long before = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < kJpegScanThreads / kWave; ++i) { if (i < wave) before += s_w[i]; total += s_w[i]; }
-    long long run = before + inc - sum;
-    for (int64_t i = lo; i < hi; ++i) {
-        const int64_t f = i / s.I;
-        pos[i] = run + 2 * (i - f);
-        if (i - f * s.I == 0) offsets[f] = run + 2 * (i - f);
-        run += sizes[i];
-    }
-    if (threadIdx.x == 0) offsets[s.N] = total + 2ll * (s.T - s.N);
-}
-
 __global__ void __launch_bounds__(kJpegThreads)
 jpeg_compact_kernel(const uint8_t* __restrict__ slots, const unsigned* __restrict__ sizes, const long long* __restrict__ pos, const JpegShape s,
                     uint8_t* __restrict__ out, int64_t out_capacity) {
@@ -373,7 +328,9 @@ jpeg_compact_kernel(const uint8_t* __restrict__ slots, const unsigned* __restric
     const bool marker = it != s.I - 1;
     if (size > s.slot || at < 0 || at + size + (marker ? 2 : 0) > out_capacity) return;      // cannot happen for sizes this call wrote
     const uint8_t* const slot = slots + g * s.slot;
-    for (int64_t i = threadIdx.x; i < size; i += kJpegThreads) out[at + i] = slot[i];
+    // reads the slot below size + 16 <= s.slot + 16: slots are multiples of 16 bytes, and the last one is followed inside the workspace by
+    // the sizes section of at least 16 bytes (jpeg_sizes_offset)
+    copy_slot_bytes(out + at, slot, (int)size, (int)threadIdx.x, kJpegThreads);
     if (marker && threadIdx.x == 0) { out[at + size] = 0xFF; out[at + size + 1] = (uint8_t)(0xD0 + (it & 7)); }
 }
 
@@ -401,12 +358,8 @@ extern "C" int ide3d_jpeg_encode(const uint8_t* frames, int32_t n, int32_t h, in
     IDE3D_CHECK_ARG(restart_interval >= 1 && restart_interval <= 65535, "jpeg_encode: restart_interval must be 1..65535 MCUs (got %d)", restart_interval);
     IDE3D_CHECK_ARG(jpeg_shape(n, h, w, c, subsampling, restart_interval, s),
                     "jpeg_encode: %d frames of %d x %d x %d: an empty axis, a side above 65535, or 2 GiB or more in one call", n, h, w, c);
-    IDE3D_CHECK_ARG(frames && workspace && out && offsets, "jpeg_encode: null pointer");
-    IDE3D_CHECK_ARG(workspace_bytes >= jpeg_workspace(s) && ptr_aligned(workspace, 16), "jpeg_encode: workspace smaller than %lld bytes or not 16-byte aligned",
-                    (long long)jpeg_workspace(s));
-    IDE3D_CHECK_ARG(out_capacity >= (int64_t)n * s.worst && out_capacity < (1ll << 31), "jpeg_encode: out holds %lld bytes, the worst case is %lld (and below 2 GiB)",
-                    (long long)out_capacity, (long long)((int64_t)n * s.worst));
-    IDE3D_CHECK_ARG(ptr_aligned(offsets, 8), "jpeg_encode: offsets must be 8-byte aligned");
+    if (const int rc = check_stream_buffers("jpeg_encode", frames, workspace, workspace_bytes, jpeg_workspace(s), out, out_capacity, (int64_t)n * s.worst, offsets))
+        return rc;
     uint8_t* const ws = static_cast<uint8_t*>(workspace);
     unsigned* const sizes = reinterpret_cast<unsigned*>(ws + jpeg_sizes_offset(s));
     long long* const pos = reinterpret_cast<long long*>(ws + jpeg_pos_offset(s));
@@ -416,7 +369,9 @@ extern "C" int ide3d_jpeg_encode(const uint8_t* frames, int32_t n, int32_t h, in
     else if (s.mode == 1) hipLaunchKernelGGL(jpeg_interval_kernel<1>, grid, block, 0, st, frames, s, (int)quality, ws, sizes);
     else hipLaunchKernelGGL(jpeg_interval_kernel<2>, grid, block, 0, st, frames, s, (int)quality, ws, sizes);
     IDE3D_CHECK_LAUNCH("jpeg_interval");
-    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(kJpegScanThreads), 0, st, sizes, s, pos, reinterpret_cast<long long*>(offsets));
+    // RSTm: 2 bytes between two intervals of one frame
+    hipLaunchKernelGGL(segment_positions_kernel, dim3(1), dim3(kScanThreads), 0, st, sizes, 1, s.T, (int64_t)s.I, (int64_t)s.N, 0, 2, 0, pos,
+                       reinterpret_cast<long long*>(offsets));
     IDE3D_CHECK_LAUNCH("jpeg_scan");
     hipLaunchKernelGGL(jpeg_compact_kernel, grid, block, 0, st, ws, sizes, pos, s, out, out_capacity);
     IDE3D_CHECK_LAUNCH("jpeg_compact");

@@ -8,11 +8,11 @@
 //   deflate   one workgroup per segment of `segment_bytes` filtered bytes: Adler-32 partial sums, run tokens (literal + distance-1
 //             matches), histogram, length-limited Huffman lengths, the dynamic header, bit packing in LDS; or one stored block.  The
 //             segment's bytes go to its own slot of the workspace (at most n + 5 bytes)
-//   scan      one workgroup: exclusive scan of the segment sizes -> the position of every segment in `out`, `offsets`
+//   scan      segment_positions_kernel (block_scan.h): the position of every segment in `out`, `offsets`
 //   compact   one workgroup per segment: slot -> out; the frame's first segment also writes 78 01 and the combined Adler-32
 //
 // LDS atomics (integer add / or) only where the result does not depend on order: two runs are bit-equal.
-#include "common.h"
+#include "block_scan.h"
 
 namespace ide3d {
 
@@ -24,7 +24,6 @@ constexpr int kPngClSyms = 19;
 constexpr int kPngMinSeg = 1024, kPngMaxSeg = 32768;
 constexpr int kPngSlotPad = 32;                     // slot = segment_bytes + 32: n + 5 rounded up to 16, and one 16-byte group of read-ahead
 constexpr unsigned kAdler = 65521u;
-constexpr int kScanThreads = 1024;
 
 struct PngShape {
     int N, H, W, C;
@@ -418,23 +417,14 @@ png_deflate_kernel(const uint8_t* __restrict__ filtered, const PngShape s, uint8
         s_misc[3] = hclen; s_misc[4] = bits;
     }
 
-    // bits of this thread's tokens, their exclusive prefix over the workgroup
+    // bits of this thread's tokens, their exclusive prefix over the workgroup (`before`) and their sum (`body`)
     int mybits = 0;
     png_walk(s_data, lo, hi, next, [&](int v, int length, int count) {
         if (length) { int sym, eb, ev; png_length_code(length, sym, eb, ev); mybits += count * (s_len[sym] + eb + 1); }
         else mybits += count * s_len[v];
     });
-    int inc = mybits;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int upv = __shfl_up(inc, d);
-        if (lane >= d) inc += upv;
-    }
-    if (lane == kWave - 1) s_bits[wave] = inc;
-    __syncthreads();
-    int before = 0, body = 0;
-#pragma unroll
-    for (int w = 0; w < kPngDeflateThreads / kWave; ++w) { if (w < wave) before += s_bits[w]; body += s_bits[w]; }
+    int body;
+    const int before = block_exclusive_scan<kPngDeflateThreads, true>(mybits, s_bits, body);          // s_bits is used here only; its barrier also publishes s_misc[3..4]
     const int header = s_misc[4];
     const int bits = header + body + s_len[256];
     const int dyn_size = final ? (bits + 7) >> 3 : ((bits + 3 + 7) >> 3) + 4;
@@ -459,7 +449,7 @@ png_deflate_kernel(const uint8_t* __restrict__ filtered, const PngShape s, uint8
             }
         }
         __syncthreads();
-        int pos = header + before + inc - mybits;
+        int pos = header + before;
         png_walk(s_data, lo, hi, next, [&](int v, int length, int count) {
             unsigned value; int nb;
             if (length) {
@@ -490,62 +480,6 @@ png_deflate_kernel(const uint8_t* __restrict__ filtered, const PngShape s, uint8
 
 // ---- stage c: scan and compact ----------------------------------------------------------------------------------------------------
 
-// One workgroup.  pos[g] = where segment g starts in `out`: the sizes before it plus 6 bytes (78 01, Adler-32) per earlier frame plus 2.
-__global__ void __launch_bounds__(kScanThreads)
-png_scan_kernel(const PngSegInfo* __restrict__ info, const PngShape s, long long* __restrict__ pos, long long* __restrict__ offsets) {
-    __shared__ long long s_w[kScanThreads / kWave];
-    const int64_t per = cdiv64(s.T, kScanThreads);
-    const int64_t lo = min((int64_t)threadIdx.x * per, s.T), hi = min(lo + per, s.T);
-    long long sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += info[i].size;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long inc = sum;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const long long upv = __shfl_up(inc, d);
-        if (lane >= d) inc += upv;
-    }
-    if (lane == kWave - 1) s_w[wave] = inc;
-    __syncthreads();
-    long long before = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < kScanThreads / kWave; ++i) { if (i < wave) before += s_w[i]; total += s_w[i]; }
-    long long run = before + inc - sum;
-    for (int64_t i = lo; i < hi; ++i) {
-        const int64_t f = i / s.S;
-        pos[i] = run + 6 * f + 2;
-        if (i - f * s.S == 0) offsets[f] = run + 6 * f;
-        run += info[i].size;
-    }
-    if (threadIdx.x == 0) offsets[s.N] = total + 6ll * s.N;
-}
-
-// 16 bytes starting `r` (0..15) bytes into the 32 bytes (a, b)
-__device__ __forceinline__ uint4 png_shift_bytes(const uint4 a, const uint4 b, int r) {
-    const unsigned w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const unsigned sh = (unsigned)(r & 3);
-    unsigned o[4];
-    switch (r >> 2) {                                  // uniform over the workgroup
-    case 0:
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], sh);
-        break;
-    case 1:
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = __builtin_amdgcn_alignbyte(w[j + 2], w[j + 1], sh);
-        break;
-    case 2:
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = __builtin_amdgcn_alignbyte(w[j + 3], w[j + 2], sh);
-        break;
-    default:
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = __builtin_amdgcn_alignbyte(w[j + 4], w[j + 3], sh);
-        break;
-    }
-    return make_uint4(o[0], o[1], o[2], o[3]);
-}
-
 __global__ void __launch_bounds__(kPngThreads)
 png_compact_kernel(const uint8_t* __restrict__ slots, const PngSegInfo* __restrict__ info, const long long* __restrict__ pos,
                    const long long* __restrict__ offsets, const PngShape s, uint8_t* __restrict__ out, int64_t out_capacity) {
@@ -558,19 +492,7 @@ png_compact_kernel(const uint8_t* __restrict__ slots, const PngSegInfo* __restri
     const int64_t at = pos[g];
     if (size > s.seg + 5 || at < 2 || at + size + 4 > out_capacity) return;      // cannot happen for sizes this call's deflate wrote
     const uint8_t* const slot = slots + g * (int64_t)(s.seg + kPngSlotPad);
-    uint8_t* const dst = out + at;
-    // head up to the first 16-byte boundary of the destination, aligned groups, tail
-    const int head = min(size, (int)((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15));
-    const int groups = (size - head) >> 4;
-    const int r = head & 15;                           // group k reads slot bytes [head + 16 k, +16): 16-byte aligned address + r
-    if (tid < head) dst[tid] = slot[tid];
-    for (int k = tid; k < groups; k += kPngThreads) {
-        const uint8_t* const p = slot + (head - r) + 16 * k;
-        const uint4 a = *reinterpret_cast<const uint4*>(p), b = *reinterpret_cast<const uint4*>(p + 16);   // p + 32 <= size + 16 <= slot size
-        *reinterpret_cast<uint4*>(dst + head + 16 * k) = png_shift_bytes(a, b, r);
-    }
-    const int tail0 = head + 16 * groups;
-    if (tid < size - tail0) dst[tail0 + tid] = slot[tail0 + tid];
+    copy_slot_bytes(out + at, slot, size, tid, kPngThreads);          // reads the slot below size + 16 <= seg + 21: kPngSlotPad covers it
 
     if (sg != 0) return;
     // the frame's Adler-32 from its segments' partial sums: with (A_k, B_k) of segment k on its own, n_k bytes at offset o_k of F,
@@ -621,12 +543,8 @@ extern "C" int ide3d_png_encode(const uint8_t* frames, int32_t n, int32_t h, int
                     "png_encode: segment_bytes must be a power of two in [%d, %d] (got %d)", kPngMinSeg, kPngMaxSeg, segment_bytes);
     IDE3D_CHECK_ARG(png_shape(n, h, w, c, segment_bytes, s), "png_encode: %d frames of %d x %d x %d: an empty axis, or 2 GiB or more in one call", n, h, w, c);
     IDE3D_CHECK_ARG(filter_mode >= 0 && filter_mode <= 5, "png_encode: filter_mode must be 0..4 (forced) or 5 (adaptive), got %d", filter_mode);
-    IDE3D_CHECK_ARG(frames && workspace && out && offsets, "png_encode: null pointer");
-    IDE3D_CHECK_ARG(workspace_bytes >= png_workspace(s) && ptr_aligned(workspace, 16), "png_encode: workspace smaller than %lld bytes or not 16-byte aligned",
-                    (long long)png_workspace(s));
-    IDE3D_CHECK_ARG(out_capacity >= png_worst_case(s) && out_capacity < (1ll << 31), "png_encode: out holds %lld bytes, the worst case is %lld (and below 2 GiB)",
-                    (long long)out_capacity, (long long)png_worst_case(s));
-    IDE3D_CHECK_ARG(ptr_aligned(offsets, 8), "png_encode: offsets must be 8-byte aligned");
+    if (const int rc = check_stream_buffers("png_encode", frames, workspace, workspace_bytes, png_workspace(s), out, out_capacity, png_worst_case(s), offsets))
+        return rc;
     uint8_t* const ws = static_cast<uint8_t*>(workspace);
     uint8_t* const filtered = ws;
     uint8_t* const slots = ws + png_slots_offset(s);
@@ -642,7 +560,9 @@ extern "C" int ide3d_png_encode(const uint8_t* frames, int32_t n, int32_t h, int
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(png_deflate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(png_deflate_kernel, dim3((unsigned)s.T), dim3(kPngDeflateThreads), lds, st, filtered, s, slots, info);
     IDE3D_CHECK_LAUNCH("png_deflate");
-    hipLaunchKernelGGL(png_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, info, s, pos, reinterpret_cast<long long*>(offsets));
+    // 78 01 and the Adler-32 per frame, the first two in front of the frame's first segment; PngSegInfo is 4 words, `size` the first
+    hipLaunchKernelGGL(segment_positions_kernel, dim3(1), dim3(kScanThreads), 0, st, reinterpret_cast<const unsigned*>(info), 4, s.T, (int64_t)s.S,
+                       (int64_t)s.N, 6, 0, 2, pos, reinterpret_cast<long long*>(offsets));
     IDE3D_CHECK_LAUNCH("png_scan");
     hipLaunchKernelGGL(png_compact_kernel, dim3((unsigned)s.T), dim3(kPngThreads), 0, st, slots, info, pos, reinterpret_cast<const long long*>(offsets),
                        s, out, out_capacity);

@@ -2117,87 +2117,94 @@ class MeshPlugin:
         return MeshPlugin.emit(volume, threshold, table, ws, nv, nt, normals=normals, flip=flip, lattice=lattice)
 
 
-class PngPlugin:
-    """Row filters + deflate of uint8 CUDA frames (csrc/png.hip, DESIGN.md section 5.32): the compression inside `save_image` of
-    gen_images.py:115-116.  `training.png` holds the host definition of the same bytes, the container and the copies to the host."""
+class _StreamPlugin:
+    """What the two stream encoders share: the frame and buffer checks, the workspace cache, the allocation of `out` and
+    `offsets`.  A subclass gives `_name` (of its entry point), `_limits` (what it supports, for the refusal), `_ws`, and its two C calls:
+    `_sizes(lib, N, H, W, C, *args)` -> (workspace bytes, worst-case output bytes) and `_run(lib, frames, N, H, W, C, args, buffers)` -> rc,
+    `args` being the encoder's own arguments as integers."""
 
+    @classmethod
+    def _shape(cls, frames, args):
+        _require(frames.is_cuda and frames.dtype == torch.uint8 and frames.ndim == 4 and frames.is_contiguous(),
+                 f'{cls._name}: frames must be a contiguous [N, H, W, C] uint8 CUDA tensor')
+        N, H, W, C = (int(v) for v in frames.shape)
+        ws_bytes, out_bytes = cls._sizes(load(), N, H, W, C, *args)
+        _require(ws_bytes > 0 and 0 < out_bytes < 2 ** 31, f'{cls._name}: unsupported call: {N} frames of {H} x {W} x {C}, arguments {args} ({cls._limits})')
+        return (N, H, W, C), ws_bytes, out_bytes
+
+    @classmethod
+    def _launch(cls, frames, args, workspace, out, offsets):
+        (N, H, W, C), _, _ = cls._shape(frames, args)
+        for t, dt in ((workspace, torch.uint8), (out, torch.uint8), (offsets, torch.int64)):
+            _require(t.is_cuda and t.device == frames.device and t.dtype == dt and t.is_contiguous(), f'{cls._name}: workspace / out are uint8, offsets int64, on the frames\' device')
+        _require(offsets.numel() == N + 1, f'{cls._name}: offsets holds N + 1 values')
+        with _dev_guard(frames.device):
+            rc = cls._run(load(), _ptr(frames), N, H, W, C, args, (_ptr(workspace), workspace.numel(), _ptr(out), out.numel(), _ptr(offsets), _stream(frames)))
+        _check(rc, cls._name)
+
+    @classmethod
+    def _encode(cls, frames, args):
+        (N, H, W, C), ws_bytes, out_bytes = cls._shape(frames, args)
+        dev = frames.device if frames.device.index is not None else torch.device('cuda', torch.cuda.current_device())
+        ws = cls._ws.entry((ws_bytes, dev.index, _ws_domain(dev)), lambda: torch.empty([ws_bytes], dtype=torch.uint8, device=dev))[0]
+        out = torch.empty([out_bytes], dtype=torch.uint8, device=dev)
+        offsets = torch.empty([N + 1], dtype=torch.int64, device=dev)
+        cls._launch(frames, args, ws, out, offsets)
+        return out, offsets
+
+
+class PngPlugin(_StreamPlugin):
+    """Row filters + deflate of uint8 CUDA frames (csrc/png.hip, DESIGN.md section 5.32): the compression inside `save_image` of
+    gen_images.py:115-116.  `training.png` holds the host definition of the same bytes and the container."""
+
+    _name = 'png_encode'
+    _limits = '(filter mode, segment bytes): 1 or 3 channels, a power of two in [1024, 32768], below 2 GiB per call'
     _ws = _Workspaces()          # (bytes, device index, launch domain) -> filtered streams + segment slots + segment records
 
     @staticmethod
-    def _shape(frames, segment_bytes):
-        _require(frames.is_cuda and frames.dtype == torch.uint8 and frames.ndim == 4 and frames.is_contiguous(),
-                 'png_encode: frames must be a contiguous [N, H, W, C] uint8 CUDA tensor')
-        N, H, W, C = (int(v) for v in frames.shape)
-        lib = load()
-        ws_bytes, out_bytes = lib.ide3d_png_workspace_bytes(N, H, W, C, segment_bytes), lib.ide3d_png_out_bytes(N, H, W, C, segment_bytes)
-        _require(ws_bytes > 0 and 0 < out_bytes < 2 ** 31, f'png_encode: unsupported call: {N} frames of {H} x {W} x {C}, segments of {segment_bytes} bytes '
-                 '(1 or 3 channels, a power of two in [1024, 32768], below 2 GiB per call)')
-        return (N, H, W, C), ws_bytes, out_bytes
+    def _sizes(lib, N, H, W, C, filter_mode, segment_bytes):
+        return lib.ide3d_png_workspace_bytes(N, H, W, C, segment_bytes), lib.ide3d_png_out_bytes(N, H, W, C, segment_bytes)
+
+    @staticmethod
+    def _run(lib, frames, N, H, W, C, args, buffers):
+        return lib.ide3d_png_encode(frames, N, H, W, C, *args, *buffers)
 
     @staticmethod
     def launch(frames, filter_mode, segment_bytes, workspace, out, offsets):
         """ide3d_png_encode into the caller's buffers (uint8 workspace and out, int64 offsets [N + 1], all on the frames' device)."""
-        (N, H, W, C), _, _ = PngPlugin._shape(frames, segment_bytes)
-        for t, dt in ((workspace, torch.uint8), (out, torch.uint8), (offsets, torch.int64)):
-            _require(t.is_cuda and t.device == frames.device and t.dtype == dt and t.is_contiguous(), 'png_encode: workspace / out are uint8, offsets int64, on the frames\' device')
-        _require(offsets.numel() == N + 1, 'png_encode: offsets holds N + 1 values')
-        with _dev_guard(frames.device):
-            rc = load().ide3d_png_encode(_ptr(frames), N, H, W, C, int(filter_mode), int(segment_bytes), _ptr(workspace), workspace.numel(),
-                                         _ptr(out), out.numel(), _ptr(offsets), _stream(frames))
-        _check(rc, 'png_encode')
+        PngPlugin._launch(frames, (int(filter_mode), int(segment_bytes)), workspace, out, offsets)
 
     @staticmethod
     def encode(frames, filter_mode, segment_bytes):
         """-> (out uint8 [worst case], offsets int64 [N + 1]) on the device: stream k is out[offsets[k]:offsets[k + 1]]."""
-        (N, H, W, C), ws_bytes, out_bytes = PngPlugin._shape(frames, segment_bytes)
-        dev = frames.device if frames.device.index is not None else torch.device('cuda', torch.cuda.current_device())
-        ws = PngPlugin._ws.entry((ws_bytes, dev.index, _ws_domain(dev)), lambda: torch.empty([ws_bytes], dtype=torch.uint8, device=dev))[0]
-        out = torch.empty([out_bytes], dtype=torch.uint8, device=dev)
-        offsets = torch.empty([N + 1], dtype=torch.int64, device=dev)
-        PngPlugin.launch(frames, filter_mode, segment_bytes, ws, out, offsets)
-        return out, offsets
+        return PngPlugin._encode(frames, (int(filter_mode), int(segment_bytes)))
 
 
-class JpegPlugin:
+class JpegPlugin(_StreamPlugin):
     """Colour conversion, DCT, quantiser and Huffman coding of uint8 CUDA frames (csrc/jpeg.hip): the compression
-    of the Motion-JPEG video sink.  `training.jpeg` holds the host definition of the same bytes, the markers and the copies to the host."""
+    of the Motion-JPEG video sink.  `training.jpeg` holds the host definition of the same bytes and the markers."""
 
+    _name = 'jpeg_encode'
+    _limits = '(quality, subsampling, restart interval): 1 or 3 channels, sides 1..65535, 444 or 420 (RGB only), 1..65535 MCUs, below 2 GiB per call'
     _ws = _Workspaces()          # (bytes, device index, launch domain) -> interval slots + their sizes and positions
 
     @staticmethod
-    def _shape(frames, subsampling, restart_interval):
-        _require(frames.is_cuda and frames.dtype == torch.uint8 and frames.ndim == 4 and frames.is_contiguous(),
-                 'jpeg_encode: frames must be a contiguous [N, H, W, C] uint8 CUDA tensor')
-        N, H, W, C = (int(v) for v in frames.shape)
-        lib = load()
-        args = (N, H, W, C, int(subsampling), int(restart_interval))
-        ws_bytes, out_bytes = lib.ide3d_jpeg_workspace_bytes(*args), lib.ide3d_jpeg_out_bytes(*args)
-        _require(ws_bytes > 0 and 0 < out_bytes < 2 ** 31, f'jpeg_encode: unsupported call: {N} frames of {H} x {W} x {C}, subsampling {subsampling}, '
-                 f'restart interval {restart_interval} (1 or 3 channels, sides 1..65535, 444 or 420 (RGB only), 1..65535 MCUs, below 2 GiB per call)')
-        return (N, H, W, C), ws_bytes, out_bytes
+    def _sizes(lib, N, H, W, C, quality, subsampling, restart_interval):
+        return (lib.ide3d_jpeg_workspace_bytes(N, H, W, C, subsampling, restart_interval), lib.ide3d_jpeg_out_bytes(N, H, W, C, subsampling, restart_interval))
+
+    @staticmethod
+    def _run(lib, frames, N, H, W, C, args, buffers):
+        return lib.ide3d_jpeg_encode(frames, N, H, W, C, *args, *buffers)
 
     @staticmethod
     def launch(frames, quality, subsampling, restart_interval, workspace, out, offsets):
         """ide3d_jpeg_encode into the caller's buffers (uint8 workspace and out, int64 offsets [N + 1], all on the frames' device)."""
-        (N, H, W, C), _, _ = JpegPlugin._shape(frames, subsampling, restart_interval)
-        for t, dt in ((workspace, torch.uint8), (out, torch.uint8), (offsets, torch.int64)):
-            _require(t.is_cuda and t.device == frames.device and t.dtype == dt and t.is_contiguous(), 'jpeg_encode: workspace / out are uint8, offsets int64, on the frames\' device')
-        _require(offsets.numel() == N + 1, 'jpeg_encode: offsets holds N + 1 values')
-        with _dev_guard(frames.device):
-            rc = load().ide3d_jpeg_encode(_ptr(frames), N, H, W, C, int(quality), int(subsampling), int(restart_interval), _ptr(workspace), workspace.numel(),
-                                          _ptr(out), out.numel(), _ptr(offsets), _stream(frames))
-        _check(rc, 'jpeg_encode')
+        JpegPlugin._launch(frames, (int(quality), int(subsampling), int(restart_interval)), workspace, out, offsets)
 
     @staticmethod
     def encode(frames, quality, subsampling, restart_interval):
         """-> (out uint8 [worst case], offsets int64 [N + 1]) on the device: scan k is out[offsets[k]:offsets[k + 1]]."""
-        (N, H, W, C), ws_bytes, out_bytes = JpegPlugin._shape(frames, subsampling, restart_interval)
-        dev = frames.device if frames.device.index is not None else torch.device('cuda', torch.cuda.current_device())
-        ws = JpegPlugin._ws.entry((ws_bytes, dev.index, _ws_domain(dev)), lambda: torch.empty([ws_bytes], dtype=torch.uint8, device=dev))[0]
-        out = torch.empty([out_bytes], dtype=torch.uint8, device=dev)
-        offsets = torch.empty([N + 1], dtype=torch.int64, device=dev)
-        JpegPlugin.launch(frames, quality, subsampling, restart_interval, ws, out, offsets)
-        return out, offsets
+        return JpegPlugin._encode(frames, (int(quality), int(subsampling), int(restart_interval)))
 
 
 class MetricsPlugin:

@@ -47,11 +47,12 @@ an interval of b blocks at most 2 ceil(1658 b / 8) bytes (every byte FF and stuf
 Not here: progressive and arithmetic coding, 12-bit samples, 4:2:2, per-frame optimised Huffman tables, rate control, alpha, EXIF, H.264.
 """
 
-import os
 import struct
 
 import numpy as np
 import torch
+
+from training.stream_io import streams_to_host, write_files
 
 SUBSAMPLINGS = {'4:4:4': 444, '4:2:0': 420}          # the C ABI's codes
 MAX_SIDE = 65535
@@ -353,17 +354,7 @@ def encode_scans(frames, quality=90, subsampling='4:2:0', restart_interval=None)
     if not frames.is_cuda:
         return [scan_bytes(f, quality, subsampling, ri) for f in frames.contiguous().numpy()]
     from torch_utils import hip_plugin
-    from training.png import _pinned_buffer
-    out, offsets = hip_plugin.JpegPlugin.encode(frames.contiguous(), quality, SUBSAMPLINGS[subsampling], ri)
-    head = _pinned_buffer(offsets.numel() * 8).view(torch.int64)
-    head.copy_(offsets, non_blocking=True)
-    torch.cuda.current_stream(frames.device).synchronize()
-    ends = head.tolist()
-    host = _pinned_buffer(max(ends[-1], 1))[:ends[-1]]
-    host.copy_(out[:ends[-1]], non_blocking=True)
-    torch.cuda.current_stream(frames.device).synchronize()
-    raw = host.numpy().tobytes()
-    return [raw[ends[i]:ends[i + 1]] for i in range(len(ends) - 1)]
+    return streams_to_host(*hip_plugin.JpegPlugin.encode(frames.contiguous(), quality, SUBSAMPLINGS[subsampling], ri))
 
 
 def encode_jpeg(frames, quality=90, subsampling='4:2:0', restart_interval=None):
@@ -383,11 +374,4 @@ def encode_jpeg(frames, quality=90, subsampling='4:2:0', restart_interval=None):
 
 def save_jpeg(frames, paths, quality=90, subsampling='4:2:0', restart_interval=None):
     """Write frame k to paths[k] (one path for a single [H, W, C] frame)."""
-    if isinstance(paths, (str, os.PathLike)):
-        paths = [paths]
-    files = encode_jpeg(frames, quality, subsampling, restart_interval)
-    if len(files) != len(paths):
-        raise ValueError(f'save_jpeg: {len(files)} frames for {len(paths)} paths')
-    for data, path in zip(files, paths):
-        with open(path, 'wb') as f:
-            f.write(data)
+    write_files(encode_jpeg(frames, quality, subsampling, restart_interval), paths, 'save_jpeg')

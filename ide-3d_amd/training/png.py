@@ -24,12 +24,13 @@ The stream is defined HERE, in integers, and the HIP kernels reproduce it byte f
   frame     78 01, the segments, Adler-32 (big endian).
 """
 
-import os
 import struct
 import zlib
 
 import numpy as np
 import torch
+
+from training.stream_io import streams_to_host, write_files
 
 FILTERS = {'none': 0, 'sub': 1, 'up': 2, 'average': 3, 'paeth': 4, 'adaptive': 5}
 MIN_SEGMENT_BYTES, MAX_SEGMENT_BYTES = 1024, 32768
@@ -328,33 +329,13 @@ def _check_args(frames, filter, segment_bytes):
     return frames, FILTERS[filter], seg
 
 
-_pinned = {}          # bytes -> pinned staging buffer of that (rounded-up) size
-
-
-def _pinned_buffer(nbytes):
-    size = 1 << max(16, (nbytes - 1).bit_length())
-    buf = _pinned.get(size)
-    if buf is None:
-        buf = _pinned[size] = torch.empty([size], dtype=torch.uint8).pin_memory()
-    return buf[:nbytes]
-
-
 def encode_zlib(frames, filter='adaptive', segment_bytes=None):
     """The zlib streams of `encode_png` without the container: list of N `bytes`."""
     frames, mode, seg = _check_args(frames, filter, segment_bytes)
     if not frames.is_cuda:
         return [zlib_stream(f, mode, seg) for f in frames.contiguous().numpy()]
     from torch_utils import hip_plugin
-    out, offsets = hip_plugin.PngPlugin.encode(frames.contiguous(), mode, seg)
-    head = _pinned_buffer(offsets.numel() * 8).view(torch.int64)
-    head.copy_(offsets, non_blocking=True)
-    torch.cuda.current_stream(frames.device).synchronize()
-    ends = head.tolist()
-    host = _pinned_buffer(ends[-1])
-    host.copy_(out[:ends[-1]], non_blocking=True)
-    torch.cuda.current_stream(frames.device).synchronize()
-    raw = host.numpy().tobytes()
-    return [raw[ends[i]:ends[i + 1]] for i in range(len(ends) - 1)]
+    return streams_to_host(*hip_plugin.PngPlugin.encode(frames.contiguous(), mode, seg))
 
 
 def encode_png(frames, filter='adaptive', segment_bytes=None):
@@ -373,14 +354,7 @@ def encode_png(frames, filter='adaptive', segment_bytes=None):
 
 def save_png(frames, paths, filter='adaptive', segment_bytes=None):
     """Write frame k to paths[k] (one path for a single [H, W, C] frame)."""
-    if isinstance(paths, (str, os.PathLike)):
-        paths = [paths]
-    files = encode_png(frames, filter, segment_bytes)
-    if len(files) != len(paths):
-        raise ValueError(f'save_png: {len(files)} frames for {len(paths)} paths')
-    for data, path in zip(files, paths):
-        with open(path, 'wb') as f:
-            f.write(data)
+    write_files(encode_png(frames, filter, segment_bytes), paths, 'save_png')
 
 
 def image_grid_u8(tensor, nrow=8, padding=2, normalize=False, value_range=None, pad_value=0.0):

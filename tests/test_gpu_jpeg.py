@@ -87,6 +87,38 @@ def test_buffers_are_written_only_inside_their_views(gpu_device):
     assert sum(s.count(b'\xff\x00') for s in want) > 20
 
 
+@pytest.mark.parametrize('N', [1, 2])
+def test_more_intervals_than_scan_threads(gpu_device, N):
+    """Grey frames of 8 x 8800 with a restart interval of one MCU: 1100 intervals per frame, so one frame is more intervals than the
+    position scan has threads (not a multiple of them) and two frames are three sizes per thread, with the marker term (2 bytes per RSTm)
+    and the frame term both live.  Every interval is copied to a destination of its own residue modulo 16 (the out view starts 5 bytes
+    past a 16-byte boundary).  The scans equal the host definition, `offsets` their running lengths, and the guards hold."""
+    from torch_utils import hip_plugin
+    frames = torch.from_numpy(np.stack([jpeg_cases.realistic(8, 8800, 1, 40 + k) for k in range(N)])).to(gpu_device)
+    q, sub, ri = 90, '4:4:4', 1
+    lib = hip_plugin.load()
+    args = (N, 8, 8800, 1, jpeg.SUBSAMPLINGS[sub], ri)
+    ws_bytes, out_bytes = lib.ide3d_jpeg_workspace_bytes(*args), lib.ide3d_jpeg_out_bytes(*args)
+    pad, mis = 4096, 16 + 5
+    big_ws = torch.full([ws_bytes + 2 * pad], 0xA5, dtype=torch.uint8, device=gpu_device)
+    big_out = torch.full([out_bytes + 2 * pad + mis], 0xA5, dtype=torch.uint8, device=gpu_device)
+    big_off = torch.full([N + 1 + 8], -7, dtype=torch.int64, device=gpu_device)
+    ws, out, off = big_ws[pad:pad + ws_bytes], big_out[pad + mis:pad + mis + out_bytes], big_off[4:4 + N + 1]
+    assert out.data_ptr() % 16 == 5
+    hip_plugin.JpegPlugin.launch(frames, q, jpeg.SUBSAMPLINGS[sub], ri, ws, out, off)
+    torch.cuda.synchronize()
+    assert bool((big_ws[:pad] == 0xA5).all()) and bool((big_ws[pad + ws_bytes:] == 0xA5).all())
+    assert bool((big_out[:pad + mis] == 0xA5).all()) and bool((big_out[pad + mis + out_bytes:] == 0xA5).all())
+    assert bool((big_off[:4] == -7).all()) and bool((big_off[4 + N + 1:] == -7).all())
+    want = jpeg.encode_scans(frames.cpu(), q, sub, ri)
+    assert all(s.count(b'\xff\xd0') + s.count(b'\xff\xd7') >= 2 * (1100 // 8) for s in want)          # the restart markers are there
+    ends = off.tolist()
+    assert ends == [sum(len(s) for s in want[:k]) for k in range(N + 1)]
+    assert bool((out[ends[-1]:] == 0xA5).all()), 'nothing is written past the last scan'
+    raw = out[:ends[-1]].cpu().numpy().tobytes()
+    assert [raw[ends[k]:ends[k + 1]] for k in range(N)] == want
+
+
 def test_refusals_launch_nothing(gpu_device):
     from torch_utils import hip_plugin
     lib = hip_plugin.load()

@@ -83,6 +83,47 @@ def test_buffers_are_written_only_inside_their_views(gpu_device):
     assert [raw[ends[k]:ends[k + 1]] for k in range(N)] == want
 
 
+def _guarded_streams(frames, mode, seg):
+    """PngPlugin.launch into views of buffers filled with a pattern, the out view 5 bytes past a 16-byte boundary -> the streams, after
+    checking that nothing outside the views or past the last stream was written."""
+    from torch_utils import hip_plugin
+    N, H, W, C = frames.shape
+    lib = hip_plugin.load()
+    ws_bytes, out_bytes = lib.ide3d_png_workspace_bytes(N, H, W, C, seg), lib.ide3d_png_out_bytes(N, H, W, C, seg)
+    pad, mis = 4096, 16 + 5
+    big_ws = torch.full([ws_bytes + 2 * pad], 0xA5, dtype=torch.uint8, device=frames.device)
+    big_out = torch.full([out_bytes + 2 * pad + mis], 0xA5, dtype=torch.uint8, device=frames.device)
+    big_off = torch.full([N + 1 + 8], -7, dtype=torch.int64, device=frames.device)
+    ws, out, off = big_ws[pad:pad + ws_bytes], big_out[pad + mis:pad + mis + out_bytes], big_off[4:4 + N + 1]
+    assert out.data_ptr() % 16 == 5
+    hip_plugin.PngPlugin.launch(frames, mode, seg, ws, out, off)
+    torch.cuda.synchronize()
+    assert bool((big_ws[:pad] == 0xA5).all()) and bool((big_ws[pad + ws_bytes:] == 0xA5).all())
+    assert bool((big_out[:pad + mis] == 0xA5).all()) and bool((big_out[pad + mis + out_bytes:] == 0xA5).all())
+    assert bool((big_off[:4] == -7).all()) and bool((big_off[4 + N + 1:] == -7).all())
+    ends = off.tolist()
+    assert ends[0] == 0 and ends[-1] <= out_bytes and ends == sorted(ends)
+    assert bool((out[ends[-1]:] == 0xA5).all()), 'nothing is written past the last stream'
+    raw = out[:ends[-1]].cpu().numpy().tobytes()
+    return [raw[ends[k]:ends[k + 1]] for k in range(N)]
+
+
+def test_more_segments_than_scan_threads(gpu_device):
+    """3 frames of 361 x 1024 x 1, filter 'none', segments of 1024 bytes: a frame's filtered stream is 361 x 1025 bytes = 362 segments, the
+    batch 1086: two sizes per thread of the position scan, its last threads idle; a single frame is one size per thread.  The batch equals
+    the single calls, every stream inflates to the frame's filtered rows, one equals the host definition, and the guards hold."""
+    import zlib
+    frames_np = np.stack([png_cases.noisy_gradient(361, 1024, 1, 20 + k) for k in range(3)])
+    assert -(-361 * 1025 // 1024) == 362 and 3 * 362 > 1024 and (3 * 362) % 1024 != 0
+    frames = torch.from_numpy(frames_np).to(gpu_device)
+    batch = _guarded_streams(frames, png.FILTERS['none'], 1024)
+    single = [_guarded_streams(frames[k:k + 1].contiguous(), png.FILTERS['none'], 1024)[0] for k in range(3)]
+    assert batch == single
+    for k in range(3):
+        assert zlib.decompress(batch[k]) == png.filter_rows(frames_np[k], png.FILTERS['none'])[0].tobytes()
+    assert batch[1] == png.zlib_stream(frames_np[1], png.FILTERS['none'], 1024)
+
+
 def test_refusals_launch_nothing(gpu_device):
     from torch_utils import hip_plugin
     lib = hip_plugin.load()
