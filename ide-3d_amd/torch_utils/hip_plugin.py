@@ -484,6 +484,18 @@ def load():
             'ide3d_residual_join': [vp, vp, vp, i64, f32, vp],
             'ide3d_id_head': [vp, vp, vp, vp, vp, i32, i32, vp],
             'ide3d_id_head_backward': [vp, vp, vp, vp, vp, i32, i32, vp],
+            'ide3d_clip_prep': [vp, vp, vp, vp, i32, i32, i32, vp],
+            'ide3d_clip_prep_backward': [vp, vp, vp, i32, i32, i32, vp],
+            'ide3d_vit_embed': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
+            'ide3d_vit_embed_backward': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+            'ide3d_layernorm': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
+            'ide3d_layernorm_backward': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+            'ide3d_vit_attention': [vp, vp, i32, i32, i32, i32, f32, vp],
+            'ide3d_vit_attention_backward': [vp, vp, vp, i32, i32, i32, i32, f32, vp],
+            'ide3d_quickgelu': [vp, vp, i64, vp],
+            'ide3d_quickgelu_backward': [vp, vp, vp, i64, vp],
+            'ide3d_clip_head': [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+            'ide3d_clip_head_backward': [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
             'ide3d_set_conv_arithmetic': [i32],
             'ide3d_get_conv_arithmetic': [],
             'ide3d_frame_u8': [vp, vp, vp, i32, i32, i32, i32, vp, vp],
@@ -543,6 +555,8 @@ EXPORTED_SYMBOLS = (
     'ide3d_jpeg_workspace_bytes', 'ide3d_jpeg_out_bytes', 'ide3d_jpeg_encode',
     'ide3d_metrics_workspace_bytes', 'ide3d_feature_moments', 'ide3d_poly_kernel_sums', 'ide3d_knn_radii', 'ide3d_manifold_inside',
     'ide3d_augment_geometric', 'ide3d_augment_geometric_backward', 'ide3d_augment_color',
+    'ide3d_clip_prep', 'ide3d_clip_prep_backward', 'ide3d_vit_embed', 'ide3d_vit_embed_backward', 'ide3d_layernorm', 'ide3d_layernorm_backward',
+    'ide3d_vit_attention', 'ide3d_vit_attention_backward', 'ide3d_quickgelu', 'ide3d_quickgelu_backward', 'ide3d_clip_head', 'ide3d_clip_head_backward',
 )
 
 
@@ -2818,6 +2832,231 @@ class IdLossPlugin:
         return df
 
 
+class ClipLossPlugin:
+    """The passes of the CLIP image-text loss and its image gradient that are not dense products (csrc/clip_loss.hip, DESIGN.md section
+    5.37).  Tensors are contiguous float32 CUDA tensors unless a method says otherwise; token maps are channel-major, [n, C, T]."""
+
+    SIDE = 224               # kClipSide: what the reference's Upsample(7) + AvgPool2d(S / 32) produce
+    MAX_TOKENS = 64          # kAttMaxT
+    MAX_HEAD_DIM = 64        # kAttMaxD
+    EPS = 1e-5               # LayerNorm
+
+    @staticmethod
+    def _f32(t, name, dev=None, shape=None):
+        _require(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and (dev is None or t.device == dev),
+                 f'clip_loss: {name} must be a contiguous float32 CUDA tensor on the device of the other arguments')
+        if shape is not None:
+            _require(tuple(t.shape) == tuple(shape), f'clip_loss: {name} must be {list(shape)}, got {list(t.shape)}')
+        return t
+
+    @staticmethod
+    def _prep_args(shape, p, mean, std, dev):
+        _require(len(shape) == 4 and shape[1] == 3 and shape[2] == shape[3] and shape[2] >= 32 and shape[2] % 32 == 0,
+                 'clip_prep: images are [n, 3, 32 k, 32 k] with an integer k >= 1')
+        _require(1 <= p <= ClipLossPlugin.SIDE and ClipLossPlugin.SIDE % p == 0, 'clip_prep: the patch size must divide 224')
+        _require((mean is None) == (std is None), 'clip_prep: mean and std come together')
+        for name, t in (('mean', mean), ('std', std)):
+            if t is not None:
+                ClipLossPlugin._f32(t, name, dev, (3,))
+        return shape[2] // 32
+
+    @staticmethod
+    def prep(x, p, mean=None, std=None):
+        """ide3d_clip_prep: x [n, 3, S, S] -> col [n, 3 p p, 224 / p, 224 / p]: Upsample(7), AvgPool2d(S / 32), ((v + 1) / 2 - mean) / std
+        when mean and std (float32 [3] on the device) are given, unfolded into p x p patches."""
+        ClipLossPlugin._f32(x, 'x')
+        k = ClipLossPlugin._prep_args(x.shape, p, mean, std, x.device)
+        g = ClipLossPlugin.SIDE // p
+        col = torch.empty([x.shape[0], 3 * p * p, g, g], dtype=torch.float32, device=x.device)
+        with _dev_guard(x.device):
+            rc = load().ide3d_clip_prep(_ptr(x), _ptr(mean), _ptr(std), _ptr(col), x.shape[0], k, p, _stream(x))
+        _check(rc, 'clip_prep')
+        return col
+
+    @staticmethod
+    def prep_backward(dcol, size, p, std=None):
+        """ide3d_clip_prep_backward: dcol [n, 3 p p, 224 / p, 224 / p] -> the gradient of `prep`'s input of spatial `size`."""
+        ClipLossPlugin._f32(dcol, 'dcol')
+        n = dcol.shape[0]
+        k = ClipLossPlugin._prep_args((n, 3, int(size[0]), int(size[1])), p, std, std, dcol.device)
+        g = ClipLossPlugin.SIDE // p
+        _require(tuple(dcol.shape) == (n, 3 * p * p, g, g), 'clip_prep_backward: dcol [n, 3 p p, 224 / p, 224 / p]')
+        dx = torch.empty([n, 3, 32 * k, 32 * k], dtype=torch.float32, device=dcol.device)
+        with _dev_guard(dcol.device):
+            rc = load().ide3d_clip_prep_backward(_ptr(dcol), _ptr(std), _ptr(dx), n, k, p, _stream(dcol))
+        _check(rc, 'clip_prep_backward')
+        return dx
+
+    @staticmethod
+    def embed(patches, table, gamma, beta):
+        """ide3d_vit_embed: patches [n, C, T - 1] (any trailing shape with T - 1 elements), table [C, T] -> (ln_pre(tokens) [n, C, T], mean
+        [n, T], rstd [n, T])."""
+        ClipLossPlugin._f32(patches, 'patches')
+        ClipLossPlugin._f32(table, 'table', patches.device)
+        _require(patches.ndim >= 3 and table.ndim == 2, 'vit_embed: patches [n, C, T - 1], table [C, T]')
+        n, C = patches.shape[:2]
+        T = table.shape[1]
+        _require(table.shape[0] == C and patches.numel() == n * C * (T - 1) and T >= 2, 'vit_embed: patches [n, C, T - 1], table [C, T]')
+        ClipLossPlugin._f32(gamma, 'gamma', patches.device, (C,))
+        ClipLossPlugin._f32(beta, 'beta', patches.device, (C,))
+        y = torch.empty([n, C, T], dtype=torch.float32, device=patches.device)
+        mean, rstd = (torch.empty([n, T], dtype=torch.float32, device=patches.device) for _ in range(2))
+        with _dev_guard(patches.device):
+            rc = load().ide3d_vit_embed(_ptr(patches), _ptr(table), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), n, C, T,
+                                        ClipLossPlugin.EPS, _stream(patches))
+        _check(rc, 'vit_embed')
+        return y, mean, rstd
+
+    @staticmethod
+    def embed_backward(dy, patches, table, gamma, mean, rstd):
+        """ide3d_vit_embed_backward -> the gradient of the patch tokens, in the shape of `patches`."""
+        ClipLossPlugin._f32(dy, 'dy')
+        _require(dy.ndim == 3, 'vit_embed_backward: dy [n, C, T]')
+        n, C, T = dy.shape
+        dev = dy.device
+        ClipLossPlugin._f32(patches, 'patches', dev)
+        _require(patches.shape[:2] == dy.shape[:2] and patches.numel() == n * C * (T - 1) and T >= 2, 'vit_embed_backward: patches [n, C, T - 1]')
+        ClipLossPlugin._f32(table, 'table', dev, (C, T))
+        ClipLossPlugin._f32(gamma, 'gamma', dev, (C,))
+        ClipLossPlugin._f32(mean, 'mean', dev, (n, T))
+        ClipLossPlugin._f32(rstd, 'rstd', dev, (n, T))
+        dp = torch.empty_like(patches)
+        with _dev_guard(dev):
+            rc = load().ide3d_vit_embed_backward(_ptr(dy), _ptr(patches), _ptr(table), _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dp), n, C, T, _stream(dy))
+        _check(rc, 'vit_embed_backward')
+        return dp
+
+    @staticmethod
+    def layernorm(x, gamma, beta, tokens=None):
+        """ide3d_layernorm: x [n, C, T] -> (y [n, C, tokens], mean [n, tokens], rstd [n, tokens]): LayerNorm over C of the first `tokens`
+        tokens (default: all; 1 = the class token, read in place)."""
+        ClipLossPlugin._f32(x, 'x')
+        _require(x.ndim == 3, 'layernorm: x [n, C, T]')
+        n, C, pitch = x.shape
+        T = pitch if tokens is None else int(tokens)
+        _require(1 <= T <= pitch, 'layernorm: 1 <= tokens <= T')
+        ClipLossPlugin._f32(gamma, 'gamma', x.device, (C,))
+        ClipLossPlugin._f32(beta, 'beta', x.device, (C,))
+        y = torch.empty([n, C, T], dtype=torch.float32, device=x.device)
+        mean, rstd = (torch.empty([n, T], dtype=torch.float32, device=x.device) for _ in range(2))
+        with _dev_guard(x.device):
+            rc = load().ide3d_layernorm(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), n, C, T, pitch, ClipLossPlugin.EPS, _stream(x))
+        _check(rc, 'layernorm')
+        return y, mean, rstd
+
+    @staticmethod
+    def layernorm_backward(dy, x, gamma, mean, rstd, add=None):
+        """ide3d_layernorm_backward: dy [n, C, tokens] -> dx in the shape of x [n, C, T] (+ add [n, C, T]); an exact 0 past `tokens`."""
+        ClipLossPlugin._f32(dy, 'dy')
+        ClipLossPlugin._f32(x, 'x', dy.device)
+        _require(dy.ndim == 3 and x.ndim == 3 and dy.shape[:2] == x.shape[:2] and dy.shape[2] <= x.shape[2], 'layernorm_backward: dy [n, C, tokens], x [n, C, T]')
+        n, C, T = dy.shape
+        pitch = x.shape[2]
+        ClipLossPlugin._f32(gamma, 'gamma', dy.device, (C,))
+        ClipLossPlugin._f32(mean, 'mean', dy.device, (n, T))
+        ClipLossPlugin._f32(rstd, 'rstd', dy.device, (n, T))
+        if add is not None:
+            ClipLossPlugin._f32(add, 'add', dy.device, x.shape)
+        dx = torch.empty_like(x)
+        with _dev_guard(dy.device):
+            rc = load().ide3d_layernorm_backward(_ptr(dy), _ptr(x), _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(add), _ptr(dx), n, C, T, pitch, _stream(dy))
+        _check(rc, 'layernorm_backward')
+        return dx
+
+    @staticmethod
+    def _att_args(qkv, heads):
+        ClipLossPlugin._f32(qkv, 'qkv')
+        _require(qkv.ndim == 3 and heads >= 1 and qkv.shape[1] % (3 * heads) == 0, 'vit_attention: qkv [n, 3 heads d, T]')
+        n, C3, T = qkv.shape
+        d = C3 // (3 * heads)
+        _require(d % 4 == 0 and 4 <= d <= ClipLossPlugin.MAX_HEAD_DIM and 1 <= T <= ClipLossPlugin.MAX_TOKENS,
+                 f'vit_attention: head dimension a multiple of 4 and <= {ClipLossPlugin.MAX_HEAD_DIM}, T <= {ClipLossPlugin.MAX_TOKENS}')
+        return n, d, T
+
+    @staticmethod
+    def attention(qkv, heads):
+        """ide3d_vit_attention: qkv [n, 3 C, T] -> [n, C, T], softmax(q k^T / sqrt(d)) v per head."""
+        n, d, T = ClipLossPlugin._att_args(qkv, heads)
+        out = torch.empty([n, heads * d, T], dtype=torch.float32, device=qkv.device)
+        with _dev_guard(qkv.device):
+            rc = load().ide3d_vit_attention(_ptr(qkv), _ptr(out), n, heads, d, T, float(d) ** -0.5, _stream(qkv))
+        _check(rc, 'vit_attention')
+        return out
+
+    @staticmethod
+    def attention_backward(qkv, dout, heads):
+        """ide3d_vit_attention_backward: dout [n, C, T] -> dqkv [n, 3 C, T]."""
+        n, d, T = ClipLossPlugin._att_args(qkv, heads)
+        ClipLossPlugin._f32(dout, 'dout', qkv.device, (n, heads * d, T))
+        dqkv = torch.empty_like(qkv)
+        with _dev_guard(qkv.device):
+            rc = load().ide3d_vit_attention_backward(_ptr(qkv), _ptr(dout), _ptr(dqkv), n, heads, d, T, float(d) ** -0.5, _stream(qkv))
+        _check(rc, 'vit_attention_backward')
+        return dqkv
+
+    @staticmethod
+    def quickgelu(x):
+        """ide3d_quickgelu: x * sigmoid(1.702 x), in the shape of x."""
+        ClipLossPlugin._f32(x, 'x')
+        _require(x.numel() > 0, 'quickgelu: empty operand')
+        y = torch.empty_like(x)
+        with _dev_guard(x.device):
+            rc = load().ide3d_quickgelu(_ptr(x), _ptr(y), x.numel(), _stream(x))
+        _check(rc, 'quickgelu')
+        return y
+
+    @staticmethod
+    def quickgelu_backward(dy, x):
+        """ide3d_quickgelu_backward -> dx; x: the pre-activation."""
+        ClipLossPlugin._f32(x, 'x')
+        ClipLossPlugin._f32(dy, 'dy', x.device, x.shape)
+        _require(x.numel() > 0, 'quickgelu_backward: empty operand')
+        dx = torch.empty_like(x)
+        with _dev_guard(x.device):
+            rc = load().ide3d_quickgelu_backward(_ptr(dy), _ptr(x), _ptr(dx), x.numel(), _stream(x))
+        _check(rc, 'quickgelu_backward')
+        return dx
+
+    @staticmethod
+    def head(f, text, base=None):
+        """ide3d_clip_head: f [n, D], text [T, D], base [n, D] or None -> (out [n, T] = 1 - cos(f - base, text), e [n, D], norm [n], tnorm [T],
+        mean [] = the mean of out, summed in float64 before its values are rounded)."""
+        ClipLossPlugin._f32(f, 'f')
+        _require(f.ndim == 2, 'clip_head: f [n, D]')
+        n, D = f.shape
+        ClipLossPlugin._f32(text, 'text', f.device)
+        _require(text.ndim == 2 and text.shape[1] == D and text.shape[0] >= 1, 'clip_head: text [T, D]')
+        T = text.shape[0]
+        if base is not None:
+            ClipLossPlugin._f32(base, 'base', f.device, (n, D))
+        e = torch.empty_like(f)
+        norm, tnorm = torch.empty([n], dtype=torch.float32, device=f.device), torch.empty([T], dtype=torch.float32, device=f.device)
+        out = torch.empty([n, T], dtype=torch.float32, device=f.device)
+        rowsum, mean = torch.empty([n], dtype=torch.float64, device=f.device), torch.empty([], dtype=torch.float32, device=f.device)
+        with _dev_guard(f.device):
+            rc = load().ide3d_clip_head(_ptr(f), _ptr(base), _ptr(text), _ptr(e), _ptr(norm), _ptr(tnorm), _ptr(out), _ptr(rowsum), _ptr(mean), n, D, T,
+                                        _stream(f))
+        _check(rc, 'clip_head')
+        return out, e, norm, tnorm, mean
+
+    @staticmethod
+    def head_backward(e, text, norm, tnorm, dout):
+        """ide3d_clip_head_backward: dout [n, T] on the device -> df [n, D]."""
+        ClipLossPlugin._f32(e, 'e')
+        n, D = e.shape
+        ClipLossPlugin._f32(text, 'text', e.device)
+        T = text.shape[0]
+        _require(tuple(text.shape) == (T, D), 'clip_head_backward: text [T, D]')
+        ClipLossPlugin._f32(norm, 'norm', e.device, (n,))
+        ClipLossPlugin._f32(tnorm, 'tnorm', e.device, (T,))
+        ClipLossPlugin._f32(dout, 'dout', e.device, (n, T))
+        df = torch.empty_like(e)
+        with _dev_guard(e.device):
+            rc = load().ide3d_clip_head_backward(_ptr(e), _ptr(text), _ptr(norm), _ptr(tnorm), _ptr(dout), _ptr(df), n, D, T, _stream(e))
+        _check(rc, 'clip_head_backward')
+        return df
+
+
 def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epilogue='conv', x_amax=False):
     """Host-only (works without a GPU): the kernel family, tile and grid `modconv2d` would launch for this shape -> dict of the
     ide3d_modconv_plan_info fields, `kind` as a name from PLAN_KINDS.  epilogue: 'conv' (noise, bias, lrelu, gain sqrt(2): the 3x3 layers),
@@ -3418,4 +3657,5 @@ PLUGINS = {
     'vgg_loss_plugin': VggLossPlugin,
     'parse_loss_plugin': ParseLossPlugin,
     'id_loss_plugin': IdLossPlugin,
+    'clip_loss_plugin': ClipLossPlugin,
 }

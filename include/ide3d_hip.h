@@ -1440,6 +1440,64 @@ int ide3d_feat_l1_tap_backward(const float* a, const float* t, const float* g, f
                                int64_t planes, int32_t h, int32_t w, int64_t count, void* stream);
 int ide3d_maxpool2_relu_backward(const float* y, const float* dpool, float* dz, int64_t planes, int32_t h, int32_t w, void* stream);
 
+/*
+ * ABI 8 (entry points added).  The CLIP image-text loss of the text-guided editing and domain adaptation paths
+ * (inversion/models/StyleCLIP/criteria/clip_loss.py:6-17, used at mapper/training/coach.py:206-209 and
+ * optimization/run_optimization.py:49-62): one minus the cosine between the embedding a frozen CLIP ViT image encoder gives the rendered
+ * image and text embeddings, and its image gradient through the encoder: everything that is not a dense product (those are shared-weight
+ * 1x1 ide3d_modconv2d launches over channel-major token maps [n, C, T], ide3d_residual_join and ide3d_linear); csrc/clip_loss.hip,
+ * DESIGN.md section 5.37.  Dense fp32 in device memory.  No atomics, fixed-order sums (float64 where they end in one number),
+ * bit-reproducible; no host synchronisation.
+ *
+ * ide3d_clip_prep — `AvgPool2d(S / 32)(Upsample(scale_factor=7)(x))` (clip_loss.py:10-11, 14), the optional CLIP normalisation
+ *   ((v + 1) / 2 - mean[c]) / std[c] (mean and std: DEVICE float[3], both or neither) and the unfolding into p x p patches in one pass:
+ *   x [n, 3, 32 k, 32 k] -> col [n, 3 p p, 224 / p, 224 / p] in the channel order of ide3d_unfold2d, (ci p + ky) p + kx.  A pooled pixel
+ *   is sum_s sum_t count(s) count(t) x[s, t] / k^2 with the integer counts |[Y k, Y k + k) n [7 s, 7 s + 7)|, summed in float64.
+ *   ide3d_clip_prep_backward — the adjoint in gather form: each input pixel sums the pooled pixels whose windows hold it, rows then
+ *   columns ascending (std: the same pointer as forward, or NULL).
+ * ide3d_vit_embed — `x = ln_pre(cat([class_embedding, patches]) + positional_embedding)` of CLIP's VisionTransformer.forward: patches
+ *   [n, C, T - 1] (the patch convolution's output), table [C, T] = positional_embedding^T with class_embedding added to column 0 ->
+ *   y [n, C, T]; mean, rstd [n, T] are saved.  ide3d_vit_embed_backward — LayerNorm backward to the patch tokens [n, C, T - 1]; the class
+ *   column is dropped.
+ * ide3d_layernorm — `LayerNorm(C)` (eps inside the square root) over the channels of each token: x [n, C, pitch] (tokens 0 .. T - 1 of
+ *   rows of `pitch` floats are read: T = 1, pitch = the map's T is `ln_post` on the class token in place) -> y [n, C, T], mean, rstd
+ *   [n, T]; two passes, float64 sums.  ide3d_layernorm_backward — to the input only (gamma and beta are frozen):
+ *   dx = rstd (g - mean_c g - xhat mean_c (g xhat)) + add with g = dy gamma; add (NULL or [n, C, pitch]) is the residual stream's
+ *   gradient; dx [n, C, pitch], an exact 0 in the columns past T.
+ * ide3d_vit_attention — `nn.MultiheadAttention` between its two projections: qkv [n, 3 heads d, T] (q, k, v stacked along the channels,
+ *   head h = channels h d .. h d + d - 1 of each) -> out [n, heads d, T] = softmax_j(scale q_i . k_j) v_j; d a multiple of 4, d, T <= 64;
+ *   one workgroup per (image, head), q, k, v and the T x T scores in LDS, max subtraction, the denominator in float64 in ascending order.
+ *   ide3d_vit_attention_backward — dout [n, heads d, T] -> dqkv [n, 3 heads d, T]; the probabilities are recomputed from q and k:
+ *   dV = P^T dO, dS = P (dP - rowsum(dP P)) with dP = dO V^T, dQ = scale dS K, dK = scale dS^T Q.
+ * ide3d_quickgelu — CLIP's `QuickGELU`: y = x sigmoid(1.702 x) over `count` dense floats; 16-byte accesses when every operand is 16-byte
+ *   aligned.  ide3d_quickgelu_backward — dx = dy (s + 1.702 x s (1 - s)), s = sigmoid(1.702 x), from the saved PRE-activation x.
+ * ide3d_clip_head — `1 - logits_per_image / 100` (clip_loss.py:15-16) from the embeddings: f [n, D], base [n, D] or NULL, text [T, D] ->
+ *   e [n, D] = (f - base) / |f - base|, norm [n] = |f - base|, tnorm [T] = |text_r| and out [n, T] = 1 - e . text_r / |text_r| (base: the
+ *   frozen generator's embeddings of the directional loss); rowsum [n] (float64, 8-byte aligned) = each image's row sum before its values
+ *   are rounded, and mean[0] = their ascending float64 sum over n T, rounded once (a finishing launch): the scalar of a training step.
+ *   A zero norm divides by zero, as the definition does.
+ * ide3d_clip_head_backward — df = (g - e (e . g)) / norm with g = -sum_r dout[i, r] text_r / |text_r|; dout: DEVICE [n, T].
+ */
+int ide3d_clip_prep(const float* x, const float* mean, const float* std, float* col, int32_t n, int32_t k, int32_t p, void* stream);
+int ide3d_clip_prep_backward(const float* dcol, const float* std, float* dx, int32_t n, int32_t k, int32_t p, void* stream);
+int ide3d_vit_embed(const float* patches, const float* table, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
+                    int32_t n, int32_t C, int32_t T, float eps, void* stream);
+int ide3d_vit_embed_backward(const float* dy, const float* patches, const float* table, const float* gamma, const float* mean,
+                             const float* rstd, float* dpatches, int32_t n, int32_t C, int32_t T, void* stream);
+int ide3d_layernorm(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int32_t n, int32_t C,
+                    int32_t T, int32_t pitch, float eps, void* stream);
+int ide3d_layernorm_backward(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* add,
+                             float* dx, int32_t n, int32_t C, int32_t T, int32_t pitch, void* stream);
+int ide3d_vit_attention(const float* qkv, float* out, int32_t n, int32_t heads, int32_t d, int32_t T, float scale, void* stream);
+int ide3d_vit_attention_backward(const float* qkv, const float* dout, float* dqkv, int32_t n, int32_t heads, int32_t d, int32_t T,
+                                 float scale, void* stream);
+int ide3d_quickgelu(const float* x, float* y, int64_t count, void* stream);
+int ide3d_quickgelu_backward(const float* dy, const float* x, float* dx, int64_t count, void* stream);
+int ide3d_clip_head(const float* f, const float* base, const float* text, float* e, float* norm, float* tnorm, float* out, double* rowsum,
+                    float* mean, int32_t n, int32_t D, int32_t T, void* stream);
+int ide3d_clip_head_backward(const float* e, const float* text, const float* norm, const float* tnorm, const float* dout, float* df,
+                             int32_t n, int32_t D, int32_t T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
