@@ -496,6 +496,10 @@ def load():
             'ide3d_quickgelu_backward': [vp, vp, vp, i64, vp],
             'ide3d_clip_head': [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
             'ide3d_clip_head_backward': [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+            'ide3d_minibatch_std': [vp, vp, i32, i32, i32, i32, i32, i32, vp],
+            'ide3d_minibatch_std_backward': [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+            'ide3d_adv_head': [vp, vp, vp, vp, i32, i32, i32, vp],
+            'ide3d_adv_head_backward': [vp, vp, vp, vp, vp, i32, i32, i32, vp],
             'ide3d_set_conv_arithmetic': [i32],
             'ide3d_get_conv_arithmetic': [],
             'ide3d_frame_u8': [vp, vp, vp, i32, i32, i32, i32, vp, vp],
@@ -557,6 +561,7 @@ EXPORTED_SYMBOLS = (
     'ide3d_augment_geometric', 'ide3d_augment_geometric_backward', 'ide3d_augment_color',
     'ide3d_clip_prep', 'ide3d_clip_prep_backward', 'ide3d_vit_embed', 'ide3d_vit_embed_backward', 'ide3d_layernorm', 'ide3d_layernorm_backward',
     'ide3d_vit_attention', 'ide3d_vit_attention_backward', 'ide3d_quickgelu', 'ide3d_quickgelu_backward', 'ide3d_clip_head', 'ide3d_clip_head_backward',
+    'ide3d_minibatch_std', 'ide3d_minibatch_std_backward', 'ide3d_adv_head', 'ide3d_adv_head_backward',
 )
 
 
@@ -3057,6 +3062,83 @@ class ClipLossPlugin:
         return df
 
 
+class AdvLossPlugin:
+    """The passes of the discriminator's adversarial loss and its image gradient that are not convolutions, FIR passes, joins or linear
+    layers (csrc/adv_loss.hip).  Tensors are contiguous float32 CUDA tensors."""
+
+    MAX_M = 8192             # kAdvMaxM
+
+    @staticmethod
+    def _f32(t, name, dev=None, shape=None):
+        _require(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and (dev is None or t.device == dev),
+                 f'adv_loss: {name} must be a contiguous float32 CUDA tensor on the device of the other arguments')
+        if shape is not None:
+            _require(tuple(t.shape) == tuple(shape), f'adv_loss: {name} must be {list(shape)}, got {list(t.shape)}')
+        return t
+
+    @staticmethod
+    def _group(n, group_size):
+        """The `group` argument of the entry points for a layer's `group_size` (None: the whole batch): min(group_size, n)."""
+        return n if group_size is None else min(int(group_size), n)
+
+    @staticmethod
+    def minibatch_std(x, group_size, features=1):
+        """ide3d_minibatch_std: x [n, c, h, w] -> [n, c + features, h, w], `MinibatchStdLayer(group_size, features)(x)`."""
+        AdvLossPlugin._f32(x, 'x')
+        _require(x.ndim == 4, 'minibatch_std: x [n, c, h, w]')
+        n, c, h, w = x.shape
+        y = torch.empty([n, c + features, h, w], dtype=torch.float32, device=x.device)
+        with _dev_guard(x.device):
+            rc = load().ide3d_minibatch_std(_ptr(x), _ptr(y), n, c, h, w, AdvLossPlugin._group(n, group_size), features, _stream(x))
+        _check(rc, 'minibatch_std')
+        return y
+
+    @staticmethod
+    def minibatch_std_backward(x, dy, group_size, features=1):
+        """ide3d_minibatch_std_backward: dy [n, c + features, h, w] -> dx [n, c, h, w]; x: the layer's input."""
+        AdvLossPlugin._f32(x, 'x')
+        _require(x.ndim == 4, 'minibatch_std_backward: x [n, c, h, w]')
+        n, c, h, w = x.shape
+        AdvLossPlugin._f32(dy, 'dy', x.device, (n, c + features, h, w))
+        dx = torch.empty_like(x)
+        with _dev_guard(x.device):
+            rc = load().ide3d_minibatch_std_backward(_ptr(x), _ptr(dy), _ptr(dx), n, c, h, w, AdvLossPlugin._group(n, group_size), features, _stream(x))
+        _check(rc, 'minibatch_std_backward')
+        return dx
+
+    @staticmethod
+    def head(o, cmap, sign):
+        """ide3d_adv_head -> (logit [n, 1], loss []): logit = (o * cmap).sum(1) / sqrt(M) (cmap None: o is [n, 1] and logit = o),
+        loss = softplus(sign * logit).mean()."""
+        AdvLossPlugin._f32(o, 'o')
+        _require(o.ndim == 2, 'adv_head: o [n, M]')
+        n, M = o.shape
+        if cmap is not None:
+            AdvLossPlugin._f32(cmap, 'cmap', o.device, (n, M))
+        logit = torch.empty([n, 1], dtype=torch.float32, device=o.device)
+        loss = torch.empty([], dtype=torch.float32, device=o.device)
+        with _dev_guard(o.device):
+            rc = load().ide3d_adv_head(_ptr(o), _ptr(cmap), _ptr(logit), _ptr(loss), n, M, int(sign), _stream(o))
+        _check(rc, 'adv_head')
+        return logit, loss
+
+    @staticmethod
+    def head_backward(o, cmap, logit, dloss, sign):
+        """ide3d_adv_head_backward -> do [n, M]; dloss: a one-element float32 tensor on the device."""
+        AdvLossPlugin._f32(o, 'o')
+        n, M = o.shape
+        if cmap is not None:
+            AdvLossPlugin._f32(cmap, 'cmap', o.device, (n, M))
+        AdvLossPlugin._f32(logit, 'logit', o.device, (n, 1))
+        _require(dloss.is_cuda and dloss.dtype == torch.float32 and dloss.device == o.device and dloss.numel() == 1,
+                 'adv_head_backward: dloss must be one float32 on the device')
+        do = torch.empty_like(o)
+        with _dev_guard(o.device):
+            rc = load().ide3d_adv_head_backward(_ptr(o), _ptr(cmap), _ptr(logit), _ptr(dloss), _ptr(do), n, M, int(sign), _stream(o))
+        _check(rc, 'adv_head_backward')
+        return do
+
+
 def modconv_plan(n, cin, cout, h, w, k=3, mode=0, per_image=False, arith=0, epilogue='conv', x_amax=False):
     """Host-only (works without a GPU): the kernel family, tile and grid `modconv2d` would launch for this shape -> dict of the
     ide3d_modconv_plan_info fields, `kind` as a name from PLAN_KINDS.  epilogue: 'conv' (noise, bias, lrelu, gain sqrt(2): the 3x3 layers),
@@ -3658,4 +3740,5 @@ PLUGINS = {
     'parse_loss_plugin': ParseLossPlugin,
     'id_loss_plugin': IdLossPlugin,
     'clip_loss_plugin': ClipLossPlugin,
+    'adv_loss_plugin': AdvLossPlugin,
 }

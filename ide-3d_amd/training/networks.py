@@ -936,6 +936,48 @@ def _plain_conv_form(lay, x):
     return form
 
 
+def _plain_conv_launch(x, ws, bias, form, fir, pads, act, gain, clamp, arith=0):
+    """The launches of a Conv2dLayer's inference branches for `form` (see `_plain_conv_form`) on the scaled weight `ws` -> (f, y): f is what
+    the convolution read (x, or its FIR pass), y = clamp(act(conv(ws, f) + bias) * gain).  `_PlainConvGrad.forward` and the frozen
+    discriminator's walker (training/adv_loss.py) both launch a layer here."""
+    spec = bias_act.activation_funcs[act]
+    p0, p1 = pads
+    if form == 'conv':
+        f, mode = x.contiguous(), 0
+    elif form == 'fir_conv1':
+        f, mode = upfirdn2d.upfirdn2d(x, fir, down=2, padding=[p0, p1, p0, p1]).contiguous(), 0
+    else:
+        f, mode = upfirdn2d.upfirdn2d(x, fir, padding=[p0, p1, p0, p1]).contiguous(), 1
+    y = _modconv_plugin.modconv2d(f, ws, None, None, None, 0.0, bias, spec.cuda_idx, spec.def_alpha, gain,
+                                  -1.0 if clamp is None else clamp, mode=mode, arith=arith)
+    return f, y
+
+
+def _plain_conv_act_grad(dy, y, act, gain, clamp):
+    """dz = dy * act'(.) of `_plain_conv_launch`'s epilogue from its output y (ide3d_modconv_act_backward; no launch where it is the identity)."""
+    dz = dy.contiguous()
+    if act == 'linear' and gain == 1 and clamp is None:
+        return dz
+    spec = bias_act.activation_funcs[act]
+    return _modconv_grad_plugin.act_backward(dz, y, spec.cuda_idx, spec.def_alpha, gain, -1.0 if clamp is None else clamp)[0]
+
+
+def _plain_conv_input_grad(dz, ws, form, fir, pads, x_size, arith=0):
+    """The input gradient of `_plain_conv_launch` from dz: conv(ws^T flipped, dz) (mode 0), or convT(ws^T, dz) (mode 2) for the stride-2 3x3,
+    then the FIR adjoint."""
+    if form == 'fir_conv3':
+        df = _modconv_plugin.modconv2d(dz, _grad_weight(ws, False), None, None, None, 0.0, None, 1, 0.0, 1.0, -1.0, mode=2, arith=arith)
+    else:
+        df = _modconv_plugin.modconv2d(dz, _grad_weight(ws, True), None, None, None, 0.0, None, 1, 0.0, 1.0, -1.0, arith=arith)
+    if form == 'conv':
+        return df
+    # the adjoint of upfirdn2d(x, fir, down, padding) (torch_utils/ops/upfirdn2d.py, _Upfirdn2dHip.backward): up and down exchanged, the filter flipped
+    down = 2 if form == 'fir_conv1' else 1
+    fw, (p0, p1) = fir.shape[-1], pads
+    q = [fw - p0 - 1, x_size[1] - df.shape[3] * down + p0, fw - p0 - 1, x_size[0] - df.shape[2] * down + p0]
+    return upfirdn2d.upfirdn2d(df, fir, up=down, padding=q, flip_filter=True)
+
+
 class _PlainConvGrad(torch.autograd.Function):
     """A trainable Conv2dLayer (up 1, down 1 or 2, k 1 or 3, linear / lrelu): forward = the launches of the layer's inference branches, so
     that it equals them bit for bit; gradients for x, weight and bias, with ws = weight * weight_gain what the launches read.
@@ -948,17 +990,8 @@ class _PlainConvGrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, form, fir, pads, weight_gain, act, gain, clamp):
-        spec = bias_act.activation_funcs[act]
         ws = _scaled_weight(weight, weight_gain)
-        p0, p1 = pads
-        if form == 'conv':
-            f, mode = x.contiguous(), 0
-        elif form == 'fir_conv1':
-            f, mode = upfirdn2d.upfirdn2d(x, fir, down=2, padding=[p0, p1, p0, p1]).contiguous(), 0
-        else:
-            f, mode = upfirdn2d.upfirdn2d(x, fir, padding=[p0, p1, p0, p1]).contiguous(), 1
-        y = _modconv_plugin.modconv2d(f, ws, None, None, None, 0.0, bias, spec.cuda_idx, spec.def_alpha, gain,
-                                      -1.0 if clamp is None else clamp, mode=mode)
+        f, y = _plain_conv_launch(x, ws, bias, form, fir, pads, act, gain, clamp)
         ctx.save_for_backward(f, y)
         ctx.ws, ctx.form, ctx.fir, ctx.pads, ctx.weight_gain, ctx.act, ctx.gain, ctx.clamp = ws, form, fir, pads, weight_gain, act, gain, clamp
         ctx.x_size, ctx.w_shape = tuple(x.shape[2:]), tuple(weight.shape)
@@ -968,25 +1001,11 @@ class _PlainConvGrad(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         f, y = ctx.saved_tensors
-        spec = bias_act.activation_funcs[ctx.act]
-        dz = dy.contiguous()
-        if not (ctx.act == 'linear' and ctx.gain == 1 and ctx.clamp is None):
-            dz, _ = _modconv_grad_plugin.act_backward(dz, y, spec.cuda_idx, spec.def_alpha, ctx.gain, -1.0 if ctx.clamp is None else ctx.clamp)
+        dz = _plain_conv_act_grad(dy, y, ctx.act, ctx.gain, ctx.clamp)
         form, k = ctx.form, ctx.w_shape[-1]
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            if form == 'fir_conv3':
-                df = _modconv_plugin.modconv2d(dz, _grad_weight(ctx.ws, False), None, None, None, 0.0, None, 1, 0.0, 1.0, -1.0, mode=2)
-            else:
-                df = _modconv_plugin.modconv2d(dz, _grad_weight(ctx.ws, True), None, None, None, 0.0, None, 1, 0.0, 1.0, -1.0)
-            if form == 'conv':
-                dx = df
-            else:
-                # the adjoint of upfirdn2d(x, fir, down, padding) (torch_utils/ops/upfirdn2d.py, _Upfirdn2dHip.backward): up and down exchanged, the filter flipped
-                down = 2 if form == 'fir_conv1' else 1
-                fw, (p0, p1) = ctx.fir.shape[-1], ctx.pads
-                q = [fw - p0 - 1, ctx.x_size[1] - df.shape[3] * down + p0, fw - p0 - 1, ctx.x_size[0] - df.shape[2] * down + p0]
-                dx = upfirdn2d.upfirdn2d(df, ctx.fir, up=down, padding=q, flip_filter=True)
+            dx = _plain_conv_input_grad(dz, ctx.ws, form, ctx.fir, ctx.pads, ctx.x_size)
         if ctx.needs_input_grad[1]:
             if k == 1:
                 dws = _modconv_grad_plugin.head_weight_grad(dz, f).sum(dim=0)
@@ -1438,3 +1457,15 @@ class SegSynthesisBlock(torch.nn.Module):
         assert img is None or img.dtype == torch.float32
         assert seg is None or seg.dtype == torch.float32
         return x, img, seg
+
+
+# ---- the discriminator (training/discriminator.py) under the names pickles and `dnnlib.util.construct_class_by_name` know it by ----------
+_DISCRIMINATOR_NAMES = ('DiscriminatorBlock', 'MinibatchStdLayer', 'DiscriminatorEpilogue', 'Discriminator')
+
+
+def __getattr__(name):
+    # resolved on first use: training.discriminator imports this module for its layers
+    if name in _DISCRIMINATOR_NAMES:
+        from training import discriminator
+        return getattr(discriminator, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

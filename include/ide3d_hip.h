@@ -1498,6 +1498,33 @@ int ide3d_clip_head(const float* f, const float* base, const float* text, float*
 int ide3d_clip_head_backward(const float* e, const float* text, const float* norm, const float* tnorm, const float* dout, float* df,
                              int32_t n, int32_t D, int32_t T, void* stream);
 
+/*
+ * ABI 8 (entry points added).  The StyleGAN2 discriminator's adversarial loss (inversion/networks.py:1271-1502,
+ * apps/train_hybrid_encoder.py:100-117, 302-313) and its image gradient: what is not a convolution, a FIR pass, a join or a linear layer
+ * (those are ide3d_upfirdn2d, ide3d_modconv2d, ide3d_modconv_act_backward, ide3d_residual_join, ide3d_linear and
+ * ide3d_linear_backward_input); csrc/adv_loss.hip, DESIGN.md section 5.38.  Dense fp32 in device memory.  No atomics, float64 sums in a
+ * fixed order, bit-reproducible; no host synchronisation.  Bad arguments return IDE3D_EINVAL before any launch.
+ *
+ * ide3d_minibatch_std — `MinibatchStdLayer.forward` and its concatenation in one launch: x [n, c, h, w] -> y [n, c + features, h, w].
+ *   Channels 0 .. c - 1 of y are bit copies of x.  With G = group (0: n) and sample g (n / G) + j member g of group j (the grouping of
+ *   `x.reshape(G, -1, ...)`), channel c + f of every sample of group j holds the mean over the c / features channels of feature f and the
+ *   h w pixels of sqrt(var_G(x) + 1e-8), computed in float64 and rounded once.  n % G != 0 or c % features != 0: IDE3D_EINVAL.
+ * ide3d_minibatch_std_backward — dy [n, c + features, h, w] -> dx [n, c, h, w] = dy[:, :c] + D[j, f] / (c / features h w) *
+ *   (x - mean_G) / (G std), D[j, f] = the sum of dy[:, c + f] over the group's samples and pixels; std is recomputed from x.  The
+ *   derivative of the subtracted mean contributes nothing: the deviations of a group sum to zero.  With G = 1 the second term is an exact 0.
+ * ide3d_adv_head — the conditional projection and the logistic loss: o, cmap [n, M] -> logit [n] = o_i . cmap_i / sqrt(M) (cmap NULL:
+ *   M must be 1 and logit = o) and loss[0] = mean_i softplus(sign logit_i), softplus(z) = max(z, 0) + log1p(exp(-|z|)) in float64.
+ *   sign: -1 (generator, real images) or +1 (fake images of the discriminator's loss).
+ * ide3d_adv_head_backward — do [n, M] = dloss sign sigmoid(sign logit_i) / n * cmap[i, m] / sqrt(M).  dloss: DEVICE pointer to the
+ *   upstream scalar gradient.
+ */
+int ide3d_minibatch_std(const float* x, float* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t group, int32_t features, void* stream);
+int ide3d_minibatch_std_backward(const float* x, const float* dy, float* dx, int32_t n, int32_t c, int32_t h, int32_t w, int32_t group,
+                                 int32_t features, void* stream);
+int ide3d_adv_head(const float* o, const float* cmap, float* logit, float* loss, int32_t n, int32_t M, int32_t sign, void* stream);
+int ide3d_adv_head_backward(const float* o, const float* cmap, const float* logit, const float* dloss, float* dout, int32_t n, int32_t M,
+                            int32_t sign, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
