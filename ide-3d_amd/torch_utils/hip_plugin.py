@@ -419,6 +419,13 @@ def load():
             'ide3d_poly_kernel_sums': [vp, i64, i64, vp, i64, i64, i32, vp, vp, i32, i32, vp, i64, vp, vp],
             'ide3d_knn_radii': [vp, i64, i32, i64, i32, vp, i64, vp, vp],
             'ide3d_manifold_inside': [vp, i64, i64, vp, i64, i64, i32, vp, vp, i64, vp, vp],
+            'ide3d_ppl_prep': [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp],
+            'ide3d_lpips_pair_workspace_bytes': [ctypes.POINTER(_LpipsTap), i32, i32],
+            'ide3d_lpips_pair_distances': [ctypes.POINTER(_LpipsTap), i32, i32, f32, vp, i64, vp, vp],
+            'ide3d_trimmed_mean': [vp, i64, i64, i64, vp, vp],
+            'ide3d_inception_score_workspace_bytes': [i64, i32, i32],
+            'ide3d_inception_score': [vp, i64, i32, i64, i32, vp, i64, vp, vp],
+            'ide3d_label_iou': [vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, vp],
             'ide3d_augment_geometric': [vp, vp, i32, i32, i32, i32, i64, i64, vp, vp, vp, vp, vp, vp],
             'ide3d_augment_geometric_backward': [vp, vp, i32, i32, i32, i32, i64, i64, vp, vp, vp, vp, vp],
             'ide3d_augment_color': [vp, vp, i32, i32, i64, i64, i64, vp, i32, vp],
@@ -562,6 +569,8 @@ EXPORTED_SYMBOLS = (
     'ide3d_clip_prep', 'ide3d_clip_prep_backward', 'ide3d_vit_embed', 'ide3d_vit_embed_backward', 'ide3d_layernorm', 'ide3d_layernorm_backward',
     'ide3d_vit_attention', 'ide3d_vit_attention_backward', 'ide3d_quickgelu', 'ide3d_quickgelu_backward', 'ide3d_clip_head', 'ide3d_clip_head_backward',
     'ide3d_minibatch_std', 'ide3d_minibatch_std_backward', 'ide3d_adv_head', 'ide3d_adv_head_backward',
+    'ide3d_ppl_prep', 'ide3d_lpips_pair_workspace_bytes', 'ide3d_lpips_pair_distances', 'ide3d_trimmed_mean',
+    'ide3d_inception_score_workspace_bytes', 'ide3d_inception_score', 'ide3d_label_iou',
 )
 
 
@@ -2305,6 +2314,138 @@ class MetricsPlugin:
         _check(rc, 'manifold_inside')
 
 
+class MetricsEvalPlugin:
+    """The arithmetic between the networks of PPL, Inception Score and mIoU (csrc/metrics_eval.hip).
+    `training.metrics` holds the host definitions and the routing.  Every function works in the caller's buffers, on the current stream;
+    an output or workspace passed as None is allocated here."""
+
+    LABEL_DTYPES = {torch.int64: 0, torch.uint8: 1}
+
+    @staticmethod
+    def _buffer(t, dtype, numel, dev, what):
+        _require(isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous() and t.numel() >= numel,
+                 f'{what}: needs a contiguous {dtype} buffer of {numel} elements on {dev}')
+        return t
+
+    @staticmethod
+    def ppl_prep(x, mean, std, window=None, f=1, in_scale=1.0, in_shift=0.0, out=None):
+        """ide3d_ppl_prep: x [n, 3, H, W] -> ((f x f area mean inside window (y0, x0, h, w)) * in_scale + in_shift - mean) / std."""
+        LpipsPlugin._f32(x, 'x')
+        _require(x.ndim == 4 and x.shape[1] == 3, 'ppl_prep: x must be [n, 3, H, W]')
+        n, _, H, W = (int(v) for v in x.shape)
+        y0, x0, h, w = (int(v) for v in (window if window is not None else (0, 0, H, W)))
+        f = int(f)
+        _require(f >= 1 and h >= 1 and w >= 1 and h % f == 0 and w % f == 0 and 0 <= y0 and y0 + h <= H and 0 <= x0 and x0 + w <= W,
+                 f'ppl_prep: the window ({y0}, {x0}, {h}, {w}) must lie inside the {H} x {W} image and f = {f} must divide it')
+        mean = LpipsPlugin._f32(mean.reshape(-1), 'mean', x.device, (3,))
+        std = LpipsPlugin._f32(std.reshape(-1), 'std', x.device, (3,))
+        if out is None:
+            out = torch.empty([n, 3, h // f, w // f], dtype=torch.float32, device=x.device)
+        MetricsEvalPlugin._buffer(out, torch.float32, n * 3 * (h // f) * (w // f), x.device, 'ppl_prep: out')
+        with _dev_guard(x.device):
+            rc = load().ide3d_ppl_prep(_ptr(x), _ptr(out), _ptr(mean), _ptr(std), n, H, W, y0, x0, h, w, f, float(in_scale), float(in_shift), _stream(x))
+        _check(rc, 'ppl_prep')
+        return out
+
+    @staticmethod
+    def _pair_taps(acts, lins):
+        k = len(acts)
+        _require(1 <= k <= LPIPS_MAX_TAPS and len(lins) == k, f'lpips_pair_distances: 1..{LPIPS_MAX_TAPS} taps, one lin vector each')
+        dev, n2 = acts[0].device, int(acts[0].shape[0])
+        _require(n2 >= 2 and n2 % 2 == 0, 'lpips_pair_distances: every tap must hold 2 n images')
+        taps = (_LpipsTap * k)()
+        for i, (a, l) in enumerate(zip(acts, lins)):
+            LpipsPlugin._f32(a, 'tap', dev)
+            _require(a.ndim == 4 and a.shape[0] == n2, 'lpips_pair_distances: every tap must be [2 n, c, h, w]')
+            taps[i].a, (taps[i].c, taps[i].h, taps[i].w) = a.data_ptr(), a.shape[1:]
+            taps[i].lin = LpipsPlugin._f32(l, 'lin', dev, (a.shape[1],)).data_ptr()
+        return taps, k, n2 // 2, dev
+
+    @staticmethod
+    def pair_workspace_bytes(acts, lins):
+        taps, k, n, _ = MetricsEvalPlugin._pair_taps(acts, lins)
+        nbytes = load().ide3d_lpips_pair_workspace_bytes(taps, k, n)
+        _require(nbytes > 0, 'lpips_pair_distances: unsupported taps')
+        return nbytes
+
+    @staticmethod
+    def lpips_pair_distances(acts, lins, scale, workspace=None, dist=None):
+        """ide3d_lpips_pair_distances -> dist float32 [n]: scale * LPIPS(image i, image i + n) from the raw taps [2 n, c, h, w]."""
+        taps, k, n, dev = MetricsEvalPlugin._pair_taps(acts, lins)
+        lib = load()
+        if workspace is None:
+            nbytes = lib.ide3d_lpips_pair_workspace_bytes(taps, k, n)
+            _require(nbytes > 0, 'lpips_pair_distances: unsupported taps')
+            workspace = torch.empty([nbytes], dtype=torch.uint8, device=dev)
+        MetricsEvalPlugin._buffer(workspace, torch.uint8, 0, dev, 'lpips_pair_distances: workspace')
+        if dist is None:
+            dist = torch.empty([n], dtype=torch.float32, device=dev)
+        MetricsEvalPlugin._buffer(dist, torch.float32, n, dev, 'lpips_pair_distances: dist')
+        with _dev_guard(dev):
+            rc = lib.ide3d_lpips_pair_distances(taps, k, n, float(scale), _ptr(workspace), workspace.numel(), _ptr(dist), _stream(acts[0]))
+        _check(rc, 'lpips_pair_distances')
+        return dist
+
+    @staticmethod
+    def trimmed_mean(x, lo_rank, hi_rank, out=None):
+        """ide3d_trimmed_mean -> out float64 [4] = (mean of the x between the two order statistics, lo, hi, count)."""
+        _require(isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim == 1 and x.is_contiguous() and x.numel() > 0,
+                 'trimmed_mean: x must be a contiguous float32 CUDA vector')
+        if out is None:
+            out = torch.empty([4], dtype=torch.float64, device=x.device)
+        MetricsEvalPlugin._buffer(out, torch.float64, 4, x.device, 'trimmed_mean: out')
+        with _dev_guard(x.device):
+            rc = load().ide3d_trimmed_mean(_ptr(x), x.numel(), int(lo_rank), int(hi_rank), _ptr(out), _stream(x))
+        _check(rc, 'trimmed_mean')
+        return out
+
+    @staticmethod
+    def inception_workspace_bytes(n, d, splits):
+        nbytes = load().ide3d_inception_score_workspace_bytes(int(n), int(d), int(splits))
+        _require(nbytes >= 0, f'inception_score: unsupported call ({n} x {d} probabilities in {splits} splits): 1 <= d <= 8192, 1 <= splits <= 4096, splits <= n <= 2^22')
+        return nbytes
+
+    @staticmethod
+    def inception_score(p, splits, workspace=None, kl=None):
+        """ide3d_inception_score -> kl float64 [splits]: per split the mean over its rows of sum_j p (log p - log mean_j)."""
+        n, d, stride = MetricsPlugin._features(p, 'inception_score')
+        if workspace is None:
+            workspace = torch.empty([max(16, MetricsEvalPlugin.inception_workspace_bytes(n, d, splits))], dtype=torch.uint8, device=p.device)
+        MetricsEvalPlugin._buffer(workspace, torch.uint8, 0, p.device, 'inception_score: workspace')
+        if kl is None:
+            kl = torch.empty([int(splits)], dtype=torch.float64, device=p.device)
+        MetricsEvalPlugin._buffer(kl, torch.float64, int(splits), p.device, 'inception_score: kl')
+        with _dev_guard(p.device):
+            rc = load().ide3d_inception_score(_ptr(p), n, d, stride, int(splits), _ptr(workspace), workspace.numel(), _ptr(kl), _stream(p))
+        _check(rc, 'inception_score')
+        return kl
+
+    @staticmethod
+    def label_iou(a, b, classes, remap=None, counts=None, iou=None):
+        """ide3d_label_iou -> (iou float32 [n], counts int32 [n, classes, 2]) of two label maps [n, ...] (int64 or uint8, one dtype)."""
+        _require(isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.is_cuda and b.device == a.device and a.dtype == b.dtype
+                 and a.dtype in MetricsEvalPlugin.LABEL_DTYPES and a.shape == b.shape and a.ndim >= 2 and a.is_contiguous() and b.is_contiguous()
+                 and a.numel() > 0, 'label_iou: two contiguous int64 or uint8 CUDA label maps [n, ...] of one shape, dtype and device')
+        n, classes = int(a.shape[0]), int(classes)
+        hw = a.numel() // n
+        _require(1 <= classes <= 32, f'label_iou: classes must be 1..32, got {classes}')
+        n_in = 0
+        if remap is not None:
+            MetricsEvalPlugin._buffer(remap, torch.int32, 1, a.device, 'label_iou: remap')
+            n_in = remap.numel()
+        if counts is None:
+            counts = torch.empty([n, classes, 2], dtype=torch.int32, device=a.device)
+        if iou is None:
+            iou = torch.empty([n], dtype=torch.float32, device=a.device)
+        MetricsEvalPlugin._buffer(counts, torch.int32, n * classes * 2, a.device, 'label_iou: counts')
+        MetricsEvalPlugin._buffer(iou, torch.float32, n, a.device, 'label_iou: iou')
+        with _dev_guard(a.device):
+            rc = load().ide3d_label_iou(_ptr(a), _ptr(b), MetricsEvalPlugin.LABEL_DTYPES[a.dtype], n, hw, _ptr(remap), n_in, classes, _ptr(counts), _ptr(iou),
+                                        _stream(a))
+        _check(rc, 'label_iou')
+        return iou, counts
+
+
 class AugmentPlugin:
     """The geometric and colour stages of the ADA pipeline on float32 CUDA images (csrc/augment.hip): what
     training/augment.py:290-306 and 363-368 do, as one launch each way.  `training.augment` draws the parameters, folds the matrices and
@@ -3720,6 +3861,7 @@ PLUGINS = {
     'png_plugin': PngPlugin,
     'jpeg_plugin': JpegPlugin,
     'metrics_plugin': MetricsPlugin,
+    'metrics_eval_plugin': MetricsEvalPlugin,
     'augment_plugin': AugmentPlugin,
     'lowres_plugin': LowresPlugin,
     'bias_act_plugin': BiasActPlugin,

@@ -365,3 +365,296 @@ def feature_stats_for_images(batches, detector, max_items=None, detector_kwargs=
                 break
             stats.append_torch(detector(_three_channels(images), **detector_kwargs))
     return stats
+
+
+# ====================================================================================================================================
+# Perceptual path length, Inception Score and mIoU (metrics/perceptual_path_length.py, metrics/inception_score.py,
+# apps/calc_losses_on_images.py; csrc/metrics_eval.hip).  As above: every function has a host definition that CPU
+# tensors and numpy arrays take, and float32 (labels: int64 / uint8) CUDA tensors take the kernels.
+#
+#   PPL        dist = |lpips(G(w_t)) - lpips(G(w_{t+eps}))|^2 / eps^2 per sample; PPL = the mean of the distances between their 1 % and
+#              99 % order statistics (`percentile(..., 'lower')` and `(..., 'higher')`, both ends and their ties kept).
+#   IS         per split of the rows of p [n, d]: kl = mean_i sum_j p_ij (log p_ij - log mean_i p_ij); IS = mean and std of exp(kl).
+#              A zero probability gives NaN (0 * -inf), as the reference's numpy lines do.
+#   mIoU       per image, the mean over ALL classes of |a == c and b == c| / (|a == c or b == c| + 1e-6) in float32.
+# ====================================================================================================================================
+
+_MULTI_GPU = ('the feature exchange between GPUs (num_gpus > 1) is not implemented; collect per-rank statistics and add their raw sums')
+
+
+def _single_gpu(what, num_gpus):
+    if num_gpus > 1:
+        raise NotImplementedError(f'{what}: {_MULTI_GPU}')
+
+
+# ---- PPL --------------------------------------------------------------------------------------------------------------------------
+
+def slerp(a, b, t):
+    """Spherical interpolation of batches of vectors (perceptual_path_length.py:22-31): both ends normalised, the result on the unit sphere."""
+    unit = lambda v: torch.nn.functional.normalize(v, dim=-1, eps=0.0)
+    start, end = unit(a), unit(b)
+    cosine = torch.linalg.vecdot(start, end, dim=-1).unsqueeze(-1)
+    angle = torch.acos(cosine) * t                           # the arc walked from `start`, a fraction t of the angle between the ends
+    tangent = unit(end - cosine * start)                     # the unit direction at `start` in the plane of the two, towards `end`
+    return unit(torch.cos(angle) * start + torch.sin(angle) * tangent)
+
+
+def _rgb_of(out):
+    """The RGB image of what `G.synthesis` returns (a tensor, a tuple that starts with it, or the `return_dict` form)."""
+    if isinstance(out, dict):
+        return out['image']
+    return out[0] if isinstance(out, (tuple, list)) else out
+
+
+class PPLSampler(torch.nn.Module):
+    """perceptual_path_length.PPLSampler: `forward(c) -> dist [n]` for camera / conditioning labels c [n, c_dim], with the reference's
+    constructor arguments and its order of RNG calls (`rand` for t, one `randn([2 n, z_dim]).chunk(2)`, `randn_like` into every
+    `*.noise_const` of the sampler's own deep copy of G).  `vgg16`:
+      a `training.lpips.LPIPS('vgg')` module - float32 CUDA images then run ide3d_ppl_prep -> the fused feature walk over the 2 n images ->
+        ide3d_lpips_pair_distances (13 activations are written, no normalised taps, no feature vector); anything else takes the torch
+        definition of the same distance through the module;
+      any other callable `vgg16(img_0_255, resize_images=False, return_lpips=True) -> [2 n, F]` (the reference's detector) - the reference's
+        lines as torch ops.
+    `last_path`: 'hip' or 'torch', the path of the last call."""
+
+    def __init__(self, G, G_kwargs, epsilon, space, sampling, crop, vgg16):
+        import copy
+        assert space in ['z', 'w']
+        assert sampling in ['full', 'end']
+        super().__init__()
+        self.G = copy.deepcopy(G)
+        self.G_kwargs = G_kwargs
+        self.epsilon = epsilon
+        self.space = space
+        self.sampling = sampling
+        self.crop = crop
+        self.vgg16 = copy.deepcopy(vgg16)
+        self.last_path = None
+
+    def images(self, c):
+        """The 2 n images of one batch (t first, then t + epsilon), as synthesis returns them."""
+        n = c.shape[0]
+        t = torch.rand([n], device=c.device) * (1 if self.sampling == 'full' else 0)
+        z0, z1 = torch.randn([n * 2, self.G.z_dim], device=c.device).chunk(2)
+        if self.space == 'w':
+            w0, w1 = self.G.mapping(z=torch.cat([z0, z1]), c=torch.cat([c, c])).chunk(2)
+            wt0 = w0.lerp(w1, t.unsqueeze(1).unsqueeze(2))
+            wt1 = w0.lerp(w1, t.unsqueeze(1).unsqueeze(2) + self.epsilon)
+        else:
+            zt0 = slerp(z0, z1, t.unsqueeze(1))
+            zt1 = slerp(z0, z1, t.unsqueeze(1) + self.epsilon)
+            wt0, wt1 = self.G.mapping(z=torch.cat([zt0, zt1]), c=torch.cat([c, c])).chunk(2)
+        for name, buf in self.G.named_buffers():
+            if name.endswith('.noise_const'):
+                buf.copy_(torch.randn_like(buf))
+        kwargs = dict(self.G_kwargs)
+        kwargs.setdefault('c', torch.cat([c, c]))          # this synthesis network renders from the camera label
+        return _rgb_of(self.G.synthesis(ws=torch.cat([wt0, wt1]), noise_mode='const', force_fp32=True, **kwargs))
+
+    def _window(self, img):
+        """(y0, x0, h, w) of the centre crop (perceptual_path_length.py:72-75), or the whole image, and the area factor down to 256."""
+        H, W = (int(v) for v in img.shape[2:])
+        window = (0, 0, H, W)
+        if self.crop:
+            assert H == W
+            c = H // 8
+            window = (c * 3, c * 2, c * 4, c * 4)
+        factor = max(self.G.img_resolution // 256, 1)
+        return window, factor
+
+    def distances(self, img):
+        """dist [n] of 2 n images in -1..1."""
+        from training import feature_loss, lpips
+        (y0, x0, h, w), f = self._window(img)
+        eps2 = self.epsilon ** 2
+        lp = self.vgg16
+        if not (isinstance(lp, lpips.LPIPS) and type(lp.net) is lpips.VGG16Features):
+            # the reference's lines 71-89 for its detector
+            img = img[:, :, y0:y0 + h, x0:x0 + w]
+            if f > 1:
+                img = img.reshape([-1, img.shape[1], img.shape[2] // f, f, img.shape[3] // f, f]).mean([3, 5])
+            img = (img + 1) * (255 / 2)
+            if img.shape[1] == 1:
+                img = img.repeat([1, 3, 1, 1])
+            lpips_t0, lpips_t1 = lp(img, resize_images=False, return_lpips=True).chunk(2)
+            self.last_path = 'torch'
+            return (lpips_t0 - lpips_t1).square().sum(1) / eps2
+        if img.shape[1] == 1:
+            img = img.repeat([1, 3, 1, 1])
+        if (isinstance(img, torch.Tensor) and img.is_cuda and h % f == 0 and w % f == 0 and lp._sides_ok(h // f, w // f)
+                and lp._on_hip(img.contiguous())):
+            P = hip_plugin.MetricsEvalPlugin
+            x = img.detach().contiguous()
+            with torch.no_grad():
+                saved = feature_loss.forward_walk(feature_loss.HipOps.get(), feature_loss.plan_of(lp.net),
+                                                  lambda: P.ppl_prep(x, lp.net.mean, lp.net.std, (y0, x0, h, w), f), False)
+                dist = P.lpips_pair_distances(feature_loss.tapped(saved), lp._lin_vectors(), 1.0 / eps2)
+            self.last_path = 'hip'
+            return dist
+        z = lpips._prep_torch(img[:, :, y0:y0 + h, x0:x0 + w], lp.net, f, 1.0, 0.0)
+        dist = None
+        for a, l in zip(lp.net.taps(z), lp.lin):
+            u0, u1 = lpips._Normalize.apply(a).chunk(2)
+            d = ((u0 - u1).square() * l[1].weight).sum(dim=1).mean(dim=(1, 2))
+            dist = d if dist is None else dist + d
+        self.last_path = 'torch'
+        return dist / eps2
+
+    def forward(self, c):
+        return self.distances(self.images(c))
+
+
+def percentile_ranks(n):
+    """(lo_rank, hi_rank): the positions in sorted order that `np.percentile(x, 1, method='lower')` and `(x, 99, method='higher')` pick
+    from n values, in integers."""
+    if n < 1:
+        raise ValueError('percentile_ranks: no values')
+    return (n - 1) // 100, -((-99 * (n - 1)) // 100)
+
+
+def trimmed_mean_host(x, lo_rank, hi_rank):
+    """The numpy float64 definition of ide3d_trimmed_mean -> (mean, lo, hi, count); any NaN in x: (nan, nan, nan, 0)."""
+    x = np.asarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x).reshape(-1)
+    if not 0 <= lo_rank <= hi_rank < x.size:
+        raise ValueError(f'trimmed_mean: ranks must satisfy 0 <= lo <= hi < n, got {lo_rank}, {hi_rank}, n = {x.size}')
+    if np.isnan(x).any():
+        return float('nan'), float('nan'), float('nan'), 0
+    part = np.partition(x, (lo_rank, hi_rank))
+    lo, hi = part[lo_rank], part[hi_rank]
+    kept = x[(x >= lo) & (x <= hi)].astype(np.float64)
+    with np.errstate(invalid='ignore'):
+        return float(kept.sum() / kept.size), float(lo), float(hi), int(kept.size)
+
+
+def ppl_from_distances(dist):
+    """The trimmed mean of perceptual_path_length.py:119-122.  A float32 CUDA vector takes `ide3d_trimmed_mean` and ONE read of its
+    mean; CPU tensors and numpy arrays the numpy float64 definition."""
+    n = int(dist.numel() if isinstance(dist, torch.Tensor) else np.asarray(dist).size)
+    lo_rank, hi_rank = percentile_ranks(n)
+    if _on_device(dist):
+        out = hip_plugin.MetricsEvalPlugin.trimmed_mean(dist.detach().reshape(-1).contiguous(), lo_rank, hi_rank)
+        return float(out[0].item())
+    return trimmed_mean_host(dist, lo_rank, hi_rank)[0]
+
+
+def compute_ppl(G, vgg16, c_iter, num_samples, epsilon, space, sampling, crop, batch_size, G_kwargs={}, num_gpus=1, rank=0):
+    """perceptual_path_length.compute_ppl: `num_samples` distances, `batch_size` at a time with labels from `c_iter`, then their trimmed mean.
+    The distances stay where the sampler computes them until the one final read."""
+    _single_gpu('compute_ppl', num_gpus)
+    device = next(G.parameters()).device
+    sampler = PPLSampler(G=G, G_kwargs=G_kwargs, epsilon=epsilon, space=space, sampling=sampling, crop=crop, vgg16=vgg16)
+    sampler.eval().requires_grad_(False).to(device)
+    dist = []
+    with torch.no_grad():
+        for _batch_start in range(0, num_samples, batch_size):
+            dist.append(sampler(next(c_iter)))
+    return ppl_from_distances(torch.cat(dist)[:num_samples])
+
+
+def ppl2_wend(G, vgg16, c_iter, num_samples=50000, G_kwargs={}, num_gpus=1, rank=0):
+    """`ppl2_wend` of metrics/metric_main.py: PPL in W at the path end points, full image."""
+    return compute_ppl(G, vgg16, c_iter, num_samples=num_samples, epsilon=1e-4, space='w', sampling='end', crop=False, batch_size=2,
+                       G_kwargs=G_kwargs, num_gpus=num_gpus, rank=rank)
+
+
+# ---- Inception Score --------------------------------------------------------------------------------------------------------------
+
+def _check_splits(n, num_splits):
+    if num_splits < 1 or n < num_splits:
+        raise ValueError(f'inception_score: {n} rows cannot fill {num_splits} splits')
+
+
+def inception_kl_host(probs, num_splits):
+    """The numpy float64 definition -> kl [num_splits] (inception_score.py:31-34 without the exp)."""
+    p = _f64(probs)
+    n = p.shape[0]
+    _check_splits(n, num_splits)
+    kl = np.empty([num_splits], np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        for i in range(num_splits):
+            part = p[i * n // num_splits:(i + 1) * n // num_splits]
+            kl[i] = np.mean(np.sum(part * (np.log(part) - np.log(np.mean(part, axis=0, keepdims=True))), axis=1))
+    return kl
+
+
+def inception_kl(probs, num_splits):
+    """-> numpy float64 [num_splits]; float32 CUDA probabilities take `ide3d_inception_score`."""
+    if not _on_device(probs):
+        return inception_kl_host(probs, num_splits)
+    p = _rows(probs)
+    _check_splits(int(p.shape[0]), num_splits)
+    return hip_plugin.MetricsEvalPlugin.inception_score(p, num_splits).cpu().numpy()
+
+
+def inception_score(probs, num_splits=10):
+    """-> (mean, std) of exp(kl) over the splits of probs [n, d] (inception_score.py:30-36)."""
+    scores = np.exp(inception_kl(probs, num_splits))
+    return float(np.mean(scores)), float(np.std(scores))
+
+
+def is50k(G, detector, c_iter, num_gen=50000, num_splits=10, batch_size=64, batch_gen=None, G_kwargs={}, num_gpus=1, rank=0):
+    """`is50k` of metrics/metric_main.py: `detector` is the Inception network as a callable that returns class probabilities (it receives
+    `no_output_bias=True`, as in the reference); the probabilities stay on the device they are computed on."""
+    _single_gpu('is50k', num_gpus)
+    stats = feature_stats_for_generator(G, detector, c_iter, max_items=num_gen, batch_size=batch_size, batch_gen=batch_gen, G_kwargs=G_kwargs,
+                                        detector_kwargs=dict(no_output_bias=True), capture_all=True)
+    return inception_score(stats.get_all_torch(), num_splits)
+
+
+# ---- mIoU -------------------------------------------------------------------------------------------------------------------------
+
+def _labels_np(x):
+    x = np.asarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x).astype(np.int64)
+    return x.reshape(x.shape[0], -1)
+
+
+def label_iou_host(a, b, classes=19, remap=None):
+    """The numpy definition -> (iou float32 [n], counts int32 [n, classes, 2]) as CPU tensors."""
+    a, b = _labels_np(a), _labels_np(b)
+    if a.shape != b.shape:
+        raise ValueError(f'label_iou: the maps differ in shape ({a.shape}, {b.shape})')
+    if remap is not None:
+        table = np.asarray(remap.detach().cpu().numpy() if isinstance(remap, torch.Tensor) else remap).astype(np.int64).reshape(-1)
+        a, b = (np.where((m >= 0) & (m < table.size), table[np.clip(m, 0, table.size - 1)], -1) for m in (a, b))
+    counts = np.zeros([a.shape[0], classes, 2], np.int32)
+    for c in range(classes):
+        ia, ib = a == c, b == c
+        counts[:, c, 0] = (ia & ib).sum(axis=1)
+        counts[:, c, 1] = (ia | ib).sum(axis=1)
+    terms = counts[:, :, 0].astype(np.float32) / (counts[:, :, 1].astype(np.float32) + np.float32(1e-6))
+    return torch.from_numpy(terms.mean(axis=1, dtype=np.float32)), torch.from_numpy(counts)
+
+
+def label_iou(a, b, classes=19, remap=None):
+    """-> (iou float32 [n], counts int32 [n, classes, 2]: intersection and union per class) of two label maps [n, ...].  `remap`: a table
+    applied to both maps first (a label outside the table, or outside [0, classes) after it, counts for no class).  int64 or uint8 CUDA maps
+    take `ide3d_label_iou`; anything else the numpy definition."""
+    if not (1 <= classes <= 32):
+        raise ValueError(f'label_iou: classes must be 1..32, got {classes}')
+    on_dev = all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.int64, torch.uint8) for t in (a, b)) and a.dtype == b.dtype
+    if not on_dev:
+        return label_iou_host(a, b, classes, remap)
+    if remap is not None:
+        remap = torch.as_tensor(remap).to(device=a.device, dtype=torch.int32).reshape(-1).contiguous()
+    return hip_plugin.MetricsEvalPlugin.label_iou(a.detach().contiguous(), b.detach().contiguous(), classes, remap)
+
+
+class mIOU(torch.nn.Module):
+    """apps/calc_losses_on_images.mIOU: `forward(source, target) -> [n]`, images in -1..1.  Both are resized to `size`^2 (bilinear,
+    `align_corners=True`), parsed by `bisNet` (`training.parse_loss.labels`: the argmax class ids) and compared class by class after the
+    `celebahq` remap of `face_parsing.id_remap`, which the kernel applies; no one-hot tensor exists."""
+
+    def __init__(self, bisNet, classes=19, size=512):
+        super().__init__()
+        from training import face_parsing
+        self.bisNet = bisNet
+        self.classes, self.size = classes, size
+        self.register_buffer('remap', torch.tensor(face_parsing.REMAP, dtype=torch.int32), persistent=False)
+
+    def labels(self, img):
+        from training import parse_loss
+        img = torch.nn.functional.interpolate(img, size=(self.size, self.size), mode='bilinear', align_corners=True)
+        return parse_loss.labels(self.bisNet, img)
+
+    def forward(self, source, target):
+        return label_iou(self.labels(source), self.labels(target), self.classes, self.remap.to(source.device))[0]

@@ -1525,6 +1525,51 @@ int ide3d_adv_head(const float* o, const float* cmap, float* logit, float* loss,
 int ide3d_adv_head_backward(const float* o, const float* cmap, const float* logit, const float* dloss, float* dout, int32_t n, int32_t M,
                             int32_t sign, void* stream);
 
+/*
+ * ABI 8 (entry points added).  The arithmetic between the networks of the remaining metrics: perceptual path length, Inception Score and
+ * the mIoU of parser labels; csrc/metrics_eval.hip, DESIGN.md section 5.39.  No float atomics: every floating-point sum is float64 in an
+ * order fixed by the launch geometry, so two runs are bit-equal; integer counts use integer adds.  No host synchronisation.  A null,
+ * misaligned or undersized buffer or an out-of-range size returns IDE3D_EINVAL before any launch.
+ *
+ * ide3d_ppl_prep replaces metrics/perceptual_path_length.py:71-83 and the z-score in front of the feature net: x [n, 3, H, W] ->
+ *   y [n, 3, h / f, w / f], y = ((mean of the f x f block inside the window [y0 : y0 + h, x0 : x0 + w]) * in_scale + in_shift - mean[c]) /
+ *   std[c].  1 <= f <= 64 divides h and w; the window lies inside the image.  With the full window it is bit-equal to ide3d_lpips_prep
+ *   (the same summation order).  mean, std: 3 floats each (DEVICE).
+ * ide3d_lpips_pair_distances replaces perceptual_path_length.py:89: taps as for ide3d_lpips_head, each `a` [2 n, c, h, w] (t and out
+ *   unused); per tap u = a * (float)(1 / (sqrt(sum_c a^2) + 1e-10)), the head's normalisation; dist[i] = scale * sum over taps of
+ *   (1 / (h w)) sum_{h,w} sum_c lin[c] (u_i - u_{i+n})^2 for i < n, the sums in float64, dist float32 [n]; scale = 1 / epsilon^2.  k
+ *   launches (one float64 partial per workgroup -> workspace of ide3d_lpips_pair_workspace_bytes(), 8-byte aligned) + 1 finishing launch.
+ *   Identical images give exactly 0.  1 <= n <= 2^20.
+ * ide3d_trimmed_mean replaces perceptual_path_length.py:119-122: x [n] fp32, 1 <= n <= 2^24, ranks 0 <= lo_rank <= hi_rank < n.
+ *   lo, hi = the lo_rank-th and hi_rank-th smallest values (radix select on the order-preserving integer image of the float, 8-bit LDS
+ *   histograms; no sort); out[4] (float64) = {mean of all x with lo <= x <= hi compared as floats (ties at either end are all kept), lo,
+ *   hi, their count}.  Any NaN in x: out = {NaN, NaN, NaN, 0}, as numpy's percentile and mean give.  One workgroup.  The reference's
+ *   ranks are lo_rank = (n - 1) / 100 and hi_rank = ceil(99 (n - 1) / 100) in integers.
+ * ide3d_inception_score replaces metrics/inception_score.py:31-34: p [n, d] fp32 with a row stride >= d, split s = rows
+ *   [s n / S, (s + 1) n / S); kl[s] (float64) = mean over the split's rows of sum_j p (log p - log m_j), m_j the column mean over the split,
+ *   everything in float64.  1 <= d <= 8192, 1 <= S <= 4096, S <= n <= 2^22.  A zero probability yields NaN (0 * -inf), as the reference's
+ *   numpy lines do.  exp, mean and std over the S values are the caller's.  Workspace: ide3d_inception_score_workspace_bytes(), 16-byte
+ *   aligned (log m, then the column sums and the row sums per chunk of at least 32 rows, at most 256 chunks per split).
+ * ide3d_label_iou replaces apps/calc_losses_on_images.py:28-30 after the one-hot: a, b [n, hw] label maps (int64 or uint8 by `dtype`);
+ *   remap: NULL (n_in = 0), or int32 [n_in] (DEVICE) applied to both maps first (a label outside [0, n_in) counts for no class);
+ *   1 <= classes <= 32, 1 <= hw < 2^31.  counts int32 [n, classes, 2] = per class the pixels where both maps carry it and where either does;
+ *   iou[i] (float32) = mean over ALL classes of float(inter) / (float(union) + 1e-6f), summed in class order.  A label outside
+ *   [0, classes) after the remap counts for no class.
+ */
+#define IDE3D_LABEL_INT64 0
+#define IDE3D_LABEL_UINT8 1
+int ide3d_ppl_prep(const float* x, float* y, const float* mean, const float* std_, int32_t n, int32_t H, int32_t W, int32_t y0,
+                   int32_t x0, int32_t h, int32_t w, int32_t f, float in_scale, float in_shift, void* stream);
+int64_t ide3d_lpips_pair_workspace_bytes(const ide3d_lpips_tap* taps, int32_t k, int32_t n);
+int ide3d_lpips_pair_distances(const ide3d_lpips_tap* taps, int32_t k, int32_t n, float scale, void* workspace, int64_t workspace_bytes,
+                               float* dist, void* stream);
+int ide3d_trimmed_mean(const float* x, int64_t n, int64_t lo_rank, int64_t hi_rank, double* out, void* stream);
+int64_t ide3d_inception_score_workspace_bytes(int64_t n, int32_t d, int32_t splits);
+int ide3d_inception_score(const float* p, int64_t n, int32_t d, int64_t row_stride, int32_t splits, void* workspace, int64_t workspace_bytes,
+                          double* kl, void* stream);
+int ide3d_label_iou(const void* a, const void* b, int32_t dtype, int32_t n, int64_t hw, const int32_t* remap, int32_t n_in, int32_t classes,
+                    int32_t* counts, float* iou, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
