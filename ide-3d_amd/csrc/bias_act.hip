@@ -5,7 +5,9 @@
 // kernel that moves 16 bytes per lane per access (global_load_dwordx4), grid-strides over
 // 256 CUs x 8 workgroups, and resolves the bias index once per 16-byte vector whenever the
 // bias stride allows it.  Algorithmic traffic: 2 * numel * sizeof(T) (+ xref/yref/dy reads for
-// the gradient forms).
+// the gradient forms).  The gradient forms take x + b (xref) where the caller kept x and the stored y otherwise: from x + b the
+// derivative carries nothing of the rounding of y in the storage type or of the division by the gain (tests/test_gpu_bias_act.py), and
+// lrelu with a negative slope, whose y is positive on both sides of the kink, can only be decided from it.
 #include "common.h"
 #include "knobs.h"
 
@@ -14,7 +16,7 @@ namespace ide3d {
 template <class T, int N> struct alignas(sizeof(T) * N) Vec { T v[N]; };
 
 template <class M>
-__device__ __forceinline__ M act_eval(int A, int G, M x, M xref, M yy, M alpha, M& yref, M gain) {
+__device__ __forceinline__ M act_eval(int A, int G, M x, M xref, bool has_x, M yy, M alpha, M& yref, M gain) {
     const M one = (M)1, two = (M)2;
     const M expRange = (M)80, halfExpRange = (M)40;
     const M seluScale = (M)1.0507009873554804934193349852946;
@@ -30,40 +32,75 @@ __device__ __forceinline__ M act_eval(int A, int G, M x, M xref, M yy, M alpha, 
         break;
     case 3:  // lrelu
         if (G == 0) y = (x > 0) ? x : x * alpha;
-        if (G == 1) y = (yy > 0) ? x : x * alpha;
+        // the side of the kink: from x + b where the caller kept x (it has to for alpha < 0, where y is positive on both sides)
+        if (G == 1) y = ((has_x ? xref : yy) > 0) ? x : x * alpha;
         break;
     case 4:  // tanh
         if (G == 0) y = tanh(x);
-        if (G == 1) y = x * (one - yy * yy);
-        if (G == 2) y = x * (one - yy * yy) * (-two * yy);
+        // Gradients: from x + b where the caller kept x (the op does for every smooth activation), so that nothing of the rounding of
+        // the stored y or of the division by the gain enters; from y otherwise, as the reference kernel does.
+        // 1 - tanh^2 = 4 e / (1 + e)^2 with e = exp(-2 |x|): no cancellation next to |tanh| = 1
+        if (G >= 1 && has_x) {
+            const M e = exp(-two * fabs(xref)), d = one + e;
+            const M sech2 = (M)4 * e / (d * d), t = (xref < 0) ? -(one - e) / d : (one - e) / d;
+            y = (G == 1) ? x * sech2 : x * sech2 * (-two * t);
+        } else {
+            if (G == 1) y = x * (one - yy * yy);
+            if (G == 2) y = x * (one - yy * yy) * (-two * yy);
+        }
         break;
     case 5:  // sigmoid
         if (G == 0) y = (x < -expRange) ? (M)0 : one / (exp(-x) + one);
-        if (G == 1) y = x * yy * (one - yy);
-        if (G == 2) y = x * yy * (one - yy) * (one - two * yy);
+        if (G >= 1 && has_x) {          // s (1 - s) = e / (1 + e)^2 with e = exp(-|x|)
+            const M e = exp(-fabs(xref)), d = one + e;
+            const M s1 = e / (d * d), s = (xref < 0) ? e / d : one / d;
+            y = (G == 1) ? x * s1 : x * s1 * (one - two * s);
+        } else {
+            if (G == 1) y = x * yy * (one - yy);
+            if (G == 2) y = x * yy * (one - yy) * (one - two * yy);
+        }
         break;
     case 6:  // elu
         if (G == 0) y = (x >= 0) ? x : expm1(x);
-        if (G == 1) y = (yy >= 0) ? x : x * (yy + one);
-        if (G == 2) y = (yy >= 0) ? (M)0 : x * (yy + one);
+        if (G >= 1 && has_x) {
+            y = (xref >= 0) ? ((G == 1) ? x : (M)0) : x * exp(xref);
+        } else {
+            if (G == 1) y = (yy >= 0) ? x : x * (yy + one);
+            if (G == 2) y = (yy >= 0) ? (M)0 : x * (yy + one);
+        }
         break;
     case 7:  // selu
         if (G == 0) y = (x >= 0) ? seluScale * x : (seluScale * seluAlpha) * expm1(x);
-        if (G == 1) y = (yy >= 0) ? x * seluScale : x * (yy + seluScale * seluAlpha);
-        if (G == 2) y = (yy >= 0) ? (M)0 : x * (yy + seluScale * seluAlpha);
+        if (G >= 1 && has_x) {
+            y = (xref >= 0) ? ((G == 1) ? x * seluScale : (M)0) : x * ((seluScale * seluAlpha) * exp(xref));
+        } else {
+            if (G == 1) y = (yy >= 0) ? x * seluScale : x * (yy + seluScale * seluAlpha);
+            if (G == 2) y = (yy >= 0) ? (M)0 : x * (yy + seluScale * seluAlpha);
+        }
         break;
     case 8:  // softplus
         if (G == 0) y = (x > (M)20) ? x : log1p(exp(x));
-        if (G == 1) y = x * (one - exp(-yy));
-        if (G == 2) { M c = exp(-yy); y = x * c * (one - c); }
+        // above the threshold the definition is y = x: slope 1 and curvature 0, not 1 - e^-y and e^-y (1 - e^-y), which are 2e-9 away.
+        // With x + b at hand (the op keeps x for the smooth activations) the slope is sigmoid(x + b) itself and carries nothing of the
+        // rounding of the stored y; from y alone, yy > 20 stands for x > 20.
+        if (has_x) {
+            M s = one / (one + exp(-xref));
+            if (G == 1) y = (xref > (M)20) ? x : x * s;
+            if (G == 2) y = (xref > (M)20) ? (M)0 : x * s * (one - s);
+        } else {
+            if (G == 1) y = (yy > (M)20) ? x : x * (one - exp(-yy));
+            if (G == 2) { M c = exp(-yy); y = (yy > (M)20) ? (M)0 : x * c * (one - c); }
+        }
         break;
     case 9:  // swish
         if (G == 0) {
             y = (x < -expRange) ? (M)0 : x / (exp(-x) + one);
         } else {
-            M c = exp(xref), d = c + one;
-            if (G == 1) y = (xref > halfExpRange) ? x : x * c * (xref + d) / (d * d);
-            else        y = (xref > halfExpRange) ? (M)0 : x * c * (xref * (two - d) + two * d) / (d * d * d);
+            // with s = sigmoid(x): (x s)' = s (1 + x (1 - s)), (x s)'' = s (1 - s) (2 + x (1 - 2 s)); s (1 - s) = e / (1 + e)^2, e = exp(-|x|)
+            const M e = exp(-fabs(xref)), d = one + e;
+            const M s1 = e / (d * d), s = (xref < 0) ? e / d : one / d, q = (xref < 0) ? one / d : e / d;          // q = 1 - s
+            if (G == 1) y = (xref > halfExpRange) ? x : x * (s + xref * s1);
+            else        y = (xref > halfExpRange) ? (M)0 : x * s1 * (two + xref * (q - s));
             yref = (xref < -expRange) ? (M)0 : xref / (exp(-xref) + one) * gain;
         }
         break;
@@ -74,12 +111,12 @@ __device__ __forceinline__ M act_eval(int A, int G, M x, M xref, M yy, M alpha, 
 template <class T, int A>
 __device__ __forceinline__ typename Elem<T>::math_t
 bias_act_one(typename Elem<T>::math_t x, typename Elem<T>::math_t b, typename Elem<T>::math_t xref,
-             typename Elem<T>::math_t yref, typename Elem<T>::math_t dy, int G,
+             typename Elem<T>::math_t yref, typename Elem<T>::math_t dy, bool has_x, int G,
              typename Elem<T>::math_t alpha, typename Elem<T>::math_t gain, typename Elem<T>::math_t clamp) {
     using M = typename Elem<T>::math_t;
     M yy = (gain != 0) ? yref / gain : (M)0;
     if (G == 0) x += b; else xref += b;
-    M y = act_eval<M>(A, G, x, xref, yy, alpha, yref, gain);
+    M y = act_eval<M>(A, G, x, xref, has_x, yy, alpha, yref, gain);
     y *= gain * dy;
     if (clamp >= 0) {
         if (G == 0) y = (y > -clamp && y < clamp) ? y : ((y >= 0) ? clamp : -clamp);
@@ -114,7 +151,7 @@ bias_act_vec_kernel(const T* __restrict__ x, const T* __restrict__ b, const T* _
             M xr = xref ? Elem<T>::ld(&vxr.v[k]) : (M)0;
             M yr = yref ? Elem<T>::ld(&vyr.v[k]) : (M)0;
             M d  = dy   ? Elem<T>::ld(&vdy.v[k]) : (M)1;
-            M r = bias_act_one<T, A>(Elem<T>::ld(&vx.v[k]), bv, xr, yr, d, G, alpha, gain, clamp);
+            M r = bias_act_one<T, A>(Elem<T>::ld(&vx.v[k]), bv, xr, yr, d, xref != nullptr, G, alpha, gain, clamp);
             Elem<T>::st(&vo.v[k], r);
         }
         reinterpret_cast<V*>(y)[iv] = vo;
@@ -150,7 +187,7 @@ bias_act_plane_kernel(const T* __restrict__ x, const T* __restrict__ b, T* __res
         V vo;
 #pragma unroll
         for (int k = 0; k < VEC; ++k)
-            Elem<T>::st(&vo.v[k], bias_act_one<T, A>(Elem<T>::ld(&vx[it].v[k]), bv, (M)0, (M)0, (M)1, 0, alpha, gain, clamp));
+            Elem<T>::st(&vo.v[k], bias_act_one<T, A>(Elem<T>::ld(&vx[it].v[k]), bv, (M)0, (M)0, (M)1, false, 0, alpha, gain, clamp));
         yv[i] = vo;
     }
 }
@@ -170,7 +207,7 @@ bias_act_scalar_kernel(const T* __restrict__ x, const T* __restrict__ b, const T
         M xr = xref ? Elem<T>::ld(xref + i) : (M)0;
         M yr = yref ? Elem<T>::ld(yref + i) : (M)0;
         M d  = dy   ? Elem<T>::ld(dy + i)   : (M)1;
-        Elem<T>::st(y + i, bias_act_one<T, A>(Elem<T>::ld(x + i), bv, xr, yr, d, G, alpha, gain, clamp));
+        Elem<T>::st(y + i, bias_act_one<T, A>(Elem<T>::ld(x + i), bv, xr, yr, d, xref != nullptr, G, alpha, gain, clamp));
     }
 }
 
@@ -240,6 +277,7 @@ extern "C" int ide3d_bias_act(const void* x, const void* b, const void* xref, co
     IDE3D_CHECK_ARG(grad >= 0 && grad <= 2, "bias_act: grad must be 0, 1 or 2 (got %d)", grad);
     IDE3D_CHECK_ARG(b == nullptr || (size_b > 0 && step_b > 0), "bias_act: bad bias geometry");
     IDE3D_CHECK_ARG(grad < 2 || dy != nullptr, "bias_act: grad=2 needs dy");
+    IDE3D_CHECK_ARG(!(act == 3 && grad == 1 && alpha < 0) || xref != nullptr, "bias_act: the gradient of lrelu with a negative slope needs xref (y is positive on both sides of the kink)");
     if (b == nullptr) { size_b = 1; step_b = 1; }
     hipStream_t st = (hipStream_t)stream;
     switch (dtype) {

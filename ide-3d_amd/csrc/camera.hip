@@ -55,12 +55,18 @@ cam2world_kernel(const float* __restrict__ forward, const float* __restrict__ or
     f = normalized(f);
     const V3 left = normalized(cross(V3{0.f, 1.f, 0.f}, f));
     const V3 up = normalized(cross(f, left));
-    // translation @ rotation with rotation[:3, :3] = columns (-left, up, -forward): [R | origin; 0 0 0 1] exactly
+    // translation @ rotation with rotation[:3, :3] = columns (-left, up, -forward): [R | origin; 0 0 0 1] for finite vectors.  The
+    // reference forms it as a matrix product, whose zero factors meet every entry of a column: a degenerate forward vector (parallel
+    // to the up axis: left = 0 / 0; of length zero) makes the whole column NaN, the last row included.  z* is that sum of zero products:
+    // +-0 for a finite column (adding it changes nothing but the sign of a zero), NaN otherwise.
+    const float zl = 0.f * left.x + 0.f * left.y + 0.f * left.z;
+    const float zu = 0.f * up.x + 0.f * up.y + 0.f * up.z;
+    const float zf = 0.f * f.x + 0.f * f.y + 0.f * f.z;
     float* m = out + (int64_t)i * 16;
-    m[0] = -left.x; m[1] = up.x; m[2]  = -f.x; m[3]  = o.x;
-    m[4] = -left.y; m[5] = up.y; m[6]  = -f.y; m[7]  = o.y;
-    m[8] = -left.z; m[9] = up.z; m[10] = -f.z; m[11] = o.z;
-    m[12] = 0.f;    m[13] = 0.f; m[14] = 0.f;  m[15] = 1.f;
+    m[0] = -left.x + zl; m[1] = up.x + zu; m[2]  = -f.x + zf; m[3]  = o.x;
+    m[4] = -left.y + zl; m[5] = up.y + zu; m[6]  = -f.y + zf; m[7]  = o.y;
+    m[8] = -left.z + zl; m[9] = up.z + zu; m[10] = -f.z + zf; m[11] = o.z;
+    m[12] = zl * zl;     m[13] = zu * zu;  m[14] = zf * zf;   m[15] = 1.f;
 }
 
 // The needed-cell map of the plane gate (include/ide3d_hip.h `ide3d_plane_cells`): one thread per (image, ray, step).  The sample's world

@@ -10,7 +10,11 @@
 
 namespace ide3d {
 
+// The definition rounds the product and the sum separately (two ATen operations).  Contracted into one fused multiply-add the sum is
+// rounded once, and where the product's rounding carries the sum across an integer the truncated byte differs (126 of the 256 byte
+// boundaries have such an fp32 input within 64 ulp; tests/frame_cases.py).  One more vector instruction per value in a kernel bound by HBM.
 __device__ __forceinline__ unsigned to_u8(float v) {
+#pragma clang fp contract(off)
     float t = v * 127.5f + 128.0f;
     t = fminf(fmaxf(t, 0.0f), 255.0f);
     return (unsigned)t;     // truncation, like .to(torch.uint8)
@@ -48,8 +52,12 @@ frame_u8_kernel(const float* __restrict__ img, const float* __restrict__ seg, co
             const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const bool take = (vv[j] > best[j]) || (vv[j] != vv[j] && best[j] == best[j]);
-                if (take) { best[j] = vv[j]; arg[j] = c; }
+                // vv > best, or vv is the first NaN: best is a number and vv is not below or equal to it.  One unordered compare and
+                // two selects per pixel; spelled as `(vv > best) || (vv != vv && best == best)` under an `if`, the compiler's code took a
+                // NaN for the last three pixels of a lane and not for the first (tests/test_gpu_frame.py, NaN in one class).
+                const bool take = !(vv[j] <= best[j]) && best[j] == best[j];
+                best[j] = take ? vv[j] : best[j];
+                arg[j] = take ? c : arg[j];
             }
         }
         unsigned sc[4][3];

@@ -114,7 +114,8 @@ class _BiasActHip(torch.autograd.Function):
         x = x.contiguous(memory_format=ctx.layout)
         b = _null_tensor if b is None else b.contiguous()
         y = x if (_is_identity(call) and not b.numel()) else _launch(call, 0, x, b, _null_tensor, _null_tensor, _null_tensor)
-        wants_x = ('x' in spec.ref) or spec.has_2nd_grad        # what the derivative is expressed in
+        # what the derivative is expressed in; lrelu with a negative slope has y > 0 on both sides of the kink, so its side comes from x
+        wants_x = ('x' in spec.ref) or spec.has_2nd_grad or (call.act == 'lrelu' and call.alpha < 0)
         ctx.save_for_backward(x if wants_x else _null_tensor, b if wants_x else _null_tensor, y if 'y' in spec.ref else _null_tensor)
         return y
 
